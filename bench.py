@@ -17,7 +17,11 @@ The whole product path is ctypes -> libmibn.so (HIP kernels + RCCL through the C
 is no second transport behind mibn_comm_*: if it is unavailable on a rank, the launch exits non-zero.
 
 Rank 0 prints ONE JSON line with the driver's contract fields plus
-  `roofline`      dominant kernel: algorithmic bytes per launch / HIP-event duration, vs the 8 TB/s HBM peak
+  `roofline`      dominant kernel: algorithmic bytes per launch / HIP-event duration, vs the 8 TB/s HBM peak (from the timed
+                  steps' own HIP events)
+A plain run does only that: set-up, warm-up, the timed steps and the line.  `--full` (N = 1) adds the side measurements, each a
+run of its own after the timed steps (`--no-cpu` / `--no-configs` drop parts of them):
+  `roofline.per_kernel_serialised`  the level's kernels with their launches serialised (three more steps)
   `cpu_baseline`  kind "reference": the UNMODIFIED reference (sorobn's pandas path, from oracle/_ref) timed on this box's
                   host cores on the first requests of the same stream, no cost filter, under a wall budget: one process
                   (cores 1 - the reference is single-threaded) and an N-process aggregate with N stated; the C port of
@@ -30,6 +34,10 @@ Rank 0 prints ONE JSON line with the driver's contract fields plus
                   weighting, fit, Chow-Liu) with the unmodified reference timed beside each
 `--config c5` times the Gibbs configuration instead (a step = 100 k single-site updates x 128 chains per GPU + the
 int64 histogram reduce).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as float64 .npy files: `posteriors.npy`
+([requests per step, 4], the gathered posteriors) for C3, `histogram.npy` (the step's pooled chain histogram) for C5.  The
+inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -595,7 +603,14 @@ def main():
     ap.add_argument("--sync", action="store_true", help="one blocking mibn_query_batch per step instead of the two-deep pipeline")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (experiments), e.g. --opt chunk=32768")
     ap.add_argument("--threads", type=int, default=0, help="planner threads of this rank (0 = host threads / ranks on the node)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps: the side measurements (serialised kernels, configs, CPU baseline, planner-thread variants; "
+                         "N > 1: shard cost imbalance) - a plain run measures the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64, at most 64 MB in all)")
     a = ap.parse_args()
+    if a.only_configs and a.dump_outputs:
+        ap.error("--dump-outputs needs the timed steps (not --only-configs)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -667,8 +682,8 @@ def main():
     stream = sharding.ShardedStream(eng, comm, to_var[qv][:, None], to_var[ev], ec, G, sub_batch=a.batch, balance=a.balance,
                                     pipelined=not a.sync)
 
-    def run(steps):
-        res = stream.run(steps)
+    def run(steps, keep=False):
+        res = stream.run(steps, keep=keep)
         eng.drain()  # every launch finished and its HIP-event time booked
         return res
 
@@ -676,7 +691,7 @@ def main():
     barrier()
     st0, ks0 = eng.total_stats(), eng.total_kernel_stats()
     t0 = time.perf_counter()
-    timed = run(range(a.warmup, total_steps))
+    timed = run(range(a.warmup, total_steps), keep=bool(a.dump_outputs))  # (keep: the gathered posteriors of every step, for the dump)
     barrier()
     dt = time.perf_counter() - t0
     st1, ks1 = eng.total_stats(), eng.total_kernel_stats()
@@ -724,9 +739,14 @@ def main():
                 "imbalance_gpu_busy_max_over_mean": float(ranks[:, 2].max() / max(1e-9, ranks[:, 2].mean())),
                 "note": "the first 1 M requests of the C3 stream (rng seed 1) in one pass, beside the stepped figure `value`"}
 
+    configs = a.full and not a.no_configs
+    cpu = a.full and not a.no_cpu
     if rank == 0:
         n_queries = a.steps * G
         assert timed["requests"] == n_queries and abs(timed["mass"] - n_queries) < 1e-6 * n_queries, (timed["requests"], timed["mass"])
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, posteriors=timed["gathered"][total_steps - 1])
+            del timed["gathered"]
         my_requests = n_queries if world == 1 else a.steps * (stream.ranges(a.warmup)[0][1] - stream.ranges(a.warmup)[0][0])  # (rank 0's own)
         # dominant kernel = the specialisation with the most HIP-event time over the timed region
         # (the device planner's pair of kernels moves no section-8(d) bytes: it is listed under "kernels", never the roofline's kernel)
@@ -812,7 +832,7 @@ def main():
                                        "(tools/rocprof_summary.py, profiles/r04_o_rocprofv3_summary.txt).  The kernels' own event durations (per_kernel) then include "
                                        "each other's share of the chip; per_kernel_serialised = the same kernels right after the timed region with the launches "
                                        "serialised (overlap=0), for comparison with earlier rounds.")
-        if world == 1 and not a.no_configs and "||" in dom:
+        if world == 1 and configs and "||" in dom:
             # the two kernels by themselves: a few calls with the launches of a level one after the other (option overlap = 0)
             try:
                 eng.set_option("overlap", 0)
@@ -836,7 +856,7 @@ def main():
                 out["roofline"]["per_kernel_serialised"] = {"error": repr(e)}
         if full is not None:
             out["full_stream"] = full
-        if world > 1:
+        if world > 1 and a.full:
             lo = a.warmup * G
             cost = eng.estimate_costs(to_var[qv[lo:lo + G]][:, None], to_var[ev[lo:lo + G]])
             out["shard_cost_imbalance"] = {
@@ -845,9 +865,9 @@ def main():
                 "note": "max / mean shard cost (planner estimate) of one step's global batch, outside the clock; the C3 stream is "
                         "i.i.d., so equal counts already balance to ~1 % - and the estimate itself (0.1 s per 65 536 requests on "
                         "every rank) would cost more inside a step than it can win: --balance cost is an option, count the default"}
-        if world == 1 and not a.no_configs:
+        if world == 1 and configs:
             try:
-                out["configs"] = other_configs(device, with_cpu=not a.no_cpu)
+                out["configs"] = other_configs(device, with_cpu=cpu)
             except Exception as e:  # the headline line must not die with a side measurement
                 out["configs"] = {"error": repr(e)}
             # SURVEY 8(d)'s n_evidence variants of the C3 stream on this engine (the final kernels, the timed region's options)
@@ -856,7 +876,7 @@ def main():
                     out["configs"][f"C3_n_evidence_{ne}"] = c3_variant(eng, to_var, ne, calls=24, warmup_calls=16, batch=a.batch)
                 except Exception as e:  # noqa: BLE001
                     out["configs"][f"C3_n_evidence_{ne}"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu:
+        if world == 1 and cpu:
             # GPU posteriors of the first 200 requests of the stream (what the reference legs work on)
             n_ref = 200
             post200 = eng.query_fixed(to_var[qv[:n_ref]][:, None], to_var[ev[:n_ref]], ec[:n_ref])
@@ -897,7 +917,7 @@ def main():
                 out["cpu_baseline"] = port
                 out["cpu_baseline"]["note"] = "oracle/_ref unavailable on this box: " + (ref[0]["error"] if ref else "not built")
             out["max_abs_marginal_err_vs_oracle"] = err_port
-        if world == 1 and not a.no_configs and not a.threads:
+        if world == 1 and configs and not a.threads:
             # a rank with ONE / TWO / FOUR planner threads (8 ranks sharing a small CPU quota): a fresh engine whose pool has that many
             # workers; the adaptive policy hands planning to order_kernel + emit_kernel where the host's workers would bound the
             # pipeline (the main engine's arena is released first).  Calls of 32 768: such a rank's shard of a 2^18-request step on
@@ -927,13 +947,30 @@ def main():
             except Exception as e:  # noqa: BLE001
                 out["configs"]["C3_query_many_pandas"] = {"error": repr(e)}
             try:
-                out["configs"].update(f_configs(device, with_cpu=not a.no_cpu))
+                out["configs"].update(f_configs(device, with_cpu=cpu))
             except Exception as e:  # noqa: BLE001
                 out["configs"]["F_rows"] = {"error": repr(e)}
         out["summary"] = summary_of(out)  # LAST key: what a 2 000-byte tail of the line still shows
         print(json.dumps(out), flush=True)
     comm.barrier()
     comm.close()
+
+
+DUMP_LIMIT_BYTES = 63_000_000  # the 64 MB budget of --dump-outputs, less room for the .npy headers
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  An array over the 64 MB budget is replaced by a fixed sample
+    of its rows (default_rng(0), ascending) and the row numbers are written beside it as <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.asarray(x, np.float64)
+        if x.nbytes > DUMP_LIMIT_BYTES // len(arrays):
+            row_bytes = x.nbytes // x.shape[0] + 8  # (+ its row number)
+            rows = np.sort(np.random.default_rng(0).choice(x.shape[0], DUMP_LIMIT_BYTES // len(arrays) // row_bytes, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            x = x[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), x)
 
 
 def summary_of(out):
@@ -1010,6 +1047,8 @@ def run_c5(a, rank, world, local_rank, device, backend):
     if world > 1:
         dt = float(comm.allreduce_max([dt])[0])
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, histogram=h)
         est = hist / float(hist.sum())
         out = {"metric": "Gibbs single-site updates/sec on 50-node 8-state grid BN (config 5)",
                "value": a.steps * total_chains * iters / dt, "unit": "updates/s", "n_gpus": world, "steps": a.steps,

@@ -2,9 +2,8 @@
 Parity with the reference's random stream is unpinned (it needs the absent `vose` sampler), so the GPU kernels are
 checked statistically: against the exact posterior (sample marginals, rejection sampling) and against the exact
 limit of the reference's likelihood-weighting estimator, computed by enumeration.  A CPU-only test confirms that
-limit against the unmodified reference itself (build container only)."""
+limit against an estimate of the unmodified reference itself (recorded in tests/golden/likelihood_sprinkler.json)."""
 import itertools
-import os
 
 import numpy as np
 import pandas as pd
@@ -49,17 +48,15 @@ def llh_weighting_limit(bn, query, event):
     return {k: v / z for k, v in mean.items()}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/sorobn"), reason="reference only exists in the build container")
 def test_reference_likelihood_weighting_converges_to_the_enumerated_limit():
-    from oracle import refload
-    ref = refload.load().examples.sprinkler()
-    ref._rng.seed(5)
-    got = ref.query("Rain", event={"Sprinkler": True}, algorithm="likelihood", n_iterations=6000)
+    """The reference's own estimate (6 000 iterations, its rng seeded 5), recorded by tests/golden/make_likelihood_sprinkler.py."""
+    got = gu.load("likelihood_sprinkler.json")
+    assert got["network"] == "sprinkler" and got["n_iterations"] == 6000 and len(got["estimate"]) == 2
     mine = netspec.build(_spec("sprinkler"), sorobn_amd.BayesNet)
-    lim = llh_weighting_limit(mine, ("Rain",), {"Sprinkler": True})
+    lim = llh_weighting_limit(mine, (got["query"],), got["event"])
     f = flatten(mine)
-    for lab, p in got.items():
-        assert abs(p - lim[(f.code_of(f.id["Rain"], lab),)]) < 0.03
+    for lab, p in got["estimate"]:
+        assert abs(float.fromhex(p) - lim[(f.code_of(f.id[got["query"]], lab),)]) < 0.03
 
 
 @pytest.mark.gpu

@@ -4,7 +4,7 @@
 # Stages (run in the order given; every stage writes gpurun_out/<tag>_*):
 #   host          nproc, cgroup CPU quota, CPU model, VRAM
 #   tests[:expr]  pytest -m gpu (optionally -k expr)
-#   bench         the bench line as the driver runs it (--steps 20 --warmup 5)
+#   bench         the bench line with its side measurements (--steps 20 --warmup 5 --full)
 #   full          bench.py --full-stream (configs 3 / 4 as written: the first 1 M requests once)
 #   profile       rocprofv3 kernel trace + FETCH_SIZE / WRITE_SIZE passes of the bench command (tools/gpu_profile.sh)
 #   sq            one pass of SQ counters over the bench command (fractions of SQ_WAVE_CYCLES per kernel)
@@ -41,7 +41,7 @@ tests*)
   else timeout 1800 python -m pytest tests -m gpu -x -q --durations=8 > $OUT/${TAG}_pytest_gpu.log 2>&1; fi
   echo "pytest rc $?" >> $OUT/${TAG}_pytest_gpu.log; tail -14 $OUT/${TAG}_pytest_gpu.log | cut -c1-240 ;;
 bench)
-  timeout 1200 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench.log 2> $OUT/${TAG}_bench.err
+  timeout 1200 python bench.py --steps 20 --warmup 5 --full > $OUT/${TAG}_bench.log 2> $OUT/${TAG}_bench.err
   echo "bench rc $?"; line "driver-shaped" < $OUT/${TAG}_bench.log; tail -3 $OUT/${TAG}_bench.err | cut -c1-300 ;;
 full)
   timeout 400 python bench.py --steps 4 --warmup 2 --no-cpu --no-configs --full-stream > $OUT/${TAG}_full_stream.log 2>&1
