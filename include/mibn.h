@@ -101,6 +101,21 @@ int mibn_query_batch_ex(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_o
                         const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                         const int64_t *out_off, double *out);
 
+/*
+ * Most probable explanation: for each request b, codes[b*n_vars + v] = the label code of v in argmax_x P(x, e_b) over every
+ * variable not in e_b (evidence variables carry their code), log_p[b] = natural log of that joint probability.
+ *   e_off[B+1], e_vars[], e_codes[]   CSR evidence, as in mibn_query_batch (no query variables: every other variable is maximised)
+ *   codes[B*n_vars], log_p[B]         outputs
+ * Max-product variable elimination (every CPT, no pruning), one elimination step per variable, each writing an argmax table that a
+ * traceback kernel decodes on the device.  Ties go to the lowest code.  Zero-probability evidence (or a code of -1) gives
+ * log_p = -inf and code -1 for every non-evidence variable; single-state non-evidence variables get code 0.  Blocking and
+ * host-planned, chunked by the arena budget; it changes no option and no state a later query call reads.  mibn_last_stats /
+ * mibn_last_kernel_stats ("ve_max_kernel", "mpe_traceback_kernel") describe it; alg_bytes includes the argmax bytes written.
+ * Errors: MIBN_E_ARG for unknown or duplicate evidence variables; MIBN_E_LIMIT for a variable of more than 65 536 states.
+ */
+int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                   int32_t *codes, double *log_p);
+
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {
     double alg_bytes;      /* sum over steps of 8*(sum input cells + output cells) */

@@ -21,7 +21,7 @@ SYMBOLS = [
     "mibn_query_batch_ex", "mibn_plan_order", "mibn_estimate_costs", "mibn_device_synchronize", "mibn_gibbs_shard",
     "mibn_comm_unique_id", "mibn_comm_init", "mibn_comm_destroy", "mibn_comm_allgather_f64",
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
-    "mibn_comm_probe", "mibn_device_info", "mibn_comm_count",
+    "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
@@ -75,6 +75,7 @@ def lib():
         L.mibn_set_order_hints.argtypes = [vp, C.c_int32, i32p]
         L.mibn_query_batch.argtypes = [vp, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_query_batch_ex.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
+        L.mibn_mpe_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i32p, f64p]
         L.mibn_plan_order.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, i32p, i32p]
         L.mibn_estimate_costs.argtypes = [vp, C.c_int64, i64p, i32p, i64p, i32p, f64p]
         L.mibn_device_synchronize.argtypes = [vp]
@@ -256,6 +257,30 @@ class Engine:
         out, out_off = self.query_batch(q_off, qvars.reshape(-1), e_off, evars.reshape(-1),
                                         ecodes.reshape(-1), flags=flags)
         return out.reshape(B, -1) if B else out.reshape(0, 0)
+
+    def mpe_batch(self, e_off, e_vars, e_codes):
+        """CSR evidence -> (codes[B, n_vars] int32, log_p[B] float64): the most probable explanation of every request
+        (mibn_mpe_batch)."""
+        n_vars = len(self.card)
+        e_off = _i64(e_off)
+        B = len(e_off) - 1
+        e_vars, e_codes = _i32(e_vars), _i32(e_codes)
+        codes = np.empty((B, n_vars), np.int32)
+        log_p = np.empty(B, np.float64)
+        if B == 0:
+            return codes, log_p
+        self._check(self._L.mibn_mpe_batch(self._h, B, _p(e_off, C.c_int64), _p(e_vars, C.c_int32), _p(e_codes, C.c_int32),
+                                           _p(codes, C.c_int32), _p(log_p, C.c_double)))
+        return codes, log_p
+
+    def mpe(self, evars, ecodes):
+        """Fixed-shape batch: evars[B, ne], ecodes[B, ne] -> (codes[B, n_vars], log_p[B]), like query_fixed."""
+        evars = _i32(evars)
+        B = len(evars)
+        evars = evars.reshape(B, -1)
+        ecodes = _i32(ecodes).reshape(B, -1)
+        e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
+        return self.mpe_batch(e_off, evars.reshape(-1), ecodes.reshape(-1))
 
     def submit_fixed(self, qvars, evars, ecodes):
         """Asynchronous query_fixed: returns a handle for wait().  At most two calls in flight."""

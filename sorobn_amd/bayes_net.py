@@ -889,6 +889,94 @@ class BayesNet:
             event[k] = v
         return pd.Series(event)
 
+    # ---- most probable explanation (an extension: max-product elimination on the device, mibn_mpe_batch) ----------------------
+    def _mpe_ids(self, names):
+        """Variable ids of `names` (the reference's KeyError for an unknown one) and the same KeyError as `query` when a node has
+        no CPT: every variable takes part in an MPE.  Unknown names raise before any engine exists."""
+        known = set(self._all_names())
+        for n in names:
+            if n not in known:
+                raise KeyError(n)
+        be = self.backend
+        ids = [be.var_id(n) for n in names]
+        if be.flat.missing:
+            raise KeyError(be.flat.names[min(be.flat.missing)])
+        return be, ids
+
+    @staticmethod
+    def _label_table(f, v):
+        """Labels of variable v by code, with None at index -1 (code -1 = no answer)."""
+        dom = np.empty(int(f.card[v]) + 1, dtype=object)
+        dom[:-1] = list(f.domains[v])
+        dom[-1] = None
+        return dom
+
+    def mpe(self, event: dict = None, return_log_prob=False):
+        """Most probable explanation: the single most probable completion of `event`, argmax_x P(x, event) over every variable
+        not in `event`.  Returns a Series of labels indexed by every variable (sorted names); evidence variables keep their
+        labels.  Zero-probability or out-of-domain evidence gives None for the other variables (and a log probability of
+        -inf).  With `return_log_prob`, returns (series, natural log of P(x*, event)).  Ties go to the lowest label code."""
+        event = dict(event or {})
+        be, ev = self._mpe_ids(list(event))
+        f = be.flat
+        codes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
+        out, log_p = be.engine.mpe(np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev)))
+        names = self._all_names()
+        vals = []
+        for name in names:
+            if name in event:
+                vals.append(event[name])
+            else:
+                v = f.id[name]
+                vals.append(self._label_table(f, v)[out[0, v]])
+        series = pd.Series(vals, index=pd.Index(names), dtype=object)
+        return (series, float(log_p[0])) if return_log_prob else series
+
+    def mpe_frame(self, events: pd.DataFrame, return_log_prob=False, sub_batch=32768):
+        """`mpe` for every row of `events`, in the convention of `query_frame`: the columns are evidence variables, NaN / None =
+        not observed in that row.  Rows are grouped by their pattern of observed columns, one engine call per group (in
+        sub-batches of `sub_batch` rows).  Returns a DataFrame with the index of `events` and one column per variable (sorted
+        names); with `return_log_prob`, (frame, log probabilities as a numpy array).
+
+        A row that names every variable - observed values and missing ones (NaN / None) - gets what `impute` returns for it (up
+        to ties between equally probable assignments), without `impute`'s posterior table of prod(card(missing)) cells."""
+        cols = list(events.columns)
+        be, ev_all = self._mpe_ids(cols)
+        f = be.flat
+        ev_ids = np.array(ev_all, np.int32)
+        n = len(events)
+        codes = np.empty((n, len(cols)), np.int32)
+        observed = np.empty((n, len(cols)), bool)
+        for j, c in enumerate(cols):
+            col = events[c]
+            observed[:, j] = col.notna().to_numpy()
+            codes[:, j] = pd.Index(f.domains[ev_ids[j]]).get_indexer(col) if len(f.domains[ev_ids[j]]) else -1
+        nv = len(f.names)
+        out = np.zeros((n, nv), np.int32)
+        log_p = np.zeros(n, np.float64)
+        pat = observed @ (1 << np.arange(len(cols), dtype=np.int64)) if len(cols) < 63 else None
+        groups = ([np.arange(n)] if len(cols) == 0 else
+                  [np.flatnonzero(pat == p) for p in np.unique(pat)] if pat is not None else
+                  [np.array([r]) for r in range(n)])
+        for rows in groups:
+            if not len(rows):
+                continue
+            on = np.flatnonzero(observed[rows[0]])
+            for s in range(0, len(rows), sub_batch):
+                part = rows[s:s + sub_batch]
+                out[part], log_p[part] = be.engine.mpe(np.broadcast_to(ev_ids[on], (len(part), len(on))), codes[np.ix_(part, on)])
+        names = self._all_names()
+        data = {}
+        for name in names:
+            v = f.id[name]
+            col = self._label_table(f, v)[out[:, v]]
+            if name in events.columns:  # evidence keeps its label (also where it lies outside the domain)
+                obs = events[name].notna().to_numpy()
+                col[obs] = events[name].to_numpy(dtype=object)[obs]
+            data[name] = col
+        frame = pd.DataFrame(data, index=events.index, columns=names)
+        return (frame, log_p) if return_log_prob else frame
+
     # ---- SURVEY.md section 8f rank 1: the joint and likelihoods (bayes_net.py:398-465, 934-973) -----------------
     def _all_names(self):
         names = []

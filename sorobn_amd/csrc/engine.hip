@@ -26,6 +26,7 @@
 #include "tiny_kernel.hip.h"
 #include "sweep_kernel.hip.h"
 #include "ve_kernel.hip.h"
+#include "max_kernel.hip.h"
 #include "wave_plan_kernel.hip.h"
 
 using namespace mibn;
@@ -174,6 +175,9 @@ __global__ __launch_bounds__(MIBN_PLAN_WG, MIBN_EMIT_WAVES_PER_EU) void emit_ker
 // proved erratic end to end (planning wall time doubles, runs between 155 k and 204 k queries/s against a steady
 // 194-204 k with two: profiles/r02_q_chunk_sets.log), so it stays an experiment.
 constexpr int kChunkSets = 4;
+// statistics slots: the classes of work (split_kinds), the kernels of mibn_query_batch as launched (stat_name), then the two of
+// mibn_mpe_batch
+constexpr int kStatSlots = kNumKernels + 9;
 
 struct mibn_ctx {
     Network net;
@@ -339,8 +343,28 @@ struct mibn_ctx {
     } comm;
     std::string err;
     mibn_stats stats{}, total{};               // last call / since creation
-    mibn_kernel_stat kstats[kNumKernels + 7];  // per class (split_kinds) + the level kernel as a whole + the tiny kernel + the LDS-DMA sweep kernel
-    mibn_kernel_stat ktotal[kNumKernels + 7];  // + the device planner's pair of kernels + the concurrent launch pair of a level (option overlap)
+    mibn_kernel_stat kstats[kStatSlots];  // per class (split_kinds) + the level kernel as a whole + the tiny kernel + the LDS-DMA sweep kernel
+    mibn_kernel_stat ktotal[kStatSlots];  // + the device planner's pair of kernels + the concurrent launch pair of a level (option overlap)
+                                          // + ve_max_kernel and mpe_traceback_kernel (mibn_mpe_batch: last-call statistics only)
+    // mibn_mpe_batch (blocking, host-planned): buffers of its own - nothing a query call reads - beside the arena of lane 0
+    struct Mpe {
+        std::vector<ProgBuf> bufs;  // malloc-backed program buffers, one per worker
+        BatchPlan plan;
+        Schedule sched;
+        uint32_t *d_prog = nullptr;
+        size_t prog_cap = 0;
+        uint64_t *d_prog_off = nullptr, *d_arena_off = nullptr;
+        size_t prog_off_cap = 0, arena_off_cap = 0;
+        Item *d_items = nullptr;
+        size_t items_cap = 0;
+        uint32_t *d_wg_item = nullptr;
+        size_t wg_item_cap = 0;
+        double *d_m = nullptr, *d_log_p = nullptr;
+        size_t m_cap = 0, log_p_cap = 0;
+        int32_t *d_codes = nullptr;
+        size_t codes_cap = 0;
+        std::vector<hipEvent_t> ev;
+    } mpe;
     // options
     double arena_gb = 200.0;  // scratch budget of all lanes together (of the 288 GB)
     hipStream_t stream2 = nullptr;  // lane 1 (lane 0 = stream)
@@ -567,6 +591,19 @@ void mibn_destroy(mibn_t *h) {
         }
         for (auto &sg : h->res_stage)
             if (sg.p) (void)hipHostFree(sg.p);
+        {
+            mibn_ctx::Mpe &M = h->mpe;
+            for (auto &b : M.bufs) b.release();
+            (void)hipFree(M.d_prog);
+            (void)hipFree(M.d_prog_off);
+            (void)hipFree(M.d_arena_off);
+            (void)hipFree(M.d_items);
+            (void)hipFree(M.d_wg_item);
+            (void)hipFree(M.d_m);
+            (void)hipFree(M.d_log_p);
+            (void)hipFree(M.d_codes);
+            for (auto e : M.ev) (void)hipEventDestroy(e);
+        }
         if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
         if (h->stream2) (void)hipStreamDestroy(h->stream2);
         for (auto &la : h->aux)
@@ -805,7 +842,7 @@ void ensure_pool(mibn_ctx *h) {
 
 // name of statistics slot k: the classes of work (split_kinds), then the kernels as launched
 const char *stat_name(int k) {
-    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : "ve_mfma_kernel"))))));
+    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : "mpe_traceback_kernel"))))))));
 }
 
 // wait for a set's launches and book their HIP-event durations per kernel
@@ -1415,7 +1452,7 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
     h->search_ms = 0;
     h->emit_ms = 0;
     h->stats = mibn_stats{};
-    for (int k = 0; k <= kNumKernels + 6; ++k) {
+    for (int k = 0; k < kStatSlots; ++k) {
         h->kstats[k] = mibn_kernel_stat{};
         std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
     }
@@ -2032,6 +2069,211 @@ static int run_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off,
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------- most probable explanation
+// mibn_mpe_batch: max programs (planner.h) planned by the workers, run level by level by ve_max_kernel on the main stream, decoded by
+// mpe_traceback_kernel, downloaded - chunk by chunk, each chunk cut into waves by the arena budget like a query call.  Blocking and
+// host-planned: no tiny kernel, no device planner, no plan templates, no adaptive policy; the options are read, never written.  The
+// arena of lane 0 is shared with the query calls (after the streams have drained); the statistics are those of the last call only.
+static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes, double *log_p) {
+    if (!h || B < 0 || !e_off || (B && (!codes || !log_p))) return MIBN_E_ARG;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    const double t_start = now_ms();
+    h->stats = mibn_stats{};
+    for (int k = 0; k < kStatSlots; ++k) {
+        h->kstats[k] = mibn_kernel_stat{};
+        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
+    }
+    if (B == 0) return MIBN_OK;
+    const Network &net = h->net;
+    const int nv = net.n_vars;
+    for (int v = 0; v < nv; ++v)
+        if (net.card[v] > 65536) { h->err = "mpe: variable " + std::to_string(v) + " has more than 65 536 states (argmax entries are 16 bits)"; return MIBN_E_LIMIT; }
+    // validation (unknown ids, duplicates) and the out-of-domain-evidence short cut
+    std::vector<char> skip((size_t)B, 0);
+    for (int64_t b = 0; b < B; ++b) {
+        Request rq;
+        rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
+        rq.evars = e_vars + e_off[b];
+        const std::string e = rq.ne < 0 ? std::string("negative evidence count") : validate_mpe_request(net, rq);
+        if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
+        for (int i = 0; i < rq.ne; ++i) {
+            const int32_t c = e_codes[e_off[b] + i];
+            if (c < 0 || c >= net.card[rq.evars[i]]) skip[(size_t)b] = 1;  // label outside the domain: zero probability
+        }
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    ensure_pool(h);
+    // an asynchronous query call may still use the arena of lane 0
+    for (hipStream_t q : {h->search_stream, h->copy_stream, h->stream, h->stream2})
+        if (q) HIP_TRY(h, hipStreamSynchronize(q));
+    for (auto &la : h->aux)
+        for (hipStream_t a : la)
+            if (a) HIP_TRY(h, hipStreamSynchronize(a));
+    mibn_ctx::Mpe &M = h->mpe;
+    if (M.bufs.size() < (size_t)h->pool->size()) M.bufs.resize((size_t)h->pool->size());
+    const hipStream_t S = h->stream;
+    std::vector<int64_t> q_off((size_t)B + 1, 0), out_off((size_t)B + 1);
+    std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: m
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0])) / 8.0);
+    size_t n_ev = 0;
+    auto event = [&](size_t &idx) -> int {
+        if (n_ev == M.ev.size()) {
+            hipEvent_t e;
+            HIP_TRY(h, hipEventCreate(&e));
+            M.ev.push_back(e);
+        }
+        idx = n_ev++;
+        HIP_TRY(h, hipEventRecord(M.ev[idx], S));
+        return MIBN_OK;
+    };
+    struct Timed { int slot; size_t e0, e1; double bytes, items; };
+    std::vector<Timed> timed;
+    int rc;
+    for (int64_t b0 = 0, b1 = 0; b0 < B; b0 = b1) {
+        b1 = std::min(B, b0 + std::max<int64_t>(1, h->chunk));
+        const int64_t n = b1 - b0;
+        double t0 = now_ms();
+        BatchPlan &ck = M.plan;
+        plan_batch(net, *h->pool, M.bufs, b0, b1, q_off.data(), nullptr, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck, false,
+                   nullptr, nullptr, -1, true);
+        if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
+        h->stats.plan_ms += now_ms() - t0;
+        t0 = now_ms();
+        if ((rc = ensure(h, M.d_prog, M.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
+        if ((rc = ensure(h, M.d_prog_off, M.prog_off_cap, (size_t)n))) return rc;
+        if ((rc = ensure(h, M.d_m, M.m_cap, (size_t)n))) return rc;
+        if ((rc = ensure(h, M.d_log_p, M.log_p_cap, (size_t)n))) return rc;
+        if ((rc = ensure(h, M.d_codes, M.codes_cap, (size_t)n * (size_t)std::max(1, nv)))) return rc;
+        size_t base = 0;
+        for (size_t t = 0; t < ck.thread_words.size(); ++t) {
+            if (ck.thread_words[t]) HIP_TRY(h, hipMemcpyAsync(M.d_prog + base, M.bufs[t].data, ck.thread_words[t] * 4, hipMemcpyHostToDevice, S));
+            base += ck.thread_words[t];
+        }
+        HIP_TRY(h, hipMemcpyAsync(M.d_prog_off, ck.prog_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
+        HIP_TRY(h, hipMemsetAsync(M.d_m, 0, (size_t)n * 8, S));  // (skipped requests never write theirs: zero probability)
+        h->stats.h2d_ms += now_ms() - t0;
+        // waves: consecutive requests whose arenas (intermediates + argmax tables) fit the budget together
+        for (int64_t r0 = 0; r0 < n;) {
+            int64_t r1 = r0, cells = 0;
+            while (r1 < n) {
+                const int64_t need = (ck.arena_need[(size_t)r1] + 15) & ~int64_t(15);
+                if (r1 > r0 && cells + need > budget_cells) break;
+                cells += need;
+                ++r1;
+            }
+            if (cells > budget_cells) { h->err = "a request needs " + std::to_string(8.0 * cells / 1e9) + " GB of scratch, above the arena budget"; return MIBN_E_NOMEM; }
+            t0 = now_ms();
+            Schedule &sc = M.sched;
+            build_schedule(net, ck, M.bufs, r0, r1, sc);
+            h->stats.plan_ms += now_ms() - t0;
+            const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
+            if (need_bytes > h->arena_bytes[0]) {
+                HIP_TRY(h, hipStreamSynchronize(S));
+                if (h->d_arena[0]) { HIP_TRY(h, hipFree(h->d_arena[0])); h->d_arena[0] = nullptr; h->arena_bytes[0] = 0; }
+                const size_t want = std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3));
+                HIP_TRY(h, hipMalloc(&h->d_arena[0], want));
+                h->arena_bytes[0] = want;
+            }
+            t0 = now_ms();
+            if ((rc = ensure(h, M.d_arena_off, M.arena_off_cap, (size_t)(r1 - r0)))) return rc;
+            if ((rc = ensure(h, M.d_items, M.items_cap, std::max<size_t>(1, sc.items.size())))) return rc;
+            if ((rc = ensure(h, M.d_wg_item, M.wg_item_cap, std::max<size_t>(1, sc.wg_item.size())))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(M.d_arena_off, sc.arena_off.data(), (size_t)(r1 - r0) * 8, hipMemcpyHostToDevice, S));
+            if (!sc.items.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_items, sc.items.data(), sc.items.size() * sizeof(Item), hipMemcpyHostToDevice, S));
+            if (!sc.wg_item.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_wg_item, sc.wg_item.data(), sc.wg_item.size() * sizeof(uint32_t), hipMemcpyHostToDevice, S));
+            h->stats.h2d_ms += now_ms() - t0;
+            LevelArgs A;
+            A.prog = M.d_prog;
+            A.prog_off = M.d_prog_off + r0;
+            A.arena_off = M.d_arena_off;
+            A.pool = h->d_pool;
+            A.arena = h->d_arena[0];
+            A.results = M.d_m;  // (FINAL offsets are chunk-relative: request b's m at b - b0)
+            A.items = M.d_items;
+            // one launch per level: every class of work of a max schedule (segments, GENERIC tiles) is ve_max_kernel's
+            for (size_t li = 0; li < sc.launches.size();) {
+                size_t lj = li + 1;
+                double bytes = sc.launches[li].alg_bytes;
+                size_t grid = sc.launches[li].grid;
+                for (; lj < sc.launches.size() && sc.launches[lj].level == sc.launches[li].level; ++lj) {
+                    bytes += sc.launches[lj].alg_bytes;
+                    grid += sc.launches[lj].grid;
+                }
+                const Launch &L = sc.launches[li];
+                A.wg_item = M.d_wg_item + L.wg_level;
+                A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
+                size_t e0 = 0, e1 = 0;
+                if ((rc = event(e0))) return rc;
+                hipLaunchKernelGGL(ve_max_kernel, dim3((unsigned)grid), dim3(kWG), 0, S, A);
+                if ((rc = event(e1))) return rc;
+                timed.push_back({kNumKernels + 7, e0, e1, bytes, (double)grid});
+                h->stats.n_workgroups += (double)grid;
+                li = lj;
+            }
+            TracebackArgs T;
+            T.prog = M.d_prog;
+            T.prog_off = M.d_prog_off + r0;
+            T.arena_off = M.d_arena_off;
+            T.arena = h->d_arena[0];
+            T.m = M.d_m + r0;
+            T.codes = M.d_codes + (size_t)r0 * (size_t)nv;
+            T.log_p = M.d_log_p + r0;
+            T.n_req = (uint32_t)(r1 - r0);
+            T.n_vars = nv;
+            size_t e0 = 0, e1 = 0;
+            if ((rc = event(e0))) return rc;
+            hipLaunchKernelGGL(mpe_traceback_kernel, dim3((unsigned)(r1 - r0)), dim3(kTracebackWG), 0, S, T);
+            if ((rc = event(e1))) return rc;
+            timed.push_back({kNumKernels + 8, e0, e1, 0.0, (double)(r1 - r0)});
+            HIP_TRY(h, hipGetLastError());
+            // the next wave re-uses the arena, the schedule buffers and the host schedule
+            HIP_TRY(h, hipStreamSynchronize(S));
+            h->stats.arena_bytes = std::max(h->stats.arena_bytes, (double)need_bytes);
+            for (const Timed &t : timed) {
+                float ms = 0;
+                HIP_TRY(h, hipEventElapsedTime(&ms, M.ev[t.e0], M.ev[t.e1]));
+                mibn_kernel_stat &ks = h->kstats[t.slot];
+                ks.launches += 1;
+                ks.ms += ms;
+                ks.alg_bytes += t.bytes;
+                ks.items += t.items;
+                h->stats.kernel_ms += ms;
+                h->stats.n_launches += 1;
+            }
+            timed.clear();
+            n_ev = 0;
+            r0 = r1;
+        }
+        t0 = now_ms();
+        HIP_TRY(h, hipMemcpyAsync(codes + (size_t)b0 * (size_t)nv, M.d_codes, (size_t)n * (size_t)nv * 4, hipMemcpyDeviceToHost, S));
+        HIP_TRY(h, hipMemcpyAsync(log_p + b0, M.d_log_p, (size_t)n * 8, hipMemcpyDeviceToHost, S));
+        HIP_TRY(h, hipStreamSynchronize(S));
+        h->stats.d2h_ms += now_ms() - t0;
+        h->stats.alg_bytes += ck.st.alg_bytes;
+        h->stats.alg_flops += ck.st.alg_flops;
+        h->stats.n_steps += ck.st.n_steps;
+        h->stats.max_step_cells = std::max(h->stats.max_step_cells, ck.st.max_step_cells);
+    }
+    h->stats.total_ms = now_ms() - t_start;
+    return MIBN_OK;
+}
+
+extern "C" int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes,
+                              double *log_p) {
+    const int rc = run_mpe_body(h, B, e_off, e_vars, e_codes, codes, log_p);
+    if (rc != MIBN_OK && h && !h->planner_only && h->stream) {  // (nothing of the call may still run when the caller sees the error)
+        const std::string keep = h->err;
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipGetLastError();
+        h->err = keep;
+    }
+    return rc;
+}
+
 extern "C" int mibn_query_batch(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *q_vars,
                                 const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                 const int64_t *out_off, double *out) {
@@ -2084,7 +2326,7 @@ extern "C" int mibn_total_stats(const mibn_t *h, mibn_stats *out) {
 extern "C" int mibn_total_kernel_stats(const mibn_t *h, int32_t cap, mibn_kernel_stat *out, int32_t *n) {
     if (!h || !out || !n) return MIBN_E_ARG;
     int k = 0;
-    for (int i = 0; i <= kNumKernels + 6 && k < cap; ++i)
+    for (int i = 0; i < kStatSlots && k < cap; ++i)
         if (h->ktotal[i].launches > 0) out[k++] = h->ktotal[i];
     *n = k;
     return MIBN_OK;
@@ -2093,7 +2335,7 @@ extern "C" int mibn_total_kernel_stats(const mibn_t *h, int32_t cap, mibn_kernel
 extern "C" int mibn_last_kernel_stats(const mibn_t *h, int32_t cap, mibn_kernel_stat *out, int32_t *n) {
     if (!h || !out || !n) return MIBN_E_ARG;
     int k = 0;
-    for (int i = 0; i <= kNumKernels + 6 && k < cap; ++i)
+    for (int i = 0; i < kStatSlots && k < cap; ++i)
         if (h->kstats[i].launches > 0) out[k++] = h->kstats[i];
     *n = k;
     return MIBN_OK;

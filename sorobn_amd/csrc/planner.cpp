@@ -299,6 +299,17 @@ bool request_is_valid(const Network &net, const Request &rq) {
     return true;
 }
 
+std::string validate_mpe_request(const Network &net, const Request &rq) {
+    Bits ev;
+    for (int i = 0; i < rq.ne; ++i) {
+        int v = rq.evars[i];
+        if (v < 0 || v >= net.n_vars) return "unknown evidence variable id " + std::to_string(v);
+        if (ev.test(v)) return "duplicate evidence variable id " + std::to_string(v);
+        ev.set(v);
+    }
+    return "";
+}
+
 std::string validate_request(const Network &net, const Request &rq) {
     if (request_is_valid(net, rq)) return "";
     if (rq.nq < 1) return "At least one query variable has to be specified";  // bayes_net.py:840-841
@@ -526,6 +537,116 @@ std::string emit_error_message(int err) {
     return "planner error " + std::to_string(err);
 }
 
+// Max program of one request (planner.h, "MAX programs"): the factors of emit_begin (every CPT, evidence-sliced), one GENERIC step
+// per variable of `order` with its argmax table, the final product of the remaining scalars, then the traceback record.  Host
+// only - the device planner does not emit max programs.  Returns 0 or a kEmitErr*.
+static int emit_run_max(const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq, const int32_t *order,
+                        int n_order, int64_t &argmax_cells) {
+    EmitNet en = en_sum;  // every step GENERIC: no output is ever "big" enough for a streaming form, no fused or swept variables
+    en.big_iters = std::numeric_limits<int64_t>::max();
+    en.outer = en.fuse = en.chain = en.sweep = 0;
+    PF *pool = S.pool;
+    S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
+    Emitter em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr};
+    for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
+    const size_t count_pos = prog.size;
+    prog.push(0);
+    const double steps0 = st.n_steps;
+    std::vector<char> alive((size_t)S.pool_cap, 0);
+    for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
+    const PF **ins = S.ins;
+    // pre-multiply the smallest tables while more than kMaxIn remain (product-only steps, no argmax)
+    auto limit = [&](int n_in) -> int {
+        while (n_in > kMaxIn && !em.err) {
+            if (S.n_pool + 1 > S.pool_cap) { em.err = kEmitErrPool; return 0; }
+            std::stable_sort(ins, ins + n_in, [](const PF *a, const PF *b) { return a->cells < b->cells; });
+            PF &o = pool[S.n_pool++];
+            pf_reset(o);
+            em.emit(ins, kMaxIn, nullptr, 0, false, 0, o, false);
+            for (int k = kMaxIn; k < n_in; ++k) ins[k - kMaxIn] = ins[k];
+            n_in -= kMaxIn;
+            ins[n_in++] = &o;
+        }
+        return n_in;
+    };
+    struct Rec { uint64_t off; int32_t x, n; int32_t vars[kRawAxes]; int64_t strides[kRawAxes]; };
+    std::vector<Rec> recs;
+    recs.reserve((size_t)n_order);
+    for (int i = 0; i < n_order; ++i) {
+        const int32_t x = order[i];
+        int n_in = 0;
+        for (int idx = 0; idx < S.n_pool; ++idx)
+            if (alive[(size_t)idx] && pool[idx].scope.test(x)) { ins[n_in++] = &pool[idx]; alive[(size_t)idx] = 0; }
+        if (!n_in) continue;  // (cannot happen: x's own CPT mentions it)
+        n_in = limit(n_in);
+        if (em.err) return em.err;
+        // the argmax table is allocated before the step's output - and before its inputs go back to the arena: the kernel writes it
+        // while it reads them
+        Bits u;
+        u.nw = en.nw;
+        for (int j = 0; j < n_in; ++j) u.or_(ins[j]->scope);
+        u.clr(x);
+        double cells = 1;
+        u.for_each([&](int v) { cells *= en.card[v]; });
+        if (cells >= (double)(1ll << 31)) return kEmitErrCells;
+        const int64_t am_cells = ((int64_t)cells * 2 + 7) / 8;  // uint16 entries, in doubles
+        const int64_t am_off = em.arena.alloc(am_cells);
+        argmax_cells += (am_cells + 15) & ~int64_t(15);
+        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
+        PF &o = pool[S.n_pool++];
+        pf_reset(o);
+        const size_t step_base = prog.size;
+        em.emit(ins, n_in, &x, 1, false, 0, o, false);
+        if (em.err) return em.err;
+        uint32_t *w = prog.data + step_base;
+        w[1] |= kFlagMax << 16;
+        w[7] = (uint32_t)((uint64_t)am_off & 0xffffffffu);
+        w[8] = (uint32_t)((uint64_t)am_off >> 32);
+        w[9] += (uint32_t)(((int64_t)cells + 15) / 16);  // (the argmax bytes, in the step's units of 32 bytes)
+        st.alg_bytes += 2.0 * cells;
+        Rec r;
+        r.off = (uint64_t)am_off;
+        r.x = x;
+        r.n = o.n;
+        for (int a = 0; a < o.n; ++a) { r.vars[a] = o.vars[a]; r.strides[a] = o.strides[a]; }
+        recs.push_back(r);
+        alive[(size_t)(S.n_pool - 1)] = 1;
+    }
+    // m = the product of what is left (all scalars), one cell, not normalised
+    st.out_cells = 1;
+    int n_in = 0;
+    for (int idx = 0; idx < S.n_pool; ++idx)
+        if (alive[(size_t)idx]) ins[n_in++] = &pool[idx];
+    n_in = limit(n_in);
+    if (em.err) return em.err;
+    if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
+    PF &o = pool[S.n_pool++];
+    pf_reset(o);
+    em.emit(ins, n_in, nullptr, 0, true, rq.out_off, o, false);
+    if (em.err) return em.err;
+    prog.data[count_pos] = (uint32_t)(st.n_steps - steps0);
+    st.arena_cells = std::max(st.arena_cells, em.arena.top);
+    // traceback record
+    prog.push((uint32_t)recs.size());
+    prog.push((uint32_t)rq.ne);
+    for (int i = 0; i < rq.ne; ++i) {
+        prog.push((uint32_t)rq.evars[i]);
+        prog.push((uint32_t)(rq.ecodes ? rq.ecodes[i] : 0));
+    }
+    for (size_t k = recs.size(); k-- > 0;) {
+        const Rec &r = recs[k];
+        prog.push((uint32_t)(r.off & 0xffffffffu));
+        prog.push((uint32_t)(r.off >> 32));
+        prog.push((uint32_t)r.x);
+        prog.push((uint32_t)r.n);
+        for (int a = 0; a < r.n; ++a) {
+            prog.push((uint32_t)r.vars[a]);
+            prog.push((uint32_t)r.strides[a]);
+        }
+    }
+    return 0;
+}
+
 // One request on the host: the shared emission (emit_core.h) around the choice of the elimination order.
 static std::string plan_request_rec(const Network &net, const Request &rq, ProgBuf &prog, PlanStats &st, PlanRecord *rec) {
     PROF(0);
@@ -552,7 +673,11 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     }
     // relevant = query | event | ancestors(...)  (bayes_net.py:763-765); hidden = relevant - query - event (766); factors =
     // evidence-sliced CPTs of the relevant nodes (768-776)
-    if (int e = emit_begin(en, ES, rq.nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, rq.no_prune)) return emit_error_message(e);
+    // (a max program has no query variable and never prunes: every non-evidence variable is maximised out)
+    const bool mx = rq.max_mode;
+    const int nq = mx ? 0 : rq.nq;
+    const bool no_prune = mx || rq.no_prune;
+    if (int e = emit_begin(en, ES, nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, no_prune)) return emit_error_message(e);
     const Bits &hidden = ES.hidden;
 
     // candidate elimination orders, cheapest by the byte model wins
@@ -566,9 +691,11 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     } else if (net.n_vars <= 128) {
         PROF(1);
         OrderScratch &OS = order_scratch();
-        order_search(net.order_view(), OS, rq.nq, rq.qvars, rq.ne, rq.evars, rq.no_prune);
+        OrderNet on = net.order_view();
+        if (mx) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms max programs do not use)
+        order_search(on, OS, nq, rq.qvars, rq.ne, rq.evars, no_prune);
         best.assign(OS.best, OS.best + OS.n_best);
-        if (net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
+        if (!mx && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
     } else if (hidden.any()) {
         std::vector<Bits> &scopes = S.scopes;
         std::vector<double> &scells = S.scope_cells;
@@ -581,7 +708,7 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
             if (c < best_cost) { best_cost = c; best.swap(cand); }
         };
         int qdepth = std::numeric_limits<int>::max();
-        for (int i = 0; i < rq.nq; ++i) qdepth = std::min(qdepth, (int)net.depth[rq.qvars[i]]);
+        for (int i = 0; i < nq; ++i) qdepth = std::min(qdepth, (int)net.depth[rq.qvars[i]]);
         // the candidate sweeps are the hidden variables in the order of a per-network sorted list (Network::set /
         // set_hints): filtered, not sorted, per request
         auto filtered = [&](const std::vector<int32_t> &sorted_all, int lo_depth, int hi_depth) {
@@ -632,6 +759,12 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     const size_t start_words = prog.size;
     const EmitStats es0 = es;
     const size_t rec_consts0 = rec ? rec->consts.size() : 0, rec_finals0 = rec ? rec->finals.size() : 0;
+    if (mx) {
+        const int e = emit_run_max(en, ES, eb, es, rq, best.data(), (int)best.size(), st.argmax_cells);
+        st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
+        st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
+        return emit_error_message(e);
+    }
     int e = emit_run(en, ES, eb, es, rec, rq.nq, rq.qvars, rq.out_off, best.data(), (int)best.size() MIBN_PROF_PASS);
     if (!e && !second.empty()) {
         // the runner-up of the byte model emitted too: the program that moves fewer bytes stays (the first on a tie, or if the
@@ -939,7 +1072,7 @@ PlanCache &plan_cache(const TemplateStore *ts) {
 void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs, int64_t b0, int64_t b1,
                 const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
                 const int32_t *e_codes, const int64_t *out_off, const char *skip, BatchPlan &ck, bool no_prune,
-                const uint8_t *orders, const int32_t *order_len, int64_t out_first) {
+                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode) {
     const int64_t n = b1 - b0;
     const int T = pool.size();
     if ((int)bufs.size() < T) bufs.resize(T);
@@ -959,7 +1092,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
     std::vector<std::string> terr(T);
     // dynamic distribution in blocks of 32 requests: request costs vary 100x and a worker may lose its core to
     // another rank's planner, a static split would wait for the slowest worker
-    TemplateStore *store = net.plan_cache ? template_store(net) : nullptr;
+    TemplateStore *store = (net.plan_cache && !max_mode) ? template_store(net) : nullptr;
     std::atomic<int64_t> next{0};
     constexpr int64_t kBlock = 32;
     const EmitNet en = net.emit_view();
@@ -978,7 +1111,16 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             ck.local_off[i] = prog.size;
             ck.thread_of[i] = t;
             ck.tag_first[i] = (uint32_t)tags.size();
-            if (skip && skip[b]) { prog.push(0); continue; }  // zero steps: result stays all-zero
+            if (skip && skip[b]) {  // zero steps: result stays all-zero
+                prog.push(0);
+                if (max_mode) {  // (an empty traceback record: m = 0 reads as zero probability)
+                    const int32_t ne = (int32_t)(e_off[b + 1] - e_off[b]);
+                    prog.push(0);
+                    prog.push((uint32_t)ne);
+                    for (int32_t k = 0; k < ne; ++k) { prog.push((uint32_t)e_vars[e_off[b] + k]); prog.push((uint32_t)e_codes[e_off[b] + k]); }
+                }
+                continue;
+            }
             Request rq;
             rq.nq = (int32_t)(q_off[b + 1] - q_off[b]);
             rq.qvars = q_vars + q_off[b];
@@ -987,6 +1129,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             rq.ecodes = e_codes + e_off[b];
             rq.out_off = out_off[b] - out_off[out_first >= 0 ? out_first : b0];
             rq.no_prune = no_prune;
+            rq.max_mode = max_mode;
             if (orders) { rq.order = orders + (size_t)i * 128; rq.n_order = order_len[i]; }
             PlanStats st;
             // plan templates (see above): probe at the start of every window, stay on while shapes repeat

@@ -88,6 +88,7 @@ struct Request {
     const int32_t *ecodes = nullptr;  // may be null for plan-only statistics
     int64_t out_off = 0;              // offset (doubles) into the batch result buffer
     bool no_prune = false;            // MIBN_Q_NOPRUNE: every CPT takes part (full_joint_dist / predict_proba, bayes_net.py:460)
+    bool max_mode = false;            // max program (mibn_mpe_batch): max-product elimination of every non-evidence variable, nq = 0
     const uint8_t *order = nullptr;   // elimination order found elsewhere (the device order search), n_order entries
     int32_t n_order = -1;             // -1: search on the host
 };
@@ -96,6 +97,7 @@ struct PlanStats {
     double alg_bytes = 0, alg_flops = 0, n_steps = 0, max_step_cells = 0;
     int64_t arena_cells = 0;  // scratch cells this request needs in its arena slot
     int64_t out_cells = 0;
+    int64_t argmax_cells = 0;  // max programs: arena cells (doubles) of the argmax tables, included in arena_cells
     std::vector<int32_t> *order = nullptr;  // optional: receives the elimination order the plan executes (mibn_plan_order)
 };
 
@@ -173,6 +175,21 @@ struct PlanStats {
 //      flag SWEEP_CANON (w1): see kFlagSweepCanon.  The loop digit of a stage is sweep_loop_digit(k, dig), the thread fields are
 //      the other free digits in ascending order.
 //      A work item = Network::sweep_iters consecutive tiles; one workgroup of kSweepWG lanes per item.
+//
+//   MAX programs (Request::max_mode, mibn_mpe_batch): max-product elimination of EVERY non-evidence variable (no pruning: a
+//      barren node does not maximise to 1), no query variable - the FINAL step multiplies the remaining scalars into one cell,
+//      m = max_x P(x, e), not normalised.  Every step is GENERIC with one eliminated variable (no FIBER / OUTER / CHAIN / SWEEP,
+//      no fused pairs: their kernels only sum), candidate orders compared by plain section-8(d) bytes.  A step that eliminates
+//      a variable (cx > 1) carries
+//      flag MAX (kFlagMax, w1 bit 16 + 5): psi[o] = max_x prod_j phi_j[..], and argmax[o] = the lowest x that attains it
+//      w7, w8 = offset (doubles, arena-relative) of its argmax table: one uint16 per output cell, output cell order
+//      Argmax tables are never released back to the arena while the request runs (PlanStats::argmax_cells).  Product-only
+//      steps (cx = 1, inputs beyond kMaxIn pre-multiplied) carry no flag.
+//      After the last step follows the TRACEBACK record of the request:
+//          n_rec, n_ev, (evidence variable, code) x n_ev,
+//          per elimination step, last eliminated first:  argmax off lo, off hi, x, n_out, (output variable, stride) x n_out
+//      x* = argmax[sum_v code[v] * stride_v]: every output variable of a step is eliminated later, so the reverse walk has
+//      already decoded it.  A request whose evidence code lies outside its domain is the program "0" + a record with n_rec = 0.
 // Growable word buffer the planner appends programs to.  The engine backs it with pinned host memory
 // (so the upload is a true async DMA) and keeps it across calls; the default backing is malloc.
 struct ProgBuf {
@@ -224,8 +241,9 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
                 const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
                 const int32_t *e_codes, const int64_t *out_off, const char *skip, BatchPlan &bp, bool no_prune = false,
                 const uint8_t *orders = nullptr, const int32_t *order_len = nullptr,  // orders[(b - b0) * 128 ..]: device order search
-                int64_t out_first = -1);  // result offsets relative to out_off[out_first] (default: b0) - the host's share of a chunk whose
+                int64_t out_first = -1,   // result offsets relative to out_off[out_first] (default: b0) - the host's share of a chunk whose
                                           // first requests the device plans
+                bool max_mode = false);   // max programs (mibn_mpe_batch; q_off all zero, no plan templates)
 
 // Shard-balancing estimate (mibn_estimate_costs): section-8(d) bytes of the cheaper of the two sweep orders of every
 // request of a CSR batch - the byte model only, nothing is emitted.
@@ -276,5 +294,6 @@ void build_schedule(const Network &net, const BatchPlan &bp, const std::vector<P
 // Validate a request (unknown ids, duplicates, overlap) - bayes_net.py:840-845 and the KeyError of 770.
 std::string validate_request(const Network &net, const Request &rq);  // "" or the reference's error message
 bool request_is_valid(const Network &net, const Request &rq);          // the same checks without building a message
+std::string validate_mpe_request(const Network &net, const Request &rq);  // evidence only (unknown ids, duplicates): "" or the message
 
 }  // namespace mibn

@@ -86,7 +86,9 @@ __device__ __forceinline__ void lanes_sync() {
     }
 }
 
-template <int NIN, int MAXC, int CX, int LANES>
+// MAX (max programs, planner.h; max_kernel.hip.h): psi[o] = max_x prod_j phi_j[..] instead of the sum, and a step flagged kFlagMax
+// stores the lowest maximising x of every output cell in its argmax table (uint16, arena offset w7 / w8).
+template <int NIN, int MAXC, int CX, int LANES, bool MAX = false>
 __device__ __forceinline__ void generic_body(const uint32_t *sw, int (*sh_hoff)[kTileMax], const double *__restrict__ pool,
                                              double *__restrict__ slot, double *__restrict__ results, const int tid,
                                              const int h_begin, const int h_end) {
@@ -98,6 +100,10 @@ __device__ __forceinline__ void generic_body(const uint32_t *sw, int (*sh_hoff)[
     const int lo_cells = (int)sw[2];
     const uint64_t out_off = (uint64_t)sw[4] | ((uint64_t)sw[5] << 32);
     double *__restrict__ outp = (fin ? results : slot) + out_off;
+    uint16_t *__restrict__ amp = nullptr;
+    if constexpr (MAX) {
+        if ((sw[1] >> 16) & kFlagMax) amp = reinterpret_cast<uint16_t *>(slot + ((uint64_t)sw[7] | ((uint64_t)sw[8] << 32)));
+    }
 
     const double *inp[NIN];
     int xs[NIN];
@@ -162,7 +168,22 @@ __device__ __forceinline__ void generic_body(const uint32_t *sw, int (*sh_hoff)[
 #pragma unroll
                 for (int c = 0; c < MAXC; ++c) {
                     const int l = l0 + c * LANES;
-                    if (l < lo_cells) {
+                    if constexpr (MAX) {
+                        if (l < lo_cells) {
+                            double best = inp[0][ho[0] + lo_off[0][c]];
+#pragma unroll
+                            for (int j = 1; j < NIN; ++j) best *= inp[j][ho[j] + lo_off[j][c]];
+                            int arg = 0;
+                            for (int x = 1; x < cx; ++x) {
+                                double p = inp[0][ho[0] + lo_off[0][c] + x * xs[0]];
+#pragma unroll
+                                for (int j = 1; j < NIN; ++j) p *= inp[j][ho[j] + lo_off[j][c] + x * xs[j]];
+                                if (p > best) { best = p; arg = x; }  // (strict: ties keep the lowest x)
+                            }
+                            outp[orow + l] = best;
+                            if (amp) amp[orow + l] = (uint16_t)arg;
+                        }
+                    } else if (l < lo_cells) {
                         double acc = 0.0;
                         if (CX) {
 #pragma unroll
@@ -189,27 +210,31 @@ __device__ __forceinline__ void generic_body(const uint32_t *sw, int (*sh_hoff)[
     }
 }
 
-template <int NIN, int MAXC, int LANES>
+template <int NIN, int MAXC, int LANES, bool MAX = false>
 __device__ __forceinline__ void generic_call(const uint32_t *sw, int (*sh_hoff)[kTileMax], const double *pool, double *slot,
                                           double *results, int tid, int h_begin, int h_end) {
     const int cx = (int)(sw[1] & 0xffff);
+    if constexpr (MAX) {  // (one body for every cx: the max loop runs at run time)
+        generic_body<NIN, MAXC, 0, LANES, true>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end);
+        return;
+    }
     if (cx == 4) generic_body<NIN, MAXC, 4, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end);
     else if (cx == 2) generic_body<NIN, MAXC, 2, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end);
     else generic_body<NIN, MAXC, 0, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end);
 }
 
 // (cells per lane: the lane-varying block holds up to kLoMax = 512 cells for <= 3 inputs, kLoTarget = 256 beyond)
-template <int LANES>
+template <int LANES, bool MAX = false>
 __device__ __forceinline__ void generic_dispatch(int n_in, const uint32_t *sw, int (*sh_hoff)[kTileMax], const double *pool,
                                                  double *slot, double *results, int tid, int h_begin, int h_end) {
     constexpr int M3 = LANES == kWG ? kLoMax / kWG : 2, M6 = LANES == kWG ? kLoTarget / kWG : 1;  // cells per lane and pass
     switch (n_in) {
-        case 1: generic_call<1, M3, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
-        case 2: generic_call<2, M3, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
-        case 3: generic_call<3, M3, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
-        case 4: generic_call<4, M6, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
-        case 5: generic_call<5, M6, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
-        default: generic_call<6, M6, LANES>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
+        case 1: generic_call<1, M3, LANES, MAX>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
+        case 2: generic_call<2, M3, LANES, MAX>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
+        case 3: generic_call<3, M3, LANES, MAX>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
+        case 4: generic_call<4, M6, LANES, MAX>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
+        case 5: generic_call<5, M6, LANES, MAX>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
+        default: generic_call<6, M6, LANES, MAX>(sw, sh_hoff, pool, slot, results, tid, h_begin, h_end); break;
     }
 }
 
@@ -905,6 +930,8 @@ __device__ __forceinline__ void normalise_wave(double *__restrict__ p, int n, in
 // back, on its own.  A chain of dependent tiny steps is latency, not bandwidth, and a wave is enough for one (< 4 096 output
 // cells per step): four chains per workgroup, twelve per CU, hide four times as much of it as one.  The wave's copy of the
 // step descriptor and its offset table live in its quarter of the first 12 KB of shT (a segment has no T).
+// MAX: the steps of a max program (max_kernel.hip.h) - its FINAL step is not normalised.
+template <bool MAX = false>
 __device__ __forceinline__ void segment_wave(const LevelArgs &A, const uint32_t first, const int n_valid, double *shT, const int tid) {
     const int wave = tid >> 6, lane = tid & 63;
     if (wave >= n_valid) return;
@@ -934,8 +961,8 @@ __device__ __forceinline__ void segment_wave(const LevelArgs &A, const uint32_t 
 #pragma unroll
             for (int k = 0; k < kPre; ++k) nxt[k] = p[words + lane + 64 * k];
         }
-        generic_dispatch<64>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
-        if ((w_step[1] >> 16) & kFlagFinal) {
+        generic_dispatch<64, MAX>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
+        if (!MAX && ((w_step[1] >> 16) & kFlagFinal)) {
             const uint64_t out_off = (uint64_t)w_step[4] | ((uint64_t)w_step[5] << 32);
             lanes_sync<64>();
             normalise_wave(A.results + out_off, (int)(w_step[2] * w_step[3]), lane);
