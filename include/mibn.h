@@ -95,8 +95,16 @@ int mibn_query_batch(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *
  *   MIBN_Q_NOPRUNE   multiply every CPT instead of pruning to the ancestors of the query / evidence variables
  *                    (bayes_net.py:763-765): the semantics of full_joint_dist / predict_proba (bayes_net.py:460), where
  *                    with sparse or unnormalised CPTs a barren node does not sum to 1.
+ *   MIBN_Q_UNNORMALISED  write sum_hidden prod factors = P(q, e), the joint, instead of the posterior P(q | e) (same C-order, no
+ *                    division by the sum).  A request may then have ZERO query variables: its out slice is one cell, P(e) - the
+ *                    probability of the evidence.  Zero-probability evidence or a code of -1 gives 0; empty evidence gives 1.0
+ *                    with pruning (the relevant set is empty) and Z = the mass of the product of every CPT with MIBN_Q_NOPRUNE.
+ *                    May be combined with MIBN_Q_NOPRUNE.  Without it, zero query variables are rejected as before.  Flagged
+ *                    calls are planned by the host's workers (no device planner, no plan templates, no adaptive policy: the
+ *                    options gpu_emit / gpu_search do not change their results, and the call writes no option or policy state).
  */
 #define MIBN_Q_NOPRUNE 1
+#define MIBN_Q_UNNORMALISED 2
 int mibn_query_batch_ex(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars,
                         const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                         const int64_t *out_off, double *out);

@@ -26,6 +26,7 @@ SYMBOLS = [
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 Q_NOPRUNE = 1
+Q_UNNORMALISED = 2  # P(q, e) instead of P(q | e); zero query variables allowed: one cell, P(e) (see mibn.h)
 COMM_ID_BYTES = 128
 
 
@@ -186,7 +187,7 @@ class Engine:
         self._check(self._L.mibn_set_option(self._h, name.encode(), float(value)))
 
     def query_batch(self, q_off, q_vars, e_off, e_vars, e_codes, out_off=None, flags=0):
-        """CSR request batch -> flat float64 posteriors (+ out_off).  flags: Q_NOPRUNE (per call, see mibn.h)."""
+        """CSR request batch -> flat float64 posteriors (+ out_off).  flags: Q_NOPRUNE, Q_UNNORMALISED (per call, see mibn.h)."""
         q_off, e_off = _i64(q_off), _i64(e_off)
         q_vars, e_vars, e_codes = _i32(q_vars), _i32(e_vars), _i32(e_codes)
         B = len(q_off) - 1
@@ -244,7 +245,7 @@ class Engine:
 
     def query_fixed(self, qvars, evars, ecodes, flags=0):
         """Fixed-shape batch: qvars[B, nq], evars[B, ne], ecodes[B, ne] -> posteriors[B, cells]
-        (all requests must have the same query-table size)."""
+        (all requests must have the same query-table size).  nq = 0 (flags with Q_UNNORMALISED): one cell per request, P(e)."""
         if len(qvars) == 0:
             return np.zeros((0, 0), np.float64)
         qvars = _i32(qvars).reshape(len(qvars), -1)

@@ -977,7 +977,117 @@ class BayesNet:
         frame = pd.DataFrame(data, index=events.index, columns=names)
         return (frame, log_p) if return_log_prob else frame
 
+    # ---- evidence likelihood P(e) (an extension: sum-product elimination without normalisation, MIBN_Q_UNNORMALISED) --------
+    def _evidence_ids(self, names):
+        """Variable ids of the evidence columns `names`: unknown names raise KeyError before any engine exists; a node without a
+        CPT raises the KeyError of `query` (every CPT takes part in the normalised joint)."""
+        known = set(self._all_names())
+        for n in names:
+            if n not in known:
+                raise KeyError(n)
+        be = self.backend
+        if be.flat.missing:
+            raise KeyError(be.flat.names[min(be.flat.missing)])
+        return be, np.array([be.var_id(n) for n in names], np.int32)
+
+    @staticmethod
+    def _cpts_are_distributions(be):
+        """True when every CPT row (parent configuration) is present and sums to 1 within 1e-12: the product of the CPTs is then
+        normalised (Z = 1) and a barren node sums out to 1, so P(e) may prune to the ancestors of the evidence.  Cached per
+        backend (a backend is rebuilt when the CPTs change)."""
+        ok = getattr(be, "_cpts_normalised", None)
+        if ok is None:
+            f = be.flat
+            ok = True
+            for v in range(len(f.card)):
+                a, b = int(f.value_off[v]), int(f.value_off[v + 1])
+                rows = np.asarray(f.values[a:b], np.float64).reshape(-1, int(f.card[v]))
+                if not (np.all(f.present[a:b] == 1.0) and np.all(np.abs(rows.sum(axis=1) - 1.0) <= 1e-12)):
+                    ok = False
+                    break
+            be._cpts_normalised = ok
+        return ok
+
+    def _evidence_rows(self, be, ev_ids, codes, observed, sub_batch=32768):
+        """P(row) of every row of `codes` [n, len(ev_ids)] under the normalised joint, where observed[r, j] says whether row r
+        observes column j.  Rows are grouped by their pattern of observed columns, one engine call (no query variable,
+        Q_UNNORMALISED) per group and sub-batch.  A code of -1 gives 0.  With CPTs that are not all distributions every CPT takes
+        part (Q_NOPRUNE) and the result is divided by Z, the mass of the empty event: one more request per call."""
+        n = len(codes)
+        out = np.zeros(n, np.float64)
+        if n == 0:
+            return out
+        eng = be.engine
+        flags = _capi.Q_UNNORMALISED
+        z = 1.0
+        if not self._cpts_are_distributions(be):
+            flags |= _capi.Q_NOPRUNE
+            none = np.zeros((1, 0), np.int32)
+            z = float(eng.query_fixed(none, none, none, flags=flags)[0, 0])
+        if observed.shape[1] == 0:
+            groups = [np.arange(n)]
+        else:
+            _, inv = np.unique(observed, axis=0, return_inverse=True)
+            inv = np.asarray(inv).reshape(-1)
+            groups = [np.flatnonzero(inv == g) for g in range(int(inv.max()) + 1)]
+        for rows in groups:
+            on = np.flatnonzero(observed[rows[0]])
+            for s in range(0, len(rows), sub_batch):
+                part = rows[s:s + sub_batch]
+                out[part] = eng.query_fixed(np.zeros((len(part), 0), np.int32), np.broadcast_to(ev_ids[on], (len(part), len(on))),
+                                            codes[np.ix_(part, on)], flags=flags)[:, 0]
+        if flags & _capi.Q_NOPRUNE:
+            out = out / z if z > 0 else np.zeros(n, np.float64)
+        return out
+
+    def evidence_proba(self, X, log=False, sub_batch=32768):
+        """Probability of an observed event, P(e) = the normalised joint summed over every unobserved variable: the reference's
+        `predict_proba` "also for a partial event" (bayes_net.py:934-962), without its dense table of the observed columns.
+
+        A dict gives a float.  A DataFrame gives a float64 Series with X's index: each row is an event, NaN / None = not observed
+        in that row (the convention of `query_frame` and `mpe_frame`).  Rows are grouped by their pattern of observed columns, one
+        engine call per group (in sub-batches of `sub_batch` rows).  A label outside its domain, or an event of probability zero,
+        gives 0 (log: -inf).  Unknown column names raise KeyError before any engine work.  With `log`, natural logarithms; a
+        P(e) below the smallest double reads as 0 and its log as -inf."""
+        if isinstance(X, dict):
+            cols = list(X)
+            be, ev_ids = self._evidence_ids(cols)
+            f = be.flat
+            observed = np.array([X[c] is not None for c in cols], bool).reshape(1, len(cols))
+            codes = np.array([f.code_of(int(v), X[c]) if X[c] is not None else -1 for c, v in zip(cols, ev_ids)],
+                             np.int32).reshape(1, len(cols))
+            p = float(self._evidence_rows(be, ev_ids, codes, observed, sub_batch)[0])
+            if log:
+                return float(np.log(p)) if p > 0 else -np.inf
+            return p
+        cols = list(X.columns)
+        be, ev_ids = self._evidence_ids(cols)
+        f = be.flat
+        n = len(X)
+        codes = np.empty((n, len(cols)), np.int32)
+        observed = np.empty((n, len(cols)), bool)
+        for j, c in enumerate(cols):
+            col = X[c]
+            observed[:, j] = col.notna().to_numpy()
+            codes[:, j] = pd.Index(f.domains[ev_ids[j]]).get_indexer(col) if len(f.domains[ev_ids[j]]) else -1
+        p = self._evidence_rows(be, ev_ids, codes, observed, sub_batch)
+        if log:
+            with np.errstate(divide="ignore"):
+                p = np.log(p)
+        return pd.Series(p, index=X.index, dtype=np.float64)
+
+    def log_likelihood(self, X, sub_batch=32768) -> float:
+        """Log-likelihood of a data set: the sum over its rows of log P(row) (`evidence_proba`; NaN / None = not observed in
+        that row).  A row of probability zero makes it -inf."""
+        if isinstance(X, dict):
+            return self.evidence_proba(X, log=True, sub_batch=sub_batch)
+        return float(self.evidence_proba(X, log=True, sub_batch=sub_batch).sum())
+
     # ---- SURVEY.md section 8f rank 1: the joint and likelihoods (bayes_net.py:398-465, 934-973) -----------------
+    # cells of the observed columns' dense table from which predict_proba answers row by row through P(e): the planner builds no
+    # table of 2^31 cells or more, so the dense path cannot run there
+    PREDICT_DENSE_CELL_CAP = 2 ** 31
+
     def _all_names(self):
         names = []
         for P in self.P.values():
@@ -998,7 +1108,11 @@ class BayesNet:
         """Likelihood of one sample (dict -> float) or of the rows of a DataFrame (bayes_net.py:934-962).  The
         reference marginalises its full joint onto the observed columns; here the unobserved variables are
         eliminated on the device, which is the same table.  As in the reference, a single observed column returns
-        that column's marginal (not indexed by the rows), and a row of probability zero raises KeyError."""
+        that column's marginal (not indexed by the rows), and a row of probability zero raises KeyError.
+
+        Where the observed columns' dense table would have `PREDICT_DENSE_CELL_CAP` cells or more - beyond what the planner can
+        build (a table of 2^31 cells) - the rows are answered one by one through P(e) (`evidence_proba`) instead; the Series has
+        the same shape (same index, same name, KeyError for a row of probability zero)."""
         if isinstance(X, dict):
             return self.predict_proba(pd.DataFrame([X])).iloc[0]
         names = self._all_names()
@@ -1033,6 +1147,17 @@ class BayesNet:
         bad = np.zeros(len(X), bool)
         for c in codes:
             bad |= c < 0
+        if float(np.prod([float(c) for c in shape])) >= self.PREDICT_DENSE_CELL_CAP:
+            # (wide rows: P(row) per row, every column observed; a row the dense look-up would miss stays bad)
+            _, ev_ids = self._evidence_ids(observed)
+            cm = np.stack(codes, axis=1).astype(np.int32) if len(X) else np.zeros((0, len(ids)), np.int32)
+            vals = self._evidence_rows(be, ev_ids, np.where(bad[:, None], -1, cm).astype(np.int32), np.ones(cm.shape, bool))
+            bad |= ~(vals > 0)
+            if bad.any():
+                rows = X[observed][bad].head(5).itertuples(index=False, name=None)
+                raise KeyError(f"{[tuple(r) for r in rows]} not in index")
+            idx = pd.MultiIndex(levels=[f.dom_index[v] for v in ids], codes=codes, names=list(observed), verify_integrity=False)
+            return pd.Series(vals, index=idx, name=name)
         dense = be.marginal(observed)
         flat = np.ravel_multi_index([np.where(bad, 0, c) for c in codes], shape) if len(X) else np.zeros(0, np.int64)
         vals = dense[flat]

@@ -58,6 +58,7 @@ constexpr int kSweepStageWords = 5, kSweepSmallWords = 7;
 constexpr uint32_t kFlagSweepCanon = 16;  // stage j contracts digit k-1-j (first eliminated = slowest axis, the layout rule): the
                                           // kernel's compile-time stage geometry applies
 constexpr uint32_t kFlagMax = 32;  // GENERIC step of a max program (planner.h): max instead of sum, the argmax table at w7 / w8
+constexpr uint32_t kFlagRaw = 64;  // FINAL (GENERIC) step of a MIBN_Q_UNNORMALISED request (planner.h): the table is not normalised
 // the loop digit of a stage (the digit a lane's four fibers differ in): the highest one that is neither contracted nor -
 // the usual ctrl of a grid sweep - its lower neighbour
 MIBN_HD constexpr int sweep_loop_digit(int k, int dig) {

@@ -1413,6 +1413,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
         rq.qvars = q_vars + q_off[b];
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
+        rq.raw = (flags & MIBN_Q_UNNORMALISED) != 0;
         std::string why = validate_request(h->net, rq);
         if (why.empty()) why = "out_off does not match the query table size";
         h->err = "request " + std::to_string(b) + ": " + why;
@@ -1465,6 +1466,20 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
         const int rc_tiny = run_tiny(h, flags | (h->net.prune ? 0u : (uint32_t)MIBN_Q_NOPRUNE), B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, t_start);
         if (rc_tiny != 1) return rc_tiny;  // 1: a request does not fit the kernel (query table too large) - plan it
     }
+    // MIBN_Q_UNNORMALISED (P(q, e) / P(e) requests): planned by the host's workers with the options' base search effort - no device
+    // planner, no adaptive policy; the net's policy-tuned fields are restored on every exit
+    const bool raw = (flags & MIBN_Q_UNNORMALISED) != 0;
+    struct NetEffort {
+        Network *net = nullptr;
+        double second_above = 0, minfill_above = 0;
+        ~NetEffort() { if (net) { net->second_above = second_above; net->minfill_above = minfill_above; } }
+    } keep_effort;
+    if (raw) {
+        keep_effort.net = &h->net;
+        keep_effort.second_above = h->net.second_above;
+        keep_effort.minfill_above = h->net.minfill_above;
+        h->net.minfill_above = h->base_minfill;
+    }
     // validation (bayes_net.py:840-845) and the out-of-domain-evidence short cut
     std::vector<char> skip((size_t)B, 0);
     for (int64_t b = 0; b < B; ++b) {
@@ -1473,6 +1488,7 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
         rq.qvars = q_vars + q_off[b];
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
+        rq.raw = raw;
         if (!request_is_valid(h->net, rq)) { h->err = "request " + std::to_string(b) + ": " + validate_request(h->net, rq); return MIBN_E_ARG; }
         int64_t cells = 1;
         for (int i = 0; i < rq.nq; ++i) cells *= h->net.card[rq.qvars[i]];
@@ -1481,19 +1497,22 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
             int32_t c = e_codes[e_off[b] + i];
             if (c < 0 || c >= h->net.card[rq.evars[i]]) skip[b] = 1;  // label outside the domain -> empty posterior
         }
+        // P(e) of empty evidence with pruning: the relevant set is empty and the program's FINAL step has no input - the empty
+        // product, 1.0, which no kernel form computes: the host writes it after the download
+        if (raw && rq.nq == 0 && rq.ne == 0 && h->net.prune && !(flags & MIBN_Q_NOPRUNE)) skip[b] = 2;
     }
     ensure_pool(h);
     if (h->trace) std::fprintf(stderr, "[mibn plan] validation of %lld requests %.2f ms\n", (long long)B, now_ms() - t_start);
     double call_fixed_ms = now_ms() - t_start;  // the host's side of this call besides planning (the share rule of wave_plan_kernel)
     double call_plan_ms = 0;  // the workers' planning of the host's shares and the waits for the device planner: what the call's time to the last launch is NOT fixed cost
-    if (h->adaptive && !h->adaptive_seeded) {
+    if (h->adaptive && !h->adaptive_seeded && !raw) {
         // A rank with a handful of planning threads (8 ranks on a 16-CPU quota: 2-4 each) cannot plan a stream like C3 at the rate
         // its GPU executes it (67 / 133 k queries/s at 2 / 4 threads against 280 k): it starts with the device planner instead of
         // finding that out over several host-bound calls; the share controller gives the planning back where the host keeps up.
         h->adaptive_seeded = true;
         if (h->pool->size() <= 4 && h->order_net_ok && h->emit_net_ok && !h->gpu_emit) { h->gpu_emit = 1; h->auto_emit = true; }
     }
-    if (h->adaptive) {
+    if (h->adaptive && !raw) {
         // over the calls since the last adjustment: host planning wall time against GPU kernel time (retired launches)
         const double dp = h->total.plan_ms - h->seen_plan_ms, dk = h->total.kernel_ms - h->seen_kernel_ms;
         if (h->call_id <= 2) {  // the first calls pay one-time costs (thread pool, pinned buffers, first kernel load): not a trend
@@ -1571,16 +1590,16 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
     // order_effort >= 1 (more candidate orders, the byte model's best two both emitted): the wave planner has it, order_kernel / emit_kernel do
     // not - where the wave planner does not cover the network the host plans (never two kinds of plans in one stream)
     bool effort_ok = true;
-    if (h->net.order_effort >= 1 && (h->gpu_emit || h->gpu_search)) {
+    if (h->net.order_effort >= 1 && (h->gpu_emit || h->gpu_search) && !raw) {
         std::unique_ptr<WNet> probe(new WNet);
         effort_ok = h->wave_plan && h->net.wave_view(*probe);
     }
-    const bool emit_on = h->gpu_emit && h->order_net_ok && h->emit_net_ok && effort_ok;  // whole chunks planned on the device
+    const bool emit_on = !raw && h->gpu_emit && h->order_net_ok && h->emit_net_ok && effort_ok;  // whole chunks planned on the device
     // A rank that needs the device planner has no planning time to spare - and on the device the second emission costs more GPU time than
     // the bytes it saves give back (a two-thread rank: 243 against 273 k queries/s, profiles/r06_bh_ab.log): its calls take the extra
     // candidates only, on the host's share and on the device's alike.  (Like minfill_above below: the search effort follows the load.)
     h->net.second_above = (emit_on && !h->second_on_device) ? 1e300 : h->base_second_above;
-    const bool search_on = !emit_on && h->gpu_search && h->order_net_ok && h->net.order_effort < 1;
+    const bool search_on = !raw && !emit_on && h->gpu_search && h->order_net_ok && h->net.order_effort < 1;
     int64_t search_b0 = -1;
     bool search_done = false;
     // a short first chunk gets an idle GPU going while the host plans the first full-size one (first_chunk = 2: also when
@@ -1791,7 +1810,7 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
         }
         if (!on_device)
             plan_batch(h->net, *h->pool, st.bufs, b0, b1, q_off, q_vars, e_off, e_vars, e_codes, out_off, skip.data(), ck,
-                       (flags & MIBN_Q_NOPRUNE) != 0, orders, order_len);
+                       (flags & MIBN_Q_NOPRUNE) != 0, orders, order_len, -1, false, raw);
         if (on_device && h->gpu_emit == 2) {
             // test mode: the host plans the chunk too - programs, work items and statistics must agree exactly
             const size_t stride = h->emit_words;
@@ -2016,7 +2035,7 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
     //  the uploads and some 600 launches: counting validation and schedule alone - 7.7 ms of 20 - left a two-thread rank host-bound once order_effort 1
     //  made its planning dearer, profiles/r06_bi_share.log)
     if (call_plan_ms > 0) call_fixed_ms = std::max(call_fixed_ms, now_ms() - t_start - call_plan_ms);
-    if (B > 0) h->fixed_ms_per_req = h->fixed_ms_per_req > 0 ? 0.5 * h->fixed_ms_per_req + 0.5 * call_fixed_ms / (double)B : call_fixed_ms / (double)B;
+    if (B > 0 && !raw) h->fixed_ms_per_req = h->fixed_ms_per_req > 0 ? 0.5 * h->fixed_ms_per_req + 0.5 * call_fixed_ms / (double)B : call_fixed_ms / (double)B;
     if (h->trace) std::fprintf(stderr, "[mibn plan] call of %lld requests: %.2f ms to the last launch (plan %.2f, h2d %.2f)\n", (long long)B, now_ms() - t_start, h->stats.plan_ms, h->stats.h2d_ms);
     if (ticket) {
         mibn_ctx::Pending &pd = h->pend[slot];
@@ -2043,6 +2062,9 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
     HIP_TRY(h, hipMemcpyAsync(out + out_off[0], d_results, res_cells * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->stats.d2h_ms += now_ms() - t0;
+    if (raw)
+        for (int64_t b = 0; b < B; ++b)
+            if (skip[(size_t)b] == 2) out[out_off[b]] = 1.0;  // (the empty product, see the validation above)
     h->stats.total_ms = now_ms() - t_start;
     fold();
     return MIBN_OK;
@@ -2285,7 +2307,7 @@ extern "C" int mibn_query_batch_ex(mibn_t *h, uint32_t flags, int64_t B, const i
                                    const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                    const int64_t *out_off, double *out) {
     if (h && (h->pend[0].active || h->pend[1].active)) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
-    if (flags & ~(uint32_t)MIBN_Q_NOPRUNE) { if (h) h->err = "unknown query flag"; return MIBN_E_ARG; }
+    if (flags & ~(uint32_t)(MIBN_Q_NOPRUNE | MIBN_Q_UNNORMALISED)) { if (h) h->err = "unknown query flag"; return MIBN_E_ARG; }
     return run_batch(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, nullptr);
 }
 

@@ -286,7 +286,7 @@ void Network::set_hints(int32_t n_hints, const int32_t *priorities) {
 }
 
 bool request_is_valid(const Network &net, const Request &rq) {
-    if (rq.nq < 1) return false;
+    if (rq.nq < (rq.raw ? 0 : 1)) return false;
     uint64_t seen[kWords];  // (only the words the network uses: a batch validates 100 k requests on one thread)
     for (int k = 0; k < net.nw; ++k) seen[k] = 0;
     for (int i = 0; i < rq.nq + rq.ne; ++i) {
@@ -312,7 +312,7 @@ std::string validate_mpe_request(const Network &net, const Request &rq) {
 
 std::string validate_request(const Network &net, const Request &rq) {
     if (request_is_valid(net, rq)) return "";
-    if (rq.nq < 1) return "At least one query variable has to be specified";  // bayes_net.py:840-841
+    if (rq.nq < (rq.raw ? 0 : 1)) return "At least one query variable has to be specified";  // bayes_net.py:840-841
     Bits seen;
     for (int i = 0; i < rq.nq; ++i) {
         int v = rq.qvars[i];
@@ -798,6 +798,14 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
             *st.order = second;
         }
     }
+    if (!e && rq.raw) {
+        // the FINAL step - the program's last - keeps its table as it is: P(q, e), not normalised
+        const uint32_t *p0 = prog.data + start_words;
+        size_t off = start_words + 1, last = 0;
+        for (uint32_t s = 0; s < p0[0]; ++s) { last = off; off += prog.data[off + 6]; }
+        if (!p0[0] || !((prog.data[last + 1] >> 16) & kFlagFinal)) return "planner error: no FINAL step";
+        prog.data[last + 1] |= kFlagRaw << 16;
+    }
     st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
     st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
     return emit_error_message(e);
@@ -1072,7 +1080,7 @@ PlanCache &plan_cache(const TemplateStore *ts) {
 void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs, int64_t b0, int64_t b1,
                 const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
                 const int32_t *e_codes, const int64_t *out_off, const char *skip, BatchPlan &ck, bool no_prune,
-                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode) {
+                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode, bool raw) {
     const int64_t n = b1 - b0;
     const int T = pool.size();
     if ((int)bufs.size() < T) bufs.resize(T);
@@ -1092,7 +1100,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
     std::vector<std::string> terr(T);
     // dynamic distribution in blocks of 32 requests: request costs vary 100x and a worker may lose its core to
     // another rank's planner, a static split would wait for the slowest worker
-    TemplateStore *store = (net.plan_cache && !max_mode) ? template_store(net) : nullptr;
+    TemplateStore *store = (net.plan_cache && !max_mode && !raw) ? template_store(net) : nullptr;
     std::atomic<int64_t> next{0};
     constexpr int64_t kBlock = 32;
     const EmitNet en = net.emit_view();
@@ -1130,6 +1138,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             rq.out_off = out_off[b] - out_off[out_first >= 0 ? out_first : b0];
             rq.no_prune = no_prune;
             rq.max_mode = max_mode;
+            rq.raw = raw;
             if (orders) { rq.order = orders + (size_t)i * 128; rq.n_order = order_len[i]; }
             PlanStats st;
             // plan templates (see above): probe at the start of every window, stay on while shapes repeat

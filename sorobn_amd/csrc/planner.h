@@ -89,6 +89,7 @@ struct Request {
     int64_t out_off = 0;              // offset (doubles) into the batch result buffer
     bool no_prune = false;            // MIBN_Q_NOPRUNE: every CPT takes part (full_joint_dist / predict_proba, bayes_net.py:460)
     bool max_mode = false;            // max program (mibn_mpe_batch): max-product elimination of every non-evidence variable, nq = 0
+    bool raw = false;                 // MIBN_Q_UNNORMALISED: the FINAL step carries kFlagRaw (P(q, e), not normalised); nq = 0 allowed
     const uint8_t *order = nullptr;   // elimination order found elsewhere (the device order search), n_order entries
     int32_t n_order = -1;             // -1: search on the host
 };
@@ -190,6 +191,12 @@ struct PlanStats {
 //          per elimination step, last eliminated first:  argmax off lo, off hi, x, n_out, (output variable, stride) x n_out
 //      x* = argmax[sum_v code[v] * stride_v]: every output variable of a step is eliminated later, so the reverse walk has
 //      already decoded it.  A request whose evidence code lies outside its domain is the program "0" + a record with n_rec = 0.
+//
+//   UNNORMALISED requests (Request::raw, MIBN_Q_UNNORMALISED): the program of the same request without the flag, word for word,
+//      except that its FINAL step - always the last step, always GENERIC - carries
+//      flag RAW (kFlagRaw, w1 bit 16 + 6): the kernels write the product sum as it is, P(q, e), with no normalisation.
+//      nq = 0 is allowed: the FINAL step is one cell, P(e).  With pruning and no evidence the relevant set is empty and the FINAL
+//      step has no input at all (n_in = 0): the empty product, 1.0.  Planned by the host only, without plan templates.
 // Growable word buffer the planner appends programs to.  The engine backs it with pinned host memory
 // (so the upload is a true async DMA) and keeps it across calls; the default backing is malloc.
 struct ProgBuf {
@@ -243,7 +250,8 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
                 const uint8_t *orders = nullptr, const int32_t *order_len = nullptr,  // orders[(b - b0) * 128 ..]: device order search
                 int64_t out_first = -1,   // result offsets relative to out_off[out_first] (default: b0) - the host's share of a chunk whose
                                           // first requests the device plans
-                bool max_mode = false);   // max programs (mibn_mpe_batch; q_off all zero, no plan templates)
+                bool max_mode = false,    // max programs (mibn_mpe_batch; q_off all zero, no plan templates)
+                bool raw = false);        // MIBN_Q_UNNORMALISED requests (nq = 0 allowed, no plan templates)
 
 // Shard-balancing estimate (mibn_estimate_costs): section-8(d) bytes of the cheaper of the two sweep orders of every
 // request of a CSR batch - the byte model only, nothing is emitted.
@@ -291,7 +299,8 @@ struct Schedule {
 void build_schedule(const Network &net, const BatchPlan &bp, const std::vector<ProgBuf> &bufs, int64_t r0, int64_t r1,
                     Schedule &out);
 
-// Validate a request (unknown ids, duplicates, overlap) - bayes_net.py:840-845 and the KeyError of 770.
+// Validate a request (unknown ids, duplicates, overlap) - bayes_net.py:840-845 and the KeyError of 770.  nq = 0 is valid only with
+// Request::raw.
 std::string validate_request(const Network &net, const Request &rq);  // "" or the reference's error message
 bool request_is_valid(const Network &net, const Request &rq);          // the same checks without building a message
 std::string validate_mpe_request(const Network &net, const Request &rq);  // evidence only (unknown ids, duplicates): "" or the message

@@ -14,7 +14,8 @@
 //     same sum-product the reference evaluates by pointwise_mul / sum_out (233-256, 100-103), in a different order of
 //     additions (agreement ~1e-16),
 //   * normalises (790) and writes the dense posterior; zero-probability or out-of-domain evidence gives all zeros
-//     (the reference's empty Series).
+//     (the reference's empty Series).  MIBN_Q_UNNORMALISED: no normalisation - P(q, e) - and no query variable is allowed: one
+//     cell, P(e) (an empty relevant set is the empty product, 1).
 // Lanes of a wave run different loop counts (divergence), which is irrelevant next to the host work this removes: the
 // whole 100 k-request Asia batch is microseconds of kernel time.  Not HBM-bound: roofline n/a.
 #pragma once
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
         double *out = A.out + (A.out_off[b] - out0);
         const int qcells = (int)(A.out_off[b + 1] - A.out_off[b]);
         uint32_t qmask = 0, emask = 0, rel = 0;
-        bool valid = true, malformed = q1 <= q0;
+        bool valid = true, malformed = q1 <= q0 && !(A.flags & MIBN_Q_UNNORMALISED);  // (P(e): no query variable, one cell)
         int64_t want_cells = 1;
         for (int64_t i = q0; i < q1 && !malformed; ++i) {
             const int v = A.q_vars[i];
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
             out[qc] = acc;
             total += acc;
         }
-        if (total > 0.0)
+        if (total > 0.0 && !(A.flags & MIBN_Q_UNNORMALISED))
             for (int c = 0; c < qcells; ++c) out[c] = out[c] / total;  // posterior / posterior.sum(), bayes_net.py:790
     }
 }
