@@ -124,6 +124,32 @@ int mibn_query_batch_ex(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_o
 int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                    int32_t *codes, double *log_p);
 
+/*
+ * Expected counts (the E-step of BayesNet.fit_em): the requests run exactly as mibn_query_batch_ex(flags | MIBN_Q_UNNORMALISED) runs
+ * them (blocking, host-planned; MIBN_Q_NOPRUNE may be or-ed in), but the slices P(q_b, e_b) stay on the device, where expect_kernel
+ * (csrc/expect_kernel.hip.h) adds every request's posterior into one accumulation buffer.  With s_b = the sum of slice b = P(e_b):
+ *     acc[acc_base[b] + sum_k idx_k * acc_stride[q_off[b] + k]] += weight[b] * slice_b[idx] / s_b      (nothing when s_b == 0)
+ *     p_out[b] = s_b
+ *   acc_base[B], acc_stride[q_off[B]]   the target of request b: a base cell and one stride (cells, may be negative) per query
+ *                          variable, in q_vars order; the strides of a request must address distinct cells
+ *   weight[B] or NULL      per-request weight (NULL: 1.0)
+ *   n_acc, acc             the accumulation buffer (host, in/out): the call ADDS to what the caller passes, so sub-batches chain
+ *   p_out[B] or NULL       P(e_b) of every request; a request may have zero query variables (it only fills p_out)
+ * Bitwise repeatable: the same call gives the same acc bits on every run, whatever the scheduling and the "threads" option - no
+ * floating-point atomics; consecutive requests form slabs that one wave walks in order, slab partials are added in slab order.  The
+ * order across calls is the caller's.  Fast when the requests are laid out target-table major (a slab's targets span at most 2048
+ * cells; a request whose own targets span more takes a slower global path with the same ordering rule).
+ * Errors: the query path's; MIBN_E_ARG for a target that leaves [0, n_acc) - checked on the host from base, strides and
+ * cardinalities before anything is launched; MIBN_E_LIMIT for more than 8 query variables in a request.  mibn_last_stats /
+ * mibn_last_kernel_stats ("expect_kernel": its three launches together) describe the call; like mibn_mpe_batch it changes no option
+ * and no state a later query call reads.
+ */
+int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars,
+                      const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                      const int64_t *acc_base /*[B]*/, const int64_t *acc_stride /*[q_off[B]]*/,
+                      const double *weight /*[B] or NULL*/,
+                      int64_t n_acc, double *acc /*in/out, host*/, double *p_out /*[B] or NULL*/);
+
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {
     double alg_bytes;      /* sum over steps of 8*(sum input cells + output cells) */

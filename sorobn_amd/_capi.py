@@ -21,7 +21,7 @@ SYMBOLS = [
     "mibn_query_batch_ex", "mibn_plan_order", "mibn_estimate_costs", "mibn_device_synchronize", "mibn_gibbs_shard",
     "mibn_comm_unique_id", "mibn_comm_init", "mibn_comm_destroy", "mibn_comm_allgather_f64",
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
-    "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch",
+    "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
@@ -77,6 +77,7 @@ def lib():
         L.mibn_query_batch.argtypes = [vp, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_query_batch_ex.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_mpe_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i32p, f64p]
+        L.mibn_expect_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, i64p, f64p, C.c_int64, f64p, f64p]
         L.mibn_plan_order.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, i32p, i32p]
         L.mibn_estimate_costs.argtypes = [vp, C.c_int64, i64p, i32p, i64p, i32p, f64p]
         L.mibn_device_synchronize.argtypes = [vp]
@@ -273,6 +274,33 @@ class Engine:
         self._check(self._L.mibn_mpe_batch(self._h, B, _p(e_off, C.c_int64), _p(e_vars, C.c_int32), _p(e_codes, C.c_int32),
                                            _p(codes, C.c_int32), _p(log_p, C.c_double)))
         return codes, log_p
+
+    def expect_batch(self, q_off, q_vars, e_off, e_vars, e_codes, acc_base, acc_stride, acc, weight=None, flags=0):
+        """CSR request batch -> expected counts (mibn_expect_batch): every request's posterior P(q | e) is added into `acc` (a
+        contiguous float64 array, updated IN PLACE) at acc_base[b] + sum_k idx_k * acc_stride[q_off[b] + k]; returns p_out [B],
+        P(e_b) of every request.  A request may have no query variable (it only fills p_out).  flags: Q_NOPRUNE."""
+        q_off, e_off = _i64(q_off), _i64(e_off)
+        q_vars, e_vars, e_codes = _i32(q_vars), _i32(e_vars), _i32(e_codes)
+        acc_base, acc_stride = _i64(acc_base), _i64(acc_stride)
+        B = len(q_off) - 1
+        if not (isinstance(acc, np.ndarray) and acc.dtype == np.float64 and acc.flags.c_contiguous and acc.flags.writeable):
+            raise ValueError("acc must be a writeable C-contiguous float64 array (it is updated in place)")
+        if len(acc_base) != B or len(acc_stride) != len(q_vars):
+            raise ValueError("acc_base needs one entry per request, acc_stride one per query variable")
+        p_out = np.zeros(max(1, B), np.float64)
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.float64)
+            if len(w) != B:
+                raise ValueError("weight needs one entry per request")
+        pad32, pad64 = np.zeros(1, np.int32), np.zeros(1, np.int64)
+        acc_ = acc.reshape(-1) if acc.size else np.zeros(1, np.float64)
+        self._check(self._L.mibn_expect_batch(
+            self._h, int(flags), B, _p(q_off, C.c_int64), _p(q_vars if len(q_vars) else pad32, C.c_int32), _p(e_off, C.c_int64),
+            _p(e_vars if len(e_vars) else pad32, C.c_int32), _p(e_codes if len(e_codes) else pad32, C.c_int32),
+            _p(acc_base if B else pad64, C.c_int64), _p(acc_stride if len(acc_stride) else pad64, C.c_int64),
+            _p(w, C.c_double) if w is not None and B else None, int(acc.size), _p(acc_, C.c_double), _p(p_out, C.c_double)))
+        return p_out[:B]
 
     def mpe(self, evars, ecodes):
         """Fixed-shape batch: evars[B, ne], ecodes[B, ne] -> (codes[B, n_vars], log_p[B]), like query_fixed."""

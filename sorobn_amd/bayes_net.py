@@ -1181,6 +1181,12 @@ class BayesNet:
         from . import learning
         return learning.fit(self, X)
 
+    def fit_em(self, X: pd.DataFrame, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=32768):
+        """CPTs from rows with missing values by expectation-maximisation, expected counts on the device (an extension:
+        the reference's `fit` drops incomplete rows) - see `learning.fit_em`."""
+        from . import learning
+        return learning.fit_em(self, X, n_iter=n_iter, tol=tol, prior_count=prior_count, init=init, sub_batch=sub_batch)
+
 
 def accelerate(bn, device=None, backend_factory=None):
     """Attach the MI355X backend to an existing *reference* `sorobn.BayesNet` instance.

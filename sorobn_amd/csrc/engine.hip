@@ -27,6 +27,7 @@
 #include "sweep_kernel.hip.h"
 #include "ve_kernel.hip.h"
 #include "max_kernel.hip.h"
+#include "expect_kernel.hip.h"
 #include "wave_plan_kernel.hip.h"
 
 using namespace mibn;
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(MIBN_PLAN_WG, MIBN_EMIT_WAVES_PER_EU) void emit_ker
 constexpr int kChunkSets = 4;
 // statistics slots: the classes of work (split_kinds), the kernels of mibn_query_batch as launched (stat_name), then the two of
 // mibn_mpe_batch
-constexpr int kStatSlots = kNumKernels + 9;
+constexpr int kStatSlots = kNumKernels + 10;
 
 struct mibn_ctx {
     Network net;
@@ -365,6 +366,20 @@ struct mibn_ctx {
         size_t codes_cap = 0;
         std::vector<hipEvent_t> ev;
     } mpe;
+    // mibn_expect_batch (blocking, host-planned): while `expect` is set, a query call hands its device-resident results to expect_run
+    // instead of downloading them.  Buffers of its own; last-call statistics only (nothing a later query call reads).
+    struct Expect {
+        ExpectPlan plan;
+        const double *weight = nullptr;
+        int64_t B = 0, n_acc = 0;
+        double *acc = nullptr, *p_out = nullptr;  // host
+        char *d_meta = nullptr;
+        size_t meta_cap = 0;
+        double *d_f64 = nullptr;  // [acc | p_out | weight | slab partials]
+        size_t f64_cap = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+    } ex;
+    bool expect = false;
     // options
     double arena_gb = 200.0;  // scratch budget of all lanes together (of the 288 GB)
     hipStream_t stream2 = nullptr;  // lane 1 (lane 0 = stream)
@@ -604,6 +619,10 @@ void mibn_destroy(mibn_t *h) {
             (void)hipFree(M.d_codes);
             for (auto e : M.ev) (void)hipEventDestroy(e);
         }
+        (void)hipFree(h->ex.d_meta);
+        (void)hipFree(h->ex.d_f64);
+        for (hipEvent_t e : h->ex.ev)
+            if (e) (void)hipEventDestroy(e);
         if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
         if (h->stream2) (void)hipStreamDestroy(h->stream2);
         for (auto &la : h->aux)
@@ -842,7 +861,7 @@ void ensure_pool(mibn_ctx *h) {
 
 // name of statistics slot k: the classes of work (split_kinds), then the kernels as launched
 const char *stat_name(int k) {
-    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : "mpe_traceback_kernel"))))))));
+    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : (k == kNumKernels + 8 ? "mpe_traceback_kernel" : "expect_kernel")))))))));
 }
 
 // wait for a set's launches and book their HIP-event durations per kernel
@@ -1320,6 +1339,101 @@ int plan_on_device_collect(mibn_ctx *h, int64_t b0, int64_t n, BatchPlan &ck, do
 // Returns MIBN_OK / an error, or 1 when the batch does not fit the kernel and has to be planned.
 constexpr int64_t kTinyZeroCopyRequests = 64;  // one wave
 
+// mibn_expect_batch's device side: h->ex.plan over the results of the call in progress (device-resident, complete in stream order on the
+// main stream) -> acc and p_out on the host.  expect_kernel per slab, expect_reduce_kernel over the cells the slabs touch, expect_big_kernel
+// for the requests beyond the LDS image - in that order on the main stream: the addition order is the plan's.
+int expect_run(mibn_t *h, const double *d_results) {
+    mibn_ctx::Expect &X = h->ex;
+    const ExpectPlan &P = X.plan;
+    int rc;
+    // one metadata buffer: the 8-byte arrays first
+    std::vector<char> meta;
+    auto put = [&](const void *src, size_t bytes) {
+        const size_t o = meta.size();
+        meta.resize(o + ((bytes + 7) & ~size_t(7)));
+        if (bytes) std::memcpy(meta.data() + o, src, bytes);
+        return o;
+    };
+    const size_t o_req = put(P.req.data(), P.req.size() * sizeof(ExpectReq)), o_big = put(P.big.data(), P.big.size() * sizeof(ExpectReq));
+    const size_t o_ds = put(P.dim_stride.data(), P.dim_stride.size() * 8), o_sl = put(P.slab_lo.data(), P.slab_lo.size() * 8);
+    const size_t o_sp = put(P.slab_part.data(), P.slab_part.size() * 8), o_dc = put(P.dim_card.data(), P.dim_card.size() * 4);
+    const size_t o_sb = put(P.slab_begin.data(), P.slab_begin.size() * 4), o_sc = put(P.slab_cells.data(), P.slab_cells.size() * 4);
+    const size_t o_bb = put(P.blk_begin.data(), P.blk_begin.size() * 4), o_bs = put(P.blk_slab.data(), P.blk_slab.size() * 4);
+    if ((rc = ensure(h, X.d_meta, X.meta_cap, meta.size() + 16))) return rc;
+    const size_t nB = (size_t)X.B, nA = (size_t)X.n_acc;
+    const size_t f_acc = 0, f_p = nA, f_w = f_p + nB, f_part = f_w + (X.weight ? nB : 0);
+    if ((rc = ensure(h, X.d_f64, X.f64_cap, f_part + (size_t)P.part_cells + 2))) return rc;
+    for (hipEvent_t &e : X.ev)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    const hipStream_t S = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(X.d_meta, meta.data(), meta.size(), hipMemcpyHostToDevice, S));
+    if (nA) HIP_TRY(h, hipMemcpyAsync(X.d_f64 + f_acc, X.acc, nA * 8, hipMemcpyHostToDevice, S));
+    if (X.weight) HIP_TRY(h, hipMemcpyAsync(X.d_f64 + f_w, X.weight, nB * 8, hipMemcpyHostToDevice, S));
+    HIP_TRY(h, hipMemsetAsync(X.d_f64 + f_p, 0, nB * 8, S));
+    const size_t n_slabs = P.slab_cells.size();
+    double launches = 0;
+    HIP_TRY(h, hipEventRecord(X.ev[0], S));
+    if (n_slabs) {
+        ExpectArgs A;
+        A.results = d_results;
+        A.req = reinterpret_cast<const ExpectReq *>(X.d_meta + o_req);
+        A.dim_card = reinterpret_cast<const int32_t *>(X.d_meta + o_dc);
+        A.dim_stride = reinterpret_cast<const int64_t *>(X.d_meta + o_ds);
+        A.weight = X.weight ? X.d_f64 + f_w : nullptr;
+        A.slab_begin = reinterpret_cast<const int32_t *>(X.d_meta + o_sb);
+        A.slab_cells = reinterpret_cast<const int32_t *>(X.d_meta + o_sc);
+        A.slab_part = reinterpret_cast<const int64_t *>(X.d_meta + o_sp);
+        A.part = X.d_f64 + f_part;
+        A.p_out = X.d_f64 + f_p;
+        hipLaunchKernelGGL(expect_kernel, dim3((unsigned)n_slabs), dim3(64), 0, S, A);
+        launches += 1;
+    }
+    if (P.n_blocks) {
+        ExpectReduceArgs R;
+        R.part = X.d_f64 + f_part;
+        R.blk_begin = reinterpret_cast<const int32_t *>(X.d_meta + o_bb);
+        R.blk_slab = reinterpret_cast<const int32_t *>(X.d_meta + o_bs);
+        R.slab_lo = reinterpret_cast<const int64_t *>(X.d_meta + o_sl);
+        R.slab_cells = reinterpret_cast<const int32_t *>(X.d_meta + o_sc);
+        R.slab_part = reinterpret_cast<const int64_t *>(X.d_meta + o_sp);
+        R.acc = X.d_f64 + f_acc;
+        R.cell0 = P.cell0;
+        R.n_acc = X.n_acc;
+        hipLaunchKernelGGL(expect_reduce_kernel, dim3((unsigned)P.n_blocks), dim3(256), 0, S, R);
+        launches += 1;
+    }
+    if (!P.big.empty()) {
+        ExpectBigArgs G;
+        G.results = d_results;
+        G.req = reinterpret_cast<const ExpectReq *>(X.d_meta + o_big);
+        G.dim_card = reinterpret_cast<const int32_t *>(X.d_meta + o_dc);
+        G.dim_stride = reinterpret_cast<const int64_t *>(X.d_meta + o_ds);
+        G.weight = X.weight ? X.d_f64 + f_w : nullptr;
+        G.acc = X.d_f64 + f_acc;
+        G.p_out = X.d_f64 + f_p;
+        G.n_req = (int32_t)P.big.size();
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (X.n_acc + kExpectBigWG - 1) / kExpectBigWG));
+        hipLaunchKernelGGL(expect_big_kernel, dim3(grid), dim3(kExpectBigWG), 0, S, G);
+        launches += 1;
+    }
+    HIP_TRY(h, hipEventRecord(X.ev[1], S));
+    HIP_TRY(h, hipGetLastError());
+    if (nA) HIP_TRY(h, hipMemcpyAsync(X.acc, X.d_f64 + f_acc, nA * 8, hipMemcpyDeviceToHost, S));
+    if (X.p_out) HIP_TRY(h, hipMemcpyAsync(X.p_out, X.d_f64 + f_p, nB * 8, hipMemcpyDeviceToHost, S));
+    HIP_TRY(h, hipStreamSynchronize(S));
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, X.ev[0], X.ev[1]));
+    mibn_kernel_stat &ks = h->kstats[kNumKernels + 9];
+    if (!ks.name[0]) std::snprintf(ks.name, sizeof(ks.name), "%s", stat_name(kNumKernels + 9));
+    ks.launches += launches;
+    ks.ms += ms;
+    ks.alg_bytes += 8.0 * ((double)(P.req.size() + P.big.size()) + 2.0 * (double)P.part_cells + 2.0 * (double)nA);
+    ks.items += (double)X.B;
+    h->stats.kernel_ms += ms;
+    h->stats.n_launches += launches;
+    return MIBN_OK;
+}
+
 int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off,
              const int32_t *e_vars, const int32_t *e_codes, const int64_t *out_off, double *out, double t_start) {
     const size_t nq = (size_t)(q_off[B] - q_off[0]), ne = (size_t)(e_off[B] - e_off[0]);
@@ -1334,7 +1448,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     // request arrays from - and writes the posteriors and the bad-request flag to - the pinned, device-mapped staging buffer
     // itself.  No H2D / D2H copy, no timing events: one launch and one stream synchronisation (round 4 spent two DMAs each way
     // and two event records around a kernel of a few microseconds).  stats.kernel_ms is 0 for such a call.
-    const bool zero_copy = B <= kTinyZeroCopyRequests && h->tiny_zero_copy;
+    const bool zero_copy = B <= kTinyZeroCopyRequests && h->tiny_zero_copy && !h->expect;  // (expect_kernel reads the results on the device)
     const size_t bad_off = req_bytes, res_off = req_bytes + 16;
     const size_t bytes = res_off + (zero_copy ? res_cells * 8 : 0) + 64;
     mibn_ctx::Staging &sg = h->tiny_stage;
@@ -1399,7 +1513,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
         std::memcpy(out + out_off[0], p + res_off, res_cells * 8);
     } else {
         HIP_TRY(h, hipMemcpyAsync(p + bad_off, h->d_tiny_req + bad_off, 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(out + out_off[0], h->d_results[0], res_cells * 8, hipMemcpyDeviceToHost, h->stream));
+        if (!h->expect) HIP_TRY(h, hipMemcpyAsync(out + out_off[0], h->d_results[0], res_cells * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         std::memcpy(&bad, p + bad_off, 4);
         HIP_TRY(h, hipEventElapsedTime(&ms, st.ev[e0], st.ev[e1]));
@@ -1437,6 +1551,10 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
         ks->alg_bytes += io_bytes;
         ks->items += grid;
     }
+    if (h->expect) {
+        if ((rc = expect_run(h, h->d_results[0]))) return rc;
+        h->stats.total_ms = now_ms() - t_start;
+    }
     return MIBN_OK;
 }
 
@@ -1445,7 +1563,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
 // the host plans call s+1 while the GPU still runs call s.
 int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
               const int32_t *e_codes, const int64_t *out_off, double *out, int32_t *ticket) {
-    if (!h || B < 0 || !q_off || !e_off || !out_off || (B && !out)) return MIBN_E_ARG;
+    if (!h || B < 0 || !q_off || !e_off || !out_off || (B && !out && !h->expect)) return MIBN_E_ARG;
     if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
     if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
     const double t_start = now_ms();
@@ -2059,10 +2177,14 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
     }
     if ((rc = retire_all(h))) return rc;
     double t0 = now_ms();
-    HIP_TRY(h, hipMemcpyAsync(out + out_off[0], d_results, res_cells * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->expect) {  // mibn_expect_batch: the results stay on the device (a skipped request's slice is zero: it adds nothing)
+        if ((rc = expect_run(h, d_results))) return rc;
+    } else {
+        HIP_TRY(h, hipMemcpyAsync(out + out_off[0], d_results, res_cells * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
     h->stats.d2h_ms += now_ms() - t0;
-    if (raw)
+    if (raw && !h->expect)
         for (int64_t b = 0; b < B; ++b)
             if (skip[(size_t)b] == 2) out[out_off[b]] = 1.0;  // (the empty product, see the validation above)
     h->stats.total_ms = now_ms() - t_start;
@@ -2309,6 +2431,54 @@ extern "C" int mibn_query_batch_ex(mibn_t *h, uint32_t flags, int64_t B, const i
     if (h && (h->pend[0].active || h->pend[1].active)) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
     if (flags & ~(uint32_t)(MIBN_Q_NOPRUNE | MIBN_Q_UNNORMALISED)) { if (h) h->err = "unknown query flag"; return MIBN_E_ARG; }
     return run_batch(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, nullptr);
+}
+
+extern "C" int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off,
+                                 const int32_t *e_vars, const int32_t *e_codes, const int64_t *acc_base, const int64_t *acc_stride,
+                                 const double *weight, int64_t n_acc, double *acc, double *p_out) {
+    if (!h || B < 0 || n_acc < 0 || !q_off || !e_off || (n_acc && !acc)) return MIBN_E_ARG;
+    if (h->pend[0].active || h->pend[1].active) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if (flags & ~(uint32_t)(MIBN_Q_NOPRUNE | MIBN_Q_UNNORMALISED)) { h->err = "unknown query flag"; return MIBN_E_ARG; }
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (B >= 0x7ffffff0) { h->err = "expect: too many requests in one call"; return MIBN_E_LIMIT; }
+    flags |= MIBN_Q_UNNORMALISED;
+    // everything the targets depend on is checked here, on the host, before anything is launched: the requests themselves (the query
+    // path's validation), then base / strides / cardinalities against [0, n_acc)
+    std::vector<int64_t> out_off((size_t)B + 1, 0);
+    for (int64_t b = 0; b < B; ++b) {
+        Request rq;
+        rq.nq = (int32_t)(q_off[b + 1] - q_off[b]);
+        rq.qvars = q_vars + q_off[b];
+        rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
+        rq.evars = e_vars + e_off[b];
+        rq.raw = true;
+        if (rq.nq < 0 || rq.ne < 0 || !request_is_valid(h->net, rq)) { h->err = "request " + std::to_string(b) + ": " + (rq.nq < 0 || rq.ne < 0 ? std::string("negative count") : validate_request(h->net, rq)); return MIBN_E_ARG; }
+        if (rq.nq && (!acc_base || !acc_stride)) { h->err = "expect: acc_base / acc_stride missing"; return MIBN_E_ARG; }
+        int64_t cells = 1;
+        for (int i = 0; i < rq.nq; ++i) {
+            cells *= h->net.card[rq.qvars[i]];
+            if (cells > (int64_t(1) << 30)) { h->err = "request " + std::to_string(b) + ": query table too large"; return MIBN_E_LIMIT; }
+        }
+        out_off[(size_t)b + 1] = out_off[(size_t)b] + cells;
+    }
+    mibn_ctx::Expect &X = h->ex;
+    int rc = expect_plan(B, q_off, q_vars, h->net.card.data(), out_off.data(), acc_base, acc_stride, n_acc, X.plan, h->err);
+    if (rc != MIBN_OK) return rc;
+    X.weight = weight;
+    X.B = B;
+    X.n_acc = n_acc;
+    X.acc = acc;
+    X.p_out = p_out;
+    h->expect = true;
+    rc = run_batch(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off.data(), nullptr, nullptr);
+    h->expect = false;
+    if (rc != MIBN_OK) return rc;
+    // P(e) of empty evidence with pruning: the empty product (see the query path) - the planned kernels leave its cell zero
+    if (p_out && h->net.prune && !(flags & MIBN_Q_NOPRUNE))
+        for (int64_t b = 0; b < B; ++b)
+            if (q_off[b + 1] == q_off[b] && e_off[b + 1] == e_off[b]) p_out[b] = 1.0;
+    return MIBN_OK;
 }
 
 extern "C" int mibn_submit_batch(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *q_vars,

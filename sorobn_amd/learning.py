@@ -217,3 +217,259 @@ def chow_liu(X, root=None, device=None):
                 edges.append((u, v))
                 stack.append(v)
     return edges
+
+
+# ------------------------------------------------------------------- EM: CPTs from rows with missing values
+# An extension (the reference's fit drops every row that is incomplete in a family): expectation-maximisation with the
+# expected counts accumulated on the device (csrc/expect_kernel.hip.h, `mibn_expect_batch`).
+EM_MAX_MISSING = 8  # missing members of one family in one row = query variables of one expect request (kExpectMaxQ)
+EM_INITS = ("auto", "current", "counts", "uniform")
+
+
+def em_family_layout(scopes, card):
+    """Families back to back in one accumulation buffer: scopes[v] = variable ids of family v (node last) ->
+    (fam_off [V + 1], strides: per family the C-order strides of its members, in cells)."""
+    fam_off, strides = [0], []
+    for sc in scopes:
+        st = np.ones(len(sc), np.int64)
+        for k in range(len(sc) - 2, -1, -1):
+            st[k] = st[k + 1] * int(card[sc[k + 1]])
+        strides.append(st)
+        fam_off.append(fam_off[-1] + int(st[0]) * int(card[sc[0]]))
+    return np.asarray(fam_off, np.int64), strides
+
+
+def em_requests(codes, rows, scopes, strides, fam_off):
+    """The expect requests of the rows `rows` (indices into `codes` [n_rows, V], -1 = not observed), family-major: for
+    every family, in family order, and every row of `rows`, in their order, that misses a member of it - query = the
+    missing members (scope order), evidence = every observed column of the row (ascending id), target = the family's
+    table with the observed members' codes folded into the base.  Rows without any such family follow with one request
+    of no query variable each (it yields the row's P(e)).  Pure numpy on whole columns.
+    -> dict: q_off, q_vars, e_off, e_vars, e_codes, acc_base, acc_stride, row (the row of every request)."""
+    rows = np.asarray(rows, np.int64)
+    sub = codes[rows]
+    seen = sub >= 0
+    V = codes.shape[1]
+    ids = np.arange(V, dtype=np.int32)
+    nq, qv, qs, base, who = [], [], [], [], []
+    covered = np.zeros(len(rows), bool)
+    for v, sc in enumerate(scopes):
+        sc = np.asarray(sc, np.int64)
+        miss = ~seen[:, sc]
+        need = np.flatnonzero(miss.any(axis=1))
+        if not len(need):
+            continue
+        m = miss[need]
+        covered[need] = True
+        nq.append(m.sum(axis=1))
+        qv.append(np.broadcast_to(sc.astype(np.int32), m.shape)[m])
+        qs.append(np.broadcast_to(strides[v], m.shape)[m])
+        base.append(fam_off[v] + (np.where(m, 0, sub[need][:, sc]) * strides[v]).sum(axis=1))
+        who.append(need)
+    rest = np.flatnonzero(~covered)
+    if len(rest):
+        nq.append(np.zeros(len(rest), np.int64))
+        base.append(np.zeros(len(rest), np.int64))
+        who.append(rest)
+    who = np.concatenate(who) if who else np.zeros(0, np.int64)
+    nq = np.concatenate(nq) if nq else np.zeros(0, np.int64)
+    ev = seen[who]
+    return {
+        "q_off": np.concatenate([[0], np.cumsum(nq)]).astype(np.int64),
+        "q_vars": np.concatenate(qv).astype(np.int32) if qv else np.zeros(0, np.int32),
+        "e_off": np.concatenate([[0], np.cumsum(ev.sum(axis=1))]).astype(np.int64),
+        "e_vars": np.broadcast_to(ids, ev.shape)[ev],
+        "e_codes": sub[who][ev].astype(np.int32),
+        "acc_base": np.concatenate(base).astype(np.int64) if base else np.zeros(0, np.int64),
+        "acc_stride": np.concatenate(qs).astype(np.int64) if qs else np.zeros(0, np.int64),
+        "row": rows[who],
+    }
+
+
+def em_sub_batches(codes, scopes, sub_batch):
+    """Rows ordered pattern group by pattern group (rows with the same observed columns together, as `_evidence_rows`
+    groups them) and cut into runs of at most `sub_batch` requests (a row makes one request per family it is incomplete
+    in, at least one): list of row-index arrays."""
+    seen = codes >= 0
+    n = len(codes)
+    if n == 0:
+        return []
+    if seen.shape[1]:
+        _, inv = np.unique(seen, axis=0, return_inverse=True)
+        order = np.argsort(np.asarray(inv).reshape(-1), kind="stable")
+    else:
+        order = np.arange(n)
+    per_row = np.zeros(n, np.int64)
+    for sc in scopes:
+        per_row += ~seen[:, np.asarray(sc, np.int64)].all(axis=1)
+    cum = np.cumsum(np.maximum(per_row, 1)[order])
+    out, start, done = [], 0, 0
+    while start < n:
+        stop = int(np.searchsorted(cum, done + max(1, int(sub_batch)), side="right"))
+        stop = max(stop, start + 1)  # (a single row with more families than sub_batch still goes through)
+        out.append(order[start:stop])
+        done = int(cum[stop - 1])
+        start = stop
+    return out
+
+
+def em_mstep(counts, theta, card_node, prior_count=0.0):
+    """theta = (N + prior_count) / row sums over the node's states; a parent configuration with zero mass keeps its
+    previous row.  counts / theta: flat family tables (node fastest)."""
+    n = np.asarray(counts, np.float64).reshape(-1, int(card_node)) + float(prior_count)
+    mass = n.sum(axis=1, keepdims=True)
+    prev = np.asarray(theta, np.float64).reshape(-1, int(card_node))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        new = np.where(mass > 0, n / mass, prev)
+    return new.reshape(-1)
+
+
+def _em_series(node, parents, domains, values):
+    """Dense family table -> the CPT Series in the layout `prepare()` stores (levels [*parents, node], sorted)."""
+    if parents:
+        idx = pd.MultiIndex.from_product([*[domains[p] for p in parents], domains[node]], names=[*parents, node])
+        name = f"P({node} | {', '.join(map(str, parents))})"
+    else:
+        idx = pd.Index(domains[node], name=node)
+        name = f"P({node})"
+    return pd.Series(np.asarray(values, np.float64), index=idx, name=name)
+
+
+def _em_current(bn, nodes, observed_domains):
+    """(domains, thetas) of the net's CPTs as prepared, or a string saying why they cannot start EM: every node needs a
+    CPT over [*parents, node] with every row present and summing to 1, whose labels cover the observed ones."""
+    from .flatten import flatten
+    if not bn.P or any(n not in bn.P for n in nodes):
+        return "a node has no CPT"
+    try:
+        bn.prepare()
+        f = flatten(bn)
+    except (ValueError, KeyError, TypeError) as e:
+        return f"the CPTs do not flatten ({e})"
+    if list(f.names) != list(nodes):
+        return "the CPTs name variables outside the structure"
+    domains, thetas = {}, []
+    for v, node in enumerate(nodes):
+        if list(f.scope[v]) != [f.id[p] for p in bn.parents.get(node, [])] + [v]:
+            return f"the CPT of {node!r} is not over its parents and itself"
+        a, b = int(f.value_off[v]), int(f.value_off[v + 1])
+        rows = np.asarray(f.values[a:b], np.float64).reshape(-1, int(f.card[v]))
+        if not (np.all(f.present[a:b] == 1.0) and np.all(np.abs(rows.sum(axis=1) - 1.0) <= 1e-9)):
+            return f"the CPT of {node!r} lacks a row or has a row that does not sum to 1 (EM learns dense CPTs)"
+        dom = pd.Index(f.domains[v], name=node)
+        seen = observed_domains.get(node)
+        if seen is not None and len(seen) and (dom.get_indexer(seen) < 0).any():
+            return f"the CPT of {node!r} does not cover the labels observed in its column"
+        domains[node] = dom
+        thetas.append(rows.reshape(-1).copy())
+    return domains, thetas
+
+
+def fit_em(bn, X, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=32768):
+    """CPTs from rows with missing values (NaN / None = not observed in that row) by expectation-maximisation.
+
+    The structure is the net's.  A column's labels are the sorted labels observed in it (with `init="current"`: the
+    labels of the CPTs in place, which must cover them); a node whose column is absent from X or entirely missing is a
+    latent variable and needs CPTs in place.  Every iteration: the E-step adds, for every row and family, the posterior
+    of the family's members given everything the row observes to the family's table - families complete in a row by
+    the count kernel (once), the others as exact queries whose posteriors are accumulated on the device
+    (`Engine.expect_batch`) - then theta = (N + prior_count) / row sums; a parent configuration without mass keeps its
+    previous row.  A row may miss at most EM_MAX_MISSING members of one family.
+
+    init: "current" (bn.P as prepared), "counts" (the available-case counts of `fit` + 1 in every cell), "uniform",
+    "auto" ("current" where it applies, else "counts").  Stops after n_iter iterations or when the log-likelihood gains
+    less than tol * |ll|.  Leaves bn.em_log_likelihood_ (the observed-data log-likelihood of the parameters each E-step
+    STARTED from), bn.em_iterations_ and bn._counts (the last expected counts).  A row of probability zero under the
+    current parameters contributes no counts and makes that iteration's entry -inf."""
+    if int(n_iter) < 1:
+        raise ValueError("n_iter must be at least 1")
+    if not float(prior_count) >= 0:
+        raise ValueError("prior_count must not be negative")
+    if init not in EM_INITS:
+        raise ValueError(f"init must be one of {EM_INITS}, not {init!r}")
+    nodes = list(bn.nodes)
+    for c in X.columns:
+        if c not in nodes:
+            raise KeyError(c)
+    V, n = len(nodes), len(X)
+    vid = {node: v for v, node in enumerate(nodes)}
+    present = [node for node in nodes if node in X.columns]
+    raw, seen_dom, _ = encode_columns(X, present) if present else (np.zeros((n, 0), np.uint8), [], [])
+    observed = {node: seen_dom[j] for j, node in enumerate(present)}
+    latent = [node for node in nodes if node not in observed or not len(observed[node])]
+    current = _em_current(bn, nodes, observed) if init in ("auto", "current") else "not asked for"
+    if isinstance(current, str):
+        if init == "current":
+            raise ValueError(f"init='current': {current}")
+        if latent:
+            raise ValueError(f"{latent[0]!r} is never observed: a latent variable needs CPTs in place (init='current'; {current})")
+        domains = {node: observed[node] for node in nodes}
+        thetas = None
+    else:
+        domains, thetas = current
+    card = np.array([len(domains[node]) for node in nodes], np.int32)
+    scopes = [[vid[p] for p in bn.parents.get(node, [])] + [v] for v, node in enumerate(nodes)]
+    fam_off, strides = em_family_layout(scopes, card)
+    # codes in the final domains, -1 = not observed
+    codes = np.full((n, V), -1, np.int32)
+    for j, node in enumerate(present):
+        if not len(observed[node]):
+            continue
+        lut = np.append(domains[node].get_indexer(observed[node]), -1).astype(np.int32)  # (the NA code: one past the labels)
+        codes[:, vid[node]] = lut[raw[:, j]]
+    seen = codes >= 0
+    for v, sc in enumerate(scopes):
+        if n and int((~seen[:, sc]).sum(axis=1).max()) > EM_MAX_MISSING:
+            raise ValueError(f"a row misses more than {EM_MAX_MISSING} members of the family of {nodes[v]!r} "
+                             f"(the engine takes at most {EM_MAX_MISSING} query variables per expect request)")
+    # families complete in a row: counted once (they do not change between iterations)
+    full = [v for v in range(V) if all(nodes[u] not in latent for u in scopes[v])]
+    hard = np.zeros(int(fam_off[-1]), np.float64)
+    if n and full:
+        na = np.where(seen, codes, card[None, :]).astype(np.uint8)
+        cards_na = card + (~seen).any(axis=0)
+        if int(cards_na.max()) > 256:
+            raise ValueError("a column has 256 labels and missing values (max 256 codes)")
+        dense = count_tables_dropna(counting_engine(getattr(bn, "_device", None)), np.asfortranarray(na),
+                                    [domains[node] for node in nodes], cards_na, [tuple(scopes[v]) for v in full])
+        for v, d in zip(full, dense):
+            hard[fam_off[v]:fam_off[v + 1]] = d.reshape(-1)
+    if thetas is None:
+        if init == "uniform":
+            thetas = [np.full(int(fam_off[v + 1] - fam_off[v]), 1.0 / int(card[v])) for v in range(V)]
+        else:
+            thetas = [em_mstep(hard[fam_off[v]:fam_off[v + 1]] + 1.0, np.zeros(int(fam_off[v + 1] - fam_off[v])), card[v])
+                      for v in range(V)]
+    batches = em_sub_batches(codes, scopes, sub_batch)
+    requests = None if len(batches) > 8 else [em_requests(codes, rows, scopes, strides, fam_off) for rows in batches]
+    lls, counts = [], hard
+    for it in range(int(n_iter)):
+        bn.P = {node: _em_series(node, bn.parents.get(node, []), domains, thetas[v]) for v, node in enumerate(nodes)}
+        bn.prepare()
+        eng = bn.backend.engine
+        acc = np.zeros(int(fam_off[-1]), np.float64)
+        p_row = np.zeros(n, np.float64)
+        for k, rows in enumerate(batches):
+            rq = requests[k] if requests is not None else em_requests(codes, rows, scopes, strides, fam_off)
+            p = eng.expect_batch(rq["q_off"], rq["q_vars"], rq["e_off"], rq["e_vars"], rq["e_codes"], rq["acc_base"],
+                                 rq["acc_stride"], acc)
+            p_row[rq["row"][::-1]] = p[::-1]  # (any of a row's requests carries its P(e): the first one stays)
+        counts = acc + hard
+        dead = np.flatnonzero(~(p_row > 0))
+        if len(dead):  # rows of probability zero contribute nothing: their complete families come off again
+            for v in full:
+                sc = np.asarray(scopes[v], np.int64)
+                ok = dead[seen[dead][:, sc].all(axis=1)]
+                np.subtract.at(counts, fam_off[v] + (codes[ok][:, sc] * strides[v]).sum(axis=1), 1.0)
+        with np.errstate(divide="ignore"):
+            lls.append(float(np.log(p_row).sum()) if n else 0.0)
+        thetas = [em_mstep(counts[fam_off[v]:fam_off[v + 1]], thetas[v], card[v], prior_count) for v in range(V)]
+        if it and np.isfinite(lls[-1]) and np.isfinite(lls[-2]) and lls[-1] - lls[-2] < float(tol) * abs(lls[-1]):
+            break
+    bn.P = {node: _em_series(node, bn.parents.get(node, []), domains, thetas[v]) for v, node in enumerate(nodes)}
+    bn.prepare()
+    bn._counts = {node: _em_series(node, bn.parents.get(node, []), domains, counts[fam_off[v]:fam_off[v + 1]]).rename(None)
+                  for v, node in enumerate(nodes)}
+    bn.em_log_likelihood_ = lls
+    bn.em_iterations_ = len(lls)
+    return bn
