@@ -315,6 +315,41 @@ int mibn_count_tables(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t *
                       int64_t *counts);
 
 /*
+ * Score-based structure learning: a data set kept on the device and decomposable family scores computed there (an extension: the
+ * reference learns no structure but the Chow-Liu tree).  No network needed; a context may hold several data sets.
+ *
+ * mibn_dataset_create uploads the code matrix once (layout and limits of mibn_count_tables: row_major input is transposed on the
+ * device, cardinalities 1..256 or MIBN_E_LIMIT; a code >= card[col] is MIBN_E_ARG, MIBN_E_HIP if the allocation fails) and keeps it,
+ * with `card`, under *id.  mibn_dataset_destroy frees it; mibn_destroy frees what is left.  A destroyed or unknown id is MIBN_E_ARG.
+ *
+ * mibn_score_families: family f is scope_cols[scope_off[f] .. scope_off[f + 1]), parents first, CHILD LAST (at least the child, no
+ * column twice); scores[f] = its score of `kind` in natural logs.  With q = the product of the parents' cardinalities (1 without
+ * parents; the cardinalities are the data set's, whether or not every label combination occurs), r = card(child), N = n_rows, N_jk
+ * the count of child state k under parent configuration j and N_j = sum_k N_jk:
+ *   MIBN_SCORE_LOGLIK  LL = sum over cells with N_jk > 0 of N_jk * (ln N_jk - ln N_j)
+ *   MIBN_SCORE_BIC     LL - 0.5 * ln(max(N, 1)) * q * (r - 1)
+ *   MIBN_SCORE_AIC     LL - q * (r - 1)
+ *   MIBN_SCORE_BDEU    sum_j [lgamma(a/q) - lgamma(a/q + N_j)] + sum_jk [lgamma(a/(q r) + N_jk) - lgamma(a/(q r))], a = ess > 0
+ *   MIBN_SCORE_K2      sum_j [lgamma(r) - lgamma(r + N_j)] + sum_jk lgamma(1 + N_jk)
+ * (`ess` is read by MIBN_SCORE_BDEU only).  Empty configurations and empty cells contribute exactly 0.  The tables (at most 2^28
+ * cells each) are counted by the kernels of mibn_count_tables into a device buffer and reduced there; a call is cut into sub-batches
+ * by the cell budget of that buffer (option score_cells) - the caller sees one call.  The addition order depends on the shape of a
+ * family's table alone: the same family on the same rows gives the same bits in any call, alone or among others, through any handle.
+ * Blocking; validated on the host before anything is launched; writes no option or policy state; its kernels are booked in the
+ * last-call statistics only (entries count_kernel and score_kernel of mibn_last_kernel_stats).
+ */
+#define MIBN_SCORE_LOGLIK 0
+#define MIBN_SCORE_BIC 1
+#define MIBN_SCORE_AIC 2
+#define MIBN_SCORE_BDEU 3
+#define MIBN_SCORE_K2 4
+int mibn_dataset_create(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t *codes, int32_t row_major, const int32_t *card,
+                        int32_t *id);
+int mibn_dataset_destroy(mibn_t *h, int32_t id);
+int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off,
+                        const int32_t *scope_cols, double *scores);
+
+/*
  * Multi-GPU: one process per GPU, requests / chains sharded with no data-path collective; the
  * only communication is the final gather of the posteriors (exact path) or the sum of the histograms (Gibbs).  These
  * entry points sit directly on RCCL (librccl.so is dlopen'ed by mibn_comm_init - a single-GPU process never loads it) and

@@ -22,12 +22,14 @@ SYMBOLS = [
     "mibn_comm_unique_id", "mibn_comm_init", "mibn_comm_destroy", "mibn_comm_allgather_f64",
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
+    "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 Q_NOPRUNE = 1
 Q_UNNORMALISED = 2  # P(q, e) instead of P(q | e); zero query variables allowed: one cell, P(e) (see mibn.h)
 COMM_ID_BYTES = 128
+SCORE_KINDS = {"loglik": 0, "bic": 1, "aic": 2, "bdeu": 3, "k2": 4}  # MIBN_SCORE_*
 
 
 class MibnError(RuntimeError):
@@ -103,6 +105,9 @@ def lib():
         L.mibn_sample_probe.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.c_int32, f64p, f64p]
         L.mibn_sampling_query.argtypes = [vp, C.c_int32, C.c_int32, i32p, C.c_int32, i32p, i32p, C.c_int64, C.c_uint64, f64p, i64p]
         L.mibn_count_tables.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, i32p, C.c_int32, i64p, i32p, i64p, i64p]
+        L.mibn_dataset_create.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, i32p, i32p]
+        L.mibn_dataset_destroy.argtypes = [vp, C.c_int32]
+        L.mibn_score_families.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, i64p, i32p, f64p]
         L.mibn_last_stats.argtypes = [vp, C.POINTER(Stats)]
         L.mibn_last_kernel_stats.argtypes = [vp, C.c_int32, C.POINTER(KernelStat), C.POINTER(C.c_int32)]
         L.mibn_plan_stats.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, C.POINTER(Stats)]
@@ -129,6 +134,51 @@ def _i32(a):
 
 def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
+
+
+class Dataset:
+    """A code matrix resident on the device (mibn_dataset_create), made by `Engine.dataset`.  Closed by `close()`, by leaving its
+    `with` block, or when it is garbage collected; it keeps its engine alive until then."""
+
+    def __init__(self, engine, ds_id, n_rows, card):
+        self.engine = engine
+        self.id = ds_id
+        self.n_rows = n_rows
+        self.card = card
+
+    def score_families(self, families, kind="bic", ess=1.0):
+        """families: sequences of column indices, parents first, CHILD LAST -> float64 array of their scores (`kind` one of
+        SCORE_KINDS, `ess` the equivalent sample size of "bdeu"); one call, whatever the number of families.  After `close()`
+        the library refuses the id (MibnError, E_ARG)."""
+        if kind not in SCORE_KINDS:
+            raise ValueError(f"score must be one of {sorted(SCORE_KINDS)}, not {kind!r}")
+        families = [tuple(f) for f in families]
+        scope_off = np.concatenate([[0], np.cumsum([len(f) for f in families])]).astype(np.int64)
+        scope_cols = _i32([c for f in families for c in f]) if scope_off[-1] else np.zeros(1, np.int32)
+        scores = np.zeros(max(1, len(families)), np.float64)
+        eng = self.engine
+        eng._check(eng._L.mibn_score_families(eng._h, self.id, SCORE_KINDS[kind], float(ess), len(families), _p(scope_off, C.c_int64),
+                                              _p(scope_cols, C.c_int32), _p(scores, C.c_double)))
+        return scores[:len(families)]
+
+    def close(self):
+        eng = self.engine
+        if self.id >= 0 and eng is not None and getattr(eng, "_h", None) is not None and eng._h.value:
+            ds_id, self.id = self.id, -1
+            eng._check(eng._L.mibn_dataset_destroy(eng._h, ds_id))
+        self.id = -1
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:
@@ -518,6 +568,25 @@ class Engine:
                                                 _p(c_, C.c_int32), int(n_samples), int(seed) & (2**64 - 1),
                                                 _p(wsum, C.c_double), _p(counts, C.c_int64)))
         return wsum, counts
+
+    def dataset(self, codes, card):
+        """codes: uint8 [n_rows, n_cols] (row- or column-major, sent as it is) with codes[:, c] < card[c] -> a `Dataset` kept on
+        the device until it is closed: the rows are uploaded once, `Dataset.score_families` then moves only family lists and
+        scores."""
+        codes = np.asarray(codes, dtype=np.uint8)
+        if codes.ndim != 2:
+            raise ValueError("codes must be a [n_rows, n_cols] matrix")
+        if not (codes.flags.f_contiguous or codes.flags.c_contiguous):
+            codes = np.ascontiguousarray(codes)
+        row_major = 0 if codes.flags.f_contiguous else 1
+        n_rows, n_cols = codes.shape
+        card = _i32(card)
+        if len(card) != n_cols:
+            raise ValueError("card needs one entry per column")
+        ds_id = C.c_int32(-1)
+        self._check(self._L.mibn_dataset_create(self._h, n_rows, n_cols, codes.ctypes.data_as(C.POINTER(C.c_uint8)), row_major,
+                                                _p(card if len(card) else np.zeros(1, np.int32), C.c_int32), C.byref(ds_id)))
+        return Dataset(self, ds_id.value, n_rows, card)
 
     def count_tables(self, codes, card, tables):
         """codes: uint8 [n_rows, n_cols] (row- or column-major, sent as it is); tables: list of column-index tuples

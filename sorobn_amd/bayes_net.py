@@ -1187,6 +1187,13 @@ class BayesNet:
         from . import learning
         return learning.fit_em(self, X, n_iter=n_iter, tol=tol, prior_count=prior_count, init=init, sub_batch=sub_batch)
 
+    def score(self, X: pd.DataFrame, score="bic", ess=1.0) -> float:
+        """The structure's score on the complete rows of X: the sum of its families' "loglik", "bic", "aic", "bdeu" or "k2"
+        scores, counted and reduced on the device (an extension, see `learning.family_scores`).  With "loglik" it is the
+        log-likelihood of X under the CPTs `fit(X)` would learn."""
+        from . import learning
+        return learning.net_score(self, X, score=score, ess=ess)
+
 
 def accelerate(bn, device=None, backend_factory=None):
     """Attach the MI355X backend to an existing *reference* `sorobn.BayesNet` instance.

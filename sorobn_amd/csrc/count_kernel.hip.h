@@ -97,13 +97,22 @@ __global__ __launch_bounds__(256) void transpose_codes_kernel(const uint8_t *__r
     }
 }
 
-// host driver; returns MIBN_* code.  row_major: codes[row * n_cols + col] instead of codes[col * n_rows + row].  scope_off[n_tables + 1] / scope_cols: CSR list of the tables' columns;
-// counts_off[n_tables + 1]: offsets of the dense tables in `counts` (must equal the running product of cards).
-inline int count_run(hipStream_t stream, int64_t n_rows, int32_t n_cols, const uint8_t *codes, bool row_major, const int32_t *card, int32_t n_tables,
-                     const int64_t *scope_off, const int32_t *scope_cols, const int64_t *counts_off, int64_t *counts,
-                     std::string &err) {
-    // small tables (<= kCountLdsCells cells) are packed into LDS groups, in their original order; the others take the
-    // global-atomic kernel
+// The host side of a counting call in two halves, shared by mibn_count_tables (count_run below: upload, count, download) and
+// mibn_score_families (engine.hip: resident codes, the tables stay on the device).
+//   count_pack    validates the tables against the cardinalities and packs them: small tables (<= kCountLdsCells cells) into LDS groups,
+//                 in their original order, the others for the global-atomic kernel.  Host only; returns MIBN_* code.
+//   count_launch  the launches of a packed call: codes, metadata and the (zeroed) output buffer already on the device.
+// scope_off[n_tables + 1] / scope_cols: CSR list of the tables' columns; counts_off[n_tables + 1]: offsets of the dense tables in the
+// output (must equal the running product of cards).
+struct CountPack {
+    std::vector<int32_t> i32;  // tbl_begin | tbl_col | tbl_stride | tbl_lds | grp_begin | big_begin | big_col
+    std::vector<int64_t> i64;  // tbl_out | big_stride | big_out
+    size_t o_tb = 0, o_tc = 0, o_ts = 0, o_tl = 0, o_gb = 0, o_bb = 0, o_bc = 0, o_bs = 0, o_bo = 0;
+    int n_small = 0, n_big = 0, n_groups = 0;
+};
+
+inline int count_pack(int32_t n_cols, const int32_t *card, int32_t n_tables, const int64_t *scope_off, const int32_t *scope_cols,
+                      const int64_t *counts_off, CountPack &P, std::string &err) {
     constexpr int64_t kCountMaxCells = 1ll << 28;  // 2 GiB of int64 counts per table
     std::vector<int32_t> small, bigs;
     std::vector<int32_t> big_begin{0}, big_col;
@@ -112,6 +121,7 @@ inline int count_run(hipStream_t stream, int64_t n_rows, int32_t n_cols, const u
     for (int t = 0; t < n_tables; ++t) {
         int64_t cells = 1;
         const int64_t a = scope_off[t], b = scope_off[t + 1];
+        if (b < a) { err = "count: scope_off decreases"; return MIBN_E_ARG; }
         strides_of[(size_t)t].resize((size_t)(b - a));
         for (int64_t k = b - 1; k >= a; --k) {
             const int c = scope_cols[k];
@@ -159,69 +169,98 @@ inline int count_run(hipStream_t stream, int64_t n_rows, int32_t n_cols, const u
         }
         tbl_lds[n_small] = (int32_t)run;
     }
-    const int n_groups = (int)grp_begin.size() - 1;
+    P.n_small = n_small;
+    P.n_big = (int)bigs.size();
+    P.n_groups = (int)grp_begin.size() - 1;
+    P.i32.clear();
+    auto put = [&](const std::vector<int32_t> &a) { size_t o = P.i32.size(); P.i32.insert(P.i32.end(), a.begin(), a.end()); return o; };
+    P.o_tb = put(tbl_begin); P.o_tc = put(tbl_col); P.o_ts = put(tbl_stride); P.o_tl = put(tbl_lds); P.o_gb = put(grp_begin);
+    P.o_bb = put(big_begin); P.o_bc = put(big_col);
+    P.i64 = tbl_out;
+    P.o_bs = P.i64.size();
+    P.i64.insert(P.i64.end(), big_stride.begin(), big_stride.end());
+    P.o_bo = P.i64.size();
+    P.i64.insert(P.i64.end(), big_out.begin(), big_out.end());
+    return MIBN_OK;
+}
+
+// d_i32 / d_i64: P.i32 / P.i64 on the device; counts0: the device address of output cell 0 (the tables' offsets are the caller's
+// counts_off, so a call whose first table starts at counts_off[0] passes its buffer minus counts_off[0]); the cells are zero
+inline hipError_t count_launch(hipStream_t stream, const uint8_t *d_codes, int64_t n_rows, const CountPack &P, const int32_t *d_i32,
+                               const int64_t *d_i64, unsigned long long *counts0) {
+    if (n_rows > 0 && P.n_big > 0) {
+        CountBigArgs Bg;
+        Bg.codes = d_codes;
+        Bg.tbl_begin = d_i32 + P.o_bb;
+        Bg.tbl_col = d_i32 + P.o_bc;
+        Bg.tbl_stride = d_i64 + P.o_bs;
+        Bg.tbl_out = d_i64 + P.o_bo;
+        Bg.counts = counts0;
+        Bg.n_rows = n_rows;
+        const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows + 255) / 256, 1024));
+        hipLaunchKernelGGL(count_big_kernel, dim3(bx, (unsigned)P.n_big), dim3(256), 0, stream, Bg);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (n_rows > 0 && P.n_small > 0) {
+        CountArgs A;
+        A.codes = d_codes;
+        A.tbl_begin = d_i32 + P.o_tb;
+        A.tbl_col = d_i32 + P.o_tc;
+        A.tbl_stride = d_i32 + P.o_ts;
+        A.tbl_lds = d_i32 + P.o_tl;
+        A.tbl_out = d_i64;
+        A.grp_begin = d_i32 + P.o_gb;
+        A.counts = counts0;
+        A.n_rows = n_rows;
+        A.n_groups = P.n_groups;
+        const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows + 255) / 256, std::max(1, 256 * 8 / std::max(1, P.n_groups))));
+        hipLaunchKernelGGL(count_kernel, dim3(bx, (unsigned)P.n_groups), dim3(256), 0, stream, A);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// the code matrix on the device, column-major: row-major input is uploaded to `d_rows` (scratch of the same size, the caller's) and
+// transposed; both copies are asynchronous on `stream`
+inline hipError_t count_upload_codes(hipStream_t stream, int64_t n_rows, int32_t n_cols, const uint8_t *codes, bool row_major, uint8_t *d_codes,
+                                     uint8_t *d_rows) {
+    const size_t code_bytes = (size_t)n_rows * (size_t)n_cols;
+    if (!code_bytes) return hipSuccess;
+    hipError_t e;
+    if (!row_major) return hipMemcpyAsync(d_codes, codes, code_bytes, hipMemcpyHostToDevice, stream);
+    if ((e = hipMemcpyAsync(d_rows, codes, code_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(transpose_codes_kernel, dim3((unsigned)((n_rows + 63) / 64), (unsigned)((n_cols + 63) / 64)), dim3(256), 0, stream, d_rows,
+                       d_codes, n_rows, n_cols);
+    return hipGetLastError();
+}
+
+// mibn_count_tables' driver; returns MIBN_* code.  row_major: codes[row * n_cols + col] instead of codes[col * n_rows + row].
+inline int count_run(hipStream_t stream, int64_t n_rows, int32_t n_cols, const uint8_t *codes, bool row_major, const int32_t *card, int32_t n_tables,
+                     const int64_t *scope_off, const int32_t *scope_cols, const int64_t *counts_off, int64_t *counts,
+                     std::string &err) {
+    CountPack P;
+    const int rc = count_pack(n_cols, card, n_tables, scope_off, scope_cols, counts_off, P, err);
+    if (rc != MIBN_OK) return rc;
     const int64_t total = counts_off[n_tables] - counts_off[0];
     uint8_t *d_codes = nullptr, *d_rows = nullptr;
     int32_t *d_i32 = nullptr;
     int64_t *d_i64 = nullptr;
     unsigned long long *d_counts = nullptr;
-    std::vector<int32_t> pack;
-    auto put = [&](const std::vector<int32_t> &a) { size_t o = pack.size(); pack.insert(pack.end(), a.begin(), a.end()); return o; };
-    const size_t o_tb = put(tbl_begin), o_tc = put(tbl_col), o_ts = put(tbl_stride), o_tl = put(tbl_lds), o_gb = put(grp_begin);
-    const size_t o_bb = put(big_begin), o_bc = put(big_col);
-    std::vector<int64_t> pack64(tbl_out);
-    const size_t o_bs = pack64.size();
-    pack64.insert(pack64.end(), big_stride.begin(), big_stride.end());
-    const size_t o_bo = pack64.size();
-    pack64.insert(pack64.end(), big_out.begin(), big_out.end());
     auto fail = [&](hipError_t e) { err = std::string("count: ") + hipGetErrorString(e); hipFree(d_codes); hipFree(d_rows); hipFree(d_i32); hipFree(d_i64); hipFree(d_counts); return MIBN_E_HIP; };
     hipError_t e;
     const size_t code_bytes = (size_t)n_rows * (size_t)n_cols;
     if ((e = hipMalloc(&d_codes, std::max<size_t>(16, code_bytes))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_i32, 4 * std::max<size_t>(1, pack.size()))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_i64, 8 * std::max<size_t>(1, pack64.size()))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&d_i32, 4 * std::max<size_t>(1, P.i32.size()))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&d_i64, 8 * std::max<size_t>(1, P.i64.size()))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&d_counts, 8 * std::max<int64_t>(1, total))) != hipSuccess) return fail(e);
-    if (row_major && code_bytes) {
-        if ((e = hipMalloc(&d_rows, code_bytes)) != hipSuccess) return fail(e);
-        if ((e = hipMemcpyAsync(d_rows, codes, code_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
-        hipLaunchKernelGGL(transpose_codes_kernel, dim3((unsigned)((n_rows + 63) / 64), (unsigned)((n_cols + 63) / 64)), dim3(256), 0, stream,
-                           d_rows, d_codes, n_rows, n_cols);
-        if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    } else if ((e = hipMemcpyAsync(d_codes, codes, code_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) {
-        return fail(e);
-    }
-    if ((e = hipMemcpyAsync(d_i32, pack.data(), 4 * pack.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(d_i64, pack64.data(), 8 * pack64.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+    if (row_major && code_bytes && (e = hipMalloc(&d_rows, code_bytes)) != hipSuccess) return fail(e);
+    if ((e = count_upload_codes(stream, n_rows, n_cols, codes, row_major, d_codes, d_rows)) != hipSuccess) return fail(e);
+    if ((e = hipMemcpyAsync(d_i32, P.i32.data(), 4 * P.i32.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+    if ((e = hipMemcpyAsync(d_i64, P.i64.data(), 8 * P.i64.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
     if ((e = hipMemsetAsync(d_counts, 0, 8 * std::max<int64_t>(1, total), stream)) != hipSuccess) return fail(e);
-    CountArgs A;
-    A.codes = d_codes;
-    A.tbl_begin = d_i32 + o_tb;
-    A.tbl_col = d_i32 + o_tc;
-    A.tbl_stride = d_i32 + o_ts;
-    A.tbl_lds = d_i32 + o_tl;
-    A.tbl_out = d_i64;
-    A.grp_begin = d_i32 + o_gb;
-    A.counts = d_counts - counts_off[0];
-    A.n_rows = n_rows;
-    A.n_groups = n_groups;
-    if (n_rows > 0 && !bigs.empty()) {
-        CountBigArgs Bg;
-        Bg.codes = d_codes;
-        Bg.tbl_begin = d_i32 + o_bb;
-        Bg.tbl_col = d_i32 + o_bc;
-        Bg.tbl_stride = d_i64 + o_bs;
-        Bg.tbl_out = d_i64 + o_bo;
-        Bg.counts = d_counts - counts_off[0];
-        Bg.n_rows = n_rows;
-        const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows + 255) / 256, 1024));
-        hipLaunchKernelGGL(count_big_kernel, dim3(bx, (unsigned)bigs.size()), dim3(256), 0, stream, Bg);
-        if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    }
-    if (n_rows > 0 && n_small > 0) {
-        const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows + 255) / 256, std::max(1, 256 * 8 / std::max(1, n_groups))));
-        hipLaunchKernelGGL(count_kernel, dim3(bx, (unsigned)n_groups), dim3(256), 0, stream, A);
-        if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    }
+    if ((e = count_launch(stream, d_codes, n_rows, P, d_i32, d_i64, d_counts - counts_off[0])) != hipSuccess) return fail(e);
     std::vector<unsigned long long> host((size_t)std::max<int64_t>(1, total));
     if ((e = hipMemcpyAsync(host.data(), d_counts, 8 * (size_t)std::max<int64_t>(1, total), hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);

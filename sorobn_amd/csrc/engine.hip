@@ -22,6 +22,7 @@
 #include "gibbs_kernel.hip.h"
 #include "sample_kernel.hip.h"
 #include "count_kernel.hip.h"
+#include "score_kernel.hip.h"
 #include "planner.h"
 #include "tiny_kernel.hip.h"
 #include "sweep_kernel.hip.h"
@@ -177,8 +178,13 @@ __global__ __launch_bounds__(MIBN_PLAN_WG, MIBN_EMIT_WAVES_PER_EU) void emit_ker
 // 194-204 k with two: profiles/r02_q_chunk_sets.log), so it stays an experiment.
 constexpr int kChunkSets = 4;
 // statistics slots: the classes of work (split_kinds), the kernels of mibn_query_batch as launched (stat_name), then the two of
-// mibn_mpe_batch
-constexpr int kStatSlots = kNumKernels + 10;
+// mibn_mpe_batch, the one of mibn_expect_batch and the two phases of mibn_score_families
+constexpr int kStatSlots = kNumKernels + 12;
+// mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
+// 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
+// the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
+// beside the 288 GB of the device.  A single larger table (up to 2^28 cells) gets a sub-batch - and a buffer - of its own.
+constexpr int64_t kScoreCellBudget = int64_t(1) << 22;
 
 struct mibn_ctx {
     Network net;
@@ -380,6 +386,26 @@ struct mibn_ctx {
         hipEvent_t ev[2] = {nullptr, nullptr};
     } ex;
     bool expect = false;
+    // mibn_dataset_create / mibn_score_families: code matrices resident on the device (id = index; a destroyed entry keeps its slot, so an
+    // id is never handed out twice) and the buffers of a scoring call.  Nothing a query call reads; last-call statistics only.
+    struct Dataset {
+        uint8_t *d_codes = nullptr;  // [n_cols][n_rows]
+        int64_t n_rows = 0;
+        int32_t n_cols = 0;
+        std::vector<int32_t> card;
+        bool live = false;
+    };
+    std::vector<Dataset> datasets;
+    struct Score {
+        unsigned long long *d_counts = nullptr;
+        size_t counts_cap = 0;
+        char *d_meta = nullptr;
+        size_t meta_cap = 0;
+        double *d_f64 = nullptr;  // [scores | partials of the chunked tables]
+        size_t f64_cap = 0;
+        std::vector<hipEvent_t> ev;
+    } sc;
+    int64_t score_cells = kScoreCellBudget;  // option score_cells (test hook: forces sub-batches)
     // options
     double arena_gb = 200.0;  // scratch budget of all lanes together (of the 288 GB)
     hipStream_t stream2 = nullptr;  // lane 1 (lane 0 = stream)
@@ -621,6 +647,11 @@ void mibn_destroy(mibn_t *h) {
         }
         (void)hipFree(h->ex.d_meta);
         (void)hipFree(h->ex.d_f64);
+        for (auto &ds : h->datasets) (void)hipFree(ds.d_codes);
+        (void)hipFree(h->sc.d_counts);
+        (void)hipFree(h->sc.d_meta);
+        (void)hipFree(h->sc.d_f64);
+        for (hipEvent_t e : h->sc.ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : h->ex.ev)
             if (e) (void)hipEventDestroy(e);
         if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -703,6 +734,7 @@ int mibn_set_option(mibn_t *h, const char *name, double value) {
     else if (n == "outer") h->net.outer = value != 0;
     else if (n == "stagger") h->net.stagger = std::max(1, std::min(8, (int)value));  // groups of requests with staggered levels per chunk
     else if (n == "prune") h->net.prune = value != 0;  // 0: multiply every CPT (full_joint_dist / predict_proba semantics)  // OUTER (MFMA) form for products of two big tables  // joint elimination of two variables per pass
+    else if (n == "score_cells") h->score_cells = std::max<int64_t>(1, std::min<int64_t>(int64_t(1) << 28, (int64_t)value));  // test hook: cell budget of a sub-batch of mibn_score_families (2^28: at most 32 768 LDS groups, the grid's y limit is 65 535)
     else if (n == "small_cells") h->net.small_cells = std::max(1, std::min(kMaxT, (int)value));  // test hook: forces FIBER steps on small networks
     else { h->err = "unknown option " + n; return MIBN_E_ARG; }
     return MIBN_OK;
@@ -861,7 +893,7 @@ void ensure_pool(mibn_ctx *h) {
 
 // name of statistics slot k: the classes of work (split_kinds), then the kernels as launched
 const char *stat_name(int k) {
-    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : (k == kNumKernels + 8 ? "mpe_traceback_kernel" : "expect_kernel")))))))));
+    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : (k == kNumKernels + 8 ? "mpe_traceback_kernel" : (k == kNumKernels + 9 ? "expect_kernel" : (k == kNumKernels + 10 ? "count_kernel" : "score_kernel")))))))))));
 }
 
 // wait for a set's launches and book their HIP-event durations per kernel
@@ -2639,6 +2671,247 @@ extern "C" int mibn_count_tables(mibn_t *h, int64_t n_rows, int32_t n_cols, cons
     if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
     HIP_TRY(h, hipSetDevice(h->device));
     return count_run(h->stream, n_rows, n_cols, codes, row_major != 0, card, n_tables, scope_off, scope_cols, counts_off, counts, h->err);
+}
+
+extern "C" int mibn_dataset_create(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t *codes, int32_t row_major, const int32_t *card, int32_t *id) {
+    if (!h || !id || n_rows < 0 || n_cols < 0 || (n_rows && n_cols && !codes) || (n_cols && !card) || (row_major != 0 && row_major != 1)) return MIBN_E_ARG;
+    *id = -1;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    for (int c = 0; c < n_cols; ++c)
+        if (card[c] < 1 || card[c] > 256) { h->err = "dataset: cardinality outside 1..256"; return MIBN_E_LIMIT; }
+    // a code outside its column's domain would make the count kernels write outside a table: checked here, once
+    {
+        std::vector<uint8_t> top((size_t)n_cols, 0);
+        if (row_major) {
+            for (int64_t r = 0; r < n_rows; ++r) {
+                const uint8_t *row = codes + r * n_cols;
+                for (int c = 0; c < n_cols; ++c) top[(size_t)c] = std::max(top[(size_t)c], row[c]);
+            }
+        } else {
+            for (int c = 0; c < n_cols; ++c) {
+                const uint8_t *col = codes + (int64_t)c * n_rows;
+                uint8_t m = 0;
+                for (int64_t r = 0; r < n_rows; ++r) m = std::max(m, col[r]);
+                top[(size_t)c] = m;
+            }
+        }
+        for (int c = 0; c < n_cols; ++c)
+            if (n_rows && (int)top[(size_t)c] >= card[c]) { h->err = "dataset: column " + std::to_string(c) + " holds a code outside its cardinality"; return MIBN_E_ARG; }
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    mibn_ctx::Dataset ds;
+    const size_t code_bytes = (size_t)n_rows * (size_t)n_cols;
+    uint8_t *d_rows = nullptr;
+    hipError_t e = hipMalloc(&ds.d_codes, std::max<size_t>(16, code_bytes));
+    if (e == hipSuccess && row_major && code_bytes) e = hipMalloc(&d_rows, code_bytes);
+    if (e == hipSuccess) e = count_upload_codes(h->stream, n_rows, n_cols, codes, row_major != 0, ds.d_codes, d_rows);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_rows);
+    if (e != hipSuccess) {
+        (void)hipFree(ds.d_codes);
+        h->err = std::string("dataset: ") + hipGetErrorString(e);
+        return MIBN_E_HIP;
+    }
+    ds.n_rows = n_rows;
+    ds.n_cols = n_cols;
+    ds.card.assign(card, card + n_cols);
+    ds.live = true;
+    if (h->datasets.size() >= 0x7ffffff0u) { (void)hipFree(ds.d_codes); h->err = "dataset: too many data sets"; return MIBN_E_LIMIT; }
+    h->datasets.push_back(std::move(ds));
+    *id = (int32_t)h->datasets.size() - 1;
+    return MIBN_OK;
+}
+
+extern "C" int mibn_dataset_destroy(mibn_t *h, int32_t id) {
+    if (!h) return MIBN_E_ARG;
+    if (id < 0 || (size_t)id >= h->datasets.size() || !h->datasets[(size_t)id].live) { h->err = "dataset: unknown or destroyed id"; return MIBN_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipFree(ds.d_codes));
+    ds = mibn_ctx::Dataset{};
+    return MIBN_OK;
+}
+
+extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off, const int32_t *scope_cols,
+                                   double *scores) {
+    if (!h || n_fam < 0 || !scope_off || (n_fam && (!scope_cols || !scores))) return MIBN_E_ARG;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (h->pend[0].active || h->pend[1].active) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if (id < 0 || (size_t)id >= h->datasets.size() || !h->datasets[(size_t)id].live) { h->err = "score: unknown or destroyed data set id"; return MIBN_E_ARG; }
+    if (kind < MIBN_SCORE_LOGLIK || kind > MIBN_SCORE_K2) { h->err = "score: unknown kind"; return MIBN_E_ARG; }
+    if (kind == MIBN_SCORE_BDEU && !(ess > 0 && ess < 1e300)) { h->err = "score: bdeu needs a finite equivalent sample size above 0"; return MIBN_E_ARG; }
+    const mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
+    const double t_start = now_ms();
+    h->stats = mibn_stats{};
+    for (int k = 0; k < kStatSlots; ++k) {
+        h->kstats[k] = mibn_kernel_stat{};
+        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
+    }
+    if (n_fam == 0) return MIBN_OK;
+    // ---- everything is checked and packed on the host before anything is launched
+    std::vector<int64_t> cells_of((size_t)n_fam, 0);
+    std::vector<int32_t> fam_r((size_t)n_fam);
+    {
+        std::vector<int32_t> seen((size_t)ds.n_cols, -1);
+        for (int f = 0; f < n_fam; ++f) {
+            const int64_t a = scope_off[f], b = scope_off[f + 1];
+            if (b <= a) { h->err = "score: family " + std::to_string(f) + " is empty (the child comes last)"; return MIBN_E_ARG; }
+            int64_t cells = 1;
+            for (int64_t k = a; k < b; ++k) {
+                const int c = scope_cols[k];
+                if (c < 0 || c >= ds.n_cols) { h->err = "score: family " + std::to_string(f) + ": unknown column"; return MIBN_E_ARG; }
+                if (seen[(size_t)c] == f) { h->err = "score: family " + std::to_string(f) + " names a column twice"; return MIBN_E_ARG; }
+                seen[(size_t)c] = f;
+                cells *= ds.card[(size_t)c];
+                if (cells > (int64_t(1) << 28)) { h->err = "score: a family's table has more than " + std::to_string(int64_t(1) << 28) + " cells"; return MIBN_E_LIMIT; }
+            }
+            fam_r[(size_t)f] = ds.card[(size_t)scope_cols[b - 1]];
+            cells_of[(size_t)f] = cells;
+        }
+    }
+    // sub-batches: consecutive families while their tables fit the cell budget (a larger table goes alone)
+    struct Sub {
+        int f0 = 0, f1 = 0;
+        CountPack pack;
+        std::vector<ScoreFam> small, big;
+        std::vector<ScoreChunk> chunk;
+        std::vector<ScoreBig> big_parts;
+        int64_t cells = 0;
+        int32_t n_parts = 0;
+        size_t o_i32 = 0, o_i64 = 0, o_small = 0, o_big = 0, o_chunk = 0, o_bp = 0;  // in the metadata buffer
+    };
+    std::vector<Sub> subs;
+    int64_t max_cells = 1;
+    int32_t max_parts = 0;
+    for (int f = 0; f < n_fam;) {
+        Sub S;
+        S.f0 = f;
+        int64_t run = 0;
+        while (f < n_fam && (f == S.f0 || run + cells_of[(size_t)f] <= h->score_cells)) run += cells_of[(size_t)f++];
+        S.f1 = f;
+        S.cells = run;
+        subs.push_back(std::move(S));
+    }
+    for (Sub &S : subs) {
+        std::vector<int64_t> off((size_t)(S.f1 - S.f0) + 1, 0);  // every sub-batch starts at cell 0 of the count buffer
+        for (int f = S.f0; f < S.f1; ++f) off[(size_t)(f - S.f0) + 1] = off[(size_t)(f - S.f0)] + cells_of[(size_t)f];
+        const int rc = count_pack(ds.n_cols, ds.card.data(), S.f1 - S.f0, scope_off + S.f0, scope_cols, off.data(), S.pack, h->err);
+        if (rc != MIBN_OK) return rc;
+        for (int f = S.f0; f < S.f1; ++f) {
+            ScoreFam F;
+            F.off = off[(size_t)(f - S.f0)];
+            F.r = fam_r[(size_t)f];
+            F.q = (off[(size_t)(f - S.f0) + 1] - F.off) / F.r;
+            F.out = f;
+            if (F.q * F.r <= kScoreWaveCells) {
+                S.small.push_back(F);
+            } else {
+                const int64_t per = score_chunk_configs(F.r);
+                ScoreBig B;
+                B.part0 = S.n_parts;
+                B.n_parts = (int32_t)((F.q + per - 1) / per);
+                for (int32_t c = 0; c < B.n_parts; ++c) S.chunk.push_back(ScoreChunk{(int32_t)S.big.size(), S.n_parts + c, (int64_t)c * per});
+                S.n_parts += B.n_parts;
+                S.big.push_back(F);
+                S.big_parts.push_back(B);
+            }
+        }
+        max_cells = std::max(max_cells, S.cells);
+        max_parts = std::max(max_parts, S.n_parts);
+    }
+    std::vector<char> meta;
+    auto put = [&](const void *src, size_t bytes) {
+        const size_t o = meta.size();
+        meta.resize(o + ((bytes + 15) & ~size_t(15)));
+        if (bytes) std::memcpy(meta.data() + o, src, bytes);
+        return o;
+    };
+    for (Sub &S : subs) {
+        S.o_i64 = put(S.pack.i64.data(), S.pack.i64.size() * 8);
+        S.o_small = put(S.small.data(), S.small.size() * sizeof(ScoreFam));
+        S.o_big = put(S.big.data(), S.big.size() * sizeof(ScoreFam));
+        S.o_chunk = put(S.chunk.data(), S.chunk.size() * sizeof(ScoreChunk));
+        S.o_bp = put(S.big_parts.data(), S.big_parts.size() * sizeof(ScoreBig));
+        S.o_i32 = put(S.pack.i32.data(), S.pack.i32.size() * 4);
+    }
+    // ---- device
+    HIP_TRY(h, hipSetDevice(h->device));
+    mibn_ctx::Score &X = h->sc;
+    int rc;
+    if ((rc = ensure(h, X.d_counts, X.counts_cap, (size_t)max_cells))) return rc;
+    if ((rc = ensure(h, X.d_meta, X.meta_cap, meta.size() + 16))) return rc;
+    if ((rc = ensure(h, X.d_f64, X.f64_cap, (size_t)n_fam + (size_t)max_parts + 2))) return rc;
+    while (X.ev.size() < 3 * subs.size()) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(h, hipEventCreate(&e));
+        X.ev.push_back(e);
+    }
+    const hipStream_t S0 = h->stream;
+    double t0 = now_ms();
+    HIP_TRY(h, hipMemcpyAsync(X.d_meta, meta.data(), meta.size(), hipMemcpyHostToDevice, S0));
+    h->stats.h2d_ms += now_ms() - t0;
+    double *d_scores = X.d_f64, *d_parts = X.d_f64 + n_fam;
+    std::vector<double> count_launches(subs.size(), 0), score_launches(subs.size(), 0);
+    for (size_t s = 0; s < subs.size(); ++s) {
+        const Sub &S = subs[s];
+        // the two phases of a sub-batch follow each other on the main stream, as do the sub-batches (they share the count buffer and the
+        // partials): no host synchronisation before the scores are downloaded
+        HIP_TRY(h, hipMemsetAsync(X.d_counts, 0, 8 * (size_t)std::max<int64_t>(1, S.cells), S0));
+        HIP_TRY(h, hipEventRecord(X.ev[3 * s], S0));
+        HIP_TRY(h, count_launch(S0, ds.d_codes, ds.n_rows, S.pack, reinterpret_cast<const int32_t *>(X.d_meta + S.o_i32),
+                                reinterpret_cast<const int64_t *>(X.d_meta + S.o_i64), X.d_counts));
+        count_launches[s] = ds.n_rows > 0 ? (S.pack.n_big > 0) + (S.pack.n_small > 0) : 0;
+        HIP_TRY(h, hipEventRecord(X.ev[3 * s + 1], S0));
+        ScoreArgs A;
+        A.counts = X.d_counts;
+        A.small = reinterpret_cast<const ScoreFam *>(X.d_meta + S.o_small);
+        A.big = reinterpret_cast<const ScoreFam *>(X.d_meta + S.o_big);
+        A.chunk = reinterpret_cast<const ScoreChunk *>(X.d_meta + S.o_chunk);
+        A.big_parts = reinterpret_cast<const ScoreBig *>(X.d_meta + S.o_bp);
+        A.parts = d_parts;
+        A.scores = d_scores;
+        A.ess = ess;
+        A.n_rows = ds.n_rows;
+        A.kind = kind;
+        A.n_small = (int32_t)S.small.size();
+        A.n_big = (int32_t)S.big.size();
+        constexpr int kPerWG = kScoreWG / 64;
+        if (A.n_small) {
+            hipLaunchKernelGGL(score_kernel, dim3((unsigned)((A.n_small + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
+            score_launches[s] += 1;
+        }
+        if (A.n_big) {
+            hipLaunchKernelGGL(score_chunk_kernel, dim3((unsigned)S.chunk.size()), dim3(kScoreWG), 0, S0, A);
+            hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((A.n_big + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
+            score_launches[s] += 2;
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(X.ev[3 * s + 2], S0));
+    }
+    t0 = now_ms();
+    HIP_TRY(h, hipMemcpyAsync(scores, d_scores, (size_t)n_fam * 8, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipStreamSynchronize(S0));
+    h->stats.d2h_ms += now_ms() - t0;
+    mibn_kernel_stat &kc = h->kstats[kNumKernels + 10], &ks = h->kstats[kNumKernels + 11];
+    for (size_t s = 0; s < subs.size(); ++s) {
+        float ms_c = 0, ms_s = 0;
+        HIP_TRY(h, hipEventElapsedTime(&ms_c, X.ev[3 * s], X.ev[3 * s + 1]));
+        HIP_TRY(h, hipEventElapsedTime(&ms_s, X.ev[3 * s + 1], X.ev[3 * s + 2]));
+        const double fams = (double)(subs[s].f1 - subs[s].f0);
+        kc.launches += count_launches[s];
+        kc.ms += ms_c;
+        kc.alg_bytes += (double)ds.n_rows * (double)(scope_off[subs[s].f1] - scope_off[subs[s].f0]) + 8.0 * (double)subs[s].cells;  // codes read per family member + the tables
+        kc.items += fams;
+        ks.launches += score_launches[s];
+        ks.ms += ms_s;
+        ks.alg_bytes += 8.0 * ((double)subs[s].cells + fams + 2.0 * (double)subs[s].n_parts);
+        ks.items += fams;
+        h->stats.kernel_ms += ms_c + ms_s;
+        h->stats.n_launches += count_launches[s] + score_launches[s];
+    }
+    h->stats.total_ms = now_ms() - t_start;
+    return MIBN_OK;
 }
 
 extern "C" int mibn_plan_order(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,

@@ -7,6 +7,7 @@ by one launch of the count kernel (csrc/count_kernel.hip.h, `mibn_count_tables`)
 turned into the same pandas objects on the host.  No CPU fallback: counting needs a gfx950 device.
 """
 import itertools
+import math
 
 import numpy as np
 import pandas as pd
@@ -473,3 +474,253 @@ def fit_em(bn, X, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=3
     bn.em_log_likelihood_ = lls
     bn.em_iterations_ = len(lls)
     return bn
+
+
+# ------------------------------------------------------ score-based structure learning: greedy hill climbing
+# An extension (the reference learns no structure but the Chow-Liu tree).  The rows go to the device once
+# (`Engine.dataset`); the search below runs on the host and sends batches of families, one double per family comes back
+# (csrc/score_kernel.hip.h, `mibn_score_families`).
+SCORES = tuple(_capi.SCORE_KINDS)
+MOVES = ("add", "delete", "reverse")  # also the order in which equal gains are preferred
+
+
+def _check_score(score, ess):
+    if score not in SCORES:
+        raise ValueError(f"score must be one of {SCORES}, not {score!r}")
+    if not (float(ess) > 0 and np.isfinite(float(ess))):
+        raise ValueError("ess (the equivalent sample size of the bdeu score) must be a finite number above 0")
+
+
+def encode_complete(X, columns):
+    """`encode_columns` for complete data: a missing value in any of `columns` is an error (scores are defined on
+    complete rows; `fit_em` learns parameters from incomplete ones)."""
+    codes, domains, cards = encode_columns(X, columns)
+    for c, dom, card in zip(columns, domains, cards):
+        if card != len(dom):
+            raise ValueError(f"column {c!r} has missing values: structure scores need complete data "
+                             f"(fit_em learns the parameters of a given structure from incomplete rows)")
+    return codes, domains, cards
+
+
+def family_scores(X, families, score="bic", ess=1.0, device=None):
+    """Decomposable scores of families on the rows of X: `families` is a list of (child, parents) name pairs -> float64
+    array, one launch pair for all of them.  score: "loglik", "bic", "aic", "bdeu" (equivalent sample size `ess`) or
+    "k2", in natural logs (include/mibn.h gives the formulas)."""
+    _check_score(score, ess)
+    fams = []
+    for child, parents in families:
+        parents = [parents] if isinstance(parents, str) or not hasattr(parents, "__iter__") else list(parents)
+        for c in [child, *parents]:
+            if c not in X.columns:
+                raise ValueError(f"unknown column {c!r}")
+        if child in parents or len(set(parents)) != len(parents):
+            raise ValueError(f"the family of {child!r} names a column twice")
+        fams.append((child, parents))
+    order = list(X.columns)
+    used = sorted({c for child, parents in fams for c in [child, *parents]}, key=order.index)
+    codes, _, cards = encode_complete(X, used)
+    if not fams:
+        return np.zeros(0, np.float64)
+    pos = {c: j for j, c in enumerate(used)}
+    with counting_engine(device).dataset(codes, cards) as ds:
+        return ds.score_families([tuple(sorted(pos[p] for p in parents)) + (pos[child],) for child, parents in fams], score, ess)
+
+
+def _edge_list(edges, columns, what):
+    """(parent, child) name pairs -> index pairs, checked."""
+    pos = {c: j for j, c in enumerate(columns)}
+    out = []
+    for e in edges or ():
+        if not (isinstance(e, (tuple, list)) and len(e) == 2):
+            raise ValueError(f"{what}: {e!r} is not a (parent, child) pair")
+        u, v = e
+        for c in (u, v):
+            if c not in pos:
+                raise ValueError(f"{what}: unknown column {c!r}")
+        if u == v:
+            raise ValueError(f"{what}: {u!r} -> {v!r} is a self-loop")
+        if (pos[u], pos[v]) not in out:
+            out.append((pos[u], pos[v]))
+    return out
+
+
+class _Graph:
+    """Parent sets plus the ancestor relation, kept incrementally: anc[d, a] = a is an ancestor of d."""
+
+    def __init__(self, n, edges):
+        self.n = n
+        self.pa = [set() for _ in range(n)]
+        self.edge = np.zeros((n, n), bool)  # [child, parent]
+        self.anc = np.zeros((n, n), bool)
+        for u, v in edges:
+            if self.anc[u, v] or u == v:
+                raise ValueError("start (with the required edges) has a cycle")
+            self.add(u, v)
+
+    def add(self, u, v):
+        self.pa[v].add(u)
+        self.edge[v, u] = True
+        up = self.anc[u].copy()
+        up[u] = True
+        below = self.anc[:, v].copy()  # the descendants of v
+        below[v] = True
+        self.anc[below] |= up
+
+    def delete(self, u, v):
+        self.pa[v].discard(u)
+        self.edge[v, u] = False
+        below = self.anc[:, v].copy()
+        below[v] = True
+        todo = set(np.flatnonzero(below).tolist())
+        self.anc[below] = False
+
+        def settle(d):
+            if d in todo:
+                todo.discard(d)
+                for p in self.pa[d]:
+                    settle(p)
+                    self.anc[d] |= self.anc[p]
+                    self.anc[d, p] = True
+
+        for d in sorted(todo):
+            settle(d)
+
+    def reverse_makes_cycle(self, u, v):
+        """After u -> v is replaced by v -> u: a cycle iff u reaches v by another path."""
+        return any(self.anc[p, u] for p in self.pa[v] if p != u)
+
+
+def hill_climb(X, score="bic", ess=1.0, max_parents=3, start=None, required=(), forbidden=(), max_iter=None, epsilon=1e-4,
+               device=None, return_trace=False):
+    """Greedy hill climbing over DAGs with a decomposable score: from `start` (an edge list, e.g. `chow_liu(X)`; default the
+    empty graph) apply the legal move - add u -> v, delete u -> v, reverse u -> v - with the largest gain in score while
+    that gain exceeds `epsilon`.  Legal: the graph stays acyclic, no node gets more than `max_parents` parents, a `required`
+    edge is never removed or reversed (required edges are part of the start graph), a `forbidden` one never created.  Equal
+    gains: add before delete before reverse, then by the position of the edge's child, then of its parent, in X.columns -
+    the result is a function of the scores alone.
+
+    Returns what `BayesNet(*result)` accepts: (parent, child) tuples plus the bare names of isolated columns.  With
+    `return_trace`: (result, [(op, u, v, gain), ...] - the edge u -> v as it was before the move, for "add" the new edge -
+    and the total score of the result).
+
+    The search runs on the host; the rows are uploaded once and every iteration sends the device one batch of the families it
+    has not scored yet (scores are cached by (child, parent set): after the first sweep of n + n (n - 1) families only the one
+    or two children whose parents changed need new ones).  Complete data only.
+
+    epsilon: a design choice, not a measured quantity - far above the rounding noise of a score (~1e-9 at a million rows), far
+    below any gain that matters (one BIC parameter costs 0.5 ln N >= 0.35)."""
+    _check_score(score, ess)
+    columns = list(X.columns)
+    n = len(columns)
+    if len(set(columns)) != n:
+        raise ValueError("X has duplicate column names")
+    max_parents = int(max_parents)
+    if max_parents < 0:
+        raise ValueError("max_parents must not be negative")
+    if max_iter is not None and int(max_iter) < 0:
+        raise ValueError("max_iter must not be negative")
+    if not float(epsilon) >= 0:
+        raise ValueError("epsilon must not be negative")
+    req = _edge_list(required, columns, "required")
+    forb = _edge_list(forbidden, columns, "forbidden")
+    begin = _edge_list(start, columns, "start")
+    for e in req:
+        if e in forb:
+            raise ValueError(f"the edge {columns[e[0]]!r} -> {columns[e[1]]!r} is both required and forbidden")
+        if e not in begin:
+            begin.append(e)
+    for e in begin:
+        if e in forb:
+            raise ValueError(f"start contains the forbidden edge {columns[e[0]]!r} -> {columns[e[1]]!r}")
+    g = _Graph(n, begin)
+    for v in range(n):
+        if len(g.pa[v]) > max_parents:
+            raise ValueError(f"start gives {columns[v]!r} {len(g.pa[v])} parents (max_parents = {max_parents})")
+    codes, _, cards = encode_complete(X, columns)
+    R = np.zeros((n, n), bool)  # [child, parent]
+    F = np.zeros((n, n), bool)
+    for u, v in req:
+        R[v, u] = True
+    for u, v in forb:
+        F[v, u] = True
+    not_self = ~np.eye(n, dtype=bool)
+    cache = {}
+    trace = []
+    with counting_engine(device).dataset(codes, cards) as ds:
+
+        def ensure(keys):
+            new = [k for k in dict.fromkeys(keys) if k not in cache]
+            if new:
+                got = ds.score_families([tuple(sorted(ps)) + (c,) for c, ps in new], score, ess)
+                for k, s in zip(new, got):
+                    cache[k] = float(s)
+
+        def candidates(v):
+            """The families a move into / out of child v needs."""
+            pa = frozenset(g.pa[v])
+            keys = [(v, pa)] + [(v, pa - {p}) for p in sorted(pa)]
+            if len(pa) < max_parents:
+                keys += [(v, pa | {u}) for u in range(n) if u != v and u not in pa]
+            return keys
+
+        # delta[v, u]: what toggling the edge u -> v adds to the score of v's family (NaN: not a candidate)
+        delta = np.full((n, n), np.nan)
+
+        def refresh(children):
+            ensure([k for v in children for k in candidates(v)])
+            for v in children:
+                pa = frozenset(g.pa[v])
+                base = cache[(v, pa)]
+                delta[v, :] = np.nan
+                for p in pa:
+                    delta[v, p] = cache[(v, pa - {p})] - base
+                if len(pa) < max_parents:
+                    for u in range(n):
+                        if u != v and u not in pa:
+                            delta[v, u] = cache[(v, pa | {u})] - base
+
+        refresh(range(n))
+        it = 0
+        while max_iter is None or it < int(max_iter):
+            npar = np.array([len(p) for p in g.pa])
+            room = (npar < max_parents)[:, None]
+            E = g.edge
+            gains = []
+            add_ok = ~E & not_self & room & ~F & ~g.anc.T  # (anc.T[v, u]: v is an ancestor of u)
+            gains.append(np.where(add_ok, delta, -np.inf))
+            gains.append(np.where(E & ~R, delta, -np.inf))
+            rev = np.full((n, n), -np.inf)
+            for v, u in zip(*np.nonzero(E & ~R & ~F.T & room.T)):  # (room.T[v, u]: u can take another parent)
+                if not g.reverse_makes_cycle(u, v):
+                    rev[v, u] = delta[v, u] + delta[u, v]
+            gains.append(rev)
+            best = max(float(m.max()) if m.size else -np.inf for m in gains)
+            if not best > float(epsilon):
+                break
+            op = next(k for k, m in enumerate(gains) if m.size and float(m.max()) == best)
+            v, u = np.unravel_index(int(np.argmax(gains[op])), (n, n))  # first maximum in [child, parent] order
+            v, u = int(v), int(u)
+            if op == 0:
+                g.add(u, v)
+                changed = [v]
+            elif op == 1:
+                g.delete(u, v)
+                changed = [v]
+            else:
+                g.delete(u, v)
+                g.add(v, u)
+                changed = [v, u]
+            trace.append((MOVES[op], columns[u], columns[v], best))
+            refresh(changed)
+            it += 1
+        total = math.fsum(cache[(v, frozenset(g.pa[v]))] for v in range(n))
+    result = [(columns[u], columns[v]) for v in range(n) for u in sorted(g.pa[v])]
+    linked = {c for e in result for c in e}
+    result += [c for c in columns if c not in linked]
+    return (result, trace, total) if return_trace else result
+
+
+def net_score(bn, X, score="bic", ess=1.0):
+    """The sum of the family scores of the net's own structure on the rows of X (`BayesNet.score`)."""
+    fams = [(node, list(bn.parents.get(node, []))) for node in bn.nodes]
+    return math.fsum(family_scores(X, fams, score=score, ess=ess, device=getattr(bn, "_device", None)).tolist())
