@@ -150,6 +150,34 @@ int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off
                       const double *weight /*[B] or NULL*/,
                       int64_t n_acc, double *acc /*in/out, host*/, double *p_out /*[B] or NULL*/);
 
+/*
+ * Exact posterior sampling: independent samples of P(x | e_b) under the normalised joint, by forward filtering (one sum
+ * elimination pass per request, every table kept) and backward sampling (one walk over the kept tables per sample).
+ *   e_off[B+1], e_vars[], e_codes[]   CSR evidence, as in mibn_mpe_batch
+ *   s_off[B+1]                        request b gets s_off[b+1] - s_off[b] samples; g = s_off[b] + i is the GLOBAL ROW INDEX of its
+ *                                     i-th sample.  s_off[0] is usually 0; a caller that draws a later part of a stream (a shard, a
+ *                                     request run alone) passes the index of its first row there
+ *   codes[(s_off[B] - s_off[0]) * n_vars]   row g - s_off[0]: the label codes of sample g (evidence variables carry their code,
+ *                                     single-state variables 0)
+ *   p_e[B] or NULL                    the unnormalised mass of the evidence (the FINAL cell; P(e_b) where the CPTs are distributions)
+ *   flags                             MIBN_DRAW_PRUNE: every CPT is a complete distribution (the caller's promise) - only evidence
+ *                                     variables and their ancestors are eliminated and drawn backward, every other variable is
+ *                                     drawn forward from its CPT row, in id order, in the same kernel.  Without it every CPT takes
+ *                                     part (the rule of mibn_mpe_batch): the path of sparse or unnormalised CPTs
+ * Random stream: Philox4x32-10 keyed by `seed`, counter (g, variable id) - the convention of mibn_sample.  The codes are a function
+ * of (network, evidence, s_off, seed, flags) alone: bit for bit the same for any chunk, threads, arena budget or wave cut.
+ * A draw of x: weights w_x = prod_j phi_j in input order, total = their sum in code order, u * total against the running sum, the
+ * first x with u < acc, else the last x of positive weight - a zero-weight state is never returned.
+ * Zero mass (or a code of -1): p_e = 0 and code -1 for every non-evidence variable, as in mibn_mpe_batch.  Blocking and
+ * host-planned, chunked and cut into waves by the arena budget; it changes no option and no state a later query call reads, and
+ * books nothing into the totals.  mibn_last_stats / mibn_last_kernel_stats ("ve_sum_kernel", "posterior_draw_kernel") describe it.
+ * Errors: MIBN_E_ARG for unknown or duplicate evidence variables, a descending s_off or an unknown flag; MIBN_E_LIMIT for a
+ * variable of more than 65 536 states or a network whose sample state (256 samples x n_vars codes) does not fit the LDS.
+ */
+#define MIBN_DRAW_PRUNE 1u
+int mibn_posterior_sample_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                                const int64_t *s_off, uint64_t seed, uint32_t flags, int32_t *codes, double *p_e);
+
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {
     double alg_bytes;      /* sum over steps of 8*(sum input cells + output cells) */

@@ -22,12 +22,13 @@ SYMBOLS = [
     "mibn_comm_unique_id", "mibn_comm_init", "mibn_comm_destroy", "mibn_comm_allgather_f64",
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
-    "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families",
+    "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 Q_NOPRUNE = 1
 Q_UNNORMALISED = 2  # P(q, e) instead of P(q | e); zero query variables allowed: one cell, P(e) (see mibn.h)
+DRAW_PRUNE = 1  # mibn_posterior_sample_batch: every CPT is a complete distribution, prune to the ancestors of the evidence
 COMM_ID_BYTES = 128
 SCORE_KINDS = {"loglik": 0, "bic": 1, "aic": 2, "bdeu": 3, "k2": 4}  # MIBN_SCORE_*
 
@@ -79,6 +80,7 @@ def lib():
         L.mibn_query_batch.argtypes = [vp, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_query_batch_ex.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_mpe_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i32p, f64p]
+        L.mibn_posterior_sample_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i64p, C.c_uint64, C.c_uint32, i32p, f64p]
         L.mibn_expect_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, i64p, f64p, C.c_int64, f64p, f64p]
         L.mibn_plan_order.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, i32p, i32p]
         L.mibn_estimate_costs.argtypes = [vp, C.c_int64, i64p, i32p, i64p, i32p, f64p]
@@ -324,6 +326,37 @@ class Engine:
         self._check(self._L.mibn_mpe_batch(self._h, B, _p(e_off, C.c_int64), _p(e_vars, C.c_int32), _p(e_codes, C.c_int32),
                                            _p(codes, C.c_int32), _p(log_p, C.c_double)))
         return codes, log_p
+
+    def posterior_sample_batch(self, e_off, e_vars, e_codes, s_off, seed=0, flags=0):
+        """CSR evidence + sample offsets s_off[B + 1] -> (codes[s_off[B] - s_off[0], n_vars] int32, p_e[B] float64): exact samples of
+        P(x | e_b), row s_off[b] - s_off[0] + i the i-th sample of request b (mibn_posterior_sample_batch).  s_off[0] is the global
+        row index of the first sample (the Philox counter): 0 unless the call draws a later part of a stream.  flags: DRAW_PRUNE."""
+        n_vars = len(self.card)
+        e_off, s_off = _i64(e_off), _i64(s_off)
+        B = len(e_off) - 1
+        e_vars, e_codes = _i32(e_vars), _i32(e_codes)
+        rows = int(s_off[-1] - s_off[0]) if B else 0
+        codes = np.empty((max(0, rows), n_vars), np.int32)
+        p_e = np.empty(B, np.float64)
+        if B == 0:
+            return codes, p_e
+        e_vars_ = e_vars if len(e_vars) else np.zeros(1, np.int32)
+        e_codes_ = e_codes if len(e_codes) else np.zeros(1, np.int32)
+        codes_ = codes if codes.size else np.zeros(1, np.int32)
+        self._check(self._L.mibn_posterior_sample_batch(self._h, B, _p(e_off, C.c_int64), _p(e_vars_, C.c_int32), _p(e_codes_, C.c_int32),
+                                                        _p(s_off, C.c_int64), int(seed) & (2**64 - 1), int(flags), _p(codes_, C.c_int32),
+                                                        _p(p_e, C.c_double)))
+        return codes, p_e
+
+    def posterior_sample(self, evars, ecodes, n, seed=0, flags=0):
+        """Fixed-shape batch: evars[B, ne], ecodes[B, ne], n samples each -> (codes[B * n, n_vars], p_e[B]), like mpe."""
+        evars = _i32(evars)
+        B = len(evars)
+        evars = evars.reshape(B, -1)
+        ecodes = _i32(ecodes).reshape(B, -1)
+        e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
+        s_off = np.arange(B + 1, dtype=np.int64) * int(n)
+        return self.posterior_sample_batch(e_off, evars.reshape(-1), ecodes.reshape(-1), s_off, seed=seed, flags=flags)
 
     def expect_batch(self, q_off, q_vars, e_off, e_vars, e_codes, acc_base, acc_stride, acc, weight=None, flags=0):
         """CSR request batch -> expected counts (mibn_expect_batch): every request's posterior P(q | e) is added into `acc` (a

@@ -766,14 +766,118 @@ class BayesNet:
         return self.backend.likelihood_weighting(*query, event=event, n_iterations=n_iterations, seed=self._next_seed())
 
     def sample(self, n=1, init: dict = None, method="forward"):
-        """Forward (ancestral) samples, bayes_net.py:550-575: a Series for n == 1, else a DataFrame with sorted
-        columns; `init` forces variables to given values."""
+        """Joint samples: a Series for n == 1, else a DataFrame with sorted columns.
+
+        `method="forward"` (the reference's, bayes_net.py:550-575): forward (ancestral) sampling; `init` forces variables to given
+        values, their ancestors are still drawn from the prior.  `method="posterior"` (an extension): exact, independent samples
+        of P(x | init) under the normalised joint - `init` is evidence - by elimination and backward sampling on the device
+        (mibn_posterior_sample_batch); never a state of probability zero, also with sparse CPTs.  Evidence of probability zero
+        raises ValueError."""
+        if method == "posterior":
+            return self._posterior_sample(n, dict(init or {}))
         if method != "forward":
             raise ValueError("Unknown method, must be one of: forward")
         df = self.backend.forward_samples(max(1, n), init or {}, seed=self._next_seed())
         if n > 1:
             return df.sort_index(axis="columns")
         return df.iloc[0].rename(None)
+
+    # ---- exact posterior sampling (an extension: forward filtering, backward sampling on the device) -------------------------
+    def _draw_ids(self, names):
+        """`_mpe_ids`, with its KeyError for a node without a CPT raised before any engine exists: every variable takes part in
+        a posterior sample."""
+        for node in self.nodes:
+            if node not in self.P:
+                raise KeyError(node)
+        return self._mpe_ids(names)
+
+    def _posterior_sample(self, n, event):
+        if n < 1:
+            raise ValueError("sample: n must be at least 1")
+        be, ev = self._draw_ids(list(event))
+        f = be.flat
+        codes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
+        flags = _capi.DRAW_PRUNE if self._cpts_are_distributions(be) else 0
+        out, p_e = be.engine.posterior_sample(np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev)),
+                                              int(n), seed=self._next_seed(), flags=flags)
+        if not p_e[0] > 0:
+            raise ValueError(f"sample: the evidence of row 0 has probability zero: {event}")
+        data = {}
+        for v, name in enumerate(f.names):
+            col = self._label_table(f, v)[out[:, v]]
+            if name in event:
+                col[:] = [event[name]] * len(col)
+            data[name] = col
+        df = pd.DataFrame(data, columns=list(f.names))
+        if n > 1:
+            return df.sort_index(axis="columns")
+        return df.iloc[0].rename(None)
+
+    def sample_frame(self, events: pd.DataFrame, n=1, seed=None, sub_batch=32768, return_proba=False):
+        """`n` exact posterior samples for every row of `events`, in the convention of `mpe_frame`: the columns are evidence
+        variables, NaN / None = not observed in that row; rows are grouped by their pattern of observed columns, one engine call
+        per group (in sub-batches of `sub_batch` rows).  Returns a DataFrame of len(events) * n rows, indexed by (event index,
+        draw), one column per variable (sorted names); evidence keeps its label.  A row whose evidence has probability zero (or a
+        label outside its domain) gets None for every other variable.  `seed`: the stream of this call (default: the object's next
+        seed, as `sample`); the same seed on the same events repeats the frame.  With `return_proba`, (frame, P(evidence) of every
+        row of `events` under the normalised joint, as a numpy array)."""
+        if n < 1:
+            raise ValueError("sample_frame: n must be at least 1")
+        cols = list(events.columns)
+        be, ev_all = self._draw_ids(cols)
+        f = be.flat
+        ev_ids = np.array(ev_all, np.int32)
+        n = int(n)
+        n_ev = len(events)
+        codes = np.empty((n_ev, len(cols)), np.int32)
+        observed = np.empty((n_ev, len(cols)), bool)
+        for j, c in enumerate(cols):
+            col = events[c]
+            observed[:, j] = col.notna().to_numpy()
+            codes[:, j] = pd.Index(f.domains[ev_ids[j]]).get_indexer(col) if len(f.domains[ev_ids[j]]) else -1
+        nv = len(f.names)
+        out = np.zeros((n_ev, n, nv), np.int32)
+        mass = np.zeros(n_ev, np.float64)
+        pat = observed @ (1 << np.arange(len(cols), dtype=np.int64)) if len(cols) < 63 else None
+        groups = ([np.arange(n_ev)] if len(cols) == 0 else
+                  [np.flatnonzero(pat == p) for p in np.unique(pat)] if pat is not None else
+                  [np.array([r]) for r in range(n_ev)])
+        seed = self._next_seed() if seed is None else int(seed)
+        eng = be.engine
+        flags = _capi.DRAW_PRUNE if self._cpts_are_distributions(be) else 0
+        z = 1.0
+        done = 0
+        if return_proba and not flags:  # (CPTs that are not distributions: the mass of the empty event normalises)
+            z = float(eng.posterior_sample_batch(np.zeros(2, np.int64), [], [], np.zeros(2, np.int64), seed=seed)[1][0])
+        for rows in groups:
+            if not len(rows):
+                continue
+            on = np.flatnonzero(observed[rows[0]])
+            for s in range(0, len(rows), sub_batch):
+                part = rows[s:s + sub_batch]
+                # (global sample rows in the order the calls are made: every sample of the frame has a Philox counter of its own)
+                e_off = np.arange(len(part) + 1, dtype=np.int64) * len(on)
+                s_off = (done + np.arange(len(part) + 1, dtype=np.int64)) * n
+                got, m = eng.posterior_sample_batch(e_off, np.broadcast_to(ev_ids[on], (len(part), len(on))).reshape(-1),
+                                                    codes[np.ix_(part, on)].reshape(-1), s_off, seed=seed, flags=flags)
+                out[part] = got.reshape(len(part), n, nv)
+                mass[part] = m
+                done += len(part)
+        names = self._all_names()
+        flat_out = out.reshape(n_ev * n, nv)
+        data = {}
+        for name in names:
+            v = f.id[name]
+            col = self._label_table(f, v)[flat_out[:, v]]
+            if name in events.columns:  # evidence keeps its label (also where it lies outside the domain)
+                obs = np.repeat(events[name].notna().to_numpy(), n)
+                col[obs] = np.repeat(events[name].to_numpy(dtype=object), n)[obs]
+            data[name] = col
+        index = pd.MultiIndex.from_product([events.index, range(n)], names=[events.index.name, "draw"])
+        frame = pd.DataFrame(data, index=index, columns=names)
+        if return_proba:
+            return frame, (mass / z if z > 0 else np.zeros(n_ev, np.float64))
+        return frame
 
     # ---- public API (bayes_net.py:796-908) ------------------------------------------------------
     @staticmethod

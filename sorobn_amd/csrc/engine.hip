@@ -28,6 +28,7 @@
 #include "sweep_kernel.hip.h"
 #include "ve_kernel.hip.h"
 #include "max_kernel.hip.h"
+#include "draw_kernel.hip.h"
 #include "expect_kernel.hip.h"
 #include "wave_plan_kernel.hip.h"
 
@@ -178,8 +179,8 @@ __global__ __launch_bounds__(MIBN_PLAN_WG, MIBN_EMIT_WAVES_PER_EU) void emit_ker
 // 194-204 k with two: profiles/r02_q_chunk_sets.log), so it stays an experiment.
 constexpr int kChunkSets = 4;
 // statistics slots: the classes of work (split_kinds), the kernels of mibn_query_batch as launched (stat_name), then the two of
-// mibn_mpe_batch, the one of mibn_expect_batch and the two phases of mibn_score_families
-constexpr int kStatSlots = kNumKernels + 12;
+// mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of mibn_posterior_sample_batch
+constexpr int kStatSlots = kNumKernels + 14;
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -370,6 +371,8 @@ struct mibn_ctx {
         size_t m_cap = 0, log_p_cap = 0;
         int32_t *d_codes = nullptr;
         size_t codes_cap = 0;
+        DrawItem *d_draw_items = nullptr;  // mibn_posterior_sample_batch shares these buffers (both calls are blocking)
+        size_t draw_items_cap = 0;
         std::vector<hipEvent_t> ev;
     } mpe;
     // mibn_expect_batch (blocking, host-planned): while `expect` is set, a query call hands its device-resident results to expect_run
@@ -643,6 +646,7 @@ void mibn_destroy(mibn_t *h) {
             (void)hipFree(M.d_m);
             (void)hipFree(M.d_log_p);
             (void)hipFree(M.d_codes);
+            (void)hipFree(M.d_draw_items);
             for (auto e : M.ev) (void)hipEventDestroy(e);
         }
         (void)hipFree(h->ex.d_meta);
@@ -893,7 +897,7 @@ void ensure_pool(mibn_ctx *h) {
 
 // name of statistics slot k: the classes of work (split_kinds), then the kernels as launched
 const char *stat_name(int k) {
-    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : (k == kNumKernels + 8 ? "mpe_traceback_kernel" : (k == kNumKernels + 9 ? "expect_kernel" : (k == kNumKernels + 10 ? "count_kernel" : "score_kernel")))))))))));
+    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : (k == kNumKernels + 8 ? "mpe_traceback_kernel" : (k == kNumKernels + 9 ? "expect_kernel" : (k == kNumKernels + 10 ? "count_kernel" : (k == kNumKernels + 11 ? "score_kernel" : (k == kNumKernels + 12 ? "ve_sum_kernel" : "posterior_draw_kernel")))))))))))));
 }
 
 // wait for a set's launches and book their HIP-event durations per kernel
@@ -2440,6 +2444,287 @@ static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_
 extern "C" int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes,
                               double *log_p) {
     const int rc = run_mpe_body(h, B, e_off, e_vars, e_codes, codes, log_p);
+    if (rc != MIBN_OK && h && !h->planner_only && h->stream) {  // (nothing of the call may still run when the caller sees the error)
+        const std::string keep = h->err;
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipGetLastError();
+        h->err = keep;
+    }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- exact posterior sampling
+// mibn_posterior_sample_batch: draw programs (planner.h) planned by the workers, run level by level by ve_sum_kernel on the main
+// stream - once per request, whatever its number of samples -, then posterior_draw_kernel walks each request's draw record once
+// per sample, in launches of at most kDrawCodeWords code words whose rows are downloaded before the next one.  Chunks, waves, the
+// shared arena of lane 0 and the statistics are those of mibn_mpe_batch, whose buffers it uses (both calls are blocking).
+constexpr size_t kDrawCodeWords = size_t(64) << 20;  // 256 MB of codes on the device per draw launch
+
+static int run_draw_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, const int64_t *s_off,
+                         uint64_t seed, uint32_t flags, int32_t *codes, double *p_e) {
+    if (!h || B < 0 || !e_off || !s_off) return MIBN_E_ARG;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (flags & ~(uint32_t)MIBN_DRAW_PRUNE) { h->err = "posterior sampling: unknown flag"; return MIBN_E_ARG; }
+    for (int64_t b = 0; b < B; ++b)
+        if (s_off[b + 1] < s_off[b] || s_off[b] < 0) { h->err = "posterior sampling: s_off must be non-negative and ascending"; return MIBN_E_ARG; }
+    if (B && s_off[B] > s_off[0] && !codes) return MIBN_E_ARG;
+    const double t_start = now_ms();
+    h->stats = mibn_stats{};
+    for (int k = 0; k < kStatSlots; ++k) {
+        h->kstats[k] = mibn_kernel_stat{};
+        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
+    }
+    if (B == 0) return MIBN_OK;
+    const Network &net = h->net;
+    const int nv = net.n_vars;
+    bool wide = false;
+    for (int v = 0; v < nv; ++v) {
+        if (net.card[v] > 65536) { h->err = "posterior sampling: variable " + std::to_string(v) + " has more than 65 536 states (sample states are 16 bits)"; return MIBN_E_LIMIT; }
+        wide = wide || net.card[v] > 256;
+    }
+    const size_t lds = draw_lds_bytes(nv, wide);
+    if (lds > 150 * 1024) { h->err = "posterior sampling: network too large for the LDS-resident sample state"; return MIBN_E_LIMIT; }
+    // validation (unknown ids, duplicates) and the out-of-domain-evidence short cut
+    std::vector<char> skip((size_t)B, 0);
+    for (int64_t b = 0; b < B; ++b) {
+        Request rq;
+        rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
+        rq.evars = e_vars + e_off[b];
+        const std::string e = rq.ne < 0 ? std::string("negative evidence count") : validate_mpe_request(net, rq);
+        if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
+        for (int i = 0; i < rq.ne; ++i) {
+            const int32_t c = e_codes[e_off[b] + i];
+            if (c < 0 || c >= net.card[rq.evars[i]]) skip[(size_t)b] = 1;  // label outside the domain: zero probability
+        }
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    ensure_pool(h);
+    // an asynchronous query call may still use the arena of lane 0
+    for (hipStream_t q : {h->search_stream, h->copy_stream, h->stream, h->stream2})
+        if (q) HIP_TRY(h, hipStreamSynchronize(q));
+    for (auto &la : h->aux)
+        for (hipStream_t a : la)
+            if (a) HIP_TRY(h, hipStreamSynchronize(a));
+    mibn_ctx::Mpe &M = h->mpe;
+    if (M.bufs.size() < (size_t)h->pool->size()) M.bufs.resize((size_t)h->pool->size());
+    const hipStream_t S = h->stream;
+    std::vector<int64_t> q_off((size_t)B + 1, 0), out_off((size_t)B + 1);
+    std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: the mass of its evidence
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0])) / 8.0);
+    size_t n_ev = 0;
+    auto event = [&](size_t &idx) -> int {
+        if (n_ev == M.ev.size()) {
+            hipEvent_t e;
+            HIP_TRY(h, hipEventCreate(&e));
+            M.ev.push_back(e);
+        }
+        idx = n_ev++;
+        HIP_TRY(h, hipEventRecord(M.ev[idx], S));
+        return MIBN_OK;
+    };
+    struct Timed { int slot; size_t e0, e1; double bytes, items; };
+    std::vector<Timed> timed;
+    auto book = [&]() -> int {
+        for (const Timed &t : timed) {
+            float ms = 0;
+            HIP_TRY(h, hipEventElapsedTime(&ms, M.ev[t.e0], M.ev[t.e1]));
+            mibn_kernel_stat &ks = h->kstats[t.slot];
+            ks.launches += 1;
+            ks.ms += ms;
+            ks.alg_bytes += t.bytes;
+            ks.items += t.items;
+            h->stats.kernel_ms += ms;
+            h->stats.n_launches += 1;
+        }
+        timed.clear();
+        n_ev = 0;
+        return MIBN_OK;
+    };
+    if (lds > 64 * 1024) {
+        HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    const size_t rows_cap = std::max<size_t>(kDrawWG, kDrawCodeWords / (size_t)std::max(1, nv));
+    std::vector<double> m_init, gather;
+    std::vector<DrawItem> ditems;
+    int rc;
+    for (int64_t b0 = 0, b1 = 0; b0 < B; b0 = b1) {
+        b1 = std::min(B, b0 + std::max<int64_t>(1, h->chunk));
+        const int64_t n = b1 - b0;
+        double t0 = now_ms();
+        BatchPlan &ck = M.plan;
+        plan_batch(net, *h->pool, M.bufs, b0, b1, q_off.data(), nullptr, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck,
+                   !(flags & MIBN_DRAW_PRUNE), nullptr, nullptr, -1, false, false, true);
+        if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
+        h->stats.plan_ms += now_ms() - t0;
+        t0 = now_ms();
+        if ((rc = ensure(h, M.d_prog, M.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
+        if ((rc = ensure(h, M.d_prog_off, M.prog_off_cap, (size_t)n))) return rc;
+        if ((rc = ensure(h, M.d_m, M.m_cap, (size_t)n))) return rc;
+        size_t base = 0;
+        for (size_t t = 0; t < ck.thread_words.size(); ++t) {
+            if (ck.thread_words[t]) HIP_TRY(h, hipMemcpyAsync(M.d_prog + base, M.bufs[t].data, ck.thread_words[t] * 4, hipMemcpyHostToDevice, S));
+            base += ck.thread_words[t];
+        }
+        HIP_TRY(h, hipMemcpyAsync(M.d_prog_off, ck.prog_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
+        // a skipped request never writes its mass: zero probability.  A program without steps (pruned, no evidence) has the empty
+        // product: 1
+        m_init.assign((size_t)n, 0.0);
+        for (int64_t i = 0; i < n; ++i)
+            if (!skip[(size_t)(b0 + i)] && M.bufs[(size_t)ck.thread_of[(size_t)i]].data[ck.local_off[(size_t)i]] == 0) m_init[(size_t)i] = 1.0;
+        HIP_TRY(h, hipMemcpyAsync(M.d_m, m_init.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
+        HIP_TRY(h, hipStreamSynchronize(S));  // (m_init is rewritten by the next chunk)
+        // table bytes one sample of each request gathers (the draw kernel's "algorithmic bytes"): 8 per input and state of every entry
+        gather.assign((size_t)n, 0.0);
+        for (int64_t i = 0; i < n; ++i) {
+            const uint32_t *p = M.bufs[(size_t)ck.thread_of[(size_t)i]].data + ck.local_off[(size_t)i];
+            size_t off = 1;
+            for (uint32_t s = 0; s < p[0]; ++s) off += p[off + 6];
+            const uint32_t *rec = p + off;
+            const uint32_t n_ent = rec[0] + rec[1];
+            rec += 3 + 2 * rec[2];
+            for (uint32_t e = 0; e < n_ent; ++e) {
+                const uint32_t cx = rec[1], n_in = rec[2];
+                rec += 3;
+                for (uint32_t j = 0; j < n_in; ++j) rec += 4 + 2 * rec[3];
+                gather[(size_t)i] += 8.0 * (double)cx * (double)n_in;
+            }
+        }
+        h->stats.h2d_ms += now_ms() - t0;
+        // waves: consecutive requests whose arenas (every table is kept) fit the budget together
+        for (int64_t r0 = 0; r0 < n;) {
+            int64_t r1 = r0, cells = 0;
+            while (r1 < n) {
+                const int64_t need = (ck.arena_need[(size_t)r1] + 15) & ~int64_t(15);
+                if (r1 > r0 && cells + need > budget_cells) break;
+                cells += need;
+                ++r1;
+            }
+            if (cells > budget_cells) { h->err = "a request needs " + std::to_string(8.0 * cells / 1e9) + " GB of scratch, above the arena budget"; return MIBN_E_NOMEM; }
+            t0 = now_ms();
+            Schedule &sc = M.sched;
+            build_schedule(net, ck, M.bufs, r0, r1, sc);
+            h->stats.plan_ms += now_ms() - t0;
+            const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
+            if (need_bytes > h->arena_bytes[0]) {
+                HIP_TRY(h, hipStreamSynchronize(S));
+                if (h->d_arena[0]) { HIP_TRY(h, hipFree(h->d_arena[0])); h->d_arena[0] = nullptr; h->arena_bytes[0] = 0; }
+                const size_t want = std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3));
+                HIP_TRY(h, hipMalloc(&h->d_arena[0], want));
+                h->arena_bytes[0] = want;
+            }
+            t0 = now_ms();
+            if ((rc = ensure(h, M.d_arena_off, M.arena_off_cap, (size_t)(r1 - r0)))) return rc;
+            if ((rc = ensure(h, M.d_items, M.items_cap, std::max<size_t>(1, sc.items.size())))) return rc;
+            if ((rc = ensure(h, M.d_wg_item, M.wg_item_cap, std::max<size_t>(1, sc.wg_item.size())))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(M.d_arena_off, sc.arena_off.data(), (size_t)(r1 - r0) * 8, hipMemcpyHostToDevice, S));
+            if (!sc.items.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_items, sc.items.data(), sc.items.size() * sizeof(Item), hipMemcpyHostToDevice, S));
+            if (!sc.wg_item.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_wg_item, sc.wg_item.data(), sc.wg_item.size() * sizeof(uint32_t), hipMemcpyHostToDevice, S));
+            h->stats.h2d_ms += now_ms() - t0;
+            LevelArgs A;
+            A.prog = M.d_prog;
+            A.prog_off = M.d_prog_off + r0;
+            A.arena_off = M.d_arena_off;
+            A.pool = h->d_pool;
+            A.arena = h->d_arena[0];
+            A.results = M.d_m;  // (FINAL offsets are chunk-relative: request b's mass at b - b0)
+            A.items = M.d_items;
+            // one launch per level: every class of work of a draw schedule (segments, GENERIC tiles) is ve_sum_kernel's
+            for (size_t li = 0; li < sc.launches.size();) {
+                size_t lj = li + 1;
+                double bytes = sc.launches[li].alg_bytes;
+                size_t grid = sc.launches[li].grid;
+                for (; lj < sc.launches.size() && sc.launches[lj].level == sc.launches[li].level; ++lj) {
+                    bytes += sc.launches[lj].alg_bytes;
+                    grid += sc.launches[lj].grid;
+                }
+                const Launch &L = sc.launches[li];
+                A.wg_item = M.d_wg_item + L.wg_level;
+                A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
+                size_t e0 = 0, e1 = 0;
+                if ((rc = event(e0))) return rc;
+                hipLaunchKernelGGL(ve_sum_kernel, dim3((unsigned)grid), dim3(kWG), 0, S, A);
+                if ((rc = event(e1))) return rc;
+                timed.push_back({kNumKernels + 12, e0, e1, bytes, (double)grid});
+                h->stats.n_workgroups += (double)grid;
+                li = lj;
+            }
+            HIP_TRY(h, hipGetLastError());
+            // the draws of the wave's requests: workgroups of up to kDrawWG consecutive samples of one request, launched in groups
+            // of at most rows_cap rows (consecutive rows of `codes`: the requests of a wave are consecutive)
+            DrawArgs D;
+            D.prog = M.d_prog;
+            D.prog_off = M.d_prog_off + r0;
+            D.arena_off = M.d_arena_off;
+            D.arena = h->d_arena[0];
+            D.pool = h->d_pool;
+            D.m = M.d_m + r0;
+            D.n_vars = nv;
+            D.k0 = (uint32_t)seed;
+            D.k1 = (uint32_t)(seed >> 32) ^ 0x85EBCA6Bu;  // (the key of mibn_sample)
+            int64_t rb = r0, sb = s_off[b0 + r0];  // next sample to place: request rb, global row sb
+            while (rb < r1) {
+                ditems.clear();
+                const int64_t g_first = sb;
+                size_t rows = 0;
+                double gbytes = 0;
+                while (rb < r1 && rows < rows_cap) {
+                    const int64_t end = s_off[b0 + rb + 1];
+                    if (sb >= end) { ++rb; if (rb < r1) sb = s_off[b0 + rb]; continue; }
+                    const int64_t cnt = std::min<int64_t>({(int64_t)kDrawWG, end - sb, (int64_t)(rows_cap - rows)});
+                    ditems.push_back(DrawItem{(uint32_t)(rb - r0), (uint32_t)cnt, (uint64_t)sb, (uint64_t)(sb - g_first)});
+                    sb += cnt;
+                    rows += (size_t)cnt;
+                    gbytes += (double)cnt * gather[(size_t)rb];
+                }
+                if (ditems.empty()) break;
+                t0 = now_ms();
+                if ((rc = ensure(h, M.d_draw_items, M.draw_items_cap, ditems.size()))) return rc;
+                if ((rc = ensure(h, M.d_codes, M.codes_cap, rows * (size_t)std::max(1, nv)))) return rc;
+                HIP_TRY(h, hipMemcpyAsync(M.d_draw_items, ditems.data(), ditems.size() * sizeof(DrawItem), hipMemcpyHostToDevice, S));
+                h->stats.h2d_ms += now_ms() - t0;
+                D.items = M.d_draw_items;
+                D.codes = M.d_codes;
+                size_t e0 = 0, e1 = 0;
+                if ((rc = event(e0))) return rc;
+                if (wide) hipLaunchKernelGGL(posterior_draw_kernel<uint16_t>, dim3((unsigned)ditems.size()), dim3(kDrawWG), lds, S, D);
+                else hipLaunchKernelGGL(posterior_draw_kernel<uint8_t>, dim3((unsigned)ditems.size()), dim3(kDrawWG), lds, S, D);
+                if ((rc = event(e1))) return rc;
+                timed.push_back({kNumKernels + 13, e0, e1, gbytes, (double)rows});
+                h->stats.n_workgroups += (double)ditems.size();
+                HIP_TRY(h, hipGetLastError());
+                t0 = now_ms();
+                if (nv > 0)
+                    HIP_TRY(h, hipMemcpyAsync(codes + (size_t)(g_first - s_off[0]) * (size_t)nv, M.d_codes, rows * (size_t)nv * 4, hipMemcpyDeviceToHost, S));
+                HIP_TRY(h, hipStreamSynchronize(S));  // (the next group re-uses the items and the codes)
+                h->stats.d2h_ms += now_ms() - t0;
+            }
+            // the next wave re-uses the arena, the schedule buffers and the host schedule
+            HIP_TRY(h, hipStreamSynchronize(S));
+            h->stats.arena_bytes = std::max(h->stats.arena_bytes, (double)need_bytes);
+            if ((rc = book())) return rc;
+            r0 = r1;
+        }
+        t0 = now_ms();
+        if (p_e) HIP_TRY(h, hipMemcpyAsync(p_e + b0, M.d_m, (size_t)n * 8, hipMemcpyDeviceToHost, S));
+        HIP_TRY(h, hipStreamSynchronize(S));
+        h->stats.d2h_ms += now_ms() - t0;
+        h->stats.alg_bytes += ck.st.alg_bytes;
+        h->stats.alg_flops += ck.st.alg_flops;
+        h->stats.n_steps += ck.st.n_steps;
+        h->stats.max_step_cells = std::max(h->stats.max_step_cells, ck.st.max_step_cells);
+    }
+    h->stats.total_ms = now_ms() - t_start;
+    return MIBN_OK;
+}
+
+extern "C" int mibn_posterior_sample_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                                           const int64_t *s_off, uint64_t seed, uint32_t flags, int32_t *codes, double *p_e) {
+    const int rc = run_draw_body(h, B, e_off, e_vars, e_codes, s_off, seed, flags, codes, p_e);
     if (rc != MIBN_OK && h && !h->planner_only && h->stream) {  // (nothing of the call may still run when the caller sees the error)
         const std::string keep = h->err;
         (void)hipSetDevice(h->device);

@@ -647,6 +647,131 @@ static int emit_run_max(const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, Em
     return 0;
 }
 
+// Draw program of one request (planner.h, "DRAW programs"): the factors of emit_begin, one GENERIC sum step per variable of `order`
+// whose inputs all stay in the arena, the final product of the remaining scalars (RAW: the mass of the evidence), then the draw
+// record - backward entries for the eliminated variables, forward entries for the pruned ones.  Host only.  Returns 0 or a kEmitErr*.
+static int emit_run_draw(const Network &net, const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq,
+                         const int32_t *order, int n_order, int64_t &kept_cells) {
+    EmitNet en = en_sum;  // every step GENERIC, as in a max program: the traceback wants one step per variable
+    en.big_iters = std::numeric_limits<int64_t>::max();
+    en.outer = en.fuse = en.chain = en.sweep = 0;
+    PF *pool = S.pool;
+    S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
+    Emitter em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr};
+    for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
+    const size_t count_pos = prog.size;
+    prog.push(0);
+    const double steps0 = st.n_steps;
+    std::vector<char> alive((size_t)S.pool_cap, 0);
+    for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
+    const PF **ins = S.ins;
+    // an output keeps its arena cells for good: with alloc = 0 the emitter never hands them back when the table is consumed
+    auto keep = [&](PF &o) { o.alloc = 0; };
+    auto limit = [&](int n_in) -> int {
+        while (n_in > kMaxIn && !em.err) {
+            if (S.n_pool + 1 > S.pool_cap) { em.err = kEmitErrPool; return 0; }
+            std::stable_sort(ins, ins + n_in, [](const PF *a, const PF *b) { return a->cells < b->cells; });
+            PF &o = pool[S.n_pool++];
+            pf_reset(o);
+            em.emit(ins, kMaxIn, nullptr, 0, false, 0, o, false);
+            keep(o);
+            for (int k = kMaxIn; k < n_in; ++k) ins[k - kMaxIn] = ins[k];
+            n_in -= kMaxIn;
+            ins[n_in++] = &o;
+        }
+        return n_in;
+    };
+    struct Rec { int32_t x, n_in; const PF *in[kMaxIn]; };
+    std::vector<Rec> recs;
+    recs.reserve((size_t)n_order);
+    for (int i = 0; i < n_order; ++i) {
+        const int32_t x = order[i];
+        int n_in = 0;
+        for (int idx = 0; idx < S.n_pool; ++idx)
+            if (alive[(size_t)idx] && pool[idx].scope.test(x)) { ins[n_in++] = &pool[idx]; alive[(size_t)idx] = 0; }
+        if (!n_in) continue;  // (cannot happen: x's own CPT mentions it)
+        n_in = limit(n_in);
+        if (em.err) return em.err;
+        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
+        PF &o = pool[S.n_pool++];
+        pf_reset(o);
+        em.emit(ins, n_in, &x, 1, false, 0, o, false);
+        if (em.err) return em.err;
+        keep(o);
+        Rec r;
+        r.x = x;
+        r.n_in = n_in;
+        for (int j = 0; j < n_in; ++j) r.in[j] = ins[j];
+        recs.push_back(r);
+        alive[(size_t)(S.n_pool - 1)] = 1;
+    }
+    // the mass of the evidence: the product of what is left (all scalars), one cell, not normalised.  Nothing left (pruned, no
+    // evidence): no step, the empty product
+    st.out_cells = 1;
+    int n_in = 0;
+    for (int idx = 0; idx < S.n_pool; ++idx)
+        if (alive[(size_t)idx]) ins[n_in++] = &pool[idx];
+    if (n_in) {
+        n_in = limit(n_in);
+        if (em.err) return em.err;
+        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
+        PF &o = pool[S.n_pool++];
+        pf_reset(o);
+        const size_t step_base = prog.size;
+        em.emit(ins, n_in, nullptr, 0, true, rq.out_off, o, false);
+        if (em.err) return em.err;
+        prog.data[step_base + 1] |= kFlagRaw << 16;
+    }
+    prog.data[count_pos] = (uint32_t)(st.n_steps - steps0);
+    st.arena_cells = std::max(st.arena_cells, em.arena.top);
+    kept_cells += em.arena.top;
+    // draw record
+    std::vector<int32_t> fwd;
+    for (int v = 0; v < net.n_vars; ++v)
+        if (!S.rel.test(v) && net.card[v] > 1) fwd.push_back(v);
+    prog.push((uint32_t)recs.size());
+    prog.push((uint32_t)fwd.size());
+    prog.push((uint32_t)rq.ne);
+    for (int i = 0; i < rq.ne; ++i) {
+        prog.push((uint32_t)rq.evars[i]);
+        prog.push((uint32_t)(rq.ecodes ? rq.ecodes[i] : 0));
+    }
+    for (size_t k = recs.size(); k-- > 0;) {
+        const Rec &r = recs[k];
+        prog.push((uint32_t)r.x);
+        prog.push((uint32_t)net.card[r.x]);
+        prog.push((uint32_t)r.n_in);
+        for (int j = 0; j < r.n_in; ++j) {
+            const PF &f = *r.in[j];
+            int64_t xs = 0;
+            for (int a = 0; a < f.n; ++a)
+                if (f.vars[a] == r.x) xs = f.strides[a];
+            prog.push((uint32_t)(f.off & 0xffffffffu));
+            prog.push((uint32_t)(f.off >> 32));
+            prog.push((uint32_t)xs);
+            prog.push((uint32_t)(f.n - 1));
+            for (int a = 0; a < f.n; ++a)
+                if (f.vars[a] != r.x) { prog.push((uint32_t)f.vars[a]); prog.push((uint32_t)f.strides[a]); }
+        }
+    }
+    for (int32_t v : fwd) {
+        const std::vector<int32_t> &sc = net.scope[v];  // [*parents, v]
+        const uint64_t off = (uint64_t)net.pool_off[v] | kConstFlag;
+        uint32_t n_ax = 0;
+        for (size_t k = 0; k + 1 < sc.size(); ++k) n_ax += net.card[sc[k]] > 1;
+        prog.push((uint32_t)v);
+        prog.push((uint32_t)net.card[v]);
+        prog.push(1u);
+        prog.push((uint32_t)(off & 0xffffffffu));
+        prog.push((uint32_t)(off >> 32));
+        prog.push((uint32_t)net.cstride[v][sc.size() - 1]);
+        prog.push(n_ax);
+        for (size_t k = 0; k + 1 < sc.size(); ++k)
+            if (net.card[sc[k]] > 1) { prog.push((uint32_t)sc[k]); prog.push((uint32_t)net.cstride[v][k]); }
+    }
+    return 0;
+}
+
 // One request on the host: the shared emission (emit_core.h) around the choice of the elimination order.
 static std::string plan_request_rec(const Network &net, const Request &rq, ProgBuf &prog, PlanStats &st, PlanRecord *rec) {
     PROF(0);
@@ -674,8 +799,9 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     // relevant = query | event | ancestors(...)  (bayes_net.py:763-765); hidden = relevant - query - event (766); factors =
     // evidence-sliced CPTs of the relevant nodes (768-776)
     // (a max program has no query variable and never prunes: every non-evidence variable is maximised out)
-    const bool mx = rq.max_mode;
-    const int nq = mx ? 0 : rq.nq;
+    // (a draw program has no query variable either, and prunes to the ancestors of the evidence unless told not to)
+    const bool mx = rq.max_mode, dr = rq.draw_mode;
+    const int nq = (mx || dr) ? 0 : rq.nq;
     const bool no_prune = mx || rq.no_prune;
     if (int e = emit_begin(en, ES, nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, no_prune)) return emit_error_message(e);
     const Bits &hidden = ES.hidden;
@@ -692,10 +818,10 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
         PROF(1);
         OrderScratch &OS = order_scratch();
         OrderNet on = net.order_view();
-        if (mx) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms max programs do not use)
+        if (mx || dr) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms max / draw programs do not use)
         order_search(on, OS, nq, rq.qvars, rq.ne, rq.evars, no_prune);
         best.assign(OS.best, OS.best + OS.n_best);
-        if (!mx && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
+        if (!mx && !dr && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
     } else if (hidden.any()) {
         std::vector<Bits> &scopes = S.scopes;
         std::vector<double> &scells = S.scope_cells;
@@ -761,6 +887,12 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     const size_t rec_consts0 = rec ? rec->consts.size() : 0, rec_finals0 = rec ? rec->finals.size() : 0;
     if (mx) {
         const int e = emit_run_max(en, ES, eb, es, rq, best.data(), (int)best.size(), st.argmax_cells);
+        st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
+        st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
+        return emit_error_message(e);
+    }
+    if (dr) {
+        const int e = emit_run_draw(net, en, ES, eb, es, rq, best.data(), (int)best.size(), st.kept_cells);
         st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
         st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
         return emit_error_message(e);
@@ -1080,7 +1212,7 @@ PlanCache &plan_cache(const TemplateStore *ts) {
 void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs, int64_t b0, int64_t b1,
                 const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
                 const int32_t *e_codes, const int64_t *out_off, const char *skip, BatchPlan &ck, bool no_prune,
-                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode, bool raw) {
+                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode, bool raw, bool draw_mode) {
     const int64_t n = b1 - b0;
     const int T = pool.size();
     if ((int)bufs.size() < T) bufs.resize(T);
@@ -1100,7 +1232,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
     std::vector<std::string> terr(T);
     // dynamic distribution in blocks of 32 requests: request costs vary 100x and a worker may lose its core to
     // another rank's planner, a static split would wait for the slowest worker
-    TemplateStore *store = (net.plan_cache && !max_mode && !raw) ? template_store(net) : nullptr;
+    TemplateStore *store = (net.plan_cache && !max_mode && !raw && !draw_mode) ? template_store(net) : nullptr;
     std::atomic<int64_t> next{0};
     constexpr int64_t kBlock = 32;
     const EmitNet en = net.emit_view();
@@ -1121,9 +1253,10 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             ck.tag_first[i] = (uint32_t)tags.size();
             if (skip && skip[b]) {  // zero steps: result stays all-zero
                 prog.push(0);
-                if (max_mode) {  // (an empty traceback record: m = 0 reads as zero probability)
+                if (max_mode || draw_mode) {  // (an empty traceback / draw record: m = 0 reads as zero probability)
                     const int32_t ne = (int32_t)(e_off[b + 1] - e_off[b]);
                     prog.push(0);
+                    if (draw_mode) prog.push(0);
                     prog.push((uint32_t)ne);
                     for (int32_t k = 0; k < ne; ++k) { prog.push((uint32_t)e_vars[e_off[b] + k]); prog.push((uint32_t)e_codes[e_off[b] + k]); }
                 }
@@ -1139,6 +1272,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             rq.no_prune = no_prune;
             rq.max_mode = max_mode;
             rq.raw = raw;
+            rq.draw_mode = draw_mode;
             if (orders) { rq.order = orders + (size_t)i * 128; rq.n_order = order_len[i]; }
             PlanStats st;
             // plan templates (see above): probe at the start of every window, stay on while shapes repeat

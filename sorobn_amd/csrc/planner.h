@@ -90,6 +90,8 @@ struct Request {
     bool no_prune = false;            // MIBN_Q_NOPRUNE: every CPT takes part (full_joint_dist / predict_proba, bayes_net.py:460)
     bool max_mode = false;            // max program (mibn_mpe_batch): max-product elimination of every non-evidence variable, nq = 0
     bool raw = false;                 // MIBN_Q_UNNORMALISED: the FINAL step carries kFlagRaw (P(q, e), not normalised); nq = 0 allowed
+    bool draw_mode = false;           // draw program (mibn_posterior_sample_batch): sum elimination with every input kept, nq = 0; prunes
+                                      // to the evidence's ancestors unless no_prune
     const uint8_t *order = nullptr;   // elimination order found elsewhere (the device order search), n_order entries
     int32_t n_order = -1;             // -1: search on the host
 };
@@ -99,6 +101,7 @@ struct PlanStats {
     int64_t arena_cells = 0;  // scratch cells this request needs in its arena slot
     int64_t out_cells = 0;
     int64_t argmax_cells = 0;  // max programs: arena cells (doubles) of the argmax tables, included in arena_cells
+    int64_t kept_cells = 0;    // draw programs: arena cells of the intermediates, none of them released (= arena_cells of the request)
     std::vector<int32_t> *order = nullptr;  // optional: receives the elimination order the plan executes (mibn_plan_order)
 };
 
@@ -197,6 +200,23 @@ struct PlanStats {
 //      flag RAW (kFlagRaw, w1 bit 16 + 6): the kernels write the product sum as it is, P(q, e), with no normalisation.
 //      nq = 0 is allowed: the FINAL step is one cell, P(e).  With pruning and no evidence the relevant set is empty and the FINAL
 //      step has no input at all (n_in = 0): the empty product, 1.0.  Planned by the host only, without plan templates.
+//
+//   DRAW programs (Request::draw_mode, mibn_posterior_sample_batch): forward filtering for exact samples of P(x | e).  The factor
+//      set, the order search (plain section-8(d) bytes) and the step shape are those of a max program - one GENERIC step per
+//      eliminated variable, product-only steps above kMaxIn inputs - but the steps SUM (no MAX flag, no argmax table) and the
+//      FINAL step, one cell = the unnormalised mass of the evidence, carries flag RAW.  No intermediate is released to the arena:
+//      the backward draw reads the inputs of every elimination step again (PlanStats::kept_cells).  With Request::no_prune every
+//      CPT takes part (the MPE rule); without it only the evidence variables and their ancestors do, and the other variables are
+//      drawn forward from their CPT rows.  Without evidence a pruned program has no step at all (its mass is the empty product).
+//      After the last step follows the DRAW record of the request:
+//          n_back, n_fwd, n_ev, (evidence variable, code) x n_ev,
+//          n_back + n_fwd entries:  x, card(x), n_in,  per input: off lo, off hi (bit 63 = constants pool), stride of x, n_axes,
+//                                   (variable, stride) x n_axes
+//      Backward entries, last eliminated first: the inputs of x's elimination step in input order (a pre-multiplied product is an
+//      ordinary input), evidence already folded into the base.  x ~ w_x = prod_j phi_j[off_j + sum_v code[v] * stride_v + x * xs_j]:
+//      every axis variable is eliminated later, so the walk has drawn it already.  Forward entries, ascending id (= topological):
+//      one input, x's whole CPT with its multi-state parents as axes - evidence or drawn before.  A request whose evidence code
+//      lies outside its domain is the program "0" + a record with n_back = n_fwd = 0.
 // Growable word buffer the planner appends programs to.  The engine backs it with pinned host memory
 // (so the upload is a true async DMA) and keeps it across calls; the default backing is malloc.
 struct ProgBuf {
@@ -251,7 +271,8 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
                 int64_t out_first = -1,   // result offsets relative to out_off[out_first] (default: b0) - the host's share of a chunk whose
                                           // first requests the device plans
                 bool max_mode = false,    // max programs (mibn_mpe_batch; q_off all zero, no plan templates)
-                bool raw = false);        // MIBN_Q_UNNORMALISED requests (nq = 0 allowed, no plan templates)
+                bool raw = false,         // MIBN_Q_UNNORMALISED requests (nq = 0 allowed, no plan templates)
+                bool draw_mode = false);  // draw programs (mibn_posterior_sample_batch; q_off all zero, no plan templates; prunes unless no_prune)
 
 // Shard-balancing estimate (mibn_estimate_costs): section-8(d) bytes of the cheaper of the two sweep orders of every
 // request of a CSR batch - the byte model only, nothing is emitted.
