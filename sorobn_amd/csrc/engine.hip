@@ -178,9 +178,17 @@ __global__ __launch_bounds__(MIBN_PLAN_WG, MIBN_EMIT_WAVES_PER_EU) void emit_ker
 // proved erratic end to end (planning wall time doubles, runs between 155 k and 204 k queries/s against a steady
 // 194-204 k with two: profiles/r02_q_chunk_sets.log), so it stays an experiment.
 constexpr int kChunkSets = 4;
-// statistics slots: the classes of work (split_kinds), the kernels of mibn_query_batch as launched (stat_name), then the two of
-// mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of mibn_posterior_sample_batch
-constexpr int kStatSlots = kNumKernels + 14;
+// statistics slots: the classes of work (split_kinds: 0 .. kNumKernels - 1, kernel_name), then the kernels of mibn_query_batch as
+// launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
+// mibn_posterior_sample_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+enum StatSlot : int {
+    kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatSlots
+};
+constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
+    "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
+    "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
+    "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -354,8 +362,9 @@ struct mibn_ctx {
     mibn_kernel_stat kstats[kStatSlots];  // per class (split_kinds) + the level kernel as a whole + the tiny kernel + the LDS-DMA sweep kernel
     mibn_kernel_stat ktotal[kStatSlots];  // + the device planner's pair of kernels + the concurrent launch pair of a level (option overlap)
                                           // + ve_max_kernel and mpe_traceback_kernel (mibn_mpe_batch: last-call statistics only)
-    // mibn_mpe_batch (blocking, host-planned): buffers of its own - nothing a query call reads - beside the arena of lane 0
-    struct Mpe {
+    // the blocking, host-planned elimination calls (run_elim: mibn_mpe_batch, mibn_posterior_sample_batch): one set of buffers for
+    // both - nothing a query call reads - beside the arena of lane 0
+    struct Elim {
         std::vector<ProgBuf> bufs;  // malloc-backed program buffers, one per worker
         BatchPlan plan;
         Schedule sched;
@@ -367,14 +376,14 @@ struct mibn_ctx {
         size_t items_cap = 0;
         uint32_t *d_wg_item = nullptr;
         size_t wg_item_cap = 0;
-        double *d_m = nullptr, *d_log_p = nullptr;
+        double *d_m = nullptr, *d_log_p = nullptr;  // per request of a chunk: what its FINAL step wrote; (MPE) the logarithm of it
         size_t m_cap = 0, log_p_cap = 0;
-        int32_t *d_codes = nullptr;
+        int32_t *d_codes = nullptr;  // the decoded assignments of a chunk (MPE) / the rows of a draw launch
         size_t codes_cap = 0;
-        DrawItem *d_draw_items = nullptr;  // mibn_posterior_sample_batch shares these buffers (both calls are blocking)
+        DrawItem *d_draw_items = nullptr;
         size_t draw_items_cap = 0;
         std::vector<hipEvent_t> ev;
-    } mpe;
+    } elim;
     // mibn_expect_batch (blocking, host-planned): while `expect` is set, a query call hands its device-resident results to expect_run
     // instead of downloading them.  Buffers of its own; last-call statistics only (nothing a later query call reads).
     struct Expect {
@@ -636,7 +645,7 @@ void mibn_destroy(mibn_t *h) {
         for (auto &sg : h->res_stage)
             if (sg.p) (void)hipHostFree(sg.p);
         {
-            mibn_ctx::Mpe &M = h->mpe;
+            mibn_ctx::Elim &M = h->elim;
             for (auto &b : M.bufs) b.release();
             (void)hipFree(M.d_prog);
             (void)hipFree(M.d_prog_off);
@@ -896,8 +905,53 @@ void ensure_pool(mibn_ctx *h) {
 }
 
 // name of statistics slot k: the classes of work (split_kinds), then the kernels as launched
-const char *stat_name(int k) {
-    return k < kNumKernels ? kernel_name(k) : (k == kNumKernels ? "ve_level_kernel" : (k == kNumKernels + 1 ? "tiny_kernel" : (k == kNumKernels + 2 ? "ve_sweep_dma_kernel" : (k == kNumKernels + 3 ? "order_kernel+emit_kernel" : (k == kNumKernels + 4 ? "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel" : (k == kNumKernels + 5 ? "ve_segment_kernel" : (k == kNumKernels + 6 ? "ve_mfma_kernel" : (k == kNumKernels + 7 ? "ve_max_kernel" : (k == kNumKernels + 8 ? "mpe_traceback_kernel" : (k == kNumKernels + 9 ? "expect_kernel" : (k == kNumKernels + 10 ? "count_kernel" : (k == kNumKernels + 11 ? "score_kernel" : (k == kNumKernels + 12 ? "ve_sum_kernel" : "posterior_draw_kernel")))))))))))));
+const char *stat_name(int k) { return k < kNumKernels ? kernel_name(k) : kStatSlotNames[k - kNumKernels]; }
+
+// every call that reports last-call statistics starts from zeroed, named slots
+void reset_last_stats(mibn_ctx *h) {
+    h->stats = mibn_stats{};
+    for (int k = 0; k < kStatSlots; ++k) {
+        h->kstats[k] = mibn_kernel_stat{};
+        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
+    }
+}
+
+// Wait for everything on the context's streams (search, copy, main, lane 1, the overlap streams): wait(q) for each, up to the first
+// that fails.
+template <class Wait>
+int each_stream(mibn_ctx *h, Wait &&wait) {
+    for (hipStream_t q : {h->search_stream, h->copy_stream, h->stream, h->stream2})
+        if (q)
+            if (int rc = wait(q)) return rc;
+    for (auto &la : h->aux)
+        for (hipStream_t a : la)
+            if (a)
+                if (int rc = wait(a)) return rc;
+    return MIBN_OK;
+}
+int drain_streams(mibn_ctx *h) {
+    return each_stream(h, [h](hipStream_t q) -> int { HIP_TRY(h, hipStreamSynchronize(q)); return MIBN_OK; });
+}
+// error paths: every stream is waited for whatever it returns, and the error the call already has is the one reported
+void drain_streams_unchecked(mibn_ctx *h) {
+    (void)each_stream(h, [](hipStream_t q) -> int { (void)hipStreamSynchronize(q); return MIBN_OK; });
+}
+void drain_main_unchecked(mibn_ctx *h) {  // (the blocking elimination calls: all their work is on the main stream)
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+}
+
+// Every error exit of a call drains what the call (and, with drain_streams_unchecked, earlier asynchronous calls) already put on the
+// streams before the caller sees the error: the caller may free or reuse its request arrays and the pinned `out` the kernels and
+// copies still touch (ADVICE r3 did this for the device-planner exits only; ADVICE r4: every exit behind the first launch).
+int drained_on_error(mibn_ctx *h, int rc, void (*drain)(mibn_ctx *)) {
+    if (rc != MIBN_OK && h && !h->planner_only) {
+        const std::string keep = h->err;
+        (void)hipSetDevice(h->device);
+        drain(h);
+        (void)hipGetLastError();
+        h->err = keep;
+    }
+    return rc;
 }
 
 // wait for a set's launches and book their HIP-event durations per kernel
@@ -929,9 +983,9 @@ int retire(mibn_ctx *h, mibn_ctx::Set &st) {
                 if (e != mibn_ctx::Set::Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[e])); lo = std::min(lo, (double)x); }
             for (size_t e : {t.e1, t.e3, t.e5, t.e7})
                 if (e != mibn_ctx::Set::Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[e])); hi = std::max(hi, (double)x); }
-            for (mibn_kernel_stat *ks : {&h->kstats[kNumKernels + 4], &h->ktotal[kNumKernels + 4]}) {
-                if (ks == &h->kstats[kNumKernels + 4] && !mine) continue;
-                if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(kNumKernels + 4));
+            for (mibn_kernel_stat *ks : {&h->kstats[kStatLevelGroup], &h->ktotal[kStatLevelGroup]}) {
+                if (ks == &h->kstats[kStatLevelGroup] && !mine) continue;
+                if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(kStatLevelGroup));
                 ks->launches += 1;
                 ks->ms += std::max(0.0, hi - lo);
                 ks->alg_bytes += t.bytes;
@@ -1459,8 +1513,8 @@ int expect_run(mibn_t *h, const double *d_results) {
     HIP_TRY(h, hipStreamSynchronize(S));
     float ms = 0;
     HIP_TRY(h, hipEventElapsedTime(&ms, X.ev[0], X.ev[1]));
-    mibn_kernel_stat &ks = h->kstats[kNumKernels + 9];
-    if (!ks.name[0]) std::snprintf(ks.name, sizeof(ks.name), "%s", stat_name(kNumKernels + 9));
+    mibn_kernel_stat &ks = h->kstats[kStatExpect];
+    if (!ks.name[0]) std::snprintf(ks.name, sizeof(ks.name), "%s", stat_name(kStatExpect));
     ks.launches += launches;
     ks.ms += ms;
     ks.alg_bytes += 8.0 * ((double)(P.req.size() + P.big.size()) + 2.0 * (double)P.part_cells + 2.0 * (double)nA);
@@ -1580,7 +1634,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     h->total.alg_bytes += io_bytes;
     h->total.total_ms += h->stats.total_ms;
     h->total.d2h_ms += h->stats.d2h_ms;
-    for (mibn_kernel_stat *ks : {&h->kstats[kNumKernels + 1], &h->ktotal[kNumKernels + 1]}) {
+    for (mibn_kernel_stat *ks : {&h->kstats[kStatTiny], &h->ktotal[kStatTiny]}) {
         std::snprintf(ks->name, sizeof(ks->name), "%s", "tiny_kernel");
         ks->launches += 1;
         ks->ms += ms;
@@ -1606,11 +1660,7 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
     ++h->call_id;
     h->search_ms = 0;
     h->emit_ms = 0;
-    h->stats = mibn_stats{};
-    for (int k = 0; k < kStatSlots; ++k) {
-        h->kstats[k] = mibn_kernel_stat{};
-        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
-    }
+    reset_last_stats(h);
     const int slot = h->next_slot;
     if (h->pend[slot].active) { h->err = "two asynchronous calls are already in flight: mibn_wait the older one first"; return MIBN_E_STATE; }
     if (ticket) *ticket = slot;
@@ -1839,8 +1889,8 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
             h->emit_ms += now_ms() - tw;
             call_plan_ms += now_ms() - tw;
             if (h->trace >= 2) std::fprintf(stderr, "[mibn plan] collect returned %d at %.2f ms of the block\n", rc, now_ms() - t0);
-            for (mibn_kernel_stat *ks : {&h->kstats[kNumKernels + 3], &h->ktotal[kNumKernels + 3]}) {  // (beside the chunk in flight: their time is not GPU busy time of its own)
-                if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(kNumKernels + 3));
+            for (mibn_kernel_stat *ks : {&h->kstats[kStatPlanner], &h->ktotal[kStatPlanner]}) {  // (beside the chunk in flight: their time is not GPU busy time of its own)
+                if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(kStatPlanner));
                 ks->launches += 2;
                 ks->ms += dev_ms;
                 ks->items += (double)nd;
@@ -2137,7 +2187,7 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
                         pair.items += (double)grid;
                     }
                 }
-                st.timed.push_back({sweep ? (h->sweep_dma ? kNumKernels + 2 : kKidSweep) : (seg ? kNumKernels + 5 : (mf ? kNumKernels + 6 : (h->split_kinds ? L.kid : kNumKernels))), e0, e1, bytes, (double)grid, h->call_id});
+                st.timed.push_back({sweep ? (h->sweep_dma ? kStatSweepDma : kKidSweep) : (seg ? kStatSegment : (mf ? kStatMfma : (h->split_kinds ? L.kid : kStatLevel))), e0, e1, bytes, (double)grid, h->call_id});
                 n_wg += (double)grid;
                 li = lj;
             }
@@ -2229,46 +2279,94 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
 }
 }  // namespace
 
-// Every error exit of a call drains what the call (and earlier asynchronous calls) already put on the streams before the caller
-// sees the error: the caller may free or reuse its request arrays and the pinned `out` the kernels and copies still touch
-// (ADVICE r3 did this for the device-planner exits only; ADVICE r4: every exit behind the first launch).
 static int run_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
               const int32_t *e_codes, const int64_t *out_off, double *out, int32_t *ticket) {
-    const int rc = run_batch_body(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, ticket);
-    if (rc != MIBN_OK && h && !h->planner_only) {
-        const std::string keep = h->err;
-        (void)hipSetDevice(h->device);
-        for (hipStream_t q : {h->search_stream, h->copy_stream, h->stream, h->stream2})
-            if (q) (void)hipStreamSynchronize(q);
-        for (auto &la : h->aux)
-            for (hipStream_t a : la)
-                if (a) (void)hipStreamSynchronize(a);
-        (void)hipGetLastError();
-        h->err = keep;
-    }
-    return rc;
+    return drained_on_error(h, run_batch_body(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, ticket), drain_streams_unchecked);
 }
 
-// ---------------------------------------------------------------------------------------------- most probable explanation
-// mibn_mpe_batch: max programs (planner.h) planned by the workers, run level by level by ve_max_kernel on the main stream, decoded by
-// mpe_traceback_kernel, downloaded - chunk by chunk, each chunk cut into waves by the arena budget like a query call.  Blocking and
-// host-planned: no tiny kernel, no device planner, no plan templates, no adaptive policy; the options are read, never written.  The
-// arena of lane 0 is shared with the query calls (after the streams have drained); the statistics are those of the last call only.
-static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes, double *log_p) {
-    if (!h || B < 0 || !e_off || (B && (!codes || !log_p))) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
-    const double t_start = now_ms();
-    h->stats = mibn_stats{};
-    for (int k = 0; k < kStatSlots; ++k) {
-        h->kstats[k] = mibn_kernel_stat{};
-        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
+// ---------------------------------------------------------------------------------------------- blocking elimination calls
+// run_elim: the one driver of the blocking, host-planned elimination calls - mibn_mpe_batch and mibn_posterior_sample_batch.  It plans
+// a chunk of requests on the workers (plan_batch), uploads the programs, cuts the chunk into waves by the arena budget, runs every
+// wave level by level on the main stream and hands it to the payload for post-processing.  No tiny kernel, no device planner, no
+// plan templates, no adaptive policy; the options are read, never written.  The arena of lane 0 is shared with the query calls
+// (after the streams have drained); the buffers are mibn_ctx::Elim's; the statistics are those of the last call only.
+//
+// A payload supplies the flavour of the programs (kMaxMode / kDrawMode / no_prune: plan_batch), the level kernel with its
+// statistics slot (launch_level, kLevelSlot), the limits its network must keep (limits: checked after the statistics reset and the
+// B == 0 return, before the requests are validated - as each entry point always did), and three hooks.  Everything is on the main
+// stream S; the driver owns every buffer of ElimRun::M but d_log_p, d_codes and d_draw_items, which are the payload's.
+//   prepare(R)       once per chunk [b0, b0 + n).  Enqueued before it: the chunk's programs and prog_off (not waited for).  It
+//                    initialises d_m[0 .. n) - the cell of request i of the chunk, which the FINAL step of its program overwrites and
+//                    a skipped request (R.skip) never writes - and sizes its own buffers.  It may leave work enqueued; host memory
+//                    it uploads from must stay valid until it has synchronised S itself.
+//   after_levels(R)  once per wave [r0, r1) of the chunk.  Enqueued before it, not waited for: the wave's schedule and every level
+//                    launch, whose launch errors the driver has already collected; d_m[r0 .. r1) and the arena (request i at
+//                    M.d_arena_off[i - r0]) are complete in stream order.  It launches through R.timed_launch so that the time is
+//                    booked, checks its own launch errors, and may leave work enqueued or synchronise S itself: the driver
+//                    synchronises S after it in any case, before the next wave re-uses the arena and the schedule buffers.
+//   download(R)      once per chunk, after its last wave has been synchronised: enqueues the copies of the chunk's results to the
+//                    caller's arrays.  The driver synchronises S after it, before the next chunk re-uses d_m.
+// A hook returns MIBN_OK or the error it has set in h->err; on any error the entry point drains the main stream (drained_on_error).
+namespace {
+
+struct ElimRun {  // the call in flight, as the hooks of a payload see it
+    mibn_ctx *h;
+    mibn_ctx::Elim &M;
+    hipStream_t S;
+    const char *skip;        // per request of the call: 1 = evidence outside its domain, no program runs (zero probability)
+    int64_t b0 = 0, n = 0;   // the chunk: requests [b0, b0 + n) of the call
+    int64_t r0 = 0, r1 = 0;  // the wave: requests [r0, r1) of the chunk
+    size_t n_ev = 0;
+    struct Timed { int slot; size_t e0, e1; double bytes, items; };
+    std::vector<Timed> timed;  // the launches of the wave in flight
+
+    int event(size_t &idx) {
+        if (n_ev == M.ev.size()) {
+            hipEvent_t e;
+            HIP_TRY(h, hipEventCreate(&e));
+            M.ev.push_back(e);
+        }
+        idx = n_ev++;
+        HIP_TRY(h, hipEventRecord(M.ev[idx], S));
+        return MIBN_OK;
     }
+    // launch() between two events on S; its time is booked to statistics slot `slot` when the wave has been synchronised
+    template <class Launch>
+    int timed_launch(int slot, double bytes, double items, Launch &&launch) {
+        size_t e0 = 0, e1 = 0;
+        int rc;
+        if ((rc = event(e0))) return rc;
+        launch();
+        if ((rc = event(e1))) return rc;
+        timed.push_back({slot, e0, e1, bytes, items});
+        return MIBN_OK;
+    }
+    int book() {
+        for (const Timed &t : timed) {
+            float ms = 0;
+            HIP_TRY(h, hipEventElapsedTime(&ms, M.ev[t.e0], M.ev[t.e1]));
+            mibn_kernel_stat &ks = h->kstats[t.slot];
+            ks.launches += 1;
+            ks.ms += ms;
+            ks.alg_bytes += t.bytes;
+            ks.items += t.items;
+            h->stats.kernel_ms += ms;
+            h->stats.n_launches += 1;
+        }
+        timed.clear();
+        n_ev = 0;
+        return MIBN_OK;
+    }
+};
+
+template <class Payload>
+int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, Payload &P) {
+    const double t_start = now_ms();
+    reset_last_stats(h);
     if (B == 0) return MIBN_OK;
     const Network &net = h->net;
-    const int nv = net.n_vars;
-    for (int v = 0; v < nv; ++v)
-        if (net.card[v] > 65536) { h->err = "mpe: variable " + std::to_string(v) + " has more than 65 536 states (argmax entries are 16 bits)"; return MIBN_E_LIMIT; }
+    int rc;
+    if ((rc = P.limits(h))) return rc;
     // validation (unknown ids, duplicates) and the out-of-domain-evidence short cut
     std::vector<char> skip((size_t)B, 0);
     for (int64_t b = 0; b < B; ++b) {
@@ -2285,57 +2383,40 @@ static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_
     HIP_TRY(h, hipSetDevice(h->device));
     ensure_pool(h);
     // an asynchronous query call may still use the arena of lane 0
-    for (hipStream_t q : {h->search_stream, h->copy_stream, h->stream, h->stream2})
-        if (q) HIP_TRY(h, hipStreamSynchronize(q));
-    for (auto &la : h->aux)
-        for (hipStream_t a : la)
-            if (a) HIP_TRY(h, hipStreamSynchronize(a));
-    mibn_ctx::Mpe &M = h->mpe;
+    if ((rc = drain_streams(h))) return rc;
+    ElimRun R{h, h->elim, h->stream, skip.data()};
+    mibn_ctx::Elim &M = R.M;
     if (M.bufs.size() < (size_t)h->pool->size()) M.bufs.resize((size_t)h->pool->size());
-    const hipStream_t S = h->stream;
+    const hipStream_t S = R.S;
     std::vector<int64_t> q_off((size_t)B + 1, 0), out_off((size_t)B + 1);
-    std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: m
+    std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: d_m
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
     const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0])) / 8.0);
-    size_t n_ev = 0;
-    auto event = [&](size_t &idx) -> int {
-        if (n_ev == M.ev.size()) {
-            hipEvent_t e;
-            HIP_TRY(h, hipEventCreate(&e));
-            M.ev.push_back(e);
-        }
-        idx = n_ev++;
-        HIP_TRY(h, hipEventRecord(M.ev[idx], S));
-        return MIBN_OK;
-    };
-    struct Timed { int slot; size_t e0, e1; double bytes, items; };
-    std::vector<Timed> timed;
-    int rc;
     for (int64_t b0 = 0, b1 = 0; b0 < B; b0 = b1) {
         b1 = std::min(B, b0 + std::max<int64_t>(1, h->chunk));
         const int64_t n = b1 - b0;
+        R.b0 = b0;
+        R.n = n;
         double t0 = now_ms();
         BatchPlan &ck = M.plan;
-        plan_batch(net, *h->pool, M.bufs, b0, b1, q_off.data(), nullptr, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck, false,
-                   nullptr, nullptr, -1, true);
+        plan_batch(net, *h->pool, M.bufs, b0, b1, q_off.data(), nullptr, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck, P.no_prune,
+                   nullptr, nullptr, -1, Payload::kMaxMode, false, Payload::kDrawMode);
         if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
         h->stats.plan_ms += now_ms() - t0;
         t0 = now_ms();
         if ((rc = ensure(h, M.d_prog, M.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
         if ((rc = ensure(h, M.d_prog_off, M.prog_off_cap, (size_t)n))) return rc;
         if ((rc = ensure(h, M.d_m, M.m_cap, (size_t)n))) return rc;
-        if ((rc = ensure(h, M.d_log_p, M.log_p_cap, (size_t)n))) return rc;
-        if ((rc = ensure(h, M.d_codes, M.codes_cap, (size_t)n * (size_t)std::max(1, nv)))) return rc;
         size_t base = 0;
         for (size_t t = 0; t < ck.thread_words.size(); ++t) {
             if (ck.thread_words[t]) HIP_TRY(h, hipMemcpyAsync(M.d_prog + base, M.bufs[t].data, ck.thread_words[t] * 4, hipMemcpyHostToDevice, S));
             base += ck.thread_words[t];
         }
         HIP_TRY(h, hipMemcpyAsync(M.d_prog_off, ck.prog_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
-        HIP_TRY(h, hipMemsetAsync(M.d_m, 0, (size_t)n * 8, S));  // (skipped requests never write theirs: zero probability)
+        if ((rc = P.prepare(R))) return rc;
         h->stats.h2d_ms += now_ms() - t0;
-        // waves: consecutive requests whose arenas (intermediates + argmax tables) fit the budget together
+        // waves: consecutive requests whose arenas (intermediates + what the payload's programs keep) fit the budget together
         for (int64_t r0 = 0; r0 < n;) {
             int64_t r1 = r0, cells = 0;
             while (r1 < n) {
@@ -2345,6 +2426,8 @@ static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_
                 ++r1;
             }
             if (cells > budget_cells) { h->err = "a request needs " + std::to_string(8.0 * cells / 1e9) + " GB of scratch, above the arena budget"; return MIBN_E_NOMEM; }
+            R.r0 = r0;
+            R.r1 = r1;
             t0 = now_ms();
             Schedule &sc = M.sched;
             build_schedule(net, ck, M.bufs, r0, r1, sc);
@@ -2371,9 +2454,9 @@ static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_
             A.arena_off = M.d_arena_off;
             A.pool = h->d_pool;
             A.arena = h->d_arena[0];
-            A.results = M.d_m;  // (FINAL offsets are chunk-relative: request b's m at b - b0)
+            A.results = M.d_m;  // (FINAL offsets are chunk-relative: the cell of request b at b - b0)
             A.items = M.d_items;
-            // one launch per level: every class of work of a max schedule (segments, GENERIC tiles) is ve_max_kernel's
+            // one launch per level: every class of work of such a schedule (segments, GENERIC tiles) is the payload's level kernel's
             for (size_t li = 0; li < sc.launches.size();) {
                 size_t lj = li + 1;
                 double bytes = sc.launches[li].alg_bytes;
@@ -2385,51 +2468,20 @@ static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_
                 const Launch &L = sc.launches[li];
                 A.wg_item = M.d_wg_item + L.wg_level;
                 A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
-                size_t e0 = 0, e1 = 0;
-                if ((rc = event(e0))) return rc;
-                hipLaunchKernelGGL(ve_max_kernel, dim3((unsigned)grid), dim3(kWG), 0, S, A);
-                if ((rc = event(e1))) return rc;
-                timed.push_back({kNumKernels + 7, e0, e1, bytes, (double)grid});
+                if ((rc = R.timed_launch(Payload::kLevelSlot, bytes, (double)grid, [&] { P.launch_level((unsigned)grid, S, A); }))) return rc;
                 h->stats.n_workgroups += (double)grid;
                 li = lj;
             }
-            TracebackArgs T;
-            T.prog = M.d_prog;
-            T.prog_off = M.d_prog_off + r0;
-            T.arena_off = M.d_arena_off;
-            T.arena = h->d_arena[0];
-            T.m = M.d_m + r0;
-            T.codes = M.d_codes + (size_t)r0 * (size_t)nv;
-            T.log_p = M.d_log_p + r0;
-            T.n_req = (uint32_t)(r1 - r0);
-            T.n_vars = nv;
-            size_t e0 = 0, e1 = 0;
-            if ((rc = event(e0))) return rc;
-            hipLaunchKernelGGL(mpe_traceback_kernel, dim3((unsigned)(r1 - r0)), dim3(kTracebackWG), 0, S, T);
-            if ((rc = event(e1))) return rc;
-            timed.push_back({kNumKernels + 8, e0, e1, 0.0, (double)(r1 - r0)});
             HIP_TRY(h, hipGetLastError());
+            if ((rc = P.after_levels(R))) return rc;
             // the next wave re-uses the arena, the schedule buffers and the host schedule
             HIP_TRY(h, hipStreamSynchronize(S));
             h->stats.arena_bytes = std::max(h->stats.arena_bytes, (double)need_bytes);
-            for (const Timed &t : timed) {
-                float ms = 0;
-                HIP_TRY(h, hipEventElapsedTime(&ms, M.ev[t.e0], M.ev[t.e1]));
-                mibn_kernel_stat &ks = h->kstats[t.slot];
-                ks.launches += 1;
-                ks.ms += ms;
-                ks.alg_bytes += t.bytes;
-                ks.items += t.items;
-                h->stats.kernel_ms += ms;
-                h->stats.n_launches += 1;
-            }
-            timed.clear();
-            n_ev = 0;
+            if ((rc = R.book())) return rc;
             r0 = r1;
         }
         t0 = now_ms();
-        HIP_TRY(h, hipMemcpyAsync(codes + (size_t)b0 * (size_t)nv, M.d_codes, (size_t)n * (size_t)nv * 4, hipMemcpyDeviceToHost, S));
-        HIP_TRY(h, hipMemcpyAsync(log_p + b0, M.d_log_p, (size_t)n * 8, hipMemcpyDeviceToHost, S));
+        if ((rc = P.download(R))) return rc;
         HIP_TRY(h, hipStreamSynchronize(S));
         h->stats.d2h_ms += now_ms() - t0;
         h->stats.alg_bytes += ck.st.alg_bytes;
@@ -2441,143 +2493,105 @@ static int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_
     return MIBN_OK;
 }
 
-extern "C" int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes,
-                              double *log_p) {
-    const int rc = run_mpe_body(h, B, e_off, e_vars, e_codes, codes, log_p);
-    if (rc != MIBN_OK && h && !h->planner_only && h->stream) {  // (nothing of the call may still run when the caller sees the error)
-        const std::string keep = h->err;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipGetLastError();
-        h->err = keep;
+// ---------------------------------------------------------------------------------------------- most probable explanation
+// mibn_mpe_batch: max programs (planner.h) run by ve_max_kernel - the arena of a request holds its intermediates and argmax tables -,
+// decoded wave by wave by mpe_traceback_kernel, downloaded chunk by chunk.
+struct MpePayload {
+    static constexpr bool kMaxMode = true, kDrawMode = false, no_prune = false;
+    static constexpr int kLevelSlot = kStatMax;
+    int32_t *codes;
+    double *log_p;
+
+    int limits(mibn_ctx *h) const {
+        for (int v = 0; v < h->net.n_vars; ++v)
+            if (h->net.card[v] > 65536) { h->err = "mpe: variable " + std::to_string(v) + " has more than 65 536 states (argmax entries are 16 bits)"; return MIBN_E_LIMIT; }
+        return MIBN_OK;
     }
-    return rc;
-}
+    void launch_level(unsigned grid, hipStream_t S, const LevelArgs &A) const { hipLaunchKernelGGL(ve_max_kernel, dim3(grid), dim3(kWG), 0, S, A); }
+    int prepare(ElimRun &R) const {
+        mibn_ctx *h = R.h;
+        int rc;
+        if ((rc = ensure(h, R.M.d_log_p, R.M.log_p_cap, (size_t)R.n))) return rc;
+        if ((rc = ensure(h, R.M.d_codes, R.M.codes_cap, (size_t)R.n * (size_t)std::max(1, h->net.n_vars)))) return rc;
+        HIP_TRY(h, hipMemsetAsync(R.M.d_m, 0, (size_t)R.n * 8, R.S));  // (skipped requests never write theirs: zero probability)
+        return MIBN_OK;
+    }
+    int after_levels(ElimRun &R) const {
+        mibn_ctx *h = R.h;
+        const int nv = h->net.n_vars;
+        TracebackArgs T;
+        T.prog = R.M.d_prog;
+        T.prog_off = R.M.d_prog_off + R.r0;
+        T.arena_off = R.M.d_arena_off;
+        T.arena = h->d_arena[0];
+        T.m = R.M.d_m + R.r0;
+        T.codes = R.M.d_codes + (size_t)R.r0 * (size_t)nv;
+        T.log_p = R.M.d_log_p + R.r0;
+        T.n_req = (uint32_t)(R.r1 - R.r0);
+        T.n_vars = nv;
+        int rc;
+        if ((rc = R.timed_launch(kStatTraceback, 0.0, (double)(R.r1 - R.r0), [&] {
+                hipLaunchKernelGGL(mpe_traceback_kernel, dim3((unsigned)(R.r1 - R.r0)), dim3(kTracebackWG), 0, R.S, T);
+            })))
+            return rc;
+        HIP_TRY(h, hipGetLastError());
+        return MIBN_OK;
+    }
+    int download(ElimRun &R) const {
+        mibn_ctx *h = R.h;
+        const size_t nv = (size_t)h->net.n_vars;
+        HIP_TRY(h, hipMemcpyAsync(codes + (size_t)R.b0 * nv, R.M.d_codes, (size_t)R.n * nv * 4, hipMemcpyDeviceToHost, R.S));
+        HIP_TRY(h, hipMemcpyAsync(log_p + R.b0, R.M.d_log_p, (size_t)R.n * 8, hipMemcpyDeviceToHost, R.S));
+        return MIBN_OK;
+    }
+};
 
 // ---------------------------------------------------------------------------------------------- exact posterior sampling
-// mibn_posterior_sample_batch: draw programs (planner.h) planned by the workers, run level by level by ve_sum_kernel on the main
-// stream - once per request, whatever its number of samples -, then posterior_draw_kernel walks each request's draw record once
-// per sample, in launches of at most kDrawCodeWords code words whose rows are downloaded before the next one.  Chunks, waves, the
-// shared arena of lane 0 and the statistics are those of mibn_mpe_batch, whose buffers it uses (both calls are blocking).
+// mibn_posterior_sample_batch: draw programs (planner.h) run by ve_sum_kernel - once per request, whatever its number of samples; every
+// table is kept in the arena -, then posterior_draw_kernel walks each request's draw record once per sample, in launches of at most
+// kDrawCodeWords code words whose rows are downloaded before the next one.
 constexpr size_t kDrawCodeWords = size_t(64) << 20;  // 256 MB of codes on the device per draw launch
 
-static int run_draw_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, const int64_t *s_off,
-                         uint64_t seed, uint32_t flags, int32_t *codes, double *p_e) {
-    if (!h || B < 0 || !e_off || !s_off) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
-    if (flags & ~(uint32_t)MIBN_DRAW_PRUNE) { h->err = "posterior sampling: unknown flag"; return MIBN_E_ARG; }
-    for (int64_t b = 0; b < B; ++b)
-        if (s_off[b + 1] < s_off[b] || s_off[b] < 0) { h->err = "posterior sampling: s_off must be non-negative and ascending"; return MIBN_E_ARG; }
-    if (B && s_off[B] > s_off[0] && !codes) return MIBN_E_ARG;
-    const double t_start = now_ms();
-    h->stats = mibn_stats{};
-    for (int k = 0; k < kStatSlots; ++k) {
-        h->kstats[k] = mibn_kernel_stat{};
-        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
-    }
-    if (B == 0) return MIBN_OK;
-    const Network &net = h->net;
-    const int nv = net.n_vars;
-    bool wide = false;
-    for (int v = 0; v < nv; ++v) {
-        if (net.card[v] > 65536) { h->err = "posterior sampling: variable " + std::to_string(v) + " has more than 65 536 states (sample states are 16 bits)"; return MIBN_E_LIMIT; }
-        wide = wide || net.card[v] > 256;
-    }
-    const size_t lds = draw_lds_bytes(nv, wide);
-    if (lds > 150 * 1024) { h->err = "posterior sampling: network too large for the LDS-resident sample state"; return MIBN_E_LIMIT; }
-    // validation (unknown ids, duplicates) and the out-of-domain-evidence short cut
-    std::vector<char> skip((size_t)B, 0);
-    for (int64_t b = 0; b < B; ++b) {
-        Request rq;
-        rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
-        rq.evars = e_vars + e_off[b];
-        const std::string e = rq.ne < 0 ? std::string("negative evidence count") : validate_mpe_request(net, rq);
-        if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
-        for (int i = 0; i < rq.ne; ++i) {
-            const int32_t c = e_codes[e_off[b] + i];
-            if (c < 0 || c >= net.card[rq.evars[i]]) skip[(size_t)b] = 1;  // label outside the domain: zero probability
-        }
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    ensure_pool(h);
-    // an asynchronous query call may still use the arena of lane 0
-    for (hipStream_t q : {h->search_stream, h->copy_stream, h->stream, h->stream2})
-        if (q) HIP_TRY(h, hipStreamSynchronize(q));
-    for (auto &la : h->aux)
-        for (hipStream_t a : la)
-            if (a) HIP_TRY(h, hipStreamSynchronize(a));
-    mibn_ctx::Mpe &M = h->mpe;
-    if (M.bufs.size() < (size_t)h->pool->size()) M.bufs.resize((size_t)h->pool->size());
-    const hipStream_t S = h->stream;
-    std::vector<int64_t> q_off((size_t)B + 1, 0), out_off((size_t)B + 1);
-    std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: the mass of its evidence
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
-    const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0])) / 8.0);
-    size_t n_ev = 0;
-    auto event = [&](size_t &idx) -> int {
-        if (n_ev == M.ev.size()) {
-            hipEvent_t e;
-            HIP_TRY(h, hipEventCreate(&e));
-            M.ev.push_back(e);
-        }
-        idx = n_ev++;
-        HIP_TRY(h, hipEventRecord(M.ev[idx], S));
-        return MIBN_OK;
-    };
-    struct Timed { int slot; size_t e0, e1; double bytes, items; };
-    std::vector<Timed> timed;
-    auto book = [&]() -> int {
-        for (const Timed &t : timed) {
-            float ms = 0;
-            HIP_TRY(h, hipEventElapsedTime(&ms, M.ev[t.e0], M.ev[t.e1]));
-            mibn_kernel_stat &ks = h->kstats[t.slot];
-            ks.launches += 1;
-            ks.ms += ms;
-            ks.alg_bytes += t.bytes;
-            ks.items += t.items;
-            h->stats.kernel_ms += ms;
-            h->stats.n_launches += 1;
-        }
-        timed.clear();
-        n_ev = 0;
-        return MIBN_OK;
-    };
-    if (lds > 64 * 1024) {
-        HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    const size_t rows_cap = std::max<size_t>(kDrawWG, kDrawCodeWords / (size_t)std::max(1, nv));
+struct DrawPayload {
+    static constexpr bool kMaxMode = false, kDrawMode = true;
+    static constexpr int kLevelSlot = kStatSum;
+    const bool no_prune;
+    const int64_t *s_off;
+    const uint64_t seed;
+    int32_t *codes;
+    double *p_e;
+    bool wide = false;  // limits: a variable of more than 256 states (16-bit sample states)
+    size_t lds = 0;     // limits: the LDS-resident sample state of a workgroup
     std::vector<double> m_init, gather;
     std::vector<DrawItem> ditems;
-    int rc;
-    for (int64_t b0 = 0, b1 = 0; b0 < B; b0 = b1) {
-        b1 = std::min(B, b0 + std::max<int64_t>(1, h->chunk));
-        const int64_t n = b1 - b0;
-        double t0 = now_ms();
-        BatchPlan &ck = M.plan;
-        plan_batch(net, *h->pool, M.bufs, b0, b1, q_off.data(), nullptr, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck,
-                   !(flags & MIBN_DRAW_PRUNE), nullptr, nullptr, -1, false, false, true);
-        if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
-        h->stats.plan_ms += now_ms() - t0;
-        t0 = now_ms();
-        if ((rc = ensure(h, M.d_prog, M.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
-        if ((rc = ensure(h, M.d_prog_off, M.prog_off_cap, (size_t)n))) return rc;
-        if ((rc = ensure(h, M.d_m, M.m_cap, (size_t)n))) return rc;
-        size_t base = 0;
-        for (size_t t = 0; t < ck.thread_words.size(); ++t) {
-            if (ck.thread_words[t]) HIP_TRY(h, hipMemcpyAsync(M.d_prog + base, M.bufs[t].data, ck.thread_words[t] * 4, hipMemcpyHostToDevice, S));
-            base += ck.thread_words[t];
+
+    int limits(mibn_ctx *h) {
+        const int nv = h->net.n_vars;
+        for (int v = 0; v < nv; ++v) {
+            if (h->net.card[v] > 65536) { h->err = "posterior sampling: variable " + std::to_string(v) + " has more than 65 536 states (sample states are 16 bits)"; return MIBN_E_LIMIT; }
+            wide = wide || h->net.card[v] > 256;
         }
-        HIP_TRY(h, hipMemcpyAsync(M.d_prog_off, ck.prog_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
+        lds = draw_lds_bytes(nv, wide);
+        if (lds > 150 * 1024) { h->err = "posterior sampling: network too large for the LDS-resident sample state"; return MIBN_E_LIMIT; }
+        return MIBN_OK;
+    }
+    void launch_level(unsigned grid, hipStream_t S, const LevelArgs &A) const { hipLaunchKernelGGL(ve_sum_kernel, dim3(grid), dim3(kWG), 0, S, A); }
+    int prepare(ElimRun &R) {
+        mibn_ctx *h = R.h;
+        const mibn_ctx::Elim &M = R.M;
+        const BatchPlan &ck = M.plan;
+        const int64_t n = R.n;
+        if (R.b0 == 0 && lds > 64 * 1024) {  // (once per call, before the first draw launch)
+            HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
         // a skipped request never writes its mass: zero probability.  A program without steps (pruned, no evidence) has the empty
         // product: 1
         m_init.assign((size_t)n, 0.0);
         for (int64_t i = 0; i < n; ++i)
-            if (!skip[(size_t)(b0 + i)] && M.bufs[(size_t)ck.thread_of[(size_t)i]].data[ck.local_off[(size_t)i]] == 0) m_init[(size_t)i] = 1.0;
-        HIP_TRY(h, hipMemcpyAsync(M.d_m, m_init.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
-        HIP_TRY(h, hipStreamSynchronize(S));  // (m_init is rewritten by the next chunk)
+            if (!R.skip[(size_t)(R.b0 + i)] && M.bufs[(size_t)ck.thread_of[(size_t)i]].data[ck.local_off[(size_t)i]] == 0) m_init[(size_t)i] = 1.0;
+        HIP_TRY(h, hipMemcpyAsync(M.d_m, m_init.data(), (size_t)n * 8, hipMemcpyHostToDevice, R.S));
+        HIP_TRY(h, hipStreamSynchronize(R.S));  // (m_init is rewritten by the next chunk)
         // table bytes one sample of each request gathers (the draw kernel's "algorithmic bytes"): 8 per input and state of every entry
         gather.assign((size_t)n, 0.0);
         for (int64_t i = 0; i < n; ++i) {
@@ -2594,145 +2608,105 @@ static int run_draw_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32
                 gather[(size_t)i] += 8.0 * (double)cx * (double)n_in;
             }
         }
-        h->stats.h2d_ms += now_ms() - t0;
-        // waves: consecutive requests whose arenas (every table is kept) fit the budget together
-        for (int64_t r0 = 0; r0 < n;) {
-            int64_t r1 = r0, cells = 0;
-            while (r1 < n) {
-                const int64_t need = (ck.arena_need[(size_t)r1] + 15) & ~int64_t(15);
-                if (r1 > r0 && cells + need > budget_cells) break;
-                cells += need;
-                ++r1;
-            }
-            if (cells > budget_cells) { h->err = "a request needs " + std::to_string(8.0 * cells / 1e9) + " GB of scratch, above the arena budget"; return MIBN_E_NOMEM; }
-            t0 = now_ms();
-            Schedule &sc = M.sched;
-            build_schedule(net, ck, M.bufs, r0, r1, sc);
-            h->stats.plan_ms += now_ms() - t0;
-            const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
-            if (need_bytes > h->arena_bytes[0]) {
-                HIP_TRY(h, hipStreamSynchronize(S));
-                if (h->d_arena[0]) { HIP_TRY(h, hipFree(h->d_arena[0])); h->d_arena[0] = nullptr; h->arena_bytes[0] = 0; }
-                const size_t want = std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3));
-                HIP_TRY(h, hipMalloc(&h->d_arena[0], want));
-                h->arena_bytes[0] = want;
-            }
-            t0 = now_ms();
-            if ((rc = ensure(h, M.d_arena_off, M.arena_off_cap, (size_t)(r1 - r0)))) return rc;
-            if ((rc = ensure(h, M.d_items, M.items_cap, std::max<size_t>(1, sc.items.size())))) return rc;
-            if ((rc = ensure(h, M.d_wg_item, M.wg_item_cap, std::max<size_t>(1, sc.wg_item.size())))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(M.d_arena_off, sc.arena_off.data(), (size_t)(r1 - r0) * 8, hipMemcpyHostToDevice, S));
-            if (!sc.items.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_items, sc.items.data(), sc.items.size() * sizeof(Item), hipMemcpyHostToDevice, S));
-            if (!sc.wg_item.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_wg_item, sc.wg_item.data(), sc.wg_item.size() * sizeof(uint32_t), hipMemcpyHostToDevice, S));
-            h->stats.h2d_ms += now_ms() - t0;
-            LevelArgs A;
-            A.prog = M.d_prog;
-            A.prog_off = M.d_prog_off + r0;
-            A.arena_off = M.d_arena_off;
-            A.pool = h->d_pool;
-            A.arena = h->d_arena[0];
-            A.results = M.d_m;  // (FINAL offsets are chunk-relative: request b's mass at b - b0)
-            A.items = M.d_items;
-            // one launch per level: every class of work of a draw schedule (segments, GENERIC tiles) is ve_sum_kernel's
-            for (size_t li = 0; li < sc.launches.size();) {
-                size_t lj = li + 1;
-                double bytes = sc.launches[li].alg_bytes;
-                size_t grid = sc.launches[li].grid;
-                for (; lj < sc.launches.size() && sc.launches[lj].level == sc.launches[li].level; ++lj) {
-                    bytes += sc.launches[lj].alg_bytes;
-                    grid += sc.launches[lj].grid;
-                }
-                const Launch &L = sc.launches[li];
-                A.wg_item = M.d_wg_item + L.wg_level;
-                A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
-                size_t e0 = 0, e1 = 0;
-                if ((rc = event(e0))) return rc;
-                hipLaunchKernelGGL(ve_sum_kernel, dim3((unsigned)grid), dim3(kWG), 0, S, A);
-                if ((rc = event(e1))) return rc;
-                timed.push_back({kNumKernels + 12, e0, e1, bytes, (double)grid});
-                h->stats.n_workgroups += (double)grid;
-                li = lj;
-            }
-            HIP_TRY(h, hipGetLastError());
-            // the draws of the wave's requests: workgroups of up to kDrawWG consecutive samples of one request, launched in groups
-            // of at most rows_cap rows (consecutive rows of `codes`: the requests of a wave are consecutive)
-            DrawArgs D;
-            D.prog = M.d_prog;
-            D.prog_off = M.d_prog_off + r0;
-            D.arena_off = M.d_arena_off;
-            D.arena = h->d_arena[0];
-            D.pool = h->d_pool;
-            D.m = M.d_m + r0;
-            D.n_vars = nv;
-            D.k0 = (uint32_t)seed;
-            D.k1 = (uint32_t)(seed >> 32) ^ 0x85EBCA6Bu;  // (the key of mibn_sample)
-            int64_t rb = r0, sb = s_off[b0 + r0];  // next sample to place: request rb, global row sb
-            while (rb < r1) {
-                ditems.clear();
-                const int64_t g_first = sb;
-                size_t rows = 0;
-                double gbytes = 0;
-                while (rb < r1 && rows < rows_cap) {
-                    const int64_t end = s_off[b0 + rb + 1];
-                    if (sb >= end) { ++rb; if (rb < r1) sb = s_off[b0 + rb]; continue; }
-                    const int64_t cnt = std::min<int64_t>({(int64_t)kDrawWG, end - sb, (int64_t)(rows_cap - rows)});
-                    ditems.push_back(DrawItem{(uint32_t)(rb - r0), (uint32_t)cnt, (uint64_t)sb, (uint64_t)(sb - g_first)});
-                    sb += cnt;
-                    rows += (size_t)cnt;
-                    gbytes += (double)cnt * gather[(size_t)rb];
-                }
-                if (ditems.empty()) break;
-                t0 = now_ms();
-                if ((rc = ensure(h, M.d_draw_items, M.draw_items_cap, ditems.size()))) return rc;
-                if ((rc = ensure(h, M.d_codes, M.codes_cap, rows * (size_t)std::max(1, nv)))) return rc;
-                HIP_TRY(h, hipMemcpyAsync(M.d_draw_items, ditems.data(), ditems.size() * sizeof(DrawItem), hipMemcpyHostToDevice, S));
-                h->stats.h2d_ms += now_ms() - t0;
-                D.items = M.d_draw_items;
-                D.codes = M.d_codes;
-                size_t e0 = 0, e1 = 0;
-                if ((rc = event(e0))) return rc;
-                if (wide) hipLaunchKernelGGL(posterior_draw_kernel<uint16_t>, dim3((unsigned)ditems.size()), dim3(kDrawWG), lds, S, D);
-                else hipLaunchKernelGGL(posterior_draw_kernel<uint8_t>, dim3((unsigned)ditems.size()), dim3(kDrawWG), lds, S, D);
-                if ((rc = event(e1))) return rc;
-                timed.push_back({kNumKernels + 13, e0, e1, gbytes, (double)rows});
-                h->stats.n_workgroups += (double)ditems.size();
-                HIP_TRY(h, hipGetLastError());
-                t0 = now_ms();
-                if (nv > 0)
-                    HIP_TRY(h, hipMemcpyAsync(codes + (size_t)(g_first - s_off[0]) * (size_t)nv, M.d_codes, rows * (size_t)nv * 4, hipMemcpyDeviceToHost, S));
-                HIP_TRY(h, hipStreamSynchronize(S));  // (the next group re-uses the items and the codes)
-                h->stats.d2h_ms += now_ms() - t0;
-            }
-            // the next wave re-uses the arena, the schedule buffers and the host schedule
-            HIP_TRY(h, hipStreamSynchronize(S));
-            h->stats.arena_bytes = std::max(h->stats.arena_bytes, (double)need_bytes);
-            if ((rc = book())) return rc;
-            r0 = r1;
-        }
-        t0 = now_ms();
-        if (p_e) HIP_TRY(h, hipMemcpyAsync(p_e + b0, M.d_m, (size_t)n * 8, hipMemcpyDeviceToHost, S));
-        HIP_TRY(h, hipStreamSynchronize(S));
-        h->stats.d2h_ms += now_ms() - t0;
-        h->stats.alg_bytes += ck.st.alg_bytes;
-        h->stats.alg_flops += ck.st.alg_flops;
-        h->stats.n_steps += ck.st.n_steps;
-        h->stats.max_step_cells = std::max(h->stats.max_step_cells, ck.st.max_step_cells);
+        return MIBN_OK;
     }
-    h->stats.total_ms = now_ms() - t_start;
-    return MIBN_OK;
+    // the draws of the wave's requests: workgroups of up to kDrawWG consecutive samples of one request, launched in groups of at most
+    // rows_cap rows (consecutive rows of `codes`: the requests of a wave are consecutive)
+    int after_levels(ElimRun &R) {
+        mibn_ctx *h = R.h;
+        mibn_ctx::Elim &M = R.M;
+        const hipStream_t S = R.S;
+        const int nv = h->net.n_vars;
+        const int64_t b0 = R.b0, r0 = R.r0, r1 = R.r1;
+        const size_t rows_cap = std::max<size_t>(kDrawWG, kDrawCodeWords / (size_t)std::max(1, nv));
+        DrawArgs D;
+        D.prog = M.d_prog;
+        D.prog_off = M.d_prog_off + r0;
+        D.arena_off = M.d_arena_off;
+        D.arena = h->d_arena[0];
+        D.pool = h->d_pool;
+        D.m = M.d_m + r0;
+        D.n_vars = nv;
+        D.k0 = (uint32_t)seed;
+        D.k1 = (uint32_t)(seed >> 32) ^ 0x85EBCA6Bu;  // (the key of mibn_sample)
+        int rc;
+        int64_t rb = r0, sb = s_off[b0 + r0];  // next sample to place: request rb, global row sb
+        while (rb < r1) {
+            ditems.clear();
+            const int64_t g_first = sb;
+            size_t rows = 0;
+            double gbytes = 0;
+            while (rb < r1 && rows < rows_cap) {
+                const int64_t end = s_off[b0 + rb + 1];
+                if (sb >= end) { ++rb; if (rb < r1) sb = s_off[b0 + rb]; continue; }
+                const int64_t cnt = std::min<int64_t>({(int64_t)kDrawWG, end - sb, (int64_t)(rows_cap - rows)});
+                ditems.push_back(DrawItem{(uint32_t)(rb - r0), (uint32_t)cnt, (uint64_t)sb, (uint64_t)(sb - g_first)});
+                sb += cnt;
+                rows += (size_t)cnt;
+                gbytes += (double)cnt * gather[(size_t)rb];
+            }
+            if (ditems.empty()) break;
+            double t0 = now_ms();
+            if ((rc = ensure(h, M.d_draw_items, M.draw_items_cap, ditems.size()))) return rc;
+            if ((rc = ensure(h, M.d_codes, M.codes_cap, rows * (size_t)std::max(1, nv)))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(M.d_draw_items, ditems.data(), ditems.size() * sizeof(DrawItem), hipMemcpyHostToDevice, S));
+            h->stats.h2d_ms += now_ms() - t0;
+            D.items = M.d_draw_items;
+            D.codes = M.d_codes;
+            if ((rc = R.timed_launch(kStatDraw, gbytes, (double)rows, [&] {
+                    if (wide) hipLaunchKernelGGL(posterior_draw_kernel<uint16_t>, dim3((unsigned)ditems.size()), dim3(kDrawWG), lds, S, D);
+                    else hipLaunchKernelGGL(posterior_draw_kernel<uint8_t>, dim3((unsigned)ditems.size()), dim3(kDrawWG), lds, S, D);
+                })))
+                return rc;
+            h->stats.n_workgroups += (double)ditems.size();
+            HIP_TRY(h, hipGetLastError());
+            t0 = now_ms();
+            if (nv > 0)
+                HIP_TRY(h, hipMemcpyAsync(codes + (size_t)(g_first - s_off[0]) * (size_t)nv, M.d_codes, rows * (size_t)nv * 4, hipMemcpyDeviceToHost, S));
+            HIP_TRY(h, hipStreamSynchronize(S));  // (the next group re-uses the items and the codes)
+            h->stats.d2h_ms += now_ms() - t0;
+        }
+        return MIBN_OK;
+    }
+    int download(ElimRun &R) const {
+        if (p_e) HIP_TRY(R.h, hipMemcpyAsync(p_e + R.b0, R.M.d_m, (size_t)R.n * 8, hipMemcpyDeviceToHost, R.S));
+        return MIBN_OK;
+    }
+};
+
+// The argument checks of each entry point come first, in its own order; then the driver.
+int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes, double *log_p) {
+    if (!h || B < 0 || !e_off || (B && (!codes || !log_p))) return MIBN_E_ARG;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    MpePayload P{codes, log_p};
+    return run_elim(h, B, e_off, e_vars, e_codes, P);
+}
+
+int run_draw_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, const int64_t *s_off,
+                  uint64_t seed, uint32_t flags, int32_t *codes, double *p_e) {
+    if (!h || B < 0 || !e_off || !s_off) return MIBN_E_ARG;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (flags & ~(uint32_t)MIBN_DRAW_PRUNE) { h->err = "posterior sampling: unknown flag"; return MIBN_E_ARG; }
+    for (int64_t b = 0; b < B; ++b)
+        if (s_off[b + 1] < s_off[b] || s_off[b] < 0) { h->err = "posterior sampling: s_off must be non-negative and ascending"; return MIBN_E_ARG; }
+    if (B && s_off[B] > s_off[0] && !codes) return MIBN_E_ARG;
+    DrawPayload P{!(flags & MIBN_DRAW_PRUNE), s_off, seed, codes, p_e};
+    return run_elim(h, B, e_off, e_vars, e_codes, P);
+}
+
+}  // namespace
+
+// (nothing of a blocking call may still run on the main stream when the caller sees its error)
+extern "C" int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes,
+                              double *log_p) {
+    return drained_on_error(h, run_mpe_body(h, B, e_off, e_vars, e_codes, codes, log_p), drain_main_unchecked);
 }
 
 extern "C" int mibn_posterior_sample_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                            const int64_t *s_off, uint64_t seed, uint32_t flags, int32_t *codes, double *p_e) {
-    const int rc = run_draw_body(h, B, e_off, e_vars, e_codes, s_off, seed, flags, codes, p_e);
-    if (rc != MIBN_OK && h && !h->planner_only && h->stream) {  // (nothing of the call may still run when the caller sees the error)
-        const std::string keep = h->err;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipGetLastError();
-        h->err = keep;
-    }
-    return rc;
+    return drained_on_error(h, run_draw_body(h, B, e_off, e_vars, e_codes, s_off, seed, flags, codes, p_e), drain_main_unchecked);
 }
 
 extern "C" int mibn_query_batch(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *q_vars,
@@ -3028,11 +3002,7 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
     if (kind == MIBN_SCORE_BDEU && !(ess > 0 && ess < 1e300)) { h->err = "score: bdeu needs a finite equivalent sample size above 0"; return MIBN_E_ARG; }
     const mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
     const double t_start = now_ms();
-    h->stats = mibn_stats{};
-    for (int k = 0; k < kStatSlots; ++k) {
-        h->kstats[k] = mibn_kernel_stat{};
-        std::snprintf(h->kstats[k].name, sizeof(h->kstats[k].name), "%s", stat_name(k));
-    }
+    reset_last_stats(h);
     if (n_fam == 0) return MIBN_OK;
     // ---- everything is checked and packed on the host before anything is launched
     std::vector<int64_t> cells_of((size_t)n_fam, 0);
@@ -3178,7 +3148,7 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
     HIP_TRY(h, hipMemcpyAsync(scores, d_scores, (size_t)n_fam * 8, hipMemcpyDeviceToHost, S0));
     HIP_TRY(h, hipStreamSynchronize(S0));
     h->stats.d2h_ms += now_ms() - t0;
-    mibn_kernel_stat &kc = h->kstats[kNumKernels + 10], &ks = h->kstats[kNumKernels + 11];
+    mibn_kernel_stat &kc = h->kstats[kStatCount], &ks = h->kstats[kStatScore];
     for (size_t s = 0; s < subs.size(); ++s) {
         float ms_c = 0, ms_s = 0;
         HIP_TRY(h, hipEventElapsedTime(&ms_c, X.ev[3 * s], X.ev[3 * s + 1]));

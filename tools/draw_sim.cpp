@@ -25,28 +25,9 @@
 #include <string>
 #include <vector>
 
-#include "../sorobn_amd/csrc/planner.h"
+#include "sim_common.h"
 
 using namespace mibn;
-
-static std::vector<char> g_in;
-static size_t g_pos = 0;
-static const char *next_tok() {
-    while (g_pos < g_in.size() && (g_in[g_pos] == ' ' || g_in[g_pos] == '\n' || g_in[g_pos] == '\t' || g_in[g_pos] == '\r')) ++g_pos;
-    if (g_pos >= g_in.size()) { std::fprintf(stderr, "input ends early\n"); std::exit(2); }
-    const char *t = g_in.data() + g_pos;
-    while (g_pos < g_in.size() && !(g_in[g_pos] == ' ' || g_in[g_pos] == '\n' || g_in[g_pos] == '\t' || g_in[g_pos] == '\r')) ++g_pos;
-    if (g_pos < g_in.size()) g_in[g_pos++] = 0;
-    return t;
-}
-static int64_t geti() { return std::strtoll(next_tok(), nullptr, 10); }
-static uint64_t getu() { return std::strtoull(next_tok(), nullptr, 10); }
-static double getd() { return std::strtod(next_tok(), nullptr); }
-
-[[noreturn]] static void fail(int64_t b, const std::string &m) {
-    std::fprintf(stderr, "request %lld: %s\n", (long long)b, m.c_str());
-    std::exit(1);
-}
 
 // Philox4x32-10, counter = (i lo, i hi, stream, 0): gibbs_kernel.hip.h, philox_uniform
 static double philox_uniform(uint64_t i, uint32_t stream, uint32_t k0, uint32_t k1) {
@@ -64,30 +45,15 @@ static double philox_uniform(uint64_t i, uint32_t stream, uint32_t k0, uint32_t 
 
 int main(int argc, char **argv) {
     if (argc < 3) { std::fprintf(stderr, "usage: draw_sim net.txt codes.bin [margins.bin]\n"); return 2; }
-    FILE *f = std::fopen(argv[1], "rb");
-    if (!f) { std::perror(argv[1]); return 2; }
-    char buf[1 << 16];
-    size_t k;
-    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) g_in.insert(g_in.end(), buf, buf + k);
-    std::fclose(f);
-    g_in.push_back(0);
+    slurp(argv[1]);
     FILE *fc = std::fopen(argv[2], "wb");
     if (!fc) { std::perror(argv[2]); return 2; }
     FILE *fm = argc > 3 ? std::fopen(argv[3], "wb") : nullptr;
     if (argc > 3 && !fm) { std::perror(argv[3]); return 2; }
-    const int n = (int)geti();
-    std::vector<int32_t> card(n), scope_vars;
-    std::vector<int64_t> scope_off(n + 1), value_off(n + 1);
-    for (auto &c : card) c = (int32_t)geti();
-    for (auto &o : scope_off) o = geti();
-    scope_vars.resize((size_t)scope_off[n]);
-    for (auto &v : scope_vars) v = (int32_t)geti();
-    for (auto &o : value_off) o = geti();
-    std::vector<double> values((size_t)value_off[n]);
-    for (auto &v : values) v = getd();
     Network net;
-    const std::string e = net.set(n, card.data(), scope_off.data(), scope_vars.data(), value_off.data(), values.data());
-    if (!e.empty()) { std::fprintf(stderr, "set: %s\n", e.c_str()); return 2; }
+    read_network(net);
+    const int n = net.n_vars;
+    const std::vector<int32_t> &card = net.card;
     const uint64_t seed = getu();
     const bool prune = geti() != 0;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ 0x85EBCA6Bu;  // (the key of mibn_sample)
@@ -141,51 +107,23 @@ int main(int argc, char **argv) {
         int n_elim = 0;
         bool seen_final = false;
         for (uint32_t s = 0; s < n_steps; ++s) {
-            const uint32_t *w = prog.data() + off;
-            if ((w[0] & 0xff) != kKindGeneric) fail(b, "step " + std::to_string(s) + " is not GENERIC");
-            const int n_in = (w[0] >> 8) & 0xff, na = (w[0] >> 16) & 0xff;
-            const int cx = (int)(w[1] & 0xffff);
-            const uint32_t flags = w[1] >> 16;
+            const GenericStep g(b, s, prog.data() + off);
+            const int cx = g.cx;
+            const uint32_t flags = g.flags;
             const bool fin = flags & kFlagFinal;
             if (flags & kFlagMax) fail(b, "step " + std::to_string(s) + " carries the MAX flag");
             if (fin != (s + 1 == n_steps)) fail(b, "the FINAL step is not the last one");
             if (fin && !(flags & kFlagRaw)) fail(b, "FINAL step without the RAW flag");
             if (fin && cx > 1) fail(b, "FINAL step eliminates a variable");
             if (cx > 1) ++n_elim;
-            const int64_t cells = (int64_t)w[2] * (int64_t)w[3];
-            const int64_t out_off = (int64_t)((uint64_t)w[4] | ((uint64_t)w[5] << 32));
-            const uint32_t *p = w + kHdrWords;
-            std::vector<uint64_t> in_off(n_in);
-            std::vector<int64_t> xs(n_in);
-            for (int j = 0; j < n_in; ++j) { in_off[j] = (uint64_t)p[3 * j] | ((uint64_t)p[3 * j + 1] << 32); xs[j] = (int32_t)p[3 * j + 2]; }
-            const uint32_t *cd = p + 3 * n_in;
-            const int32_t *strd = (const int32_t *)(cd + na);
+            const int64_t cells = g.cells, out_off = g.out_off;
             if (!fin) {
                 for (auto &t : tabs)
                     if (out_off < t.first + t.second && t.first < out_off + cells) fail(b, "the output of step " + std::to_string(s) + " overlaps a kept table");
                 tabs.push_back({out_off, cells});
             }
-            std::vector<double> outv((size_t)cells);
-            std::vector<int64_t> o0(n_in);
-            for (int64_t o = 0; o < cells; ++o) {
-                int64_t r = o;
-                for (int j = 0; j < n_in; ++j) o0[j] = 0;
-                for (int a = 0; a < na; ++a) {
-                    const int64_t d = r % cd[a];
-                    r /= cd[a];
-                    for (int j = 0; j < n_in; ++j) o0[j] += d * strd[j * na + a];
-                }
-                double acc = 0;
-                for (int x = 0; x < std::max(1, cx); ++x) {
-                    double prod = 1;
-                    for (int j = 0; j < n_in; ++j) {
-                        const int64_t i = o0[j] + x * xs[j];
-                        prod *= (in_off[j] & kConstFlag) ? net.pool[(size_t)((in_off[j] & ~kConstFlag) + i)] : arena_at((int64_t)in_off[j] + i);
-                    }
-                    acc += prod;
-                }
-                outv[(size_t)o] = acc;
-            }
+            std::vector<double> outv((size_t)cells, 0.0);
+            g.visit(net, arena_at, [&](int64_t o, int, double prod) { outv[(size_t)o] += prod; });  // sum over x
             if (fin) {
                 if (cells != 1 || out_off != 0) fail(b, "FINAL step of more than one cell");
                 mass = outv[0];
@@ -193,7 +131,7 @@ int main(int argc, char **argv) {
             } else {
                 for (int64_t o = 0; o < cells; ++o) arena_at(out_off + o) = outv[(size_t)o];
             }
-            off += w[6];
+            off += g.words;
         }
         if (n_steps && !seen_final) fail(b, "no FINAL step");
         // the record

@@ -17,50 +17,17 @@
 #include <string>
 #include <vector>
 
-#include "../sorobn_amd/csrc/planner.h"
+#include "sim_common.h"
 
 using namespace mibn;
 
-static std::vector<char> g_in;
-static size_t g_pos = 0;
-static const char *next_tok() {
-    while (g_pos < g_in.size() && (g_in[g_pos] == ' ' || g_in[g_pos] == '\n' || g_in[g_pos] == '\t' || g_in[g_pos] == '\r')) ++g_pos;
-    if (g_pos >= g_in.size()) { std::fprintf(stderr, "input ends early\n"); std::exit(2); }
-    const char *t = g_in.data() + g_pos;
-    while (g_pos < g_in.size() && !(g_in[g_pos] == ' ' || g_in[g_pos] == '\n' || g_in[g_pos] == '\t' || g_in[g_pos] == '\r')) ++g_pos;
-    if (g_pos < g_in.size()) g_in[g_pos++] = 0;
-    return t;
-}
-static int64_t geti() { return std::strtoll(next_tok(), nullptr, 10); }
-static double getd() { return std::strtod(next_tok(), nullptr); }
-
-[[noreturn]] static void fail(int64_t b, const std::string &m) {
-    std::fprintf(stderr, "request %lld: %s\n", (long long)b, m.c_str());
-    std::exit(1);
-}
-
 int main(int argc, char **argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: max_sim net.txt\n"); return 2; }
-    FILE *f = std::fopen(argv[1], "rb");
-    if (!f) { std::perror(argv[1]); return 2; }
-    char buf[1 << 16];
-    size_t k;
-    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) g_in.insert(g_in.end(), buf, buf + k);
-    std::fclose(f);
-    g_in.push_back(0);
-    const int n = (int)geti();
-    std::vector<int32_t> card(n), scope_vars;
-    std::vector<int64_t> scope_off(n + 1), value_off(n + 1);
-    for (auto &c : card) c = (int32_t)geti();
-    for (auto &o : scope_off) o = geti();
-    scope_vars.resize((size_t)scope_off[n]);
-    for (auto &v : scope_vars) v = (int32_t)geti();
-    for (auto &o : value_off) o = geti();
-    std::vector<double> values((size_t)value_off[n]);
-    for (auto &v : values) v = getd();
+    slurp(argv[1]);
     Network net;
-    const std::string e = net.set(n, card.data(), scope_off.data(), scope_vars.data(), value_off.data(), values.data());
-    if (!e.empty()) { std::fprintf(stderr, "set: %s\n", e.c_str()); return 2; }
+    read_network(net);
+    const int n = net.n_vars;
+    const std::vector<int32_t> &card = net.card;
     const int64_t B = geti();
     for (int64_t b = 0; b < B; ++b) {
         const int ne = (int)geti();
@@ -102,31 +69,21 @@ int main(int argc, char **argv) {
         size_t off = 1;
         int n_flagged = 0;
         for (uint32_t s = 0; s < n_steps; ++s) {
-            const uint32_t *w = prog.data() + off;
-            if ((w[0] & 0xff) != kKindGeneric) fail(b, "step " + std::to_string(s) + " is not GENERIC");
-            const int n_in = (w[0] >> 8) & 0xff, na = (w[0] >> 16) & 0xff;
-            const int cx = (int)(w[1] & 0xffff);
-            const uint32_t flags = w[1] >> 16;
-            const bool fin = flags & kFlagFinal, mx = flags & kFlagMax;
+            const GenericStep g(b, s, prog.data() + off);
+            const int n_in = g.n_in, cx = g.cx;
+            const bool fin = g.flags & kFlagFinal, mx = g.flags & kFlagMax;
             if (cx > 1 && !mx) fail(b, "elimination step " + std::to_string(s) + " without the MAX flag");
             if (cx <= 1 && mx) fail(b, "product step " + std::to_string(s) + " with the MAX flag");
-            const int64_t cells = (int64_t)w[2] * (int64_t)w[3];
-            const int64_t out_off = (int64_t)((uint64_t)w[4] | ((uint64_t)w[5] << 32));
-            const uint32_t *p = w + kHdrWords;
-            std::vector<uint64_t> in_off(n_in);
-            std::vector<int64_t> xs(n_in);
-            for (int j = 0; j < n_in; ++j) { in_off[j] = (uint64_t)p[3 * j] | ((uint64_t)p[3 * j + 1] << 32); xs[j] = (int32_t)p[3 * j + 2]; }
-            const uint32_t *cd = p + 3 * n_in;
-            const int32_t *strd = (const int32_t *)(cd + na);
+            const int64_t cells = g.cells, out_off = g.out_off;
+            const std::vector<uint64_t> &in_off = g.in_off;
             // reads of intermediates
             for (int j = 0; j < n_in; ++j)
                 if (!(in_off[j] & kConstFlag))
                     for (size_t t = tabs.size(); t-- > 0;)
                         if (tabs[t].off == (int64_t)in_off[j]) { tabs[t].last_read = (int)s; break; }
-            int64_t am_off = -1;
+            const int64_t am_off = g.am_off;
             if (mx) {
                 ++n_flagged;
-                am_off = (int64_t)((uint64_t)w[7] | ((uint64_t)w[8] << 32));
                 const int64_t am_cells = (cells * 2 + 7) / 8;
                 for (auto &r : am)
                     if (am_off < r.first + r.second && r.first < am_off + am_cells) fail(b, "argmax tables overlap");
@@ -136,34 +93,15 @@ int main(int argc, char **argv) {
             if (!fin) tabs.push_back({out_off, cells, (int)s, (int)s});
             std::vector<double> outv((size_t)cells);
             std::vector<uint16_t> arg((size_t)cells);
-            std::vector<int64_t> o0(n_in);
-            for (int64_t o = 0; o < cells; ++o) {
-                int64_t r = o;
-                for (int j = 0; j < n_in; ++j) o0[j] = 0;
-                for (int a = 0; a < na; ++a) {
-                    const int64_t d = r % cd[a];
-                    r /= cd[a];
-                    for (int j = 0; j < n_in; ++j) o0[j] += d * strd[j * na + a];
-                }
-                double best = 0;
-                int bx = 0;
-                for (int x = 0; x < std::max(1, cx); ++x) {
-                    double prod = 1;
-                    for (int j = 0; j < n_in; ++j) {
-                        const int64_t i = o0[j] + x * xs[j];
-                        prod *= (in_off[j] & kConstFlag) ? net.pool[(size_t)((in_off[j] & ~kConstFlag) + i)] : arena_at((int64_t)in_off[j] + i);
-                    }
-                    if (x == 0 || prod > best) { best = prod; bx = x; }
-                }
-                outv[(size_t)o] = best;
-                arg[(size_t)o] = (uint16_t)bx;
-            }
+            g.visit(net, arena_at, [&](int64_t o, int x, double prod) {  // max over x, the lowest x that attains it
+                if (x == 0 || prod > outv[(size_t)o]) { outv[(size_t)o] = prod; arg[(size_t)o] = (uint16_t)x; }
+            });
             for (int64_t o = 0; o < cells; ++o) {
                 if (fin) { if (cells != 1 || out_off != 0) fail(b, "FINAL step of more than one cell"); m = outv[0]; }
                 else arena_at(out_off + o) = outv[(size_t)o];
             }
             if (mx) std::memcpy(reinterpret_cast<char *>(arena.data() + am_off), arg.data(), (size_t)cells * 2);
-            off += w[6];
+            off += g.words;
         }
         // live intermediates against argmax tables: a table written at step s and last read at step t is live over [s, t]; the argmax
         // table of step k must not overlap it when s <= k <= t (nor may a later intermediate overwrite an argmax table)
