@@ -24,6 +24,7 @@
 #include "count_kernel.hip.h"
 #include "score_kernel.hip.h"
 #include "planner.h"
+#include "plan_policy.h"
 #include "tiny_kernel.hip.h"
 #include "sweep_kernel.hip.h"
 #include "ve_kernel.hip.h"
@@ -264,22 +265,9 @@ struct mibn_ctx {
     char *d_tiny_req = nullptr;  // request arrays of the call in flight
     size_t tiny_req_cap = 0;
     Staging tiny_stage;
-    // adaptive planning (option "adaptive"): when planning, not the GPU, bounds a stream of calls (few host cores per
-    // GPU), the elimination-order search - 40 % of the planning time - moves to the device (order_kernel); for networks the
-    // device search does not cover (> 128 variables) the greedy min-fill search is reserved for ever more expensive
-    // requests instead; both are given back when the host has slack again
-    int adaptive = 0;
-    bool auto_search = false;  // gpu_search was switched on by the adaptive policy
-    bool auto_emit = false;    // gpu_emit was
-    int host_bound_streak = 0;
-    bool adaptive_seeded = false;
-    double base_minfill = 5e6, seen_plan_ms = 0, seen_kernel_ms = 0;  // (minfill_above: 2e7 up to round 6's last day; with order_effort 1 min-fill also supplies the opening candidate - 5e6: 1.7 % less GPU time per step for a tenth more planning, profiles/r06_cd_ab.log)
-    double base_second_above = 2e7;  // option second_above (the calls the device plans run without the second emission: run_batch)
+    PlanPolicy pol;                  // the adaptive planning policy and the share rule of the device planner (plan_policy.h)
     int second_on_device = 0;        // option: 1 = device-planned calls emit the runner-up too (tests: the wave planner's second emission)
-    double retired_requests = 0, seen_requests = 0;  // requests whose kernel time has been booked (the unit of kernel_ms in the policy's windows)
-    double host_rate = 0;                            // requests per ms the host's workers planned beside the device planner (smoothed; 0: not measured)
-    double kernel_ms_per_req = 0;                    // retired kernel time per request over the policy's last windows (smoothed; 0: not measured)
-    double fixed_ms_per_req = 0;                     // the host's side of a call besides planning - validation, schedule - per request (smoothed)
+    double retired_requests = 0;     // requests whose kernel time has been booked (the unit of kernel_ms in the policy's windows)
     // device order search (order_kernel)
     int plan_lanes = 0;              // requests per wave of order_kernel / emit_kernel (1..64); 0 = by the rank's planning threads: plan_lanes_now()
     int plan_waves = 16;             // waves per workgroup of the two (1..16): see order_kernel
@@ -317,9 +305,6 @@ struct mibn_ctx {
     int wave_sort = 1;                // option: 0 = by index
     Staging emit_in, emit_out;       // pinned, read / written by the kernels themselves: request arrays in, per-request results and work items out
     hipEvent_t emit_ev[2] = {nullptr, nullptr};  // around the planner's kernels
-    double emit_share = 0.75;        // the device's share of a chunk, the host's workers plan the rest meanwhile: follows the two measured
-                                     // rates so that both finish together (option emit_share: 0 < x <= 1 pins it)
-    double emit_share_opt = -1;
     BatchPlan emit_dev, emit_host;   // the two parts of a chunk before they are joined
     uint32_t emit_words = 6144;      // words of a request's program slot (doubles after a chunk that did not fit)
     int64_t emit_single = 0;         // requests of device-planned chunks the host planned because they exceeded a device limit
@@ -547,9 +532,9 @@ constexpr int kEngineSmallCells = 512;
 int mibn_create_planner(mibn_t **out) {
     if (!out) return MIBN_E_ARG;
     auto *h = new mibn_ctx();
-    h->net.order_effort = 1; h->net.second_above = h->base_second_above;  // (the engine's default; a bare Network - the tools, the oracle - keeps round 5's search)
+    h->net.order_effort = 1; h->net.second_above = h->pol.base_second_above;  // (the engine's default; a bare Network - the tools, the oracle - keeps round 5's search)
     h->net.small_cells = kEngineSmallCells;
-    h->net.minfill_above = h->base_minfill;
+    h->net.minfill_above = h->pol.base_minfill;
     h->planner_only = true;
     *out = h;
     return MIBN_OK;
@@ -562,9 +547,9 @@ int mibn_create(int device, mibn_t **out) {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return MIBN_E_NODEVICE;
     if (device < 0 || device >= n) return MIBN_E_ARG;
     auto *h = new mibn_ctx();
-    h->net.order_effort = 1; h->net.second_above = h->base_second_above;
+    h->net.order_effort = 1; h->net.second_above = h->pol.base_second_above;
     h->net.small_cells = kEngineSmallCells;
-    h->net.minfill_above = h->base_minfill;
+    h->net.minfill_above = h->pol.base_minfill;
     h->device = device;
     if (hipSetDevice(device) != hipSuccess) { delete h; return MIBN_E_NODEVICE; }
     hipDeviceProp_t prop;
@@ -707,20 +692,20 @@ int mibn_set_option(mibn_t *h, const char *name, double value) {
     else if (n == "plan_sort") h->plan_sort = (int)value;
     else if (n == "wave_sort") h->wave_sort = value != 0;  // wave_plan_kernel hands out the requests with the most relevant variables first (default 1)
     else if (n == "plan_lanes") h->plan_lanes = std::max(0, std::min(64, (int)value));  // requests per wave of the device planner's kernels
-    else if (n == "emit_share") { h->emit_share_opt = value > 0 ? std::min(1.0, value) : -1; if (value > 0) h->emit_share = h->emit_share_opt; }  // the device's share of a chunk (<= 0: follows the measured rates)
+    else if (n == "emit_share") { h->pol.emit_share_opt = value > 0 ? std::min(1.0, value) : -1; if (value > 0) h->pol.emit_share = h->pol.emit_share_opt; }  // the device's share of a chunk (<= 0: follows the measured rates)
     else if (n == "emit_words") h->emit_words = (uint32_t)std::max(1024, std::min(1 << 20, (int)value));  // words of a request's device program slot
     else if (n == "gpu_search") h->gpu_search = std::max(0, std::min(2, (int)value));  // elimination-order search on the device
         // (order_kernel): 1 = the first chunk of a call on the host, the rest of the call by one launch; 2 = every chunk, synchronously (tests)
     else if (n == "adaptive") {
-        h->adaptive = value != 0;
-        if (!h->adaptive) {  // what the policy had switched goes back
-            h->net.minfill_above = h->base_minfill;
-            if (h->auto_emit) { h->gpu_emit = 0; h->auto_emit = false; }
-            if (h->auto_search) { h->gpu_search = 0; h->auto_search = false; }
-            h->adaptive_seeded = false;
+        h->pol.adaptive = value != 0;
+        if (!h->pol.adaptive) {  // what the policy had switched goes back
+            h->net.minfill_above = h->pol.base_minfill;
+            if (h->pol.auto_emit) { h->gpu_emit = 0; h->pol.auto_emit = false; }
+            if (h->pol.auto_search) { h->gpu_search = 0; h->pol.auto_search = false; }
+            h->pol.adaptive_seeded = false;
         }
     }
-    else if (n == "minfill_above") { h->base_minfill = value; h->net.minfill_above = value; }  // bytes of the best sweep above which min-fill runs  // small-network kernel (one lane per request, no planning) where eligible
+    else if (n == "minfill_above") { h->pol.base_minfill = value; h->net.minfill_above = value; }  // bytes of the best sweep above which min-fill runs  // small-network kernel (one lane per request, no planning) where eligible
     else if (n == "fuse") h->net.fuse = value != 0;
     else if (n == "plan_cache") h->net.plan_cache = value != 0;  // plan templates for repeated request shapes
     else if (n == "chain") h->net.chain = value != 0;  // CHAIN form: three variables per pass
@@ -736,7 +721,7 @@ int mibn_set_option(mibn_t *h, const char *name, double value) {
         }
     }
     else if (n == "order_effort") h->net.order_effort = std::max(0, std::min(1, (int)value));  // 1: more candidate orders, the byte model's best two both emitted where the best is expensive (order_search.h)
-    else if (n == "second_above") { h->base_second_above = value; h->net.second_above = value; }  // modelled bytes above which the runner-up order is emitted too
+    else if (n == "second_above") { h->pol.base_second_above = value; h->net.second_above = value; }  // modelled bytes above which the runner-up order is emitted too
     else if (n == "second_on_device") h->second_on_device = value != 0;  // 1: also in the calls the device plans (default: those run without the second emission)
     else if (n == "order_weights") h->net.order_weights = std::max(0, std::min(64, (int)value));  // class-weighted byte model of the order search (0: plain section-8(d) bytes)
     else if (n == "sweep_canon") h->net.sweep_canon = value != 0;  // test hook: 0 = the sweep kernel's general path for every step
@@ -759,8 +744,8 @@ int mibn_set_network(mibn_t *h, int32_t n_vars, const int32_t *card, const int64
     std::string e = h->net.set(n_vars, card, scope_off, scope_vars, value_off, values);
     if (!e.empty()) { h->err = e; h->has_net = false; return MIBN_E_ARG; }
     h->has_net = true;
-    h->adaptive_seeded = false;  // (the adaptive policy starts over with a new network)
-    if (h->auto_emit) { h->gpu_emit = 0; h->auto_emit = false; }
+    h->pol.adaptive_seeded = false;  // (the adaptive policy starts over with a new network)
+    if (h->pol.auto_emit) { h->gpu_emit = 0; h->pol.auto_emit = false; }
     if (!h->planner_only) {
         HIP_TRY(h, hipSetDevice(h->device));
         if (h->d_pool) { HIP_TRY(h, hipFree(h->d_pool)); h->d_pool = nullptr; }
@@ -842,15 +827,19 @@ uint32_t *pinned_grow(void *, uint32_t *old, size_t used, size_t new_cap) {
     return p;
 }
 
+// a pinned staging buffer of at least `bytes` (a quarter of headroom; what it held is not kept)
+int pinned(mibn_ctx *h, mibn_ctx::Staging &sg, size_t bytes) {
+    if (bytes <= sg.cap) return MIBN_OK;
+    if (sg.p) { HIP_TRY(h, hipHostFree(sg.p)); sg.p = nullptr; sg.cap = 0; }
+    HIP_TRY(h, hipHostMalloc((void **)&sg.p, bytes + bytes / 4 + 4096, hipHostMallocDefault));
+    sg.cap = bytes + bytes / 4 + 4096;
+    return MIBN_OK;
+}
+
 // async upload through a pinned staging buffer (one per destination and set: reused only after retire())
 int upload(mibn_ctx *h, mibn_ctx::Staging &sg, void *dst, const void *src, size_t bytes) {
     if (!bytes) return MIBN_OK;
-    if (bytes > sg.cap) {
-        if (sg.p) { HIP_TRY(h, hipHostFree(sg.p)); sg.p = nullptr; sg.cap = 0; }
-        const size_t cap = bytes + bytes / 4 + 4096;
-        HIP_TRY(h, hipHostMalloc((void **)&sg.p, cap, hipHostMallocDefault));
-        sg.cap = cap;
-    }
+    if (int rc = pinned(h, sg, bytes)) return rc;
     std::memcpy(sg.p, src, bytes);
     HIP_TRY(h, hipMemcpyAsync(dst, sg.p, bytes, hipMemcpyHostToDevice, h->copy_stream));
     return MIBN_OK;
@@ -906,6 +895,18 @@ void ensure_pool(mibn_ctx *h) {
 
 // name of statistics slot k: the classes of work (split_kinds), then the kernels as launched
 const char *stat_name(int k) { return k < kNumKernels ? kernel_name(k) : kStatSlotNames[k - kNumKernels]; }
+
+// adds to statistics slot `slot`: of the last call (`last`) and / or of the totals (`total`)
+void book_stat(mibn_ctx *h, int slot, double launches, double ms, double bytes, double items, bool last, bool total) {
+    for (mibn_kernel_stat *ks : {last ? &h->kstats[slot] : nullptr, total ? &h->ktotal[slot] : nullptr}) {
+        if (!ks) continue;
+        if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(slot));
+        ks->launches += launches;
+        ks->ms += ms;
+        ks->alg_bytes += bytes;
+        ks->items += items;
+    }
+}
 
 // every call that reports last-call statistics starts from zeroed, named slots
 void reset_last_stats(mibn_ctx *h) {
@@ -983,26 +984,12 @@ int retire(mibn_ctx *h, mibn_ctx::Set &st) {
                 if (e != mibn_ctx::Set::Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[e])); lo = std::min(lo, (double)x); }
             for (size_t e : {t.e1, t.e3, t.e5, t.e7})
                 if (e != mibn_ctx::Set::Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[e])); hi = std::max(hi, (double)x); }
-            for (mibn_kernel_stat *ks : {&h->kstats[kStatLevelGroup], &h->ktotal[kStatLevelGroup]}) {
-                if (ks == &h->kstats[kStatLevelGroup] && !mine) continue;
-                if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(kStatLevelGroup));
-                ks->launches += 1;
-                ks->ms += std::max(0.0, hi - lo);
-                ks->alg_bytes += t.bytes;
-                ks->items += t.items;
-            }
+            book_stat(h, kStatLevelGroup, 1, std::max(0.0, hi - lo), t.bytes, t.items, mine, true);
             continue;
         }
         if (mine) h->stats.n_launches += 1;
         h->total.n_launches += 1;
-        for (mibn_kernel_stat *ks : {&h->kstats[t.kid], &h->ktotal[t.kid]}) {
-            if (ks == &h->kstats[t.kid] && !mine) continue;
-            if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(t.kid));
-            ks->launches += 1;
-            ks->ms += ms;
-            ks->alg_bytes += t.bytes;
-            ks->items += t.items;
-        }
+        book_stat(h, t.kid, 1, ms, t.bytes, t.items, mine, true);
         if (h->trace) std::fprintf(stderr, "[mibn launch] %-32s wgs %8.0f MB %10.2f ms %8.4f -> %7.1f GB/s\n", h->kstats[t.kid].name, t.items, t.bytes / 1e6, ms, t.bytes / ms / 1e6);
     }
     if (h->trace && st.gap_from >= 0 && st.ev_used > 0) {
@@ -1045,14 +1032,6 @@ int next_event(mibn_ctx *h, mibn_ctx::Set &st, size_t &idx, hipStream_t stream =
 }  // namespace
 
 namespace {
-int pinned(mibn_ctx *h, mibn_ctx::Staging &sg, size_t bytes) {
-    if (bytes <= sg.cap) return MIBN_OK;
-    if (sg.p) { HIP_TRY(h, hipHostFree(sg.p)); sg.p = nullptr; sg.cap = 0; }
-    HIP_TRY(h, hipHostMalloc((void **)&sg.p, bytes + bytes / 4 + 4096, hipHostMallocDefault));
-    sg.cap = bytes + bytes / 4 + 4096;
-    return MIBN_OK;
-}
-
 // Requests per wave of the device planner's kernels.  The lanes of a wave run different requests, every data-dependent branch
 // diverges, so a wave's time grows with its lanes in use: fewer lanes in more waves plan faster and take more of the chip from the
 // VE kernels.  A rank of one or two planning threads is bound by its planning capacity (host + device), not by its kernels: 24
@@ -1348,15 +1327,6 @@ int plan_on_device_launch(mibn_ctx *h, uint32_t flags, int64_t b0, int64_t b1, c
 
 // Waits for the device planner and fills `ck` for the n requests it planned, like plan_batch would (one "worker": the device).
 // *dev_ms = duration of the kernels.  Returns MIBN_OK, an error, or 1 (see above).
-#ifndef MIBN_HOST_KEEPS_UP
-#define MIBN_HOST_KEEPS_UP 1.25  // adaptive policy: (requests the host plans per ms) x (kernel ms per request) at or above which the device planner is dropped
-#endif
-#ifndef MIBN_POLICY_WINDOW_MS
-#define MIBN_POLICY_WINDOW_MS 150.0  // adaptive policy: planning and retired kernel time a window must hold before it is judged (ranks of more than four planning threads)
-#endif
-#ifndef MIBN_HOST_BOUND_RATIO
-#define MIBN_HOST_BOUND_RATIO 1.15  // adaptive policy: planner wall time over GPU kernel time above which a stream of calls counts as host-bound
-#endif
 int plan_on_device_collect(mibn_ctx *h, int64_t b0, int64_t n, BatchPlan &ck, double *dev_ms, std::vector<int64_t> *beyond_list) {
     hipStream_t P = h->search_stream;
     const size_t stride = h->emit_words;
@@ -1513,12 +1483,7 @@ int expect_run(mibn_t *h, const double *d_results) {
     HIP_TRY(h, hipStreamSynchronize(S));
     float ms = 0;
     HIP_TRY(h, hipEventElapsedTime(&ms, X.ev[0], X.ev[1]));
-    mibn_kernel_stat &ks = h->kstats[kStatExpect];
-    if (!ks.name[0]) std::snprintf(ks.name, sizeof(ks.name), "%s", stat_name(kStatExpect));
-    ks.launches += launches;
-    ks.ms += ms;
-    ks.alg_bytes += 8.0 * ((double)(P.req.size() + P.big.size()) + 2.0 * (double)P.part_cells + 2.0 * (double)nA);
-    ks.items += (double)X.B;
+    book_stat(h, kStatExpect, launches, ms, 8.0 * ((double)(P.req.size() + P.big.size()) + 2.0 * (double)P.part_cells + 2.0 * (double)nA), (double)X.B, true, false);
     h->stats.kernel_ms += ms;
     h->stats.n_launches += launches;
     return MIBN_OK;
@@ -1542,11 +1507,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     const size_t bad_off = req_bytes, res_off = req_bytes + 16;
     const size_t bytes = res_off + (zero_copy ? res_cells * 8 : 0) + 64;
     mibn_ctx::Staging &sg = h->tiny_stage;
-    if (bytes > sg.cap) {
-        if (sg.p) { HIP_TRY(h, hipHostFree(sg.p)); sg.p = nullptr; sg.cap = 0; }
-        HIP_TRY(h, hipHostMalloc((void **)&sg.p, bytes + bytes / 4, hipHostMallocDefault));
-        sg.cap = bytes + bytes / 4;
-    }
+    if ((rc = pinned(h, sg, bytes))) return rc;
     if (!zero_copy) {
         if ((rc = ensure(h, h->d_tiny_req, h->tiny_req_cap, bytes))) return rc;
         if ((rc = ensure(h, h->d_results[0], h->results_cap[0], res_cells))) return rc;
@@ -1634,13 +1595,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     h->total.alg_bytes += io_bytes;
     h->total.total_ms += h->stats.total_ms;
     h->total.d2h_ms += h->stats.d2h_ms;
-    for (mibn_kernel_stat *ks : {&h->kstats[kStatTiny], &h->ktotal[kStatTiny]}) {
-        std::snprintf(ks->name, sizeof(ks->name), "%s", "tiny_kernel");
-        ks->launches += 1;
-        ks->ms += ms;
-        ks->alg_bytes += io_bytes;
-        ks->items += grid;
-    }
+    book_stat(h, kStatTiny, 1, ms, io_bytes, grid, true, true);
     if (h->expect) {
         if ((rc = expect_run(h, h->d_results[0]))) return rc;
         h->stats.total_ms = now_ms() - t_start;
@@ -1648,128 +1603,115 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     return MIBN_OK;
 }
 
-// Plan, upload and launch a batch.  Synchronous (ticket == nullptr): waits and writes `out`.  Asynchronous: the
-// results land in a pinned buffer, *ticket identifies the call for mibn_wait; up to two calls may be in flight, so
-// the host plans call s+1 while the GPU still runs call s.
-int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
-              const int32_t *e_codes, const int64_t *out_off, double *out, int32_t *ticket) {
-    if (!h || B < 0 || !q_off || !e_off || !out_off || (B && !out && !h->expect)) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
-    const double t_start = now_ms();
-    ++h->call_id;
-    h->search_ms = 0;
-    h->emit_ms = 0;
-    reset_last_stats(h);
-    const int slot = h->next_slot;
-    if (h->pend[slot].active) { h->err = "two asynchronous calls are already in flight: mibn_wait the older one first"; return MIBN_E_STATE; }
-    if (ticket) *ticket = slot;
-    if (B == 0) return MIBN_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->tiny && h->tiny_ok && !ticket && B < 0x7ffffff0 && out_off[B] - out_off[0] >= B) {
-        const int rc_tiny = run_tiny(h, flags | (h->net.prune ? 0u : (uint32_t)MIBN_Q_NOPRUNE), B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, t_start);
-        if (rc_tiny != 1) return rc_tiny;  // 1: a request does not fit the kernel (query table too large) - plan it
+// ---------------------------------------------------------------------------------------------- shared by the query driver and run_elim
+// evidence labels outside their variables' domains: no program runs for the request (an empty posterior / zero probability)
+bool evidence_outside_domain(const Network &net, const Request &rq, const int32_t *codes) {
+    for (int i = 0; i < rq.ne; ++i)
+        if (codes[i] < 0 || codes[i] >= net.card[rq.evars[i]]) return true;
+    return false;
+}
+
+// The wave [r0, r1) of a chunk of n requests: consecutive requests whose private arenas fit the scratch budget together; a wave also
+// ends once it holds `target` cells (kFullWaves: never - every wave as full as the budget allows).  `cells`: the wave's scratch.
+constexpr int64_t kFullWaves = INT64_MAX;
+int cut_wave(mibn_ctx *h, const std::vector<int64_t> &arena_need, int64_t r0, int64_t n, int64_t budget_cells, int64_t target, int64_t &r1, int64_t &cells) {
+    for (r1 = r0, cells = 0; r1 < n; ++r1) {
+        const int64_t need = (arena_need[(size_t)r1] + 15) & ~int64_t(15);
+        if (r1 > r0 && (cells + need > budget_cells || cells >= target)) break;
+        cells += need;
     }
-    // MIBN_Q_UNNORMALISED (P(q, e) / P(e) requests): planned by the host's workers with the options' base search effort - no device
-    // planner, no adaptive policy; the net's policy-tuned fields are restored on every exit
-    const bool raw = (flags & MIBN_Q_UNNORMALISED) != 0;
-    struct NetEffort {
-        Network *net = nullptr;
-        double second_above = 0, minfill_above = 0;
-        ~NetEffort() { if (net) { net->second_above = second_above; net->minfill_above = minfill_above; } }
-    } keep_effort;
-    if (raw) {
-        keep_effort.net = &h->net;
-        keep_effort.second_above = h->net.second_above;
-        keep_effort.minfill_above = h->net.minfill_above;
-        h->net.minfill_above = h->base_minfill;
+    if (cells > budget_cells) { h->err = "a request needs " + std::to_string(8.0 * cells / 1e9) + " GB of scratch, above the arena budget"; return MIBN_E_NOMEM; }
+    return MIBN_OK;
+}
+
+// The arena of `lane` holds need_bytes: grown with headroom (chunks differ by ~10 %: re-allocating tens of GB costs hundreds of ms),
+// after S has drained - earlier launches of the lane still use the old arena.
+int grow_arena(mibn_ctx *h, int lane, size_t need_bytes, int64_t budget_cells, hipStream_t S) {
+    if (need_bytes <= h->arena_bytes[lane]) return MIBN_OK;
+    HIP_TRY(h, hipStreamSynchronize(S));
+    if (h->d_arena[lane]) { HIP_TRY(h, hipFree(h->d_arena[lane])); h->d_arena[lane] = nullptr; h->arena_bytes[lane] = 0; }
+    const size_t want = std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3));
+    HIP_TRY(h, hipMalloc(&h->d_arena[lane], want));
+    h->arena_bytes[lane] = want;
+    return MIBN_OK;
+}
+
+// The workers' program buffers of plan `ck`, back to back into d_prog from word `base` on.  Enqueued on `stream`, not waited for: `bufs`
+// must stay as they are until the copies have run.
+int upload_programs(mibn_ctx *h, uint32_t *d_prog, size_t base, const std::vector<ProgBuf> &bufs, const BatchPlan &ck, hipStream_t stream) {
+    for (size_t t = 0; t < ck.thread_words.size(); ++t) {
+        if (ck.thread_words[t]) HIP_TRY(h, hipMemcpyAsync(d_prog + base, bufs[t].data, ck.thread_words[t] * 4, hipMemcpyHostToDevice, stream));
+        base += ck.thread_words[t];
     }
-    // validation (bayes_net.py:840-845) and the out-of-domain-evidence short cut
-    std::vector<char> skip((size_t)B, 0);
-    for (int64_t b = 0; b < B; ++b) {
+    return MIBN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the query driver
+// run_query: the driver behind mibn_query_batch, mibn_query_batch_ex, mibn_submit_batch and mibn_expect_batch - plan, upload and launch a
+// batch.  Synchronous (ticket == nullptr): waits and writes `out`.  Asynchronous: the results land in a pinned buffer, *ticket identifies
+// the call for mibn_wait; up to two calls may be in flight, so the host plans call s+1 while the GPU still runs call s.
+// It is a sequence of stages over the call in flight (QueryRun); each says what it leaves enqueued, and not waited for, when it returns.
+// Host memory that asynchronous work reads or writes is pinned and owned by the context - a set's st.bufs / st.xbufs and st.stage[],
+// h->emit_in / h->emit_out, h->search_in / h->search_out, h->res_stage[] - never a local of a stage.  A stage returns MIBN_OK or the
+// error it has set in h->err, wherever it stands: run_batch drains every stream before the caller sees an error (drained_on_error).
+struct QueryRun {
+    mibn_ctx *h;
+    uint32_t flags;
+    bool raw;  // MIBN_Q_UNNORMALISED
+    int64_t B;
+    const int64_t *q_off;
+    const int32_t *q_vars;
+    const int64_t *e_off;
+    const int32_t *e_vars, *e_codes;
+    const int64_t *out_off;
+    double t_start;
+    std::vector<char> skip;  // per request: 1 = evidence outside its domain (no steps), 2 = the empty product (the host writes it)
+    int slot = 0;            // of h->d_results / h->pend
+    double *d_results = nullptr;
+    size_t res_cells = 0;
+    int n_lanes = 1;
+    int64_t budget_cells = 0;  // scratch budget of a lane
+    bool lane1_used = false;
+    bool emit_on = false, search_on = false;  // whole chunks planned on the device / the order search on the device, the emission on the host
+    int64_t search_b0 = -1;                   // the search window: requests [search_b0, B) searched by one launch, waited for once (search_done)
+    bool search_done = false, gpu_busy = false, short_first = false;
+    int64_t n_chunks = 0;
+    double call_fixed_ms = 0;  // the host's side of this call besides planning (the share rule of wave_plan_kernel)
+    double call_plan_ms = 0;   // the workers' planning of the host's shares and the waits for the device planner: what the call's time to the last launch is NOT fixed cost
+};
+
+// Stage: validation (bayes_net.py:840-845) and the out-of-domain-evidence short cut -> R.skip.  Nothing is enqueued.
+int query_validate(QueryRun &R) {
+    mibn_ctx *h = R.h;
+    R.skip.assign((size_t)R.B, 0);
+    for (int64_t b = 0; b < R.B; ++b) {
         Request rq;
-        rq.nq = (int32_t)(q_off[b + 1] - q_off[b]);
-        rq.qvars = q_vars + q_off[b];
-        rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
-        rq.evars = e_vars + e_off[b];
-        rq.raw = raw;
+        rq.nq = (int32_t)(R.q_off[b + 1] - R.q_off[b]);
+        rq.qvars = R.q_vars + R.q_off[b];
+        rq.ne = (int32_t)(R.e_off[b + 1] - R.e_off[b]);
+        rq.evars = R.e_vars + R.e_off[b];
+        rq.raw = R.raw;
         if (!request_is_valid(h->net, rq)) { h->err = "request " + std::to_string(b) + ": " + validate_request(h->net, rq); return MIBN_E_ARG; }
         int64_t cells = 1;
         for (int i = 0; i < rq.nq; ++i) cells *= h->net.card[rq.qvars[i]];
-        if (out_off[b + 1] - out_off[b] != cells) { h->err = "request " + std::to_string(b) + ": out_off does not match the query table size"; return MIBN_E_ARG; }
-        for (int i = 0; i < rq.ne; ++i) {
-            int32_t c = e_codes[e_off[b] + i];
-            if (c < 0 || c >= h->net.card[rq.evars[i]]) skip[b] = 1;  // label outside the domain -> empty posterior
-        }
+        if (R.out_off[b + 1] - R.out_off[b] != cells) { h->err = "request " + std::to_string(b) + ": out_off does not match the query table size"; return MIBN_E_ARG; }
+        if (evidence_outside_domain(h->net, rq, R.e_codes + R.e_off[b])) R.skip[(size_t)b] = 1;  // -> empty posterior
         // P(e) of empty evidence with pruning: the relevant set is empty and the program's FINAL step has no input - the empty
         // product, 1.0, which no kernel form computes: the host writes it after the download
-        if (raw && rq.nq == 0 && rq.ne == 0 && h->net.prune && !(flags & MIBN_Q_NOPRUNE)) skip[b] = 2;
+        if (R.raw && rq.nq == 0 && rq.ne == 0 && h->net.prune && !(R.flags & MIBN_Q_NOPRUNE)) R.skip[(size_t)b] = 2;
     }
-    ensure_pool(h);
-    if (h->trace) std::fprintf(stderr, "[mibn plan] validation of %lld requests %.2f ms\n", (long long)B, now_ms() - t_start);
-    double call_fixed_ms = now_ms() - t_start;  // the host's side of this call besides planning (the share rule of wave_plan_kernel)
-    double call_plan_ms = 0;  // the workers' planning of the host's shares and the waits for the device planner: what the call's time to the last launch is NOT fixed cost
-    if (h->adaptive && !h->adaptive_seeded && !raw) {
-        // A rank with a handful of planning threads (8 ranks on a 16-CPU quota: 2-4 each) cannot plan a stream like C3 at the rate
-        // its GPU executes it (67 / 133 k queries/s at 2 / 4 threads against 280 k): it starts with the device planner instead of
-        // finding that out over several host-bound calls; the share controller gives the planning back where the host keeps up.
-        h->adaptive_seeded = true;
-        if (h->pool->size() <= 4 && h->order_net_ok && h->emit_net_ok && !h->gpu_emit) { h->gpu_emit = 1; h->auto_emit = true; }
-    }
-    if (h->adaptive && !raw) {
-        // over the calls since the last adjustment: host planning wall time against GPU kernel time (retired launches)
-        const double dp = h->total.plan_ms - h->seen_plan_ms, dk = h->total.kernel_ms - h->seen_kernel_ms;
-        if (h->call_id <= 2) {  // the first calls pay one-time costs (thread pool, pinned buffers, first kernel load): not a trend
-            h->seen_plan_ms = h->total.plan_ms;
-            h->seen_kernel_ms = h->total.kernel_ms;
-            h->seen_requests = h->retired_requests;
-        } else if (dp > 20.0 && dk > 20.0 && (h->pool->size() <= 4 || (dp > MIBN_POLICY_WINDOW_MS && dk > MIBN_POLICY_WINDOW_MS))) {
-            // (a rank that is not starved judges windows of at least MIBN_POLICY_WINDOW_MS of planning AND of retired kernel time - two
-            //  to three calls: the kernel time of a call is booked when its launches retire, up to two calls late, and a window of one
-            //  call saw "100 ms of planning, 136 ms of kernels" as often as "100 against 68" on a steadily host-bound stream - n_evidence
-            //  = 16 in round 5's session D: the two host-bound windows in a row the switch asks for came once in twelve calls)
-            const double dreq = h->retired_requests - h->seen_requests;
-            if (dreq > 0) h->kernel_ms_per_req = h->kernel_ms_per_req > 0 ? 0.5 * h->kernel_ms_per_req + 0.5 * dk / dreq : dk / dreq;
-            // The device planner goes again where the host ALONE would keep up: the requests its workers plan per ms (measured
-            // beside the device planner) x the kernel time per request must cover a request with a margin - the margin also
-            // absorbs that the kernels of device-planned chunks run ~ 17 % longer than they would without the planner's kernels.
-            // (Up to session S the rule was "the device's share has fallen to 0.3": a 6-thread rank - share 0.33 - oscillated
-            // around it, 219 k queries/s; a fixed lower bar, 0.2, kept the device planner on a full-quota rank that had
-            // switched it on during its first calls: 278 k instead of 300 k.  profiles/r04_s_policy.log, r04_t_policy.log)
-            if (h->auto_emit && h->host_rate > 0 && dreq > 0 && h->host_rate * (dk / dreq) >= MIBN_HOST_KEEPS_UP) {
-                h->gpu_emit = 0;
-                h->auto_emit = false;
-                h->host_bound_streak = 0;
-            } else if (dp > MIBN_HOST_BOUND_RATIO * dk && ++h->host_bound_streak >= 2) {  // (round 6: twice in a row for every rank - a full-quota rank used to switch on one window, and the window behind a step's barrier, with the first call's planning exposed, tripped it for a per mille of the requests: profiles/r06_ce_ab.log, r06_cf_ab.log)  // (twice in a row: the kernel time of a call is booked when its
-                                                                          // launches retire, up to two calls late - one window can mislead)
-                // host-bound: first hand the order search to the device (same orders, no more bytes); networks it does
-                // not cover give up the min-fill search for ever more expensive requests instead
-                if (h->order_net_ok && h->emit_net_ok && !h->gpu_emit) {  // the whole planning, not only the search
-                    h->gpu_emit = 1;
-                    h->auto_emit = true;
-                    h->host_rate = 0;  // (measured afresh beside the device planner: a rate left over from another workload - the line's
-                                       //  n_evidence = 1 variant plans 1 000 requests per ms, n_evidence = 16 500 - made "the host alone would
-                                       //  keep up" drop the device planner one window after every switch: round 5's session ZZ)
-                }
-                else if (h->order_net_ok && !h->emit_net_ok && !h->gpu_search) { h->gpu_search = 1; h->auto_search = true; }
-                else if (!h->order_net_ok) h->net.minfill_above = std::min(h->net.minfill_above * 8.0, 1e18);
-            } else if (dp <= MIBN_HOST_BOUND_RATIO * dk) {
-                h->host_bound_streak = 0;
-            }
-            if (dp < 0.3 * dk) {
-                if (h->net.minfill_above > h->base_minfill) h->net.minfill_above = std::max(h->net.minfill_above / 8.0, h->base_minfill);
-                else if (h->auto_search) { h->gpu_search = 0; h->auto_search = false; }
-            }
-            h->seen_plan_ms = h->total.plan_ms;
-            h->seen_kernel_ms = h->total.kernel_ms;
-            h->seen_requests = h->retired_requests;
-        }
-    }
+    return MIBN_OK;
+}
+
+// Stage: call setup - the results buffer, the busy-time epoch, the arena budget and what this call plans where.  Enqueued on the main
+// stream on return: the epoch record (an idle GPU), the zeroing of d_results and zero_ev, which lane 1's stream waits for.
+int query_setup(QueryRun &R) {
+    mibn_ctx *h = R.h;
     int rc;
-    const size_t res_cells = (size_t)(out_off[B] - out_off[0]);
-    if ((rc = ensure(h, h->d_results[slot], h->results_cap[slot], res_cells))) return rc;
-    double *const d_results = h->d_results[slot];
-    const int n_lanes = h->n_streams > 1 ? 2 : 1;
+    R.res_cells = (size_t)(R.out_off[R.B] - R.out_off[0]);
+    if ((rc = ensure(h, h->d_results[R.slot], h->results_cap[R.slot], R.res_cells))) return rc;
+    R.d_results = h->d_results[R.slot];
+    R.n_lanes = h->n_streams > 1 ? 2 : 1;
     {
         bool idle = true;
         for (auto &st : h->set) idle = idle && !st.busy;
@@ -1779,458 +1721,449 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
             h->busy_until = 0;
         }
     }
-    HIP_TRY(h, hipMemsetAsync(d_results, 0, res_cells * 8, h->stream));
-    if (n_lanes > 1) {  // lane 1 starts this call's work after the results buffer is zeroed
+    HIP_TRY(h, hipMemsetAsync(R.d_results, 0, R.res_cells * 8, h->stream));
+    if (R.n_lanes > 1) {  // lane 1 starts this call's work after the results buffer is zeroed
         if (!h->zero_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->zero_ev, hipEventDisableTiming));
         HIP_TRY(h, hipEventRecord(h->zero_ev, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->zero_ev, 0));
     }
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
-    const int64_t budget_cells =
-        (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0] + h->arena_bytes[1])) / 8.0) / n_lanes;
-    bool lane1_used = false;
-    int64_t n_chunks = 0;
+    R.budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0] + h->arena_bytes[1])) / 8.0) / R.n_lanes;
     // order_effort >= 1 (more candidate orders, the byte model's best two both emitted): the wave planner has it, order_kernel / emit_kernel do
     // not - where the wave planner does not cover the network the host plans (never two kinds of plans in one stream)
     bool effort_ok = true;
-    if (h->net.order_effort >= 1 && (h->gpu_emit || h->gpu_search) && !raw) {
+    if (h->net.order_effort >= 1 && (h->gpu_emit || h->gpu_search) && !R.raw) {
         std::unique_ptr<WNet> probe(new WNet);
         effort_ok = h->wave_plan && h->net.wave_view(*probe);
     }
-    const bool emit_on = !raw && h->gpu_emit && h->order_net_ok && h->emit_net_ok && effort_ok;  // whole chunks planned on the device
+    R.emit_on = !R.raw && h->gpu_emit && h->order_net_ok && h->emit_net_ok && effort_ok;
     // A rank that needs the device planner has no planning time to spare - and on the device the second emission costs more GPU time than
     // the bytes it saves give back (a two-thread rank: 243 against 273 k queries/s, profiles/r06_bh_ab.log): its calls take the extra
     // candidates only, on the host's share and on the device's alike.  (Like minfill_above below: the search effort follows the load.)
-    h->net.second_above = (emit_on && !h->second_on_device) ? 1e300 : h->base_second_above;
-    const bool search_on = !raw && !emit_on && h->gpu_search && h->order_net_ok && h->net.order_effort < 1;
-    int64_t search_b0 = -1;
-    bool search_done = false;
+    h->net.second_above = (R.emit_on && !h->second_on_device) ? 1e300 : h->pol.base_second_above;
+    R.search_on = !R.raw && !R.emit_on && h->gpu_search && h->order_net_ok && h->net.order_effort < 1;
     // a short first chunk gets an idle GPU going while the host plans the first full-size one (first_chunk = 2: also when
     // an earlier asynchronous call still keeps the GPU busy; 0: never)
-    bool gpu_busy = false;
-    for (auto &st : h->set) gpu_busy = gpu_busy || (st.busy && st.ev_used && hipEventQuery(st.ev[st.ev_used - 1]) == hipErrorNotReady);
+    for (auto &st : h->set) R.gpu_busy = R.gpu_busy || (st.busy && st.ev_used && hipEventQuery(st.ev[st.ev_used - 1]) == hipErrorNotReady);
     (void)hipGetLastError();  // (hipErrorNotReady is an answer, not an error: do not leave it for the check after the launches)
-    const bool short_first = h->first_chunk == 2 || (h->first_chunk == 1 && !gpu_busy);
-    for (int64_t b0 = 0, b1 = 0; b0 < B; b0 = b1, ++n_chunks) {
-        // A call that finds the GPU idle (the first of a stream of calls, a blocking call) starts with a short chunk - a quarter -
-        // that gets the GPU going while the host plans the rest; in steady state - the previous call still running - a call
-        // is cut into full chunks.  (Ramping the chunks up from 1 024 requests, doubling, was measured and dropped: seven small
-        // plan_batch calls cost 95 ms of host time instead of 63, and the chunk sets - their pinned buffers sized by the small
-        // chunks they had seen - grew under the clock: profiles/r03_i_pipeline_start.log.)
-        // With the device order search on, every call starts with an eighth of a chunk whose orders the host searches while
-        // ONE launch searches the rest of the call (a call of a single chunk would otherwise be searched on the host whole).
-        const bool dev_split = search_on && h->gpu_search == 1;
-        int64_t size = h->chunk;
-        if (b0 == 0 && dev_split) size = std::max<int64_t>(1024, h->chunk / 8);
-        else if (emit_on) size = h->chunk;  // (the host has nothing to plan while a short first chunk runs)
-        else if (b0 == 0 && short_first && (B > h->chunk || !gpu_busy)) size = std::max<int64_t>(1024, h->chunk / 4);
-        b1 = std::min(B, b0 + size);
-        const int64_t n = b1 - b0;
-        mibn_ctx::Set &st = h->set[h->set_cursor];
-        const int lane = n_lanes > 1 ? (h->set_cursor & 1) : 0;  // consecutive chunks alternate between the lanes
-        hipStream_t S = lane ? h->stream2 : h->stream;
-        lane1_used = lane1_used || lane == 1;
-        h->set_cursor = (h->set_cursor + 1) % h->n_sets;
-        if ((rc = retire(h, st))) return rc;  // its buffers are about to be rewritten
-        double t0 = now_ms();
-        // device order search: the first (short) chunk of a call is searched on the host while one launch searches the
-        // rest of the call on the device; the later chunks only emit
-        const uint8_t *orders = nullptr;
-        const int32_t *order_len = nullptr;
-        if (search_on && h->gpu_search == 2) {  // test mode: every chunk searched on the device, synchronously
-            if ((rc = search_orders_async(h, flags, b0, b1, q_off, q_vars, e_off, e_vars))) return rc;
-            if ((rc = search_wait(h))) return rc;
-            orders = reinterpret_cast<const uint8_t *>(h->search_out.p);
-            order_len = reinterpret_cast<const int32_t *>(h->search_out.p + (size_t)n * 128);
-        } else if (search_on) {
-            if (n_chunks == 0 && b1 < B) {
-                if ((rc = search_orders_async(h, flags, b1, B, q_off, q_vars, e_off, e_vars))) return rc;
-                search_b0 = b1;
-            } else if (search_b0 >= 0) {
-                if (!search_done) { if ((rc = search_wait(h))) return rc; search_done = true; h->search_ms += now_ms() - t0; }
-                orders = reinterpret_cast<const uint8_t *>(h->search_out.p) + (size_t)(b0 - search_b0) * 128;
-                order_len = reinterpret_cast<const int32_t *>(h->search_out.p + (size_t)(B - search_b0) * 128) + (b0 - search_b0);
-            }
-        }
-        BatchPlan &ck = st.plan;
-        // every error exit of the device-planner path: the planner's kernels (they read pinned request arrays and write pinned
-        // results) and the chunks this call has already launched are drained before the caller sees the error - ADVICE r3
-        auto bail = [&](int code) {
-            (void)hipStreamSynchronize(h->search_stream);
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamSynchronize(h->stream2);
-            for (auto &la : h->aux)
-                for (hipStream_t a : la) (void)hipStreamSynchronize(a);
-            return code;
-        };
-        bool on_device = false;
-        std::vector<int64_t> beyond;  // requests of the device's part that exceed a device limit (kEmitErrDevice): the host plans them
-        int64_t nd = 0;          // requests [b0, b0 + nd) planned by the device, the rest by the host's workers meanwhile
-        size_t prog_base = 0;    // words of st.d_prog the device has written (the host's programs follow)
-        if (emit_on) {
-            nd = h->gpu_emit == 2 ? n : std::min<int64_t>(n, std::max<int64_t>(64, (int64_t)((double)n * std::min(h->emit_share, h->emit_share_opt > 0 ? 1.0 : (wave_mode(h) ? 0.99 : 0.95)) + 0.5)));
-            if (n - nd < 256) nd = n;  // (without a pinned share the host keeps at least a twentieth: its rate stays measured)
-            const size_t stride = h->emit_words;
-            if ((rc = plan_on_device_launch(h, flags, b0, b0 + nd, q_off, q_vars, e_off, e_vars, e_codes, out_off, skip.data(), st, (size_t)n * stride))) return bail(rc);
-            const double t_launched = now_ms();
-            BatchPlan &hp = h->emit_host, &dp = h->emit_dev;
-            double host_ms = 0, dev_ms = 0;
-            if (nd < n) {
-                const double th = now_ms();
-                plan_batch(h->net, *h->pool, st.bufs, b0 + nd, b1, q_off, q_vars, e_off, e_vars, e_codes, out_off, skip.data(), hp,
-                           (flags & MIBN_Q_NOPRUNE) != 0, nullptr, nullptr, b0);
-                host_ms = now_ms() - th;
-                call_plan_ms += host_ms;
-                if (!hp.err.empty()) { h->err = hp.err; return bail(MIBN_E_LIMIT); }
-            }
-            const double tw = now_ms();
-            rc = plan_on_device_collect(h, b0, nd, nd < n ? dp : ck, &dev_ms, &beyond);
-            h->emit_ms += now_ms() - tw;
-            call_plan_ms += now_ms() - tw;
-            if (h->trace >= 2) std::fprintf(stderr, "[mibn plan] collect returned %d at %.2f ms of the block\n", rc, now_ms() - t0);
-            for (mibn_kernel_stat *ks : {&h->kstats[kStatPlanner], &h->ktotal[kStatPlanner]}) {  // (beside the chunk in flight: their time is not GPU busy time of its own)
-                if (!ks->name[0]) std::snprintf(ks->name, sizeof(ks->name), "%s", stat_name(kStatPlanner));
-                ks->launches += 2;
-                ks->ms += dev_ms;
-                ks->items += (double)nd;
-            }
-#if defined(MIBN_EMIT_PROF)
-            if (h->trace) {
-                unsigned long long hp[12], z[12] = {0};
-                HIP_TRY(h, hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_emit_prof), sizeof(hp)));
-                HIP_TRY(h, hipMemcpyToSymbol(HIP_SYMBOL(g_emit_prof), z, sizeof(z)));
-                static const char *names[11] = {"begin (relevant set, CPT slices)", "key / pos / slot sets", "factors of x", "sweep candidates", "SWEEP 5 / 4", "CHAIN",
-                                                "SWEEP 3 / 2", "pair", "single elimination", "final product", "work items"};
-                double tot = 0;
-                for (int k = 0; k < 11; ++k) tot += (double)hp[k];
-                for (int k = 0; k < 11; ++k) std::fprintf(stderr, "[mibn emit phases] %-36s %6.1f us per request  %5.1f %%\n", names[k], (double)hp[k] / 100.0 / (double)nd, 100.0 * (double)hp[k] / tot);
-            }
-#endif
-            if (h->trace) std::fprintf(stderr, "[mibn plan] chunk of %lld: device %lld requests (upload + launch %.2f ms, kernels %.2f ms, wait + collect %.2f ms), host %lld requests %.2f ms\n",
-                                       (long long)n, (long long)nd, t_launched - t0, dev_ms, now_ms() - tw, (long long)(n - nd), host_ms);
-            if (rc < 0 || rc > 1) return bail(rc);
-            if (rc == 0 && nd < n && hp.total_words > (size_t)(n - nd) * stride) rc = 1;  // (the host's programs do not fit behind the device's)
-            on_device = rc == 0;
-            if (on_device && nd < n) {
-                // join the two parts: the device's requests first
-                const int T = (int)hp.tags.size();
-                ck.st = dp.st;
-                ck.st.alg_bytes += hp.st.alg_bytes; ck.st.alg_flops += hp.st.alg_flops; ck.st.n_steps += hp.st.n_steps;
-                ck.st.max_step_cells = std::max(dp.st.max_step_cells, hp.st.max_step_cells);
-                ck.arena_cells = std::max(dp.arena_cells, hp.arena_cells);
-                ck.err.clear();
-                ck.tags.resize((size_t)T + 1);
-                for (int t = 0; t < T; ++t) ck.tags[(size_t)t].swap(hp.tags[(size_t)t]);
-                ck.tags[(size_t)T].swap(dp.tags[0]);
-                ck.thread_words = hp.thread_words;
-                auto join = [&](auto &dst, const auto &a, const auto &b) { dst.assign(a.begin(), a.end()); dst.insert(dst.end(), b.begin(), b.end()); };
-                join(ck.cost, dp.cost, hp.cost);
-                join(ck.arena_need, dp.arena_need, hp.arena_need);
-                join(ck.tag_first, dp.tag_first, hp.tag_first);
-                join(ck.tag_count, dp.tag_count, hp.tag_count);
-                join(ck.local_off, dp.local_off, hp.local_off);
-                ck.thread_of.assign((size_t)nd, T);
-                ck.thread_of.insert(ck.thread_of.end(), hp.thread_of.begin(), hp.thread_of.end());
-                prog_base = (size_t)nd * stride;
-                ck.prog_off = dp.prog_off;
-                for (uint64_t o : hp.prog_off) ck.prog_off.push_back(prog_base + o);
-                ck.total_words = prog_base + hp.total_words;
-                // the share that would have let both finish together (the device's kernels ran beside the chunk in flight, like they will)
-                // The planner's kernels are latency-bound - one request per lane, their duration hardly depends on how many
-                // requests they plan - so the host's share is what its workers plan in that time, at the rate just measured.
-                // (whole chunks only: the tail of a call - 20 624 requests behind seven chunks of 32 768 in bench.py's 250 000-request
-                //  steps - gives the latency-bound device a smaller fraction than it takes of a full chunk; fed into the average,
-                //  the tails pushed the share below the switch-off threshold of the policy above and the planning of a 4-thread
-                //  rank oscillated between the device and the host alone: 187 k queries/s, profiles/r04_h_threads.log)
-                // (host_ms > 0.02, not > 1: a stream answered from plan templates - n_evidence = 1 once its 9 900 shapes are stored - plans
-                //  its 13 000 requests in 0.7 ms; with the old bar its rate was never measured, "the host alone would keep up" never
-                //  fired and the device planner stayed on at three quarters of every chunk: 430 instead of 550 k queries/s, session N)
-                if (host_ms > 0.02) h->host_rate = h->host_rate > 0 ? (wave_mode(h) ? 0.75 : 0.5) * h->host_rate + (wave_mode(h) ? 0.25 : 0.5) * (double)(n - nd) / host_ms : (double)(n - nd) / host_ms;
-                if (h->emit_share_opt <= 0 && host_ms > 0.02 && dev_ms > 1.0 && 4 * n >= 3 * h->chunk) {
-                    if (wave_mode(h) && h->kernel_ms_per_req > 0) {
-                        // wave_plan_kernel's time grows with the requests it is given, and it is GPU time taken from the VE kernels: the
-                        // device gets what the host cannot plan while the GPU works through the chunk -
-                        //   fixed + (n - nd) ih  <=  0.85 (kv n + kp nd)     ih: ms per request of the host's workers, kv: kernel ms per
-                        // request (retired launches, the adaptive policy's windows), kp: planner ms per request (just measured, beside
-                        // the kernels), fixed: the host's side of a call besides planning (validation, the schedule).  (The planning
-                        // rates alone left a two-thread rank host-bound - 223 against 262 k queries/s; a feedback rule on the policy's
-                        // planner-wall / kernel-time ratio counted the waits for the device as host time and ended at a share of 0.99:
-                        // profiles/r06_r_ab.log, r06_s_ab.log)
-                        // (ih: the smoothed rate and the slower of it and this chunk's - the workers of a rank with the whole CPU quota plan in
-                        //  bursts, 35 000 n_evidence = 16 requests in 38 ms one call and 74 ms the next: profiles/r06_x_share16.log)
-                        const double ih = std::max(host_ms / (double)(n - nd), h->host_rate > 0 ? 1.0 / h->host_rate : 0.0), kv = h->kernel_ms_per_req, kp = dev_ms / (double)nd;
-                        const double fixed = h->fixed_ms_per_req * (double)n;
-                        const double target = std::max(0.03, std::min(0.99, ((double)n * ih + fixed - 0.85 * kv * (double)n) / ((ih + 0.85 * kp) * (double)n)));
-                        h->emit_share = 0.5 * h->emit_share + 0.5 * target;
-                        if (h->trace) std::fprintf(stderr, "[mibn share] host %.4f ms/request (%lld in %.1f ms), kernels %.5f ms/request, planner %.5f ms/request, fixed %.1f ms -> target %.3f, share %.3f\n",
-                                                   ih, (long long)(n - nd), host_ms, kv, kp, fixed, target, h->emit_share);
-                    } else {
-                        const double host_n = (double)(n - nd) / host_ms * dev_ms;
-                        h->emit_share = std::max(0.25, std::min(1.0, 0.5 * h->emit_share + 0.5 * (1.0 - host_n / (double)n)));
-                    }
-                }
-            }
-        }
-        if (on_device && !beyond.empty()) {
-            // The requests of the device's part that exceed one of wave_plan_kernel's limits: the host plans THEM (round 6: a refused
-            // request used to send its whole chunk to the host - n_evidence = 16 met a limit five times in 200 000 requests and lost a
-            // third of its rate) - one plan_batch over the device's range with everything else masked out; a program goes into its
-            // request's own slot of the device program buffer, its work items and statistics take the place the kernel left empty.
-            std::vector<char> mask(skip.begin(), skip.end());
-            for (int64_t i = 0; i < nd; ++i) mask[(size_t)(b0 + i)] = 1;
-            for (int64_t i : beyond) mask[(size_t)(b0 + i)] = skip[(size_t)(b0 + i)];
-            BatchPlan &xp = st.xplan;
-            plan_batch(h->net, *h->pool, st.xbufs, b0, b0 + nd, q_off, q_vars, e_off, e_vars, e_codes, out_off, mask.data(), xp,
-                       (flags & MIBN_Q_NOPRUNE) != 0, nullptr, nullptr, b0);
-            if (!xp.err.empty()) { h->err = xp.err; return bail(MIBN_E_LIMIT); }
-            const size_t stride = h->emit_words;
-            const size_t X = ck.tags.size();
-            ck.tags.resize(X + xp.tags.size());
-            for (size_t t = 0; t < xp.tags.size(); ++t) ck.tags[X + t] = xp.tags[t];
-            bool fits = true;
-            for (int64_t i : beyond) {
-                const uint32_t *w = st.xbufs[(size_t)xp.thread_of[(size_t)i]].data + xp.local_off[(size_t)i];
-                size_t words = 1;
-                for (uint32_t k = 0; k < w[0]; ++k) words += w[words + 6];
-                if (words + kMaxStepWords > stride) { fits = false; break; }
-                HIP_TRY(h, hipMemcpyAsync(st.d_prog + (size_t)i * stride, w, words * 4, hipMemcpyHostToDevice, h->copy_stream));
-                ck.prog_off[(size_t)i] = (uint64_t)i * stride;
-                ck.local_off[(size_t)i] = ck.prog_off[(size_t)i];
-                ck.thread_of[(size_t)i] = (int32_t)(X + (size_t)xp.thread_of[(size_t)i]);
-                ck.tag_first[(size_t)i] = xp.tag_first[(size_t)i];
-                ck.tag_count[(size_t)i] = xp.tag_count[(size_t)i];
-                ck.cost[(size_t)i] = xp.cost[(size_t)i];
-                ck.arena_need[(size_t)i] = xp.arena_need[(size_t)i];
-            }
-            ck.st.alg_bytes += xp.st.alg_bytes; ck.st.alg_flops += xp.st.alg_flops; ck.st.n_steps += xp.st.n_steps;
-            ck.st.max_step_cells = std::max(ck.st.max_step_cells, xp.st.max_step_cells);
-            ck.arena_cells = std::max(ck.arena_cells, xp.arena_cells);
-            if (h->trace || h->emit_single < 4)
-                std::fprintf(stderr, "[mibn plan] device planner: %zu of %lld requests beyond a device limit (first: request %lld): planned on the host\n", beyond.size(), (long long)nd,
-                             (long long)(b0 + beyond[0]));
-            h->emit_single += (int64_t)beyond.size();
-            if (!fits) on_device = false;  // (a program longer than its slot: the host plans the chunk after all)
-        }
-        if (!on_device)
-            plan_batch(h->net, *h->pool, st.bufs, b0, b1, q_off, q_vars, e_off, e_vars, e_codes, out_off, skip.data(), ck,
-                       (flags & MIBN_Q_NOPRUNE) != 0, orders, order_len, -1, false, raw);
-        if (on_device && h->gpu_emit == 2) {
-            // test mode: the host plans the chunk too - programs, work items and statistics must agree exactly
-            const size_t stride = h->emit_words;
-            std::vector<uint32_t> dev((size_t)n * stride);
-            HIP_TRY(h, hipStreamSynchronize(h->copy_stream));  // (the programs of requests beyond a device limit, planned on the host above)
-            HIP_TRY(h, hipMemcpy(dev.data(), st.d_prog, dev.size() * 4, hipMemcpyDeviceToHost));
-            BatchPlan ref;
-            plan_batch(h->net, *h->pool, st.bufs, b0, b1, q_off, q_vars, e_off, e_vars, e_codes, out_off, skip.data(), ref,
-                       (flags & MIBN_Q_NOPRUNE) != 0, nullptr, nullptr);
-            if (!ref.err.empty()) { h->err = ref.err; return bail(MIBN_E_LIMIT); }
-            for (int64_t i = 0; i < n; ++i) {
-                const uint32_t *hw = st.bufs[ref.thread_of[i]].data + ref.local_off[i], *dw = dev.data() + (size_t)ck.prog_off[(size_t)i];  // (= i x stride + the words in front of the program)
-                size_t words = 1;
-                for (uint32_t k = 0; k < hw[0]; ++k) words += hw[words + 6];
-                for (size_t k = 0; k < words; ++k)
-                    if (hw[k] != dw[k]) {
-                        size_t off = 1, step = 0;  // (which step holds the word)
-                        while (step + 1 < hw[0] && off + hw[off + 6] <= k) { off += hw[off + 6]; ++step; }
-                        h->err = "device planner: request " + std::to_string(b0 + i) + " word " + std::to_string(k) + " of " + std::to_string(words) + " (step " + std::to_string(step) + " of " +
-                                 std::to_string(hw[0]) + ", kind " + std::to_string(hw[off] & 0xff) + ", word " + std::to_string(k - off) + " of the step's " + std::to_string(hw[off + 6]) + "): host " +
-                                 std::to_string(hw[k]) + " device " + std::to_string(dw[k]) + "; device program " + std::to_string(dw[0]) + " steps";
-                        return bail(MIBN_E_STATE);
-                    }
-                const Tag *ht = ref.tags[ref.thread_of[i]].data() + ref.tag_first[i], *dt = ck.tags[(size_t)ck.thread_of[i]].data() + ck.tag_first[i];
-                bool same = ref.tag_count[i] == ck.tag_count[i] && ref.arena_need[i] == ck.arena_need[i] && ref.cost[i] == ck.cost[i];
-                for (uint32_t k = 0; same && k < ref.tag_count[i]; ++k)
-                    same = ht[k].rel_off == dt[k].rel_off && ht[k].a == dt[k].a && ht[k].wgs == dt[k].wgs && ht[k].level == dt[k].level &&
-                           ht[k].kid == dt[k].kid && ht[k].bytes == dt[k].bytes;
-                if (!same) { h->err = "device planner: work items / statistics of request " + std::to_string(b0 + i) + " differ from the host's"; return bail(MIBN_E_STATE); }
-            }
-        }
-        if (!ck.err.empty()) { h->err = ck.err; (void)hipStreamSynchronize(h->stream); (void)hipStreamSynchronize(h->stream2); return MIBN_E_LIMIT; }
-        for (auto &b : st.bufs)
-            if (b.cap && !b.data) { h->err = "pinned host allocation failed"; return MIBN_E_HIP; }
-        h->stats.plan_ms += now_ms() - t0;
-        if (h->trace >= 2) std::fprintf(stderr, "[mibn plan] chunk planning block %.2f ms (on the device: %d)\n", now_ms() - t0, (int)on_device);
-        if (!on_device && (rc = ensure(h, st.d_prog, st.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
-        if ((rc = ensure(h, st.d_prog_off, st.prog_off_cap, (size_t)n))) return rc;
-        if ((rc = ensure(h, st.d_arena_off, st.arena_off_cap, (size_t)n))) return rc;
-        t0 = now_ms();
-        size_t base = prog_base;
-        for (size_t t = 0; t < ck.thread_words.size(); ++t) {
-            if (ck.thread_words[t])
-                HIP_TRY(h, hipMemcpyAsync(st.d_prog + base, st.bufs[t].data, ck.thread_words[t] * 4, hipMemcpyHostToDevice, h->copy_stream));
-            base += ck.thread_words[t];
-        }
-        if ((rc = upload(h, st.stage[0], st.d_prog_off, ck.prog_off.data(), (size_t)n * 8))) return rc;
-        h->stats.h2d_ms += now_ms() - t0;
-        // waves: consecutive requests whose private arenas fit the scratch budget together
-        // (a chunk that does not fit is cut into waves of about EQUAL scratch - ceil(total / budget) of them - not into full
-        //  waves and a remainder: round 4 runs chunks of 52 429 requests = 224 GB, close to the budget)
-        int64_t chunk_cells = 0;
-        for (int64_t r = 0; r < n; ++r) chunk_cells += (ck.arena_need[r] + 15) & ~int64_t(15);
-        const int64_t n_waves_min = std::max<int64_t>(1, (chunk_cells + budget_cells - 1) / std::max<int64_t>(1, budget_cells));
-        const int64_t wave_target = std::min(budget_cells, chunk_cells / n_waves_min + (chunk_cells / n_waves_min) / 64 + 1);
-        for (int64_t r0 = 0; r0 < n;) {
-            int64_t r1 = r0, cells = 0;
-            while (r1 < n) {
-                const int64_t need = (ck.arena_need[r1] + 15) & ~int64_t(15);
-                if (r1 > r0 && (cells + need > budget_cells || (n_waves_min > 1 && cells >= wave_target))) break;
-                cells += need;
-                ++r1;
-            }
-            if (cells > budget_cells) { h->err = "a request needs " + std::to_string(8.0 * cells / 1e9) + " GB of scratch, above the arena budget"; return MIBN_E_NOMEM; }
-            t0 = now_ms();
-            Schedule &sc = st.sched;
-            build_schedule(h->net, ck, st.bufs, r0, r1, sc);
-            h->stats.plan_ms += now_ms() - t0;
-            call_fixed_ms += now_ms() - t0;
-            if (h->trace) std::fprintf(stderr, "[mibn plan] build_schedule %.2f ms (%zu items, %zu workgroups, %zu launches)\n", now_ms() - t0, sc.items.size(), sc.wg_item.size(), sc.launches.size());
-            const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
-            if (need_bytes > h->arena_bytes[lane]) {
-                // grow with headroom (chunks differ by ~10 %): re-allocating tens of GB costs hundreds of ms
-                HIP_TRY(h, hipStreamSynchronize(S));  // earlier launches of the lane still use the old arena
-                if (h->d_arena[lane]) { HIP_TRY(h, hipFree(h->d_arena[lane])); h->d_arena[lane] = nullptr; h->arena_bytes[lane] = 0; }
-                const size_t want = std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3));
-                HIP_TRY(h, hipMalloc(&h->d_arena[lane], want));
-                h->arena_bytes[lane] = want;
-            }
-            // items / arena offsets of this wave live until the wave's launches have run: one wave per set at a
-            // time unless the chunk had to be split (then wait for the previous wave first)
-            if (r0 > 0) { HIP_TRY(h, hipStreamSynchronize(S)); HIP_TRY(h, hipStreamSynchronize(h->copy_stream)); }
-            if ((rc = ensure(h, st.d_items, st.items_cap, sc.items.size()))) return rc;
-            if ((rc = ensure(h, st.d_wg_item, st.wg_item_cap, sc.wg_item.size()))) return rc;
-            t0 = now_ms();
-            if ((rc = upload(h, st.stage[1], st.d_arena_off, sc.arena_off.data(), (size_t)(r1 - r0) * 8))) return rc;
-            if ((rc = upload(h, st.stage[2], st.d_items, sc.items.data(), sc.items.size() * sizeof(Item)))) return rc;
-            if ((rc = upload(h, st.stage[3], st.d_wg_item, sc.wg_item.data(), sc.wg_item.size() * sizeof(uint32_t)))) return rc;
-            if (!st.uploaded) HIP_TRY(h, hipEventCreateWithFlags(&st.uploaded, hipEventDisableTiming));
-            HIP_TRY(h, hipEventRecord(st.uploaded, h->copy_stream));
-            HIP_TRY(h, hipStreamWaitEvent(S, st.uploaded, 0));  // the kernels of this wave wait for its uploads only
-            h->stats.h2d_ms += now_ms() - t0;
-            LevelArgs A;
-            A.prog = st.d_prog;
-            A.prog_off = st.d_prog_off + r0;
-            A.arena_off = st.d_arena_off;
-            A.pool = h->d_pool;
-            A.arena = h->d_arena[lane];
-            A.results = d_results + (out_off[b0] - out_off[0]);
-            double n_wg = 0;
-            if (h->trace) st.gap_from = h->n_waves ? (int)((h->n_waves - 1) & 3) : -1;
-            // Every launch is bracketed by its own pair of events on the lane's stream; the wave as a whole by the first and
-            // the last one (retire() books the GPU's busy time from them).
-            size_t e_first = 0;
-            if ((rc = next_event(h, st, e_first, S))) return rc;
-            A.items = st.d_items;
-            // option overlap: the sweep launch of a level goes to a second stream, next to the level kernel's launch of the same
-            // level (their items belong to different requests); level L + 1 starts on either stream when BOTH launches of level L
-            // have finished.  The tail of one launch - a sweep workgroup lives ~100 us - then runs under the body of the other.
-            const bool two = h->overlap != 0;
-            // streams of a wave: 0 = S (the level kernel), 1 = S2 (the sweep kernel), 2 = S3 (the segment kernel, option seg_kernel).  The
-            // launches of level L run side by side; a launch of level L + 1 waits for ALL launches of level L: the one on its own
-            // stream by stream order, the others through their end events (`prev`: the ends of the previous level - not the running
-            // `last`, or the launches of one level would serialise: ADVICE r3).
-            constexpr int kNS = 4;  // (3 = S4: the MFMA kernel, option mfma_kernel)
-            hipStream_t SS[kNS] = {S, h->aux[lane][0], h->aux[lane][1], h->aux[lane][2]};
-            constexpr size_t kNone = mibn_ctx::Set::Timed::kNone;
-            long last[kNS], prev[kNS], saw[kNS][kNS];
-            for (int a = 0; a < kNS; ++a) { last[a] = prev[a] = -1; for (int b = 0; b < kNS; ++b) saw[a][b] = -1; }
-            int cur_level = -1;
-            mibn_ctx::Set::Timed pair{-2, kNone, kNone, 0.0, 0.0, h->call_id};  // the level in progress, as one concurrent launch group
-            auto close_pair = [&]() {
-                if (pair.e0 != kNone || pair.e2 != kNone || pair.e4 != kNone || pair.e6 != kNone) st.timed.push_back(pair);
-                pair = mibn_ctx::Set::Timed{-2, kNone, kNone, 0.0, 0.0, h->call_id};
-            };
-            if (two) {  // (the uploads, the previous wave's kernels: the arena is theirs until then)
-                for (int j = 1; j < kNS; ++j) HIP_TRY(h, hipStreamWaitEvent(SS[j], st.ev[e_first], 0));
-            }
-            for (size_t li = 0; li < sc.launches.size();) {
-                // one launch of the level kernel per level (all its classes of work together) unless split_kinds, one of the
-                // segment kernel for the level's segments (the first class of a level; option seg_kernel) and one of the sweep kernel
-                // for its SWEEP items (the last class: its own LDS budget)
-                size_t lj = li + 1;
-                const bool sweep = sc.launches[li].kid == kKidSweep;
-                const bool seg = h->seg_kernel && !h->split_kinds && sc.launches[li].kid == kKidSeg;
-                // (the two classes of ve_mfma_kernel are the last ones of a level in front of the sweep class: planner.cpp ClassOrder)
-                auto is_mfma1 = [&](int kid) { return h->mfma_kernel && !h->split_kinds && (kid == kKidFiber0 + 4 || kid == kKidFiber0 + 6 + 4); };
-                const bool mf = is_mfma1(sc.launches[li].kid);
-                double bytes = sc.launches[li].alg_bytes;
-                size_t grid = sc.launches[li].grid;
-                if (!h->split_kinds && !sweep && !seg)
-                    for (; lj < sc.launches.size() && sc.launches[lj].level == sc.launches[li].level && sc.launches[lj].kid != kKidSweep &&
-                           is_mfma1(sc.launches[lj].kid) == mf; ++lj) {
-                        bytes += sc.launches[lj].alg_bytes;
-                        grid += sc.launches[lj].grid;
-                    }
-                const Launch &L = sc.launches[li];
-                A.wg_item = st.d_wg_item + L.wg_level;
-                A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
-                size_t e0 = 0, e1 = 0;
-                const int si = two ? (sweep ? 1 : (seg ? 2 : (mf ? 3 : 0))) : 0;
-                hipStream_t Sx = SS[si];
-                if (two) {
-                    if (L.level != cur_level) { cur_level = L.level; for (int j = 0; j < kNS; ++j) prev[j] = last[j]; close_pair(); }
-                    for (int j = 0; j < kNS; ++j)
-                        if (j != si && prev[j] > saw[si][j]) { HIP_TRY(h, hipStreamWaitEvent(Sx, st.ev[(size_t)prev[j]], 0)); saw[si][j] = prev[j]; }
-                }
-                if ((rc = next_event(h, st, e0, Sx))) return rc;
-                if (sweep && h->sweep_dma) hipLaunchKernelGGL(ve_sweep_dma_kernel, dim3((unsigned)grid), dim3(kSweepWG), kSweepLdsBytes, Sx, A);
-                else if (sweep) hipLaunchKernelGGL(ve_sweep_kernel, dim3((unsigned)grid), dim3(kSweepWG), kSweepLdsBytes, Sx, A);
-                else if (seg) hipLaunchKernelGGL(ve_segment_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
-                else if (mf) hipLaunchKernelGGL(ve_mfma_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
-                else hipLaunchKernelGGL(ve_level_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
-                if ((rc = next_event(h, st, e1, Sx))) return rc;
-                if (two) {
-                    last[si] = (long)e1;
-                    if (!h->split_kinds) {
-                        if (si == 1) { pair.e2 = e0; pair.e3 = e1; } else if (si == 2) { pair.e4 = e0; pair.e5 = e1; } else if (si == 3) { pair.e6 = e0; pair.e7 = e1; } else { pair.e0 = e0; pair.e1 = e1; }
-                        pair.bytes += bytes;
-                        pair.items += (double)grid;
-                    }
-                }
-                st.timed.push_back({sweep ? (h->sweep_dma ? kStatSweepDma : kKidSweep) : (seg ? kStatSegment : (mf ? kStatMfma : (h->split_kinds ? L.kid : kStatLevel))), e0, e1, bytes, (double)grid, h->call_id});
-                n_wg += (double)grid;
-                li = lj;
-            }
-            {
-                if (two) {
-                    close_pair();
-                    for (int j = 1; j < kNS; ++j)  // the wave ends on S
-                        if (last[j] > saw[0][j]) HIP_TRY(h, hipStreamWaitEvent(S, st.ev[(size_t)last[j]], 0));
-                }
-                size_t e_last = 0;
-                if ((rc = next_event(h, st, e_last, S))) return rc;
-                st.timed.push_back({-1, e_first, e_last, 0.0, (double)(r1 - r0), h->call_id});
-            }
-            HIP_TRY(h, hipGetLastError());
-            if (h->trace) {
-                hipEvent_t &ge = h->gap_ev[h->n_waves & 3];
-                if (!ge) HIP_TRY(h, hipEventCreate(&ge));
-                HIP_TRY(h, hipEventRecord(ge, S));
-            }
-            ++h->n_waves;
-            st.busy = true;
-            h->stats.arena_bytes = std::max(h->stats.arena_bytes, (double)need_bytes);
-            h->stats.n_workgroups += n_wg;
-            r0 = r1;
-        }
-        h->stats.alg_bytes += ck.st.alg_bytes;
-        h->stats.alg_flops += ck.st.alg_flops;
-        h->stats.n_steps += ck.st.n_steps;
-        h->stats.max_step_cells = std::max(h->stats.max_step_cells, ck.st.max_step_cells);
+    R.short_first = h->first_chunk == 2 || (h->first_chunk == 1 && !R.gpu_busy);
+    return MIBN_OK;
+}
+
+// Requests of the chunk that starts at b0.
+// A call that finds the GPU idle (the first of a stream of calls, a blocking call) starts with a short chunk - a quarter -
+// that gets the GPU going while the host plans the rest; in steady state - the previous call still running - a call
+// is cut into full chunks.  (Ramping the chunks up from 1 024 requests, doubling, was measured and dropped: seven small
+// plan_batch calls cost 95 ms of host time instead of 63, and the chunk sets - their pinned buffers sized by the small
+// chunks they had seen - grew under the clock: profiles/r03_i_pipeline_start.log.)
+// With the device order search on, every call starts with an eighth of a chunk whose orders the host searches while
+// ONE launch searches the rest of the call (a call of a single chunk would otherwise be searched on the host whole).
+int64_t chunk_size(const QueryRun &R, int64_t b0) {
+    const mibn_ctx *h = R.h;
+    if (b0 == 0 && R.search_on && h->gpu_search == 1) return std::max<int64_t>(1024, h->chunk / 8);
+    if (R.emit_on) return h->chunk;  // (the host has nothing to plan while a short first chunk runs)
+    if (b0 == 0 && R.short_first && (R.B > h->chunk || !R.gpu_busy)) return std::max<int64_t>(1024, h->chunk / 4);
+    return h->chunk;
+}
+
+// plan_chunk, option gpu_search: the first (short) chunk of a call is searched on the host while one launch searches the rest of the
+// call on the device; the later chunks only emit -> the orders of chunk [b0, b1), or null: the host searches.  Enqueued on return
+// (first chunk only): order_kernel over [b1, B) on the search stream, from h->search_in into h->search_out.
+int search_window(QueryRun &R, int64_t b0, int64_t b1, double t0, const uint8_t *&orders, const int32_t *&order_len) {
+    mibn_ctx *h = R.h;
+    int rc;
+    if (h->gpu_search == 2) {  // test mode: every chunk searched on the device, synchronously
+        if ((rc = search_orders_async(h, R.flags, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars))) return rc;
+        if ((rc = search_wait(h))) return rc;
+        orders = reinterpret_cast<const uint8_t *>(h->search_out.p);
+        order_len = reinterpret_cast<const int32_t *>(h->search_out.p + (size_t)(b1 - b0) * 128);
+    } else if (R.n_chunks == 0 && b1 < R.B) {
+        if ((rc = search_orders_async(h, R.flags, b1, R.B, R.q_off, R.q_vars, R.e_off, R.e_vars))) return rc;
+        R.search_b0 = b1;
+    } else if (R.search_b0 >= 0) {
+        if (!R.search_done) { if ((rc = search_wait(h))) return rc; R.search_done = true; h->search_ms += now_ms() - t0; }
+        orders = reinterpret_cast<const uint8_t *>(h->search_out.p) + (size_t)(b0 - R.search_b0) * 128;
+        order_len = reinterpret_cast<const int32_t *>(h->search_out.p + (size_t)(R.B - R.search_b0) * 128) + (b0 - R.search_b0);
     }
-    auto fold = [&]() {  // the host-side counters of this call -> totals (kernel times are folded by retire())
-        h->total.plan_ms += h->stats.plan_ms;
-        h->total.h2d_ms += h->stats.h2d_ms;
-        h->total.d2h_ms += h->stats.d2h_ms;
-        h->total.total_ms += h->stats.total_ms;
-        h->total.alg_bytes += h->stats.alg_bytes;
-        h->total.alg_flops += h->stats.alg_flops;
-        h->total.n_steps += h->stats.n_steps;
-        h->total.n_workgroups += h->stats.n_workgroups;
-        h->total.arena_bytes = std::max(h->total.arena_bytes, h->stats.arena_bytes);
-        h->total.max_step_cells = std::max(h->total.max_step_cells, h->stats.max_step_cells);
-    };
-    if (lane1_used) {  // the download (main stream) follows the kernels of both lanes
+    return MIBN_OK;
+}
+
+// plan_chunk: joins the two parts of a chunk into `ck`, the device's nd requests (dp) first, the host's (hp: its programs follow the
+// device's slots of `stride` words) behind them.  Returns prog_base.  Host work only.
+size_t join_plans(BatchPlan &ck, BatchPlan &dp, BatchPlan &hp, int64_t nd, size_t stride) {
+    const int T = (int)hp.tags.size();
+    ck.st = dp.st;
+    ck.st.alg_bytes += hp.st.alg_bytes; ck.st.alg_flops += hp.st.alg_flops; ck.st.n_steps += hp.st.n_steps;
+    ck.st.max_step_cells = std::max(dp.st.max_step_cells, hp.st.max_step_cells);
+    ck.arena_cells = std::max(dp.arena_cells, hp.arena_cells);
+    ck.err.clear();
+    ck.tags.resize((size_t)T + 1);
+    for (int t = 0; t < T; ++t) ck.tags[(size_t)t].swap(hp.tags[(size_t)t]);
+    ck.tags[(size_t)T].swap(dp.tags[0]);
+    ck.thread_words = hp.thread_words;
+    auto join = [&](auto &dst, const auto &a, const auto &b) { dst.assign(a.begin(), a.end()); dst.insert(dst.end(), b.begin(), b.end()); };
+    join(ck.cost, dp.cost, hp.cost);
+    join(ck.arena_need, dp.arena_need, hp.arena_need);
+    join(ck.tag_first, dp.tag_first, hp.tag_first);
+    join(ck.tag_count, dp.tag_count, hp.tag_count);
+    join(ck.local_off, dp.local_off, hp.local_off);
+    ck.thread_of.assign((size_t)nd, T);
+    ck.thread_of.insert(ck.thread_of.end(), hp.thread_of.begin(), hp.thread_of.end());
+    const size_t prog_base = (size_t)nd * stride;
+    ck.prog_off = dp.prog_off;
+    for (uint64_t o : hp.prog_off) ck.prog_off.push_back(prog_base + o);
+    ck.total_words = prog_base + hp.total_words;
+    return prog_base;
+}
+
+// plan_chunk: the requests `beyond` of the device's part [b0, b0 + nd) that exceed one of wave_plan_kernel's limits: the host plans THEM
+// (round 6: a refused request used to send its whole chunk to the host - n_evidence = 16 met a limit five times in 200 000 requests and
+// lost a third of its rate) - one plan_batch over the device's range with everything else masked out; a program goes into its
+// request's own slot of the device program buffer, its work items and statistics take the place the kernel left empty.
+// Enqueued on the copy stream on return: the copies of those programs from st.xbufs (pinned) into st.d_prog.
+int replan_beyond(QueryRun &R, mibn_ctx::Set &st, int64_t b0, int64_t nd, const std::vector<int64_t> &beyond, bool &on_device) {
+    mibn_ctx *h = R.h;
+    BatchPlan &ck = st.plan, &xp = st.xplan;
+    std::vector<char> mask(R.skip.begin(), R.skip.end());
+    for (int64_t i = 0; i < nd; ++i) mask[(size_t)(b0 + i)] = 1;
+    for (int64_t i : beyond) mask[(size_t)(b0 + i)] = R.skip[(size_t)(b0 + i)];
+    plan_batch(h->net, *h->pool, st.xbufs, b0, b0 + nd, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, mask.data(), xp,
+               (R.flags & MIBN_Q_NOPRUNE) != 0, nullptr, nullptr, b0);
+    if (!xp.err.empty()) { h->err = xp.err; return MIBN_E_LIMIT; }
+    const size_t stride = h->emit_words;
+    const size_t X = ck.tags.size();
+    ck.tags.resize(X + xp.tags.size());
+    for (size_t t = 0; t < xp.tags.size(); ++t) ck.tags[X + t] = xp.tags[t];
+    bool fits = true;
+    for (int64_t i : beyond) {
+        const uint32_t *w = st.xbufs[(size_t)xp.thread_of[(size_t)i]].data + xp.local_off[(size_t)i];
+        size_t words = 1;
+        for (uint32_t k = 0; k < w[0]; ++k) words += w[words + 6];
+        if (words + kMaxStepWords > stride) { fits = false; break; }
+        HIP_TRY(h, hipMemcpyAsync(st.d_prog + (size_t)i * stride, w, words * 4, hipMemcpyHostToDevice, h->copy_stream));
+        ck.prog_off[(size_t)i] = (uint64_t)i * stride;
+        ck.local_off[(size_t)i] = ck.prog_off[(size_t)i];
+        ck.thread_of[(size_t)i] = (int32_t)(X + (size_t)xp.thread_of[(size_t)i]);
+        ck.tag_first[(size_t)i] = xp.tag_first[(size_t)i];
+        ck.tag_count[(size_t)i] = xp.tag_count[(size_t)i];
+        ck.cost[(size_t)i] = xp.cost[(size_t)i];
+        ck.arena_need[(size_t)i] = xp.arena_need[(size_t)i];
+    }
+    ck.st.alg_bytes += xp.st.alg_bytes; ck.st.alg_flops += xp.st.alg_flops; ck.st.n_steps += xp.st.n_steps;
+    ck.st.max_step_cells = std::max(ck.st.max_step_cells, xp.st.max_step_cells);
+    ck.arena_cells = std::max(ck.arena_cells, xp.arena_cells);
+    if (h->trace || h->emit_single < 4)
+        std::fprintf(stderr, "[mibn plan] device planner: %zu of %lld requests beyond a device limit (first: request %lld): planned on the host\n", beyond.size(), (long long)nd,
+                     (long long)(b0 + beyond[0]));
+    h->emit_single += (int64_t)beyond.size();
+    if (!fits) on_device = false;  // (a program longer than its slot: the host plans the chunk after all)
+    return MIBN_OK;
+}
+
+// plan_chunk, option gpu_emit = 2 (tests): the host plans the device-planned chunk [b0, b1) too - programs, work items and statistics
+// must agree exactly.  Synchronous: it waits for the copy stream and downloads st.d_prog; nothing is enqueued on return.
+int check_against_host(QueryRun &R, mibn_ctx::Set &st, int64_t b0, int64_t b1) {
+    mibn_ctx *h = R.h;
+    const BatchPlan &ck = st.plan;
+    const int64_t n = b1 - b0;
+    const size_t stride = h->emit_words;
+    std::vector<uint32_t> dev((size_t)n * stride);
+    HIP_TRY(h, hipStreamSynchronize(h->copy_stream));  // (the programs of requests beyond a device limit, planned on the host: replan_beyond)
+    HIP_TRY(h, hipMemcpy(dev.data(), st.d_prog, dev.size() * 4, hipMemcpyDeviceToHost));
+    BatchPlan ref;
+    plan_batch(h->net, *h->pool, st.bufs, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), ref,
+               (R.flags & MIBN_Q_NOPRUNE) != 0, nullptr, nullptr);
+    if (!ref.err.empty()) { h->err = ref.err; return MIBN_E_LIMIT; }
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t *hw = st.bufs[ref.thread_of[i]].data + ref.local_off[i], *dw = dev.data() + (size_t)ck.prog_off[(size_t)i];  // (= i x stride + the words in front of the program)
+        size_t words = 1;
+        for (uint32_t k = 0; k < hw[0]; ++k) words += hw[words + 6];
+        for (size_t k = 0; k < words; ++k)
+            if (hw[k] != dw[k]) {
+                size_t off = 1, step = 0;  // (which step holds the word)
+                while (step + 1 < hw[0] && off + hw[off + 6] <= k) { off += hw[off + 6]; ++step; }
+                h->err = "device planner: request " + std::to_string(b0 + i) + " word " + std::to_string(k) + " of " + std::to_string(words) + " (step " + std::to_string(step) + " of " +
+                         std::to_string(hw[0]) + ", kind " + std::to_string(hw[off] & 0xff) + ", word " + std::to_string(k - off) + " of the step's " + std::to_string(hw[off + 6]) + "): host " +
+                         std::to_string(hw[k]) + " device " + std::to_string(dw[k]) + "; device program " + std::to_string(dw[0]) + " steps";
+                return MIBN_E_STATE;
+            }
+        const Tag *ht = ref.tags[ref.thread_of[i]].data() + ref.tag_first[i], *dt = ck.tags[(size_t)ck.thread_of[i]].data() + ck.tag_first[i];
+        bool same = ref.tag_count[i] == ck.tag_count[i] && ref.arena_need[i] == ck.arena_need[i] && ref.cost[i] == ck.cost[i];
+        for (uint32_t k = 0; same && k < ref.tag_count[i]; ++k)
+            same = ht[k].rel_off == dt[k].rel_off && ht[k].a == dt[k].a && ht[k].wgs == dt[k].wgs && ht[k].level == dt[k].level &&
+                   ht[k].kid == dt[k].kid && ht[k].bytes == dt[k].bytes;
+        if (!same) { h->err = "device planner: work items / statistics of request " + std::to_string(b0 + i) + " differ from the host's"; return MIBN_E_STATE; }
+    }
+    return MIBN_OK;
+}
+
+// Stage: plans chunk [b0, b1) into st.plan - on the host's workers (into st.bufs), on the device (into st.d_prog), or on both.
+// on_device: st.d_prog already holds the device's programs, the host's (st.bufs) go behind them from word prog_base on.  The device
+// planner has been waited for; enqueued on return: what search_window and replan_beyond leave.
+int plan_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t b0, int64_t b1, bool &on_device, size_t &prog_base) {
+    mibn_ctx *h = R.h;
+    const int64_t n = b1 - b0;
+    const bool no_prune = (R.flags & MIBN_Q_NOPRUNE) != 0;
+    int rc;
+    const double t0 = now_ms();
+    const uint8_t *orders = nullptr;
+    const int32_t *order_len = nullptr;
+    if (R.search_on && (rc = search_window(R, b0, b1, t0, orders, order_len))) return rc;
+    BatchPlan &ck = st.plan;
+    on_device = false;
+    prog_base = 0;               // words of st.d_prog the device has written (the host's programs follow)
+    std::vector<int64_t> beyond;  // requests of the device's part that exceed a device limit (kEmitErrDevice): the host plans them
+    int64_t nd = 0;               // requests [b0, b0 + nd) planned by the device, the rest by the host's workers meanwhile
+    if (R.emit_on) {
+        nd = h->pol.device_share(n, h->gpu_emit == 2, wave_mode(h));
+        const size_t stride = h->emit_words;
+        if ((rc = plan_on_device_launch(h, R.flags, b0, b0 + nd, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), st, (size_t)n * stride))) return rc;
+        const double t_launched = now_ms();
+        BatchPlan &hp = h->emit_host, &dp = h->emit_dev;
+        double host_ms = 0, dev_ms = 0;
+        if (nd < n) {
+            const double th = now_ms();
+            plan_batch(h->net, *h->pool, st.bufs, b0 + nd, b1, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), hp, no_prune, nullptr, nullptr, b0);
+            host_ms = now_ms() - th;
+            R.call_plan_ms += host_ms;
+            if (!hp.err.empty()) { h->err = hp.err; return MIBN_E_LIMIT; }
+        }
+        const double tw = now_ms();
+        rc = plan_on_device_collect(h, b0, nd, nd < n ? dp : ck, &dev_ms, &beyond);
+        h->emit_ms += now_ms() - tw;
+        R.call_plan_ms += now_ms() - tw;
+        if (h->trace >= 2) std::fprintf(stderr, "[mibn plan] collect returned %d at %.2f ms of the block\n", rc, now_ms() - t0);
+        book_stat(h, kStatPlanner, 2, dev_ms, 0.0, (double)nd, true, true);  // (beside the chunk in flight: their time is not GPU busy time of its own)
+#if defined(MIBN_EMIT_PROF)
+        if (h->trace) {
+            unsigned long long ticks[12], z[12] = {0};
+            HIP_TRY(h, hipMemcpyFromSymbol(ticks, HIP_SYMBOL(g_emit_prof), sizeof(ticks)));
+            HIP_TRY(h, hipMemcpyToSymbol(HIP_SYMBOL(g_emit_prof), z, sizeof(z)));
+            static const char *names[11] = {"begin (relevant set, CPT slices)", "key / pos / slot sets", "factors of x", "sweep candidates", "SWEEP 5 / 4", "CHAIN",
+                                            "SWEEP 3 / 2", "pair", "single elimination", "final product", "work items"};
+            double tot = 0;
+            for (int k = 0; k < 11; ++k) tot += (double)ticks[k];
+            for (int k = 0; k < 11; ++k) std::fprintf(stderr, "[mibn emit phases] %-36s %6.1f us per request  %5.1f %%\n", names[k], (double)ticks[k] / 100.0 / (double)nd, 100.0 * (double)ticks[k] / tot);
+        }
+#endif
+        if (h->trace) std::fprintf(stderr, "[mibn plan] chunk of %lld: device %lld requests (upload + launch %.2f ms, kernels %.2f ms, wait + collect %.2f ms), host %lld requests %.2f ms\n",
+                                   (long long)n, (long long)nd, t_launched - t0, dev_ms, now_ms() - tw, (long long)(n - nd), host_ms);
+        if (rc < 0 || rc > 1) return rc;
+        if (rc == 0 && nd < n && hp.total_words > (size_t)(n - nd) * stride) rc = 1;  // (the host's programs do not fit behind the device's)
+        on_device = rc == 0;
+        if (on_device && nd < n) {
+            prog_base = join_plans(ck, dp, hp, nd, stride);
+            const bool wave = wave_mode(h);
+            const PlanPolicy::ShareStep s = h->pol.after_mixed_chunk(n, nd, host_ms, dev_ms, h->chunk, wave);
+            if (s.ruled && h->trace) std::fprintf(stderr, "[mibn share] host %.4f ms/request (%lld in %.1f ms), kernels %.5f ms/request, planner %.5f ms/request, fixed %.1f ms -> target %.3f, share %.3f\n",
+                                                  s.ih, (long long)(n - nd), host_ms, s.kv, s.kp, s.fixed, s.target, h->pol.emit_share);
+        }
+    }
+    if (on_device && !beyond.empty() && (rc = replan_beyond(R, st, b0, nd, beyond, on_device))) return rc;
+    if (!on_device)
+        plan_batch(h->net, *h->pool, st.bufs, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), ck, no_prune, orders, order_len, -1, false, R.raw);
+    if (on_device && h->gpu_emit == 2 && (rc = check_against_host(R, st, b0, b1))) return rc;
+    if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
+    for (auto &b : st.bufs)
+        if (b.cap && !b.data) { h->err = "pinned host allocation failed"; return MIBN_E_HIP; }
+    h->stats.plan_ms += now_ms() - t0;
+    if (h->trace >= 2) std::fprintf(stderr, "[mibn plan] chunk planning block %.2f ms (on the device: %d)\n", now_ms() - t0, (int)on_device);
+    return MIBN_OK;
+}
+
+// Stage: the programs the host planned and the program offsets of a chunk of n requests -> the set's device buffers.  Enqueued on the
+// copy stream on return, not waited for: the copies out of st.bufs and st.stage[0] (run_wave's `uploaded` event covers them).
+int upload_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t n, bool on_device, size_t prog_base) {
+    mibn_ctx *h = R.h;
+    const BatchPlan &ck = st.plan;
+    int rc;
+    if (!on_device && (rc = ensure(h, st.d_prog, st.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
+    if ((rc = ensure(h, st.d_prog_off, st.prog_off_cap, (size_t)n))) return rc;
+    if ((rc = ensure(h, st.d_arena_off, st.arena_off_cap, (size_t)n))) return rc;
+    const double t0 = now_ms();
+    if ((rc = upload_programs(h, st.d_prog, prog_base, st.bufs, ck, h->copy_stream))) return rc;
+    if ((rc = upload(h, st.stage[0], st.d_prog_off, ck.prog_off.data(), (size_t)n * 8))) return rc;
+    h->stats.h2d_ms += now_ms() - t0;
+    return MIBN_OK;
+}
+
+// The launches of a wave on the streams of its lane.  Option overlap: the sweep launch of a level goes to a second stream, next to the
+// level kernel's launch of the same level (their items belong to different requests); level L + 1 starts on either stream when BOTH
+// launches of level L have finished.  The tail of one launch - a sweep workgroup lives ~100 us - then runs under the body of the other.
+// Streams of a wave: 0 = S (the level kernel), 1 = S2 (the sweep kernel), 2 = S3 (the segment kernel, option seg_kernel), 3 = S4 (the MFMA
+// kernel, option mfma_kernel).  The launches of level L run side by side; a launch of level L + 1 waits for ALL launches of level L: the
+// one on its own stream by stream order, the others through their end events (`prev`: the ends of the previous level - not the running
+// `last`, or the launches of one level would serialise: ADVICE r3).  Without the option every launch goes to S and nothing waits.
+struct LevelStreams {
+    using Timed = mibn_ctx::Set::Timed;
+    static constexpr int kNS = 4;
+    mibn_ctx *h;
+    mibn_ctx::Set &st;
+    const bool two;
+    hipStream_t SS[kNS];
+    long last[kNS], prev[kNS], saw[kNS][kNS];
+    int cur_level = -1;
+    Timed pair;  // the level in progress, as one concurrent launch group
+
+    LevelStreams(mibn_ctx *h_, mibn_ctx::Set &st_, int lane, hipStream_t S)
+        : h(h_), st(st_), two(h_->overlap != 0), SS{S, h_->aux[lane][0], h_->aux[lane][1], h_->aux[lane][2]}, pair(fresh()) {
+        for (int a = 0; a < kNS; ++a) { last[a] = prev[a] = -1; for (int b = 0; b < kNS; ++b) saw[a][b] = -1; }
+    }
+    Timed fresh() const { return Timed{-2, Timed::kNone, Timed::kNone, 0.0, 0.0, h->call_id}; }
+    void close_pair() {
+        if (pair.e0 != Timed::kNone || pair.e2 != Timed::kNone || pair.e4 != Timed::kNone || pair.e6 != Timed::kNone) st.timed.push_back(pair);
+        pair = fresh();
+    }
+    int stream_of(bool sweep, bool seg, bool mf) const { return two ? (sweep ? 1 : (seg ? 2 : (mf ? 3 : 0))) : 0; }
+    // the wave's first event (the uploads, the previous wave's kernels: the arena is theirs until then) holds the other streams back
+    int begin(size_t e_first) {
+        for (int j = 1; two && j < kNS; ++j) HIP_TRY(h, hipStreamWaitEvent(SS[j], st.ev[e_first], 0));
+        return MIBN_OK;
+    }
+    // in front of a launch of `level` on stream si: it waits for the previous level's launches on the other streams
+    int before(int level, int si) {
+        if (!two) return MIBN_OK;
+        if (level != cur_level) { cur_level = level; for (int j = 0; j < kNS; ++j) prev[j] = last[j]; close_pair(); }
+        for (int j = 0; j < kNS; ++j)
+            if (j != si && prev[j] > saw[si][j]) { HIP_TRY(h, hipStreamWaitEvent(SS[si], st.ev[(size_t)prev[j]], 0)); saw[si][j] = prev[j]; }
+        return MIBN_OK;
+    }
+    // behind it: events (e0, e1) bracket the launch
+    void after(int si, size_t e0, size_t e1, double bytes, double grid) {
+        if (!two) return;
+        last[si] = (long)e1;
+        if (h->split_kinds) return;
+        if (si == 1) { pair.e2 = e0; pair.e3 = e1; } else if (si == 2) { pair.e4 = e0; pair.e5 = e1; } else if (si == 3) { pair.e6 = e0; pair.e7 = e1; } else { pair.e0 = e0; pair.e1 = e1; }
+        pair.bytes += bytes;
+        pair.items += grid;
+    }
+    // the wave ends on S
+    int end() {
+        if (!two) return MIBN_OK;
+        close_pair();
+        for (int j = 1; j < kNS; ++j)
+            if (last[j] > saw[0][j]) HIP_TRY(h, hipStreamWaitEvent(SS[0], st.ev[(size_t)last[j]], 0));
+        return MIBN_OK;
+    }
+};
+
+// Stage: wave [r0, r1) of chunk [b0, ..) of set `st` on `lane` (stream S): the schedule, the arena, the uploads, the level launches.
+// It waits for S when the arena has to grow, and for S and the copy stream when r0 > 0 (items / arena offsets of a wave live until the
+// wave's launches have run: one wave per set at a time unless the chunk had to be split).  Enqueued on return, not waited for: on the
+// copy stream the schedule's uploads out of st.stage[1..3] and the `uploaded` event; on S - and, option overlap, the lane's aux
+// streams, joined back into S - the launches of every level between their events (st.ev, st.timed: retire() books them).
+int run_wave(QueryRun &R, mibn_ctx::Set &st, int lane, hipStream_t S, int64_t b0, int64_t r0, int64_t r1) {
+    mibn_ctx *h = R.h;
+    int rc;
+    double t0 = now_ms();
+    Schedule &sc = st.sched;
+    build_schedule(h->net, st.plan, st.bufs, r0, r1, sc);
+    h->stats.plan_ms += now_ms() - t0;
+    R.call_fixed_ms += now_ms() - t0;
+    if (h->trace) std::fprintf(stderr, "[mibn plan] build_schedule %.2f ms (%zu items, %zu workgroups, %zu launches)\n", now_ms() - t0, sc.items.size(), sc.wg_item.size(), sc.launches.size());
+    const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
+    if ((rc = grow_arena(h, lane, need_bytes, R.budget_cells, S))) return rc;
+    if (r0 > 0) { HIP_TRY(h, hipStreamSynchronize(S)); HIP_TRY(h, hipStreamSynchronize(h->copy_stream)); }
+    if ((rc = ensure(h, st.d_items, st.items_cap, sc.items.size()))) return rc;
+    if ((rc = ensure(h, st.d_wg_item, st.wg_item_cap, sc.wg_item.size()))) return rc;
+    t0 = now_ms();
+    if ((rc = upload(h, st.stage[1], st.d_arena_off, sc.arena_off.data(), (size_t)(r1 - r0) * 8))) return rc;
+    if ((rc = upload(h, st.stage[2], st.d_items, sc.items.data(), sc.items.size() * sizeof(Item)))) return rc;
+    if ((rc = upload(h, st.stage[3], st.d_wg_item, sc.wg_item.data(), sc.wg_item.size() * sizeof(uint32_t)))) return rc;
+    if (!st.uploaded) HIP_TRY(h, hipEventCreateWithFlags(&st.uploaded, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(st.uploaded, h->copy_stream));
+    HIP_TRY(h, hipStreamWaitEvent(S, st.uploaded, 0));  // the kernels of this wave wait for its uploads only
+    h->stats.h2d_ms += now_ms() - t0;
+    LevelArgs A;
+    A.prog = st.d_prog;
+    A.prog_off = st.d_prog_off + r0;
+    A.arena_off = st.d_arena_off;
+    A.pool = h->d_pool;
+    A.arena = h->d_arena[lane];
+    A.results = R.d_results + (R.out_off[b0] - R.out_off[0]);
+    A.items = st.d_items;
+    double n_wg = 0;
+    if (h->trace) st.gap_from = h->n_waves ? (int)((h->n_waves - 1) & 3) : -1;
+    // Every launch is bracketed by its own pair of events on its stream; the wave as a whole by the first and the last one on S
+    // (retire() books the GPU's busy time from them).
+    size_t e_first = 0, e_last = 0;
+    if ((rc = next_event(h, st, e_first, S))) return rc;
+    LevelStreams LS(h, st, lane, S);
+    if ((rc = LS.begin(e_first))) return rc;
+    // (the two classes of ve_mfma_kernel are the last ones of a level in front of the sweep class: planner.cpp ClassOrder)
+    auto is_mfma1 = [&](int kid) { return h->mfma_kernel && !h->split_kinds && (kid == kKidFiber0 + 4 || kid == kKidFiber0 + 6 + 4); };
+    for (size_t li = 0; li < sc.launches.size();) {
+        // one launch of the level kernel per level (all its classes of work together) unless split_kinds, one of the
+        // segment kernel for the level's segments (the first class of a level; option seg_kernel) and one of the sweep kernel
+        // for its SWEEP items (the last class: its own LDS budget)
+        size_t lj = li + 1;
+        const Launch &L = sc.launches[li];
+        const bool sweep = L.kid == kKidSweep;
+        const bool seg = h->seg_kernel && !h->split_kinds && L.kid == kKidSeg;
+        const bool mf = is_mfma1(L.kid);
+        double bytes = L.alg_bytes;
+        size_t grid = L.grid;
+        if (!h->split_kinds && !sweep && !seg)
+            for (; lj < sc.launches.size() && sc.launches[lj].level == L.level && sc.launches[lj].kid != kKidSweep && is_mfma1(sc.launches[lj].kid) == mf; ++lj) {
+                bytes += sc.launches[lj].alg_bytes;
+                grid += sc.launches[lj].grid;
+            }
+        A.wg_item = st.d_wg_item + L.wg_level;
+        A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
+        size_t e0 = 0, e1 = 0;
+        const int si = LS.stream_of(sweep, seg, mf);
+        hipStream_t Sx = LS.SS[si];
+        if ((rc = LS.before(L.level, si))) return rc;
+        if ((rc = next_event(h, st, e0, Sx))) return rc;
+        if (sweep && h->sweep_dma) hipLaunchKernelGGL(ve_sweep_dma_kernel, dim3((unsigned)grid), dim3(kSweepWG), kSweepLdsBytes, Sx, A);
+        else if (sweep) hipLaunchKernelGGL(ve_sweep_kernel, dim3((unsigned)grid), dim3(kSweepWG), kSweepLdsBytes, Sx, A);
+        else if (seg) hipLaunchKernelGGL(ve_segment_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
+        else if (mf) hipLaunchKernelGGL(ve_mfma_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
+        else hipLaunchKernelGGL(ve_level_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
+        if ((rc = next_event(h, st, e1, Sx))) return rc;
+        LS.after(si, e0, e1, bytes, (double)grid);
+        st.timed.push_back({sweep ? (h->sweep_dma ? kStatSweepDma : kKidSweep) : (seg ? kStatSegment : (mf ? kStatMfma : (h->split_kinds ? L.kid : kStatLevel))), e0, e1, bytes, (double)grid, h->call_id});
+        n_wg += (double)grid;
+        li = lj;
+    }
+    if ((rc = LS.end())) return rc;
+    if ((rc = next_event(h, st, e_last, S))) return rc;
+    st.timed.push_back({-1, e_first, e_last, 0.0, (double)(r1 - r0), h->call_id});
+    HIP_TRY(h, hipGetLastError());
+    if (h->trace) {
+        hipEvent_t &ge = h->gap_ev[h->n_waves & 3];
+        if (!ge) HIP_TRY(h, hipEventCreate(&ge));
+        HIP_TRY(h, hipEventRecord(ge, S));
+    }
+    ++h->n_waves;
+    st.busy = true;
+    h->stats.arena_bytes = std::max(h->stats.arena_bytes, (double)need_bytes);
+    h->stats.n_workgroups += n_wg;
+    return MIBN_OK;
+}
+
+// the host-side counters of the last call -> totals (kernel times are folded by retire())
+void fold_stats(mibn_ctx *h) {
+    h->total.plan_ms += h->stats.plan_ms;
+    h->total.h2d_ms += h->stats.h2d_ms;
+    h->total.d2h_ms += h->stats.d2h_ms;
+    h->total.total_ms += h->stats.total_ms;
+    h->total.alg_bytes += h->stats.alg_bytes;
+    h->total.alg_flops += h->stats.alg_flops;
+    h->total.n_steps += h->stats.n_steps;
+    h->total.n_workgroups += h->stats.n_workgroups;
+    h->total.arena_bytes = std::max(h->total.arena_bytes, h->stats.arena_bytes);
+    h->total.max_step_cells = std::max(h->total.max_step_cells, h->stats.max_step_cells);
+}
+
+// Stage: completes the call.  Asynchronous (ticket): enqueued on the main stream on return, not waited for - the join of lane 1, the
+// copy of the results into h->res_stage[slot] (pinned; mibn_wait copies it to `out`, which must stay valid until then) and the `done`
+// event.  Synchronous: every set is retired, the results are downloaded to `out` (or handed to expect_run) and waited for.
+int query_finish(QueryRun &R, double *out, int32_t *ticket) {
+    mibn_ctx *h = R.h;
+    int rc;
+    if (R.lane1_used) {  // the download (main stream) follows the kernels of both lanes
         if (!h->lane_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->lane_ev, hipEventDisableTiming));
         HIP_TRY(h, hipEventRecord(h->lane_ev, h->stream2));
         HIP_TRY(h, hipStreamWaitEvent(h->stream, h->lane_ev, 0));
@@ -2238,50 +2171,122 @@ int run_batch_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, c
     // (the fixed cost of a device-planned call is everything up to its last launch but the planning itself - validation, the fallbacks, the schedule,
     //  the uploads and some 600 launches: counting validation and schedule alone - 7.7 ms of 20 - left a two-thread rank host-bound once order_effort 1
     //  made its planning dearer, profiles/r06_bi_share.log)
-    if (call_plan_ms > 0) call_fixed_ms = std::max(call_fixed_ms, now_ms() - t_start - call_plan_ms);
-    if (B > 0 && !raw) h->fixed_ms_per_req = h->fixed_ms_per_req > 0 ? 0.5 * h->fixed_ms_per_req + 0.5 * call_fixed_ms / (double)B : call_fixed_ms / (double)B;
-    if (h->trace) std::fprintf(stderr, "[mibn plan] call of %lld requests: %.2f ms to the last launch (plan %.2f, h2d %.2f)\n", (long long)B, now_ms() - t_start, h->stats.plan_ms, h->stats.h2d_ms);
+    if (R.call_plan_ms > 0) R.call_fixed_ms = std::max(R.call_fixed_ms, now_ms() - R.t_start - R.call_plan_ms);
+    if (!R.raw) h->pol.call_end(R.B, R.call_fixed_ms);
+    if (h->trace) std::fprintf(stderr, "[mibn plan] call of %lld requests: %.2f ms to the last launch (plan %.2f, h2d %.2f)\n", (long long)R.B, now_ms() - R.t_start, h->stats.plan_ms, h->stats.h2d_ms);
     if (ticket) {
-        mibn_ctx::Pending &pd = h->pend[slot];
-        mibn_ctx::Staging &sg = h->res_stage[slot];
-        const size_t bytes = res_cells * 8;
-        if (bytes > sg.cap) {
-            if (sg.p) { HIP_TRY(h, hipHostFree(sg.p)); sg.p = nullptr; sg.cap = 0; }
-            HIP_TRY(h, hipHostMalloc((void **)&sg.p, bytes + bytes / 4 + 4096, hipHostMallocDefault));
-            sg.cap = bytes + bytes / 4 + 4096;
-        }
+        mibn_ctx::Pending &pd = h->pend[R.slot];
+        mibn_ctx::Staging &sg = h->res_stage[R.slot];
+        const size_t bytes = R.res_cells * 8;
+        if ((rc = pinned(h, sg, bytes))) return rc;
         if (!pd.done) HIP_TRY(h, hipEventCreateWithFlags(&pd.done, hipEventDisableTiming));
-        HIP_TRY(h, hipMemcpyAsync(sg.p, d_results, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(sg.p, R.d_results, bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipEventRecord(pd.done, h->stream));
         pd.active = true;
-        pd.out = out + out_off[0];
-        pd.cells = res_cells;
+        pd.out = out + R.out_off[0];
+        pd.cells = R.res_cells;
         h->next_slot ^= 1;
-        h->stats.total_ms = now_ms() - t_start;
-        fold();
-        return MIBN_OK;
-    }
-    if ((rc = retire_all(h))) return rc;
-    double t0 = now_ms();
-    if (h->expect) {  // mibn_expect_batch: the results stay on the device (a skipped request's slice is zero: it adds nothing)
-        if ((rc = expect_run(h, d_results))) return rc;
     } else {
-        HIP_TRY(h, hipMemcpyAsync(out + out_off[0], d_results, res_cells * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if ((rc = retire_all(h))) return rc;
+        const double t0 = now_ms();
+        if (h->expect) {  // mibn_expect_batch: the results stay on the device (a skipped request's slice is zero: it adds nothing)
+            if ((rc = expect_run(h, R.d_results))) return rc;
+        } else {
+            HIP_TRY(h, hipMemcpyAsync(out + R.out_off[0], R.d_results, R.res_cells * 8, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        }
+        h->stats.d2h_ms += now_ms() - t0;
+        if (R.raw && !h->expect)
+            for (int64_t b = 0; b < R.B; ++b)
+                if (R.skip[(size_t)b] == 2) out[R.out_off[b]] = 1.0;  // (the empty product, see query_validate)
     }
-    h->stats.d2h_ms += now_ms() - t0;
-    if (raw && !h->expect)
-        for (int64_t b = 0; b < B; ++b)
-            if (skip[(size_t)b] == 2) out[out_off[b]] = 1.0;  // (the empty product, see the validation above)
-    h->stats.total_ms = now_ms() - t_start;
-    fold();
+    h->stats.total_ms = now_ms() - R.t_start;
+    fold_stats(h);
     return MIBN_OK;
+}
+
+int run_query(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
+              const int32_t *e_codes, const int64_t *out_off, double *out, int32_t *ticket) {
+    if (!h || B < 0 || !q_off || !e_off || !out_off || (B && !out && !h->expect)) return MIBN_E_ARG;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    QueryRun R{h, flags, (flags & MIBN_Q_UNNORMALISED) != 0, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, now_ms()};
+    ++h->call_id;
+    h->search_ms = 0;
+    h->emit_ms = 0;
+    reset_last_stats(h);
+    R.slot = h->next_slot;
+    if (h->pend[R.slot].active) { h->err = "two asynchronous calls are already in flight: mibn_wait the older one first"; return MIBN_E_STATE; }
+    if (ticket) *ticket = R.slot;
+    if (B == 0) return MIBN_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->tiny && h->tiny_ok && !ticket && B < 0x7ffffff0 && out_off[B] - out_off[0] >= B) {
+        const int rc_tiny = run_tiny(h, flags | (h->net.prune ? 0u : (uint32_t)MIBN_Q_NOPRUNE), B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, R.t_start);
+        if (rc_tiny != 1) return rc_tiny;  // 1: a request does not fit the kernel (query table too large) - plan it
+    }
+    // MIBN_Q_UNNORMALISED (P(q, e) / P(e) requests): planned by the host's workers with the options' base search effort - no device
+    // planner, no adaptive policy; the net's policy-tuned fields are restored on every exit
+    struct NetEffort {
+        Network *net = nullptr;
+        double second_above = 0, minfill_above = 0;
+        ~NetEffort() { if (net) { net->second_above = second_above; net->minfill_above = minfill_above; } }
+    } keep_effort;
+    if (R.raw) {
+        keep_effort.net = &h->net;
+        keep_effort.second_above = h->net.second_above;
+        keep_effort.minfill_above = h->net.minfill_above;
+        h->net.minfill_above = h->pol.base_minfill;
+    }
+    int rc;
+    if ((rc = query_validate(R))) return rc;
+    ensure_pool(h);
+    if (h->trace) std::fprintf(stderr, "[mibn plan] validation of %lld requests %.2f ms\n", (long long)B, now_ms() - R.t_start);
+    R.call_fixed_ms = now_ms() - R.t_start;
+    if (!R.raw) {  // the adaptive policy (plan_policy.h) turns gpu_emit, gpu_search and the network's minfill_above
+        const PlanPolicy::Knobs k = h->pol.call_start(h->call_id, (int)h->pool->size(), h->total.plan_ms, h->total.kernel_ms, h->retired_requests, h->order_net_ok,
+                                                      h->emit_net_ok, {h->gpu_emit, h->gpu_search, h->net.minfill_above});
+        h->gpu_emit = k.gpu_emit;
+        h->gpu_search = k.gpu_search;
+        h->net.minfill_above = k.minfill_above;
+    }
+    if ((rc = query_setup(R))) return rc;
+    for (int64_t b0 = 0, b1 = 0; b0 < B; b0 = b1, ++R.n_chunks) {
+        b1 = std::min(B, b0 + chunk_size(R, b0));
+        const int64_t n = b1 - b0;
+        mibn_ctx::Set &st = h->set[h->set_cursor];
+        const int lane = R.n_lanes > 1 ? (h->set_cursor & 1) : 0;  // consecutive chunks alternate between the lanes
+        hipStream_t S = lane ? h->stream2 : h->stream;
+        R.lane1_used = R.lane1_used || lane == 1;
+        h->set_cursor = (h->set_cursor + 1) % h->n_sets;
+        if ((rc = retire(h, st))) return rc;  // its buffers are about to be rewritten
+        bool on_device = false;
+        size_t prog_base = 0;
+        if ((rc = plan_chunk(R, st, b0, b1, on_device, prog_base))) return rc;
+        if ((rc = upload_chunk(R, st, n, on_device, prog_base))) return rc;
+        // waves: consecutive requests whose private arenas fit the scratch budget together
+        // (a chunk that does not fit is cut into waves of about EQUAL scratch - ceil(total / budget) of them - not into full
+        //  waves and a remainder: round 4 runs chunks of 52 429 requests = 224 GB, close to the budget)
+        const BatchPlan &ck = st.plan;
+        int64_t chunk_cells = 0;
+        for (int64_t r = 0; r < n; ++r) chunk_cells += (ck.arena_need[r] + 15) & ~int64_t(15);
+        const int64_t n_waves_min = std::max<int64_t>(1, (chunk_cells + R.budget_cells - 1) / std::max<int64_t>(1, R.budget_cells));
+        const int64_t wave_target = n_waves_min > 1 ? std::min(R.budget_cells, chunk_cells / n_waves_min + (chunk_cells / n_waves_min) / 64 + 1) : kFullWaves;
+        for (int64_t r0 = 0, r1 = 0, cells = 0; r0 < n; r0 = r1) {
+            if ((rc = cut_wave(h, ck.arena_need, r0, n, R.budget_cells, wave_target, r1, cells))) return rc;
+            if ((rc = run_wave(R, st, lane, S, b0, r0, r1))) return rc;
+        }
+        h->stats.alg_bytes += ck.st.alg_bytes;
+        h->stats.alg_flops += ck.st.alg_flops;
+        h->stats.n_steps += ck.st.n_steps;
+        h->stats.max_step_cells = std::max(h->stats.max_step_cells, ck.st.max_step_cells);
+    }
+    return query_finish(R, out, ticket);
 }
 }  // namespace
 
 static int run_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
               const int32_t *e_codes, const int64_t *out_off, double *out, int32_t *ticket) {
-    return drained_on_error(h, run_batch_body(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, ticket), drain_streams_unchecked);
+    return drained_on_error(h, run_query(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, ticket), drain_streams_unchecked);
 }
 
 // ---------------------------------------------------------------------------------------------- blocking elimination calls
@@ -2345,11 +2350,7 @@ struct ElimRun {  // the call in flight, as the hooks of a payload see it
         for (const Timed &t : timed) {
             float ms = 0;
             HIP_TRY(h, hipEventElapsedTime(&ms, M.ev[t.e0], M.ev[t.e1]));
-            mibn_kernel_stat &ks = h->kstats[t.slot];
-            ks.launches += 1;
-            ks.ms += ms;
-            ks.alg_bytes += t.bytes;
-            ks.items += t.items;
+            book_stat(h, t.slot, 1, ms, t.bytes, t.items, true, false);
             h->stats.kernel_ms += ms;
             h->stats.n_launches += 1;
         }
@@ -2375,10 +2376,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         rq.evars = e_vars + e_off[b];
         const std::string e = rq.ne < 0 ? std::string("negative evidence count") : validate_mpe_request(net, rq);
         if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
-        for (int i = 0; i < rq.ne; ++i) {
-            const int32_t c = e_codes[e_off[b] + i];
-            if (c < 0 || c >= net.card[rq.evars[i]]) skip[(size_t)b] = 1;  // label outside the domain: zero probability
-        }
+        if (evidence_outside_domain(net, rq, e_codes + e_off[b])) skip[(size_t)b] = 1;  // -> zero probability
     }
     HIP_TRY(h, hipSetDevice(h->device));
     ensure_pool(h);
@@ -2408,24 +2406,13 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         if ((rc = ensure(h, M.d_prog, M.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
         if ((rc = ensure(h, M.d_prog_off, M.prog_off_cap, (size_t)n))) return rc;
         if ((rc = ensure(h, M.d_m, M.m_cap, (size_t)n))) return rc;
-        size_t base = 0;
-        for (size_t t = 0; t < ck.thread_words.size(); ++t) {
-            if (ck.thread_words[t]) HIP_TRY(h, hipMemcpyAsync(M.d_prog + base, M.bufs[t].data, ck.thread_words[t] * 4, hipMemcpyHostToDevice, S));
-            base += ck.thread_words[t];
-        }
+        if ((rc = upload_programs(h, M.d_prog, 0, M.bufs, ck, S))) return rc;
         HIP_TRY(h, hipMemcpyAsync(M.d_prog_off, ck.prog_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
         if ((rc = P.prepare(R))) return rc;
         h->stats.h2d_ms += now_ms() - t0;
         // waves: consecutive requests whose arenas (intermediates + what the payload's programs keep) fit the budget together
-        for (int64_t r0 = 0; r0 < n;) {
-            int64_t r1 = r0, cells = 0;
-            while (r1 < n) {
-                const int64_t need = (ck.arena_need[(size_t)r1] + 15) & ~int64_t(15);
-                if (r1 > r0 && cells + need > budget_cells) break;
-                cells += need;
-                ++r1;
-            }
-            if (cells > budget_cells) { h->err = "a request needs " + std::to_string(8.0 * cells / 1e9) + " GB of scratch, above the arena budget"; return MIBN_E_NOMEM; }
+        for (int64_t r0 = 0, r1 = 0, cells = 0; r0 < n; r0 = r1) {
+            if ((rc = cut_wave(h, ck.arena_need, r0, n, budget_cells, kFullWaves, r1, cells))) return rc;
             R.r0 = r0;
             R.r1 = r1;
             t0 = now_ms();
@@ -2433,13 +2420,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
             build_schedule(net, ck, M.bufs, r0, r1, sc);
             h->stats.plan_ms += now_ms() - t0;
             const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
-            if (need_bytes > h->arena_bytes[0]) {
-                HIP_TRY(h, hipStreamSynchronize(S));
-                if (h->d_arena[0]) { HIP_TRY(h, hipFree(h->d_arena[0])); h->d_arena[0] = nullptr; h->arena_bytes[0] = 0; }
-                const size_t want = std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3));
-                HIP_TRY(h, hipMalloc(&h->d_arena[0], want));
-                h->arena_bytes[0] = want;
-            }
+            if ((rc = grow_arena(h, 0, need_bytes, budget_cells, S))) return rc;
             t0 = now_ms();
             if ((rc = ensure(h, M.d_arena_off, M.arena_off_cap, (size_t)(r1 - r0)))) return rc;
             if ((rc = ensure(h, M.d_items, M.items_cap, std::max<size_t>(1, sc.items.size())))) return rc;
@@ -2478,7 +2459,6 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
             HIP_TRY(h, hipStreamSynchronize(S));
             h->stats.arena_bytes = std::max(h->stats.arena_bytes, (double)need_bytes);
             if ((rc = R.book())) return rc;
-            r0 = r1;
         }
         t0 = now_ms();
         if ((rc = P.download(R))) return rc;

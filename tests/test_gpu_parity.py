@@ -670,9 +670,38 @@ def test_wave_planner_hands_what_it_does_not_cover_to_the_host(amd):
     assert np.array_equal(a, be.engine.query_fixed(to_var[q4[sel]][:, None], to_var[ev4[sel]], ec4[sel]))
 
 
+def test_mixed_chunk_cut_into_waves_on_two_lanes(amd):
+    """A chunk planned half by the device and half by the host's workers (the host's programs behind the device's slots), cut into several
+    waves by the arena budget, on two lanes with an arena each: the posteriors are the host-planned call's bit for bit.  The same call in
+    mode 2 (the device plans every request, checked word for word against the host planner) runs through the same waves and lanes."""
+    spec = netspec.grid_spec(10, 10, 4, seed=0)
+    bn = netspec.build(spec, amd.BayesNet)
+    be = bn.backend
+    be.engine.set_option("second_on_device", 1)  # (the same search in the host-planned and in the device-planned call)
+    q, ev, ec = netspec.c3_requests(100, 4, 1024, 4, seed=1)
+    to_var = np.array([be.flat.id[f"{i:03d}"] for i in range(100)], np.int32)
+    base = be.engine.query_fixed(to_var[q][:, None], to_var[ev], ec)
+    launches = be.engine.stats()["n_launches"]
+    need = be.engine.stats()["arena_bytes"]
+    opts = {"chunk": 512, "gpu_emit": 1, "emit_share": 0.5, "streams": 2, "arena_gb": need / 8 / 1e9}  # 256 requests each to the device and the host
+    for k, v in opts.items():
+        be.engine.set_option(k, v)
+    try:
+        got = be.engine.query_fixed(to_var[q][:, None], to_var[ev], ec)
+        assert np.array_equal(got, base)
+        assert be.engine.stats()["n_launches"] > 2 * launches
+        planned = [k for k in be.engine.kernel_stats() if k["name"] == "order_kernel+emit_kernel"]
+        assert planned and planned[0]["items"] > 0, planned
+        be.engine.set_option("gpu_emit", 2)
+        assert np.array_equal(be.engine.query_fixed(to_var[q][:, None], to_var[ev], ec), base)
+    finally:
+        for k, v in {"chunk": 32768, "gpu_emit": 0, "emit_share": -1, "streams": 1, "arena_gb": 200.0, "second_on_device": 0}.items():
+            be.engine.set_option(k, v)
+
+
 def test_adaptive_policy_starts_a_starved_rank_on_the_device_planner(amd):
     """Option adaptive (bench.py switches it on): an engine with at most four planning threads - a rank of an 8-GPU node with a
-    16-CPU quota - plans on the device from its first call (engine.hip, run_batch); the answers are the host-planned ones bit for
+    16-CPU quota - plans on the device from its first call (csrc/plan_policy.h, call_start); the answers are the host-planned ones bit for
     bit, and switching the policy off gives the planning back."""
     spec = netspec.grid_spec(10, 10, 4, seed=0)
     q, ev, ec = netspec.c3_requests(100, 4, 4096, 4, seed=1)
