@@ -272,8 +272,9 @@ int mibn_set_option(mibn_t *h, const char *name, double value);
  *   counts[prod card(q_vars)]   int64 histogram over the joint query state (C-order over q_vars,
  *             last fastest), summed over all chains and iterations; the estimate of the reference
  *             (bayes_net.py:736-737) is counts / (n_chains * n_iterations)
- * Random stream: counter-based Philox4x32-10 keyed by (seed, chain); statistical parity only (the
- * reference's stream depends on the third-party `vose` sampler, see oracle/README.md).
+ * Random stream: counter-based Philox4x32-10 keyed by (seed, chain); parity with the reference's stream
+ * is unpinned (it depends on the third-party `vose` sampler, see oracle/README.md); our own stream is pinned by
+ * tests/sample_check.py.
  */
 int mibn_gibbs(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,
                const int32_t *e_codes, const int32_t *cycle, int64_t n_chains, int64_t n_iterations,
@@ -306,7 +307,8 @@ int mibn_gibbs_conditional(mibn_t *h, int32_t n_e, const int32_t *e_vars, const 
  *                        is clamped, weight_sum[cell] = sum of the sample likelihoods (the product of P(value |
  *                        parents) over ALL nodes, as the reference computes it) and counts[cell] = samples per state;
  *                        the reference's answer is (weight_sum / counts) normalised
- * Random stream: Philox4x32-10 keyed by (seed, sample, variable); statistical parity only (see mibn_gibbs).
+ * Random stream: Philox4x32-10 keyed by (seed, sample, variable); parity with the reference's stream is unpinned,
+ * our own stream is pinned by tests/sample_check.py (see mibn_gibbs).
  */
 #define MIBN_REJECTION 1
 #define MIBN_LIKELIHOOD 2

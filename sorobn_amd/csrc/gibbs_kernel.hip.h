@@ -13,7 +13,8 @@
 // memory round trips per update.  Tables, update programs and chain state all sit in LDS when they fit, and grids take
 // the FAST form - fixed-size update records fetched one iteration ahead, the state reads of all factors issued
 // together, then all table reads (config 5: 2.38 -> 1.16 us per update, same counts bit for bit).  Random numbers:
-// Philox4x32-10 keyed by (seed, chain), counter = update index; statistical parity only (see include/mibn.h).
+// Philox4x32-10 keyed by (seed, chain), counter = update index; parity with the reference's stream is unpinned (see
+// include/mibn.h), our own stream is pinned by tests/sample_check.py.
 #pragma once
 #include <hip/hip_runtime.h>
 
