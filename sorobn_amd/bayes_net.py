@@ -37,6 +37,7 @@ import numpy as np
 import pandas as pd
 
 from . import _capi
+from .events import decode_labels, encode_frame, iter_parts, part_args, pattern_groups
 from .flatten import flatten
 
 __all__ = ["BayesNet", "accelerate", "Backend"]
@@ -783,32 +784,19 @@ class BayesNet:
         return df.iloc[0].rename(None)
 
     # ---- exact posterior sampling (an extension: forward filtering, backward sampling on the device) -------------------------
-    def _draw_ids(self, names):
-        """`_mpe_ids`, with its KeyError for a node without a CPT raised before any engine exists: every variable takes part in
-        a posterior sample."""
-        for node in self.nodes:
-            if node not in self.P:
-                raise KeyError(node)
-        return self._mpe_ids(names)
-
     def _posterior_sample(self, n, event):
         if n < 1:
             raise ValueError("sample: n must be at least 1")
-        be, ev = self._draw_ids(list(event))
+        be = self._event_backend(event, every_cpt=True)
         f = be.flat
+        ev = [f.id[name] for name in event]
         codes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
         flags = _capi.DRAW_PRUNE if self._cpts_are_distributions(be) else 0
         out, p_e = be.engine.posterior_sample(np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev)),
                                               int(n), seed=self._next_seed(), flags=flags)
         if not p_e[0] > 0:
             raise ValueError(f"sample: the evidence of row 0 has probability zero: {event}")
-        data = {}
-        for v, name in enumerate(f.names):
-            col = self._label_table(f, v)[out[:, v]]
-            if name in event:
-                col[:] = [event[name]] * len(col)
-            data[name] = col
-        df = pd.DataFrame(data, columns=list(f.names))
+        df = pd.DataFrame(decode_labels(f, self._all_names(), out, event), columns=list(f.names))
         if n > 1:
             return df.sort_index(axis="columns")
         return df.iloc[0].rename(None)
@@ -824,24 +812,17 @@ class BayesNet:
         if n < 1:
             raise ValueError("sample_frame: n must be at least 1")
         cols = list(events.columns)
-        be, ev_all = self._draw_ids(cols)
+        be = self._event_backend(cols, every_cpt=True)
         f = be.flat
-        ev_ids = np.array(ev_all, np.int32)
+        ev_ids, codes, observed = encode_frame(be, cols, events)
         n = int(n)
         n_ev = len(events)
-        codes = np.empty((n_ev, len(cols)), np.int32)
-        observed = np.empty((n_ev, len(cols)), bool)
-        for j, c in enumerate(cols):
-            col = events[c]
-            observed[:, j] = col.notna().to_numpy()
-            codes[:, j] = pd.Index(f.domains[ev_ids[j]]).get_indexer(col) if len(f.domains[ev_ids[j]]) else -1
         nv = len(f.names)
         out = np.zeros((n_ev, n, nv), np.int32)
         mass = np.zeros(n_ev, np.float64)
-        pat = observed @ (1 << np.arange(len(cols), dtype=np.int64)) if len(cols) < 63 else None
-        groups = ([np.arange(n_ev)] if len(cols) == 0 else
-                  [np.flatnonzero(pat == p) for p in np.unique(pat)] if pat is not None else
-                  [np.array([r]) for r in range(n_ev)])
+        # (the Philox counter of a sample is its position in the order the calls are made, so the grouping is part of what a seed
+        # means: a frame too wide for a bit mask keeps the one call per row, in row order, it has always had)
+        groups = pattern_groups(observed, wide_by_row=True)
         seed = self._next_seed() if seed is None else int(seed)
         eng = be.engine
         flags = _capi.DRAW_PRUNE if self._cpts_are_distributions(be) else 0
@@ -849,30 +830,17 @@ class BayesNet:
         done = 0
         if return_proba and not flags:  # (CPTs that are not distributions: the mass of the empty event normalises)
             z = float(eng.posterior_sample_batch(np.zeros(2, np.int64), [], [], np.zeros(2, np.int64), seed=seed)[1][0])
-        for rows in groups:
-            if not len(rows):
-                continue
-            on = np.flatnonzero(observed[rows[0]])
-            for s in range(0, len(rows), sub_batch):
-                part = rows[s:s + sub_batch]
-                # (global sample rows in the order the calls are made: every sample of the frame has a Philox counter of its own)
-                e_off = np.arange(len(part) + 1, dtype=np.int64) * len(on)
-                s_off = (done + np.arange(len(part) + 1, dtype=np.int64)) * n
-                got, m = eng.posterior_sample_batch(e_off, np.broadcast_to(ev_ids[on], (len(part), len(on))).reshape(-1),
-                                                    codes[np.ix_(part, on)].reshape(-1), s_off, seed=seed, flags=flags)
-                out[part] = got.reshape(len(part), n, nv)
-                mass[part] = m
-                done += len(part)
+        for part, on in iter_parts(groups, observed, sub_batch):
+            # (global sample rows in the order the calls are made: every sample of the frame has a Philox counter of its own)
+            e_off = np.arange(len(part) + 1, dtype=np.int64) * len(on)
+            s_off = (done + np.arange(len(part) + 1, dtype=np.int64)) * n
+            evars, ecodes = part_args(ev_ids, codes, part, on)
+            got, m = eng.posterior_sample_batch(e_off, evars.reshape(-1), ecodes.reshape(-1), s_off, seed=seed, flags=flags)
+            out[part] = got.reshape(len(part), n, nv)
+            mass[part] = m
+            done += len(part)
         names = self._all_names()
-        flat_out = out.reshape(n_ev * n, nv)
-        data = {}
-        for name in names:
-            v = f.id[name]
-            col = self._label_table(f, v)[flat_out[:, v]]
-            if name in events.columns:  # evidence keeps its label (also where it lies outside the domain)
-                obs = np.repeat(events[name].notna().to_numpy(), n)
-                col[obs] = np.repeat(events[name].to_numpy(dtype=object), n)[obs]
-            data[name] = col
+        data = decode_labels(f, names, out.reshape(n_ev * n, nv), events, n)
         index = pd.MultiIndex.from_product([events.index, range(n)], names=[events.index.name, "draw"])
         frame = pd.DataFrame(data, index=index, columns=names)
         if return_proba:
@@ -945,30 +913,15 @@ class BayesNet:
         q = [be.var_id(n) for n in query]
         if f.missing:
             be.encode(query, {c: None for c in events.columns})  # (raises the reference's KeyError for a node without a CPT)
-        cols = list(events.columns)
-        ev_ids = np.array([be.var_id(c) for c in cols], np.int32)
+        ev_ids, codes, observed = encode_frame(be, list(events.columns), events)
         n = len(events)
-        codes = np.empty((n, len(cols)), np.int32)
-        observed = np.empty((n, len(cols)), bool)
-        for j, c in enumerate(cols):
-            col = events[c]
-            observed[:, j] = col.notna().to_numpy()
-            codes[:, j] = pd.Index(f.domains[ev_ids[j]]).get_indexer(col) if len(f.domains[ev_ids[j]]) else -1
         name, order, levels, shape, names = be._tail(tuple(query))
         cells = int(np.prod([int(f.card[v]) for v in q]))
         out = np.zeros((n, cells), np.float64)
         # one engine call per pattern of observed columns
-        pat = observed @ (1 << np.arange(len(cols), dtype=np.int64)) if len(cols) < 63 else None
-        groups = ([np.arange(n)] if len(cols) == 0 else
-                  [np.flatnonzero(pat == p) for p in np.unique(pat)] if pat is not None else
-                  [np.array([r]) for r in range(n)])
         qarr = np.array(q, np.int32)
-        for rows in groups:
-            if not len(rows):
-                continue
-            on = np.flatnonzero(observed[rows[0]])
-            out[rows] = be.engine.query_fixed(np.broadcast_to(qarr, (len(rows), len(q))), np.broadcast_to(ev_ids[on], (len(rows), len(on))),
-                                              codes[np.ix_(rows, on)])
+        for rows, on in iter_parts(pattern_groups(observed), observed, None):
+            out[rows] = be.engine.query_fixed(np.broadcast_to(qarr, (len(rows), len(q))), *part_args(ev_ids, codes, rows, on))
         if shape is None:
             columns = levels
         else:
@@ -994,26 +947,22 @@ class BayesNet:
         return pd.Series(event)
 
     # ---- most probable explanation (an extension: max-product elimination on the device, mibn_mpe_batch) ----------------------
-    def _mpe_ids(self, names):
-        """Variable ids of `names` (the reference's KeyError for an unknown one) and the same KeyError as `query` when a node has
-        no CPT: every variable takes part in an MPE.  Unknown names raise before any engine exists."""
+    def _event_backend(self, names, every_cpt=False):
+        """The backend, for a request whose evidence variables are `names` and in which every variable takes part (MPE, posterior
+        samples, P(e)): an unknown name raises the reference's KeyError before any engine exists, a node without a CPT the
+        KeyError of `query` - with `every_cpt` also before any engine exists, and before the names are looked at."""
+        if every_cpt:
+            for node in self.nodes:
+                if node not in self.P:
+                    raise KeyError(node)
         known = set(self._all_names())
         for n in names:
             if n not in known:
                 raise KeyError(n)
         be = self.backend
-        ids = [be.var_id(n) for n in names]
         if be.flat.missing:
             raise KeyError(be.flat.names[min(be.flat.missing)])
-        return be, ids
-
-    @staticmethod
-    def _label_table(f, v):
-        """Labels of variable v by code, with None at index -1 (code -1 = no answer)."""
-        dom = np.empty(int(f.card[v]) + 1, dtype=object)
-        dom[:-1] = list(f.domains[v])
-        dom[-1] = None
-        return dom
+        return be
 
     def mpe(self, event: dict = None, return_log_prob=False):
         """Most probable explanation: the single most probable completion of `event`, argmax_x P(x, event) over every variable
@@ -1021,19 +970,14 @@ class BayesNet:
         labels.  Zero-probability or out-of-domain evidence gives None for the other variables (and a log probability of
         -inf).  With `return_log_prob`, returns (series, natural log of P(x*, event)).  Ties go to the lowest label code."""
         event = dict(event or {})
-        be, ev = self._mpe_ids(list(event))
+        be = self._event_backend(event)
         f = be.flat
+        ev = [f.id[name] for name in event]
         codes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
         out, log_p = be.engine.mpe(np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev)))
         names = self._all_names()
-        vals = []
-        for name in names:
-            if name in event:
-                vals.append(event[name])
-            else:
-                v = f.id[name]
-                vals.append(self._label_table(f, v)[out[0, v]])
-        series = pd.Series(vals, index=pd.Index(names), dtype=object)
+        data = decode_labels(f, names, out, event)
+        series = pd.Series([data[name][0] for name in names], index=pd.Index(names), dtype=object)
         return (series, float(log_p[0])) if return_log_prob else series
 
     def mpe_frame(self, events: pd.DataFrame, return_log_prob=False, sub_batch=32768):
@@ -1045,55 +989,19 @@ class BayesNet:
         A row that names every variable - observed values and missing ones (NaN / None) - gets what `impute` returns for it (up
         to ties between equally probable assignments), without `impute`'s posterior table of prod(card(missing)) cells."""
         cols = list(events.columns)
-        be, ev_all = self._mpe_ids(cols)
+        be = self._event_backend(cols)
         f = be.flat
-        ev_ids = np.array(ev_all, np.int32)
+        ev_ids, codes, observed = encode_frame(be, cols, events)
         n = len(events)
-        codes = np.empty((n, len(cols)), np.int32)
-        observed = np.empty((n, len(cols)), bool)
-        for j, c in enumerate(cols):
-            col = events[c]
-            observed[:, j] = col.notna().to_numpy()
-            codes[:, j] = pd.Index(f.domains[ev_ids[j]]).get_indexer(col) if len(f.domains[ev_ids[j]]) else -1
-        nv = len(f.names)
-        out = np.zeros((n, nv), np.int32)
+        out = np.zeros((n, len(f.names)), np.int32)
         log_p = np.zeros(n, np.float64)
-        pat = observed @ (1 << np.arange(len(cols), dtype=np.int64)) if len(cols) < 63 else None
-        groups = ([np.arange(n)] if len(cols) == 0 else
-                  [np.flatnonzero(pat == p) for p in np.unique(pat)] if pat is not None else
-                  [np.array([r]) for r in range(n)])
-        for rows in groups:
-            if not len(rows):
-                continue
-            on = np.flatnonzero(observed[rows[0]])
-            for s in range(0, len(rows), sub_batch):
-                part = rows[s:s + sub_batch]
-                out[part], log_p[part] = be.engine.mpe(np.broadcast_to(ev_ids[on], (len(part), len(on))), codes[np.ix_(part, on)])
+        for part, on in iter_parts(pattern_groups(observed), observed, sub_batch):
+            out[part], log_p[part] = be.engine.mpe(*part_args(ev_ids, codes, part, on))
         names = self._all_names()
-        data = {}
-        for name in names:
-            v = f.id[name]
-            col = self._label_table(f, v)[out[:, v]]
-            if name in events.columns:  # evidence keeps its label (also where it lies outside the domain)
-                obs = events[name].notna().to_numpy()
-                col[obs] = events[name].to_numpy(dtype=object)[obs]
-            data[name] = col
-        frame = pd.DataFrame(data, index=events.index, columns=names)
+        frame = pd.DataFrame(decode_labels(f, names, out, events), index=events.index, columns=names)
         return (frame, log_p) if return_log_prob else frame
 
     # ---- evidence likelihood P(e) (an extension: sum-product elimination without normalisation, MIBN_Q_UNNORMALISED) --------
-    def _evidence_ids(self, names):
-        """Variable ids of the evidence columns `names`: unknown names raise KeyError before any engine exists; a node without a
-        CPT raises the KeyError of `query` (every CPT takes part in the normalised joint)."""
-        known = set(self._all_names())
-        for n in names:
-            if n not in known:
-                raise KeyError(n)
-        be = self.backend
-        if be.flat.missing:
-            raise KeyError(be.flat.names[min(be.flat.missing)])
-        return be, np.array([be.var_id(n) for n in names], np.int32)
-
     @staticmethod
     def _cpts_are_distributions(be):
         """True when every CPT row (parent configuration) is present and sums to 1 within 1e-12: the product of the CPTs is then
@@ -1128,18 +1036,8 @@ class BayesNet:
             flags |= _capi.Q_NOPRUNE
             none = np.zeros((1, 0), np.int32)
             z = float(eng.query_fixed(none, none, none, flags=flags)[0, 0])
-        if observed.shape[1] == 0:
-            groups = [np.arange(n)]
-        else:
-            _, inv = np.unique(observed, axis=0, return_inverse=True)
-            inv = np.asarray(inv).reshape(-1)
-            groups = [np.flatnonzero(inv == g) for g in range(int(inv.max()) + 1)]
-        for rows in groups:
-            on = np.flatnonzero(observed[rows[0]])
-            for s in range(0, len(rows), sub_batch):
-                part = rows[s:s + sub_batch]
-                out[part] = eng.query_fixed(np.zeros((len(part), 0), np.int32), np.broadcast_to(ev_ids[on], (len(part), len(on))),
-                                            codes[np.ix_(part, on)], flags=flags)[:, 0]
+        for part, on in iter_parts(pattern_groups(observed), observed, sub_batch):
+            out[part] = eng.query_fixed(np.zeros((len(part), 0), np.int32), *part_args(ev_ids, codes, part, on), flags=flags)[:, 0]
         if flags & _capi.Q_NOPRUNE:
             out = out / z if z > 0 else np.zeros(n, np.float64)
         return out
@@ -1155,8 +1053,9 @@ class BayesNet:
         P(e) below the smallest double reads as 0 and its log as -inf."""
         if isinstance(X, dict):
             cols = list(X)
-            be, ev_ids = self._evidence_ids(cols)
+            be = self._event_backend(cols)
             f = be.flat
+            ev_ids = np.array([f.id[c] for c in cols], np.int32)
             observed = np.array([X[c] is not None for c in cols], bool).reshape(1, len(cols))
             codes = np.array([f.code_of(int(v), X[c]) if X[c] is not None else -1 for c, v in zip(cols, ev_ids)],
                              np.int32).reshape(1, len(cols))
@@ -1165,15 +1064,8 @@ class BayesNet:
                 return float(np.log(p)) if p > 0 else -np.inf
             return p
         cols = list(X.columns)
-        be, ev_ids = self._evidence_ids(cols)
-        f = be.flat
-        n = len(X)
-        codes = np.empty((n, len(cols)), np.int32)
-        observed = np.empty((n, len(cols)), bool)
-        for j, c in enumerate(cols):
-            col = X[c]
-            observed[:, j] = col.notna().to_numpy()
-            codes[:, j] = pd.Index(f.domains[ev_ids[j]]).get_indexer(col) if len(f.domains[ev_ids[j]]) else -1
+        be = self._event_backend(cols)
+        ev_ids, codes, observed = encode_frame(be, cols, X)
         p = self._evidence_rows(be, ev_ids, codes, observed, sub_batch)
         if log:
             with np.errstate(divide="ignore"):
@@ -1253,7 +1145,8 @@ class BayesNet:
             bad |= c < 0
         if float(np.prod([float(c) for c in shape])) >= self.PREDICT_DENSE_CELL_CAP:
             # (wide rows: P(row) per row, every column observed; a row the dense look-up would miss stays bad)
-            _, ev_ids = self._evidence_ids(observed)
+            self._event_backend(observed)
+            ev_ids = np.array(ids, np.int32)
             cm = np.stack(codes, axis=1).astype(np.int32) if len(X) else np.zeros((0, len(ids)), np.int32)
             vals = self._evidence_rows(be, ev_ids, np.where(bad[:, None], -1, cm).astype(np.int32), np.ones(cm.shape, bool))
             bad |= ~(vals > 0)

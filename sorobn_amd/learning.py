@@ -288,9 +288,11 @@ def em_requests(codes, rows, scopes, strides, fam_off):
 
 
 def em_sub_batches(codes, scopes, sub_batch):
-    """Rows ordered pattern group by pattern group (rows with the same observed columns together, as `_evidence_rows`
-    groups them) and cut into runs of at most `sub_batch` requests (a row makes one request per family it is incomplete
-    in, at least one): list of row-index arrays."""
+    """Rows ordered pattern group by pattern group (rows with the same observed columns together; patterns in the order of
+    `np.unique(seen, axis=0)`, column 0 most significant, rows ascending within a pattern) and cut into runs of at most
+    `sub_batch` requests (a row makes one request per family it is incomplete in, at least one): list of row-index arrays.
+    The order fixes the order in which expected counts are accumulated, and with it the last bits of `fit_em`: it is this
+    function's own, not that of `events.pattern_groups`."""
     seen = codes >= 0
     n = len(codes)
     if n == 0:

@@ -6,6 +6,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+import event_frames as ef
 import evidence_check as ec
 import golden_util as gu
 import mpe_check as mc
@@ -229,3 +230,22 @@ def test_no_side_effects_on_queries(grid):
     bn.evidence_proba({"010": 1})
     after = bn.query_many(reqs).out
     assert np.array_equal(before, after)
+
+
+def test_wide_frame_equals_per_row_dict_calls():
+    """A frame of 70 evidence columns with 3 patterns of missing cells: evidence_proba and log_likelihood equal the dict calls row
+    by row, bit for bit (log_likelihood of a frame is the pandas sum of its rows' logs: summed here the same way)."""
+    bn, f = ef.wide_net()
+    X = ef.wide_frame()
+    events = [ef.row_event(X.iloc[r]) for r in range(len(X))]
+    one = np.array([bn.evidence_proba(e) for e in events])
+    logs = np.array([bn.log_likelihood(e) for e in events])
+    got = bn.evidence_proba(X)
+    assert got.index.equals(X.index)
+    assert np.array_equal(got.to_numpy(), one), (got.to_numpy(), one)
+    assert np.array_equal(bn.evidence_proba(X, log=True).to_numpy(), logs)
+    dead = [ef.OUT_OF_DOMAIN_ROW, ef.ZERO_ROW]
+    assert (one[dead] == 0.0).all() and (np.delete(one, dead) > 0).all() and (logs[dead] == -np.inf).all()
+    assert bn.log_likelihood(X) == -np.inf
+    alive = np.delete(np.arange(len(X)), dead)
+    assert bn.log_likelihood(X.iloc[alive]) == float(pd.Series(logs[alive]).sum())

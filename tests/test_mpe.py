@@ -5,6 +5,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+import event_frames as ef
 import golden_util as gu
 import mpe_check as mc
 import netspec
@@ -173,3 +174,31 @@ def test_no_side_effects_on_queries(grid):
     assert np.array_equal(before, after)
     names = [k["name"] for k in bn.backend.engine.kernel_stats()]
     assert "ve_max_kernel" not in names
+
+
+def _assert_frame_equals_per_row_mpe(bn, events):
+    frame, lp = bn.mpe_frame(events, return_log_prob=True)
+    assert list(frame.columns) == bn._all_names() and frame.index.equals(events.index)
+    for r in range(len(events)):
+        s, l1 = bn.mpe(ef.row_event(events.iloc[r]), return_log_prob=True)
+        assert l1 == lp[r], (r, l1, lp[r])
+        assert list(frame.iloc[r]) == list(s), r
+    return frame, lp
+
+
+def test_wide_frame_equals_per_row_mpe():
+    """A frame of 70 evidence columns (rows grouped by pattern beyond the 62 columns a bit mask holds): every row, the one with
+    a label outside its domain and the one of probability zero included, is exactly what mpe() gives for it."""
+    bn, f = ef.wide_net()
+    frame, lp = _assert_frame_equals_per_row_mpe(bn, ef.wide_frame())
+    dead = [ef.OUT_OF_DOMAIN_ROW, ef.ZERO_ROW]
+    assert (lp[dead] == -np.inf).all() and np.isfinite(np.delete(lp, dead)).all()
+    assert frame.iloc[ef.OUT_OF_DOMAIN_ROW]["050"] == 7 and frame.drop(index=frame.index[dead]).notna().all().all()
+
+
+def test_narrow_frame_equals_per_row_mpe():
+    """The same assertion on the 5-column frame of the Asia example (patterns grouped by bit mask)."""
+    spec = next(e["spec"] for e in gu.load("examples.json") if e["spec"]["name"] == "asia")
+    bn = netspec.build(spec, sorobn_amd.BayesNet).use_device(0)
+    frame, lp = _assert_frame_equals_per_row_mpe(bn, ef.asia_frame())
+    assert lp[5] == -np.inf and (frame.loc["f", "Smoker"] == "maybe") and np.isfinite(lp[4])

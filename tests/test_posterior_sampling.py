@@ -10,6 +10,7 @@ import pandas as pd
 import pytest
 
 import draw_check as dc
+import event_frames as ef
 import golden_util as gu
 import mpe_check as mc
 import netspec
@@ -267,3 +268,67 @@ def test_limits_and_argument_errors(grid):
     fw = mc.flat_of(wide)
     codes = np.stack([[fw.code_of(v, x) for x in df[fw.names[v]]] for v in range(2)], axis=1)
     dc.check_samples(fw, {}, codes, ctx="wide")
+
+
+def _frame_from_engine_calls(bn, f, events, groups, n, seed):
+    """The rows of the frame `sample_frame(events, n, seed)` documents, from direct engine calls: one posterior_sample_batch call
+    per entry of `groups` (positions of rows that observe the same columns) in the order given, the samples of the frame
+    numbered in the order of the calls (s_off accumulated here), codes decoded by hand, evidence keeping its label."""
+    assert dc.cpts_are_distributions(f)  # (sample_frame then prunes: DRAW_PRUNE)
+    cols = list(events.columns)
+    codes = np.full((len(events), n, len(f.card)), -2, np.int32)
+    done = 0
+    for rows in groups:
+        on = [c for c in cols if not pd.isna(events[c].iloc[rows[0]])]
+        e_vars = [f.id[c] for c in on] * len(rows)
+        e_codes = [f.code_of(f.id[c], events[c].iloc[r]) for r in rows for c in on]
+        e_off = np.arange(len(rows) + 1, dtype=np.int64) * len(on)
+        s_off = (done + np.arange(len(rows) + 1, dtype=np.int64)) * n
+        got, _ = bn.backend.engine.posterior_sample_batch(e_off, e_vars, e_codes, s_off, seed=seed, flags=_capi.DRAW_PRUNE)
+        codes[rows] = got.reshape(len(rows), n, len(f.card))
+        done += len(rows)
+    assert done == len(events) and (codes >= -1).all()
+    want = []
+    for r in range(len(events)):
+        for d in range(n):
+            row = []
+            for name in bn._all_names():
+                v = f.id[name]
+                if name in cols and not pd.isna(events[name].iloc[r]):
+                    row.append(events[name].iloc[r])
+                else:
+                    row.append(f.domains[v][codes[r, d, v]] if codes[r, d, v] >= 0 else None)
+            want.append(row)
+    return want
+
+
+def _assert_frame_is(frame, events, n, want, bn):
+    assert list(frame.columns) == bn._all_names()
+    assert frame.index.equals(pd.MultiIndex.from_product([events.index, range(n)], names=[events.index.name, "draw"]))
+    got = frame.to_numpy(dtype=object).tolist()
+    assert got == want, [i for i, (a, b) in enumerate(zip(got, want)) if a != b]
+
+
+def test_narrow_frame_seed_contract():
+    """What a seed of sample_frame means below 63 columns, pinned against the engine: rows grouped by their pattern of observed
+    columns, groups in ascending order of the packed bit mask (column j is bit j), rows ascending within a group, one call per
+    group, sample counters running on from call to call."""
+    bn, f = _net("asia")
+    events = ef.asia_frame()
+    pat = events.notna().to_numpy() @ (1 << np.arange(events.shape[1], dtype=np.int64))
+    groups = [np.flatnonzero(pat == p) for p in np.unique(pat)]
+    assert [g.tolist() for g in groups] == [[4], [0, 7], [2, 6], [3], [5], [1]]
+    want = _frame_from_engine_calls(bn, f, events, groups, 4, 7)
+    _assert_frame_is(bn.sample_frame(events, n=4, seed=7), events, 4, want, bn)
+    assert want[5 * 4].count(None) == len(f.card) - 4 and "maybe" in want[5 * 4]  # (row f: 4 labels given, one outside its domain)
+
+
+def test_wide_frame_seed_contract():
+    """What a seed of sample_frame means at 63 columns or more: one engine call per row, in row order."""
+    bn, f = ef.wide_net()
+    events = ef.wide_frame()
+    want = _frame_from_engine_calls(bn, f, events, [[r] for r in range(len(events))], 4, 7)
+    _assert_frame_is(bn.sample_frame(events, n=4, seed=7), events, 4, want, bn)
+    for r in (ef.OUT_OF_DOMAIN_ROW, ef.ZERO_ROW):  # no sample: None wherever the row observes nothing
+        assert want[4 * r].count(None) == len(ef.MISSING[ef.ROW_PATTERN[r]])
+    assert want[4 * ef.OUT_OF_DOMAIN_ROW][50] == 7
