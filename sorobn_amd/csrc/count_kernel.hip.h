@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/mibn.h"
+#include "device_mem.h"
 
 namespace mibn {
 
@@ -244,18 +245,18 @@ inline int count_run(hipStream_t stream, int64_t n_rows, int32_t n_cols, const u
     const int rc = count_pack(n_cols, card, n_tables, scope_off, scope_cols, counts_off, P, err);
     if (rc != MIBN_OK) return rc;
     const int64_t total = counts_off[n_tables] - counts_off[0];
-    uint8_t *d_codes = nullptr, *d_rows = nullptr;
-    int32_t *d_i32 = nullptr;
-    int64_t *d_i64 = nullptr;
-    unsigned long long *d_counts = nullptr;
-    auto fail = [&](hipError_t e) { err = std::string("count: ") + hipGetErrorString(e); hipFree(d_codes); hipFree(d_rows); hipFree(d_i32); hipFree(d_i64); hipFree(d_counts); return MIBN_E_HIP; };
+    DevBuf<uint8_t> d_codes, d_rows;
+    DevBuf<int32_t> d_i32;
+    DevBuf<int64_t> d_i64;
+    DevBuf<unsigned long long> d_counts;
+    auto fail = [&](hipError_t e) { err = std::string("count: ") + hipGetErrorString(e); return MIBN_E_HIP; };
     hipError_t e;
     const size_t code_bytes = (size_t)n_rows * (size_t)n_cols;
-    if ((e = hipMalloc(&d_codes, std::max<size_t>(16, code_bytes))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_i32, 4 * std::max<size_t>(1, P.i32.size()))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_i64, 8 * std::max<size_t>(1, P.i64.size()))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_counts, 8 * std::max<int64_t>(1, total))) != hipSuccess) return fail(e);
-    if (row_major && code_bytes && (e = hipMalloc(&d_rows, code_bytes)) != hipSuccess) return fail(e);
+    if ((e = d_codes.reset(std::max<size_t>(16, code_bytes))) != hipSuccess) return fail(e);
+    if ((e = d_i32.reset(std::max<size_t>(1, P.i32.size()))) != hipSuccess) return fail(e);
+    if ((e = d_i64.reset(std::max<size_t>(1, P.i64.size()))) != hipSuccess) return fail(e);
+    if ((e = d_counts.reset((size_t)std::max<int64_t>(1, total))) != hipSuccess) return fail(e);
+    if (row_major && code_bytes && (e = d_rows.reset(code_bytes)) != hipSuccess) return fail(e);
     if ((e = count_upload_codes(stream, n_rows, n_cols, codes, row_major, d_codes, d_rows)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(d_i32, P.i32.data(), 4 * P.i32.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(d_i64, P.i64.data(), 8 * P.i64.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
@@ -265,11 +266,6 @@ inline int count_run(hipStream_t stream, int64_t n_rows, int32_t n_cols, const u
     if ((e = hipMemcpyAsync(host.data(), d_counts, 8 * (size_t)std::max<int64_t>(1, total), hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);
     for (int64_t i = 0; i < total; ++i) counts[i] = (int64_t)host[(size_t)i];
-    hipFree(d_codes);
-    hipFree(d_rows);
-    hipFree(d_i32);
-    hipFree(d_i64);
-    hipFree(d_counts);
     return MIBN_OK;
 }
 

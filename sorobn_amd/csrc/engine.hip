@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/mibn.h"
+#include "device_mem.h"
 #include "gibbs_kernel.hip.h"
 #include "sample_kernel.hip.h"
 #include "count_kernel.hip.h"
@@ -202,46 +203,39 @@ struct mibn_ctx {
     bool planner_only = false;
     int device = -1;
     int n_cu = 0;
-    hipStream_t stream = nullptr;       // kernels, gibbs, result download
-    hipStream_t copy_stream = nullptr;  // program / schedule uploads: overlap the previous chunk's kernels
-    double *d_pool = nullptr;
+    // (members are destroyed in reverse order: the streams come first here, so every buffer and event below is freed before them)
+    Stream stream;       // kernels, gibbs, result download
+    Stream copy_stream;  // program / schedule uploads: overlap the previous chunk's kernels
+    Stream stream2;      // lane 1 (lane 0 = stream)
+    Stream aux[2][3];    // option overlap, per lane: the sweep kernel's, the segment kernel's and the MFMA kernel's launches
+    Stream search_stream;  // the device planner's (plan_stream)
+    DevBuf<double> d_pool;
     // Lanes: consecutive chunks of a call alternate between two streams with an arena each and run CONCURRENTLY - requests are
     // independent, and the launch boundaries of one chunk's levels (the only synchronisation of the level-synchronous schedule)
     // then overlap with the other chunk's launches instead of leaving the tail of every launch to half-empty CUs.
-    double *d_arena[2] = {nullptr, nullptr};  // private arenas of the requests of the wave in flight, per lane
-    size_t arena_bytes[2] = {0, 0};
-    double *d_results[2] = {nullptr, nullptr};  // dense posteriors of the call in flight (two calls may overlap)
-    size_t results_cap[2] = {0, 0};             // doubles
+    DevBuf<char> d_arena[2];      // private arenas of the requests of the wave in flight, per lane (sized in bytes: grow_arena)
+    double *arena(int lane) const { return reinterpret_cast<double *>(d_arena[lane].get()); }
+    DevBuf<double> d_results[2];  // dense posteriors of the call in flight (two calls may overlap)
     struct Pending {                            // an asynchronous call whose results have not been collected yet
         bool active = false;
         double *out = nullptr;
         size_t cells = 0;
-        hipEvent_t done = nullptr;
+        Event done;
     } pend[2];
     int next_slot = 0;
     // chunk pipeline: workers plan the next chunks into pinned buffers while the GPU runs chunk i
-    ThreadPool *pool = nullptr;
-    struct Staging {  // pinned host staging: pageable sources would make hipMemcpyAsync block on the stream
-        char *p = nullptr;
-        size_t cap = 0;
-    };
+    std::unique_ptr<ThreadPool> pool;
     struct Set {
-        Staging stage[4];           // prog_off, arena_off, items, wg_item
+        PinnedBuf stage[4];         // prog_off, arena_off, items, wg_item
         std::vector<ProgBuf> bufs;  // pinned host program buffers, one per worker
         std::vector<ProgBuf> xbufs; // ... and the ones the host re-plans single requests of a device-planned chunk into (beyond a device limit)
         BatchPlan xplan;
-        uint32_t *d_prog = nullptr;
-        size_t prog_cap = 0;
-        uint64_t *d_prog_off = nullptr;
-        size_t prog_off_cap = 0;
-        uint64_t *d_arena_off = nullptr;
-        size_t arena_off_cap = 0;
-        uint32_t *d_wg_item = nullptr;
-        size_t wg_item_cap = 0;
-        Item *d_items = nullptr;
-        size_t items_cap = 0;
-        hipEvent_t uploaded = nullptr;       // the copy stream has delivered this set's programs and schedule
-        std::vector<hipEvent_t> ev;          // launch boundaries of the waves in flight
+        DevBuf<uint32_t> d_prog;
+        DevBuf<uint64_t> d_prog_off, d_arena_off;
+        DevBuf<uint32_t> d_wg_item;
+        DevBuf<Item> d_items;
+        Event uploaded;                      // the copy stream has delivered this set's programs and schedule
+        std::vector<Event> ev;               // launch boundaries of the waves in flight
         struct Timed {  // kid >= 0: one launch; -1: the wall time of a wave (kernel_ms); -2: the launches of one level on the two streams of
                         // option overlap, as ONE concurrent launch pair - events (e0, e1) of the level kernel's launch, (e2, e3) of the sweep
                         // kernel's (kNone: the level has no such launch); its duration is the span from the earlier start to the later end
@@ -254,17 +248,23 @@ struct mibn_ctx {
         int gap_from = -1;  // trace: index (in mibn_ctx::gap_ev) of the event that closed the previous wave
         BatchPlan plan;
         Schedule sched;
+        ~Set() {  // (ProgBuf is planner.h's, shared with the host tools: its backing is freed here)
+            for (auto *v : {&bufs, &xbufs})
+                for (ProgBuf &b : *v) {
+                    if (b.grow) (void)PinnedBuf::adopt(b.data).release();  // (pinned_grow's)
+                    b.release();
+                }
+        }
     } set[kChunkSets];
-    Staging res_stage[2];  // pinned landing buffers of asynchronous calls
+    PinnedBuf res_stage[2];  // pinned landing buffers of asynchronous calls
     // small-network specialisation (tiny_kernel.hip.h): one lane per request, no planning
     bool tiny_ok = false;
     int tiny = 1;              // option: 1 = use it where the network is eligible, 0 = always plan step programs
     int tiny_zero_copy = 1;    // option: calls of at most kTinyZeroCopyRequests requests read / write pinned host memory directly (run_tiny)
-    int32_t *d_tiny_meta = nullptr;
+    DevBuf<int32_t> d_tiny_meta;
     int32_t tiny_meta_words = 0;
-    char *d_tiny_req = nullptr;  // request arrays of the call in flight
-    size_t tiny_req_cap = 0;
-    Staging tiny_stage;
+    DevBuf<char> d_tiny_req;  // request arrays of the call in flight
+    PinnedBuf tiny_stage;
     PlanPolicy pol;                  // the adaptive planning policy and the share rule of the device planner (plan_policy.h)
     int second_on_device = 0;        // option: 1 = device-planned calls emit the runner-up too (tests: the wave planner's second emission)
     double retired_requests = 0;     // requests whose kernel time has been booked (the unit of kernel_ms in the policy's windows)
@@ -279,32 +279,26 @@ struct mibn_ctx {
                                      // and the stream's own order already mixes the sizes; balancing the sums exactly (3) shortens the
                                      // planner's kernels by 2 % and moves nothing.  32 lanes, four threads: 259 / 265 / 265 / 258 k.
     int gpu_search = 0;              // option: 1 = search elimination orders on the device (networks of <= 128 variables)
-    hipStream_t search_stream = nullptr;
-    char *d_order_net = nullptr;     // the OrderNet arrays
+    DevBuf<char> d_order_net;        // the OrderNet arrays
     OrderNet order_net_dev;          // pointers into d_order_net
     bool order_net_ok = false;
-    uint8_t *d_orders = nullptr;
-    size_t orders_cap = 0;
-    int32_t *d_order_len = nullptr;
-    size_t order_len_cap = 0;
-    OrderScratch *d_order_scratch = nullptr;
-    size_t order_scratch_cap = 0;
-    Staging search_in, search_out;   // pinned: request arrays in, orders + lengths out
+    DevBuf<uint8_t> d_orders;
+    DevBuf<int32_t> d_order_len;
+    DevBuf<OrderScratch> d_order_scratch;
+    PinnedBuf search_in, search_out;  // pinned: request arrays in, orders + lengths out
     double search_ms = 0;            // host wall time spent waiting for the device search (last call)
     // device program emission (emit_kernel)
     int gpu_emit = 0;                // option: 1 = the device plans whole chunks (order search + emission), 2 = the same, checked
                                      // word for word against the host's planner (tests)
-    char *d_emit_net = nullptr;      // the EmitNet arrays
+    DevBuf<char> d_emit_net;         // the EmitNet arrays
     EmitNet emit_net_dev;            // pointers into d_emit_net
     bool emit_net_ok = false;
-    char *d_emit_scratch = nullptr;  // planning state, one slice per lane
-    size_t emit_scratch_cap = 0;
-    uint32_t *d_emit_cursor = nullptr;
-    uint32_t *d_plan_perm = nullptr;  // the order in which wave_plan_kernel's waves draw the requests of a chunk (plan_sort_kernel: the long ones first)
-    size_t plan_perm_cap = 0;
+    DevBuf<char> d_emit_scratch;     // planning state, one slice per lane
+    DevBuf<uint32_t> d_emit_cursor;
+    DevBuf<uint32_t> d_plan_perm;     // the order in which wave_plan_kernel's waves draw the requests of a chunk (plan_sort_kernel: the long ones first)
     int wave_sort = 1;                // option: 0 = by index
-    Staging emit_in, emit_out;       // pinned, read / written by the kernels themselves: request arrays in, per-request results and work items out
-    hipEvent_t emit_ev[2] = {nullptr, nullptr};  // around the planner's kernels
+    PinnedBuf emit_in, emit_out;     // pinned, read / written by the kernels themselves: request arrays in, per-request results and work items out
+    Event emit_ev[2];                // around the planner's kernels
     BatchPlan emit_dev, emit_host;   // the two parts of a chunk before they are joined
     uint32_t emit_words = 6144;      // words of a request's program slot (doubles after a chunk that did not fit)
     int64_t emit_single = 0;         // requests of device-planned chunks the host planned because they exceeded a device limit
@@ -312,12 +306,12 @@ struct mibn_ctx {
     int wave_plan = 1;               // option: 1 = chunks the device plans go through wave_plan_kernel where the network is covered (wave_plan.h)
     int plan_priority = 2;           // option: the device planner's stream priority (2 highest - the default since round 4 -, 1 normal, 0 lowest); before the first device-planned chunk
     int wave_wgs = 0;                // option: workgroups of a wave_plan_kernel launch (0: one per four requests - the whole chip at once)
-    WNet *wnet_host = nullptr;       // the packed network + options as uploaded last
-    WNet *d_wnet = nullptr;
+    std::unique_ptr<WNet> wnet_host;  // the packed network + options as uploaded last
+    DevBuf<WNet> d_wnet;
     bool wnet_ok = false;
     double emit_ms = 0;              // host wall time spent waiting for the device planner (last call)
     uint64_t emit_chunks = 0, emit_fallbacks = 0;
-    hipEvent_t gap_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // trace: ends of the last waves (GPU idle time between waves)
+    Event gap_ev[4];          // trace: ends of the last waves (GPU idle time between waves)
     uint64_t n_waves = 0;
     int n_sets = 2;           // chunk sets in use (option "chunk_sets": 2..4; two per lane: one on the GPU, one being planned)
     int set_cursor = 0;    // the chunk set the next chunk plans into: alternates across calls, so that a call of one chunk
@@ -325,6 +319,8 @@ struct mibn_ctx {
     uint64_t call_id = 0;  // kernel time retired later is booked to the call that launched it
     // RCCL (multi-GPU gather / reduce), loaded on demand
     struct Comm {
+        Stream stream;  // collectives run on their own stream: the gather of batch s must not queue behind the
+                        // kernels of batch s + 1, which the two-deep pipeline has already submitted
         void *dl = nullptr;
         ncclComm_t comm = nullptr;
         int rank = 0, world = 1;
@@ -337,10 +333,7 @@ struct mibn_ctx {
         decltype(&ncclReduce) Reduce = nullptr;
         decltype(&ncclAllReduce) AllReduce = nullptr;
         decltype(&ncclGetErrorString) GetErrorString = nullptr;
-        void *d_send = nullptr, *d_recv = nullptr;
-        size_t send_cap = 0, recv_cap = 0;
-        hipStream_t stream = nullptr;  // collectives run on their own stream: the gather of batch s must not queue behind the
-                                       // kernels of batch s + 1, which the two-deep pipeline has already submitted
+        DevBuf<char> d_send, d_recv;
     } comm;
     std::string err;
     mibn_stats stats{}, total{};               // last call / since creation
@@ -353,21 +346,15 @@ struct mibn_ctx {
         std::vector<ProgBuf> bufs;  // malloc-backed program buffers, one per worker
         BatchPlan plan;
         Schedule sched;
-        uint32_t *d_prog = nullptr;
-        size_t prog_cap = 0;
-        uint64_t *d_prog_off = nullptr, *d_arena_off = nullptr;
-        size_t prog_off_cap = 0, arena_off_cap = 0;
-        Item *d_items = nullptr;
-        size_t items_cap = 0;
-        uint32_t *d_wg_item = nullptr;
-        size_t wg_item_cap = 0;
-        double *d_m = nullptr, *d_log_p = nullptr;  // per request of a chunk: what its FINAL step wrote; (MPE) the logarithm of it
-        size_t m_cap = 0, log_p_cap = 0;
-        int32_t *d_codes = nullptr;  // the decoded assignments of a chunk (MPE) / the rows of a draw launch
-        size_t codes_cap = 0;
-        DrawItem *d_draw_items = nullptr;
-        size_t draw_items_cap = 0;
-        std::vector<hipEvent_t> ev;
+        DevBuf<uint32_t> d_prog;
+        DevBuf<uint64_t> d_prog_off, d_arena_off;
+        DevBuf<Item> d_items;
+        DevBuf<uint32_t> d_wg_item;
+        DevBuf<double> d_m, d_log_p;  // per request of a chunk: what its FINAL step wrote; (MPE) the logarithm of it
+        DevBuf<int32_t> d_codes;      // the decoded assignments of a chunk (MPE) / the rows of a draw launch
+        DevBuf<DrawItem> d_draw_items;
+        std::vector<Event> ev;
+        ~Elim() { for (ProgBuf &b : bufs) b.release(); }
     } elim;
     // mibn_expect_batch (blocking, host-planned): while `expect` is set, a query call hands its device-resident results to expect_run
     // instead of downloading them.  Buffers of its own; last-call statistics only (nothing a later query call reads).
@@ -376,17 +363,15 @@ struct mibn_ctx {
         const double *weight = nullptr;
         int64_t B = 0, n_acc = 0;
         double *acc = nullptr, *p_out = nullptr;  // host
-        char *d_meta = nullptr;
-        size_t meta_cap = 0;
-        double *d_f64 = nullptr;  // [acc | p_out | weight | slab partials]
-        size_t f64_cap = 0;
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        DevBuf<char> d_meta;
+        DevBuf<double> d_f64;  // [acc | p_out | weight | slab partials]
+        Event ev[2];
     } ex;
     bool expect = false;
     // mibn_dataset_create / mibn_score_families: code matrices resident on the device (id = index; a destroyed entry keeps its slot, so an
     // id is never handed out twice) and the buffers of a scoring call.  Nothing a query call reads; last-call statistics only.
     struct Dataset {
-        uint8_t *d_codes = nullptr;  // [n_cols][n_rows]
+        DevBuf<uint8_t> d_codes;  // [n_cols][n_rows]
         int64_t n_rows = 0;
         int32_t n_cols = 0;
         std::vector<int32_t> card;
@@ -394,26 +379,21 @@ struct mibn_ctx {
     };
     std::vector<Dataset> datasets;
     struct Score {
-        unsigned long long *d_counts = nullptr;
-        size_t counts_cap = 0;
-        char *d_meta = nullptr;
-        size_t meta_cap = 0;
-        double *d_f64 = nullptr;  // [scores | partials of the chunked tables]
-        size_t f64_cap = 0;
-        std::vector<hipEvent_t> ev;
+        DevBuf<unsigned long long> d_counts;
+        DevBuf<char> d_meta;
+        DevBuf<double> d_f64;  // [scores | partials of the chunked tables]
+        std::vector<Event> ev;
     } sc;
     int64_t score_cells = kScoreCellBudget;  // option score_cells (test hook: forces sub-batches)
     // options
     double arena_gb = 200.0;  // scratch budget of all lanes together (of the 288 GB)
-    hipStream_t stream2 = nullptr;  // lane 1 (lane 0 = stream)
-    hipStream_t aux[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // option overlap, per lane: the sweep kernel's, the segment kernel's and the MFMA kernel's launches
     int mfma_kernel = 1;            // round 5: the one-table fp64-MFMA pair classes of a level as a launch of ve_mfma_kernel (128 VGPRs, four
                                     // waves per SIMD) on a fourth stream instead of workgroups of ve_level_kernel (168 VGPRs, three): 296.2 -> 300.4 k queries/s,
                                     // all kernels 4.56 -> 4.63 TB/s, three interleaved repetitions each (profiles/r05_b_ab.log)
     int seg_kernel = 1;             // the segments of a level as a launch of ve_segment_kernel (12 KB of LDS per workgroup) instead of workgroups
                                     // of ve_level_kernel (40 KB, 168 VGPRs)
-    hipEvent_t epoch = nullptr;     // reference of the busy-time bookkeeping (re-recorded when the GPU is idle)
-    hipEvent_t lane_ev = nullptr, zero_ev = nullptr;  // end of lane 1's work of a call / results buffer zeroed
+    Event epoch;                    // reference of the busy-time bookkeeping (re-recorded when the GPU is idle)
+    Event lane_ev, zero_ev;         // end of lane 1's work of a call / results buffer zeroed
     double busy_until = 0;          // ms since epoch up to which GPU time has been booked as kernel_ms
     int n_streams = 1;  // lanes.  1 (default): every chunk on the main stream, one after the other.  2: consecutive chunks run concurrently
                         // (+3 % with 8 192-request chunks, profiles/r02_y_lanes*.log; the per-launch event times then include the other lane's
@@ -461,8 +441,7 @@ static int upload_order_net(mibn_ctx *h) {
     const size_t o_hint = put(net.hint_flat.data(), nh * n * 4), o_log = put(net.log2card.data(), n * 8);
     const size_t o_anc = put(net.anc2.data(), n * sizeof(B2)), o_sc = put(net.scope2.data(), n * sizeof(B2));
     const size_t o_fam = put(net.fam2.data(), n * sizeof(B2));
-    if (h->d_order_net) { HIP_TRY(h, hipFree(h->d_order_net)); h->d_order_net = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->d_order_net, buf.size()));
+    HIP_TRY(h, h->d_order_net.reset(buf.size()));
     HIP_TRY(h, hipMemcpy(h->d_order_net, buf.data(), buf.size(), hipMemcpyHostToDevice));
     OrderNet &o = h->order_net_dev;
     o = net.order_view();
@@ -496,8 +475,7 @@ static int upload_emit_net(mibn_ctx *h) {
     const size_t o_card = put(net.card.data(), n * 4), o_log = put(net.log2card.data(), n * 8), o_pool = put(net.pool_off.data(), n * 8);
     const size_t o_soff = put(net.scope_off32.data(), (n + 1) * 4), o_sv = put(net.scope_flat.data(), net.scope_flat.size() * 4);
     const size_t o_ss = put(net.cstride_flat.data(), net.cstride_flat.size() * 8), o_anc = put(net.anc_flat.data(), net.anc_flat.size() * 8);
-    if (h->d_emit_net) { HIP_TRY(h, hipFree(h->d_emit_net)); h->d_emit_net = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->d_emit_net, buf.size()));
+    HIP_TRY(h, h->d_emit_net.reset(buf.size()));
     HIP_TRY(h, hipMemcpy(h->d_emit_net, buf.data(), buf.size(), hipMemcpyHostToDevice));
     EmitNet &e = h->emit_net_dev;
     e = net.emit_view();
@@ -559,15 +537,9 @@ int mibn_create(int device, mibn_t **out) {
         return MIBN_E_NODEVICE;
     }
     h->n_cu = prop.multiProcessorCount;
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->aux[0][0], hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->aux[0][1], hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->aux[1][0], hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->aux[1][1], hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->aux[0][2], hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->aux[1][2], hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) == hipSuccess;
+    bool ok = true;
+    for (Stream *q : {&h->stream, &h->stream2, &h->aux[0][0], &h->aux[0][1], &h->aux[1][0], &h->aux[1][1], &h->aux[0][2], &h->aux[1][2], &h->copy_stream})
+        ok = ok && q->ensure(hipStreamNonBlocking) == hipSuccess;
     // the sweep kernel keeps its 64 KiB tile, the T tables and the step descriptor in dynamic LDS (two workgroups per CU)
     ok = ok && hipFuncSetAttribute((const void *)ve_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes) == hipSuccess;
     ok = ok && hipFuncSetAttribute((const void *)ve_sweep_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes) == hipSuccess;
@@ -578,88 +550,13 @@ int mibn_create(int device, mibn_t **out) {
 
 void mibn_destroy(mibn_t *h) {
     if (!h) return;
-    delete h->pool;
     if (!h->planner_only) {
         (void)hipSetDevice(h->device);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
-        (void)mibn_comm_destroy(h);
-        (void)hipFree(h->d_pool);
         if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-        (void)hipFree(h->d_arena[0]);
-        (void)hipFree(h->d_arena[1]);
-        if (h->epoch) (void)hipEventDestroy(h->epoch);
-        if (h->lane_ev) (void)hipEventDestroy(h->lane_ev);
-        if (h->zero_ev) (void)hipEventDestroy(h->zero_ev);
-        (void)hipFree(h->d_tiny_meta);
-        (void)hipFree(h->d_tiny_req);
-        (void)hipFree(h->d_order_net);
-        (void)hipFree(h->d_orders);
-        (void)hipFree(h->d_order_len);
-        (void)hipFree(h->d_order_scratch);
-        (void)hipFree(h->d_emit_net);
-        (void)hipFree(h->d_wnet);
-        delete h->wnet_host;
-        (void)hipFree(h->d_emit_scratch);
-        (void)hipFree(h->d_emit_cursor);
-        if (h->d_plan_perm) (void)hipFree(h->d_plan_perm);
-        if (h->emit_in.p) (void)hipHostFree(h->emit_in.p);
-        if (h->emit_out.p) (void)hipHostFree(h->emit_out.p);
-        if (h->search_in.p) (void)hipHostFree(h->search_in.p);
-        if (h->search_out.p) (void)hipHostFree(h->search_out.p);
-        if (h->search_stream) (void)hipStreamDestroy(h->search_stream);
-        if (h->tiny_stage.p) (void)hipHostFree(h->tiny_stage.p);
-        for (int k = 0; k < 2; ++k) {
-            (void)hipFree(h->d_results[k]);
-            if (h->pend[k].done) (void)hipEventDestroy(h->pend[k].done);
-        }
-        for (auto &st : h->set) {
-            for (auto &b : st.bufs)
-                if (b.data) (void)hipHostFree(b.data);
-            for (auto &b : st.xbufs)
-                if (b.data) (void)hipHostFree(b.data);
-            (void)hipFree(st.d_prog);
-            (void)hipFree(st.d_prog_off);
-            (void)hipFree(st.d_arena_off);
-            (void)hipFree(st.d_items);
-            (void)hipFree(st.d_wg_item);
-            for (auto &sg : st.stage)
-                if (sg.p) (void)hipHostFree(sg.p);
-            for (auto e : st.ev) (void)hipEventDestroy(e);
-            if (st.uploaded) (void)hipEventDestroy(st.uploaded);
-        }
-        for (auto &sg : h->res_stage)
-            if (sg.p) (void)hipHostFree(sg.p);
-        {
-            mibn_ctx::Elim &M = h->elim;
-            for (auto &b : M.bufs) b.release();
-            (void)hipFree(M.d_prog);
-            (void)hipFree(M.d_prog_off);
-            (void)hipFree(M.d_arena_off);
-            (void)hipFree(M.d_items);
-            (void)hipFree(M.d_wg_item);
-            (void)hipFree(M.d_m);
-            (void)hipFree(M.d_log_p);
-            (void)hipFree(M.d_codes);
-            (void)hipFree(M.d_draw_items);
-            for (auto e : M.ev) (void)hipEventDestroy(e);
-        }
-        (void)hipFree(h->ex.d_meta);
-        (void)hipFree(h->ex.d_f64);
-        for (auto &ds : h->datasets) (void)hipFree(ds.d_codes);
-        (void)hipFree(h->sc.d_counts);
-        (void)hipFree(h->sc.d_meta);
-        (void)hipFree(h->sc.d_f64);
-        for (hipEvent_t e : h->sc.ev) (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->ex.ev)
-            if (e) (void)hipEventDestroy(e);
-        if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-        if (h->stream2) (void)hipStreamDestroy(h->stream2);
-        for (auto &la : h->aux)
-            for (hipStream_t a : la)
-                if (a) (void)hipStreamDestroy(a);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
+        (void)mibn_comm_destroy(h);
     }
-    delete h;
+    delete h;  // (the members free what they own: buffers and events first, the streams last)
 }
 
 const char *mibn_last_error(const mibn_t *h) { return h ? h->err.c_str() : "null handle"; }
@@ -748,16 +645,14 @@ int mibn_set_network(mibn_t *h, int32_t n_vars, const int32_t *card, const int64
     if (h->pol.auto_emit) { h->gpu_emit = 0; h->pol.auto_emit = false; }
     if (!h->planner_only) {
         HIP_TRY(h, hipSetDevice(h->device));
-        if (h->d_pool) { HIP_TRY(h, hipFree(h->d_pool)); h->d_pool = nullptr; }
-        size_t bytes = std::max<size_t>(8, h->net.pool.size() * sizeof(double));
-        HIP_TRY(h, hipMalloc(&h->d_pool, bytes));
+        HIP_TRY(h, h->d_pool.reset(std::max<size_t>(1, h->net.pool.size())));
         HIP_TRY(h, hipMemcpy(h->d_pool, h->net.pool.data(), h->net.pool.size() * sizeof(double), hipMemcpyHostToDevice));
         h->tiny_ok = tiny_eligible(h->net);
-        if (h->d_tiny_meta) { HIP_TRY(h, hipFree(h->d_tiny_meta)); h->d_tiny_meta = nullptr; }
+        HIP_TRY(h, h->d_tiny_meta.release());
         if (h->tiny_ok) {
             const std::vector<int32_t> meta = tiny_meta(h->net);
             h->tiny_meta_words = (int32_t)meta.size();
-            HIP_TRY(h, hipMalloc(&h->d_tiny_meta, meta.size() * 4));
+            HIP_TRY(h, h->d_tiny_meta.reset(meta.size()));
             HIP_TRY(h, hipMemcpy(h->d_tiny_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice));
             h->tiny_ok = tiny_lds_bytes((int)h->net.pool.size(), h->tiny_meta_words) <= 64 * 1024;
         }
@@ -807,41 +702,34 @@ int mibn_plan_stats(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, 
 namespace {
 
 template <class T>
-int ensure(mibn_ctx *h, T *&ptr, size_t &cap, size_t need) {
-    if (need <= cap) return MIBN_OK;
-    if (ptr) { HIP_TRY(h, hipFree(ptr)); ptr = nullptr; cap = 0; }
-    size_t n = need + need / 2 + 1024;
-    HIP_TRY(h, hipMalloc(&ptr, n * sizeof(T)));
-    cap = n;
+int ensure(mibn_ctx *h, DevBuf<T> &buf, size_t need) {
+    HIP_TRY(h, buf.ensure(need));
     return MIBN_OK;
 }
 
 // pinned backing of the program buffers: the upload is then a real async DMA that overlaps planning
 uint32_t *pinned_grow(void *, uint32_t *old, size_t used, size_t new_cap) {
-    uint32_t *p = nullptr;
-    if (hipHostMalloc((void **)&p, new_cap * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return nullptr;
+    PinnedBuf fresh;
+    if (fresh.reset(new_cap * sizeof(uint32_t)) != hipSuccess) return nullptr;
     if (old) {
-        std::memcpy(p, old, used * sizeof(uint32_t));
-        (void)hipHostFree(old);
+        std::memcpy(fresh.get(), old, used * sizeof(uint32_t));
+        (void)PinnedBuf::adopt(old).release();
     }
-    return p;
+    return reinterpret_cast<uint32_t *>(fresh.detach());
 }
 
 // a pinned staging buffer of at least `bytes` (a quarter of headroom; what it held is not kept)
-int pinned(mibn_ctx *h, mibn_ctx::Staging &sg, size_t bytes) {
-    if (bytes <= sg.cap) return MIBN_OK;
-    if (sg.p) { HIP_TRY(h, hipHostFree(sg.p)); sg.p = nullptr; sg.cap = 0; }
-    HIP_TRY(h, hipHostMalloc((void **)&sg.p, bytes + bytes / 4 + 4096, hipHostMallocDefault));
-    sg.cap = bytes + bytes / 4 + 4096;
+int pinned(mibn_ctx *h, PinnedBuf &sg, size_t bytes) {
+    HIP_TRY(h, sg.ensure(bytes));
     return MIBN_OK;
 }
 
 // async upload through a pinned staging buffer (one per destination and set: reused only after retire())
-int upload(mibn_ctx *h, mibn_ctx::Staging &sg, void *dst, const void *src, size_t bytes) {
+int upload(mibn_ctx *h, PinnedBuf &sg, void *dst, const void *src, size_t bytes) {
     if (!bytes) return MIBN_OK;
     if (int rc = pinned(h, sg, bytes)) return rc;
-    std::memcpy(sg.p, src, bytes);
-    HIP_TRY(h, hipMemcpyAsync(dst, sg.p, bytes, hipMemcpyHostToDevice, h->copy_stream));
+    std::memcpy(sg.get(), src, bytes);
+    HIP_TRY(h, hipMemcpyAsync(dst, sg.get(), bytes, hipMemcpyHostToDevice, h->copy_stream));
     return MIBN_OK;
 }
 
@@ -882,7 +770,7 @@ int default_threads() {
 
 void ensure_pool(mibn_ctx *h) {
     if (h->pool) return;
-    h->pool = new ThreadPool(h->threads > 0 ? h->threads : default_threads());
+    h->pool.reset(new ThreadPool(h->threads > 0 ? h->threads : default_threads()));
     for (auto &st : h->set) {
         st.bufs.resize(h->pool->size());
         st.xbufs.resize(h->pool->size());
@@ -921,13 +809,13 @@ void reset_last_stats(mibn_ctx *h) {
 // that fails.
 template <class Wait>
 int each_stream(mibn_ctx *h, Wait &&wait) {
-    for (hipStream_t q : {h->search_stream, h->copy_stream, h->stream, h->stream2})
+    for (hipStream_t q : {h->search_stream.get(), h->copy_stream.get(), h->stream.get(), h->stream2.get()})
         if (q)
             if (int rc = wait(q)) return rc;
     for (auto &la : h->aux)
-        for (hipStream_t a : la)
+        for (const Stream &a : la)
             if (a)
-                if (int rc = wait(a)) return rc;
+                if (int rc = wait(a.get())) return rc;
     return MIBN_OK;
 }
 int drain_streams(mibn_ctx *h) {
@@ -1019,12 +907,9 @@ int retire_all(mibn_ctx *h) {
 }
 
 int next_event(mibn_ctx *h, mibn_ctx::Set &st, size_t &idx, hipStream_t stream = nullptr) {
-    if (st.ev_used == st.ev.size()) {
-        hipEvent_t e;
-        HIP_TRY(h, hipEventCreate(&e));
-        st.ev.push_back(e);
-    }
+    if (st.ev_used == st.ev.size()) st.ev.emplace_back();
     idx = st.ev_used++;
+    HIP_TRY(h, st.ev[idx].ensure());
     HIP_TRY(h, hipEventRecord(st.ev[idx], stream ? stream : h->stream));
     return MIBN_OK;
 }
@@ -1043,6 +928,15 @@ namespace {
 // latency-bound: theirs hardly does): the host's share of a chunk may shrink to a hundredth
 static bool wave_mode(const mibn_ctx *h) { return h->wave_plan && h->wnet_ok; }
 
+// The planning stream, created on first use with the priority of option plan_priority.
+static int plan_stream(mibn_ctx *h) {
+    if (h->search_stream) return MIBN_OK;
+    int lo = 0, hi = 0;
+    HIP_TRY(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
+    HIP_TRY(h, h->search_stream.ensure(hipStreamNonBlocking, h->plan_priority >= 2 ? hi : (h->plan_priority == 1 ? (lo + hi) / 2 : lo)));
+    return MIBN_OK;
+}
+
 static int plan_lanes_now(const mibn_ctx *h) {
     if (h->plan_lanes > 0) return h->plan_lanes;
     return h->pool && h->pool->size() <= 2 && h->chunk > 32768 ? 24 : 32;
@@ -1058,27 +952,23 @@ int search_orders_async(mibn_ctx *h, uint32_t flags, int64_t b0, int64_t b1, con
                         const int64_t *e_off, const int32_t *e_vars) {
     const int64_t n = b1 - b0;
     int rc;
-    if (!h->search_stream) {
-        int lo = 0, hi = 0;
-        HIP_TRY(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIP_TRY(h, hipStreamCreateWithPriority(&h->search_stream, hipStreamNonBlocking, h->plan_priority >= 2 ? hi : (h->plan_priority == 1 ? (lo + hi) / 2 : lo)));
-    }
+    if ((rc = plan_stream(h))) return rc;
     const size_t nq = (size_t)(q_off[b1] - q_off[b0]), ne = (size_t)(e_off[b1] - e_off[b0]);
     const size_t off_bytes = (size_t)(n + 1) * 8;
     const size_t in_bytes = 2 * off_bytes + (nq + ne) * 4 + 64;
     if ((rc = pinned(h, h->search_in, in_bytes))) return rc;
     if ((rc = pinned(h, h->search_out, (size_t)n * 132))) return rc;
-    if ((rc = ensure(h, h->d_order_scratch, h->order_scratch_cap, (size_t)std::min(n, kSearchSlice)))) return rc;
-    int64_t *qo = reinterpret_cast<int64_t *>(h->search_in.p), *eo = qo + (n + 1);
+    if ((rc = ensure(h, h->d_order_scratch, (size_t)std::min(n, kSearchSlice)))) return rc;
+    int64_t *qo = reinterpret_cast<int64_t *>(h->search_in.get()), *eo = qo + (n + 1);
     for (int64_t i = 0; i <= n; ++i) { qo[i] = q_off[b0 + i] - q_off[b0]; eo[i] = e_off[b0 + i] - e_off[b0]; }
-    char *pv = h->search_in.p + 2 * off_bytes;
+    char *pv = h->search_in.get() + 2 * off_bytes;
     std::memcpy(pv, q_vars + q_off[b0], nq * 4);
     if (ne) std::memcpy(pv + nq * 4, e_vars + e_off[b0], ne * 4);
     // (no copies on this stream - the kernel reads the request arrays from, and writes the orders to, pinned host memory: a DMA
     // copy here queues behind the previous call's result download on the copy engine, i.e. behind that call's kernels)
-    const char *d_req = h->search_in.p;
-    uint8_t *orders_out = reinterpret_cast<uint8_t *>(h->search_out.p);
-    int32_t *len_out = reinterpret_cast<int32_t *>(h->search_out.p + (size_t)n * 128);
+    const char *d_req = h->search_in.get();
+    uint8_t *orders_out = reinterpret_cast<uint8_t *>(h->search_out.get());
+    int32_t *len_out = reinterpret_cast<int32_t *>(h->search_out.get() + (size_t)n * 128);
     for (int64_t s0 = 0; s0 < n; s0 += kSearchSlice) {
         const int64_t m = std::min(kSearchSlice, n - s0);
         OrderArgs A;
@@ -1127,11 +1017,7 @@ int plan_on_device_launch(mibn_ctx *h, uint32_t flags, int64_t b0, int64_t b1, c
                           const int32_t *e_vars, const int32_t *e_codes, const int64_t *out_off, const char *skip, mibn_ctx::Set &st, size_t prog_words) {
     const int64_t n = b1 - b0;
     int rc;
-    if (!h->search_stream) {
-        int lo = 0, hi = 0;
-        HIP_TRY(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIP_TRY(h, hipStreamCreateWithPriority(&h->search_stream, hipStreamNonBlocking, h->plan_priority >= 2 ? hi : (h->plan_priority == 1 ? (lo + hi) / 2 : lo)));
-    }
+    if ((rc = plan_stream(h))) return rc;
     hipStream_t P = h->search_stream;
     const size_t nq = (size_t)(q_off[b1] - q_off[b0]), ne = (size_t)(e_off[b1] - e_off[b0]);
     const size_t off_bytes = (size_t)(n + 1) * 8;
@@ -1145,37 +1031,33 @@ int plan_on_device_launch(mibn_ctx *h, uint32_t flags, int64_t b0, int64_t b1, c
     // them is rebuilt per chunk (10 KB) and uploaded when it has changed
     bool wave = false;
     if (h->wave_plan && h->order_net_ok) {
-        if (!h->wnet_host) { h->wnet_host = new WNet; std::memset(h->wnet_host, 0, sizeof(WNet)); h->wnet_ok = false; }
-        WNet *fresh = new WNet;
+        if (!h->wnet_host) { h->wnet_host.reset(new WNet); std::memset(h->wnet_host.get(), 0, sizeof(WNet)); h->wnet_ok = false; }
+        std::unique_ptr<WNet> fresh(new WNet);
         if (h->net.wave_view(*fresh)) {
-            if (!h->d_wnet) HIP_TRY(h, hipMalloc(&h->d_wnet, sizeof(WNet)));
-            if (!h->wnet_ok || std::memcmp(fresh, h->wnet_host, sizeof(WNet)) != 0) {
-                HIP_TRY(h, hipMemcpy(h->d_wnet, fresh, sizeof(WNet), hipMemcpyHostToDevice));
-                std::memcpy(h->wnet_host, fresh, sizeof(WNet));
+            if (!h->d_wnet) HIP_TRY(h, h->d_wnet.reset(1));
+            if (!h->wnet_ok || std::memcmp(fresh.get(), h->wnet_host.get(), sizeof(WNet)) != 0) {
+                HIP_TRY(h, hipMemcpy(h->d_wnet, fresh.get(), sizeof(WNet), hipMemcpyHostToDevice));
+                std::memcpy(h->wnet_host.get(), fresh.get(), sizeof(WNet));
                 h->wnet_ok = true;
             }
             wave = true;
         }
-        delete fresh;
     }
     if ((rc = pinned(h, h->emit_in, in_bytes))) return rc;
     if ((rc = pinned(h, h->emit_out, (size_t)n * sizeof(EmitMeta) + tag_cap * sizeof(Tag) + 64))) return rc;
-    if (!h->d_emit_cursor) HIP_TRY(h, hipMalloc(&h->d_emit_cursor, 64));
+    if (!h->d_emit_cursor) HIP_TRY(h, h->d_emit_cursor.reset(16));  // (64 bytes)
     if (!wave) {
-    if ((rc = ensure(h, h->d_orders, h->orders_cap, (size_t)n * 128))) return rc;
-    if ((rc = ensure(h, h->d_order_len, h->order_len_cap, (size_t)n))) return rc;
-    if ((rc = ensure(h, h->d_order_scratch, h->order_scratch_cap, (size_t)slice))) return rc;
+    if ((rc = ensure(h, h->d_orders, (size_t)n * 128))) return rc;
+    if ((rc = ensure(h, h->d_order_len, (size_t)n))) return rc;
+    if ((rc = ensure(h, h->d_order_scratch, (size_t)slice))) return rc;
     }
-    if (!wave && (size_t)slice * scratch_stride > h->emit_scratch_cap) {
-        if (h->d_emit_scratch) { HIP_TRY(h, hipFree(h->d_emit_scratch)); h->d_emit_scratch = nullptr; h->emit_scratch_cap = 0; }
-        const size_t want = (size_t)std::max<int64_t>(slice, std::min<int64_t>(h->chunk, kPlanSlice)) * scratch_stride;
-        HIP_TRY(h, hipMalloc(&h->d_emit_scratch, want));
-        h->emit_scratch_cap = want;
-    }
-    if ((rc = ensure(h, st.d_prog, st.prog_cap, std::max(prog_words, (size_t)n * stride) + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)  // (+ room for the host's share of the chunk)
-    if (!h->emit_ev[0]) { HIP_TRY(h, hipEventCreate(&h->emit_ev[0])); HIP_TRY(h, hipEventCreate(&h->emit_ev[1])); }
+    if (!wave && (size_t)slice * scratch_stride > h->d_emit_scratch.cap())
+        HIP_TRY(h, h->d_emit_scratch.reset((size_t)std::max<int64_t>(slice, std::min<int64_t>(h->chunk, kPlanSlice)) * scratch_stride));
+    if ((rc = ensure(h, st.d_prog, std::max(prog_words, (size_t)n * stride) + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)  // (+ room for the host's share of the chunk)
+    HIP_TRY(h, h->emit_ev[0].ensure());
+    HIP_TRY(h, h->emit_ev[1].ensure());
     // the request arrays of the chunk in one pinned buffer: [q_off | e_off | out_off | q_vars | e_vars | e_codes | skip]
-    char *pin = h->emit_in.p;
+    char *pin = h->emit_in.get();
     int64_t *qo = reinterpret_cast<int64_t *>(pin), *eo = qo + (n + 1), *oo = eo + (n + 1);
     for (int64_t i = 0; i <= n; ++i) { qo[i] = q_off[b0 + i] - q_off[b0]; eo[i] = e_off[b0 + i] - e_off[b0]; oo[i] = out_off[b0 + i] - out_off[b0]; }
     char *pv = pin + 3 * off_bytes;
@@ -1228,8 +1110,8 @@ int plan_on_device_launch(mibn_ctx *h, uint32_t flags, int64_t b0, int64_t b1, c
     // kernels - on the copy engine: the planner started when the chunk in flight had finished, never beside it.)
     HIP_TRY(h, hipEventRecord(h->emit_ev[0], P));
     const char *d = pin;
-    EmitMeta *meta_out = reinterpret_cast<EmitMeta *>(h->emit_out.p);
-    Tag *tags_out = reinterpret_cast<Tag *>(h->emit_out.p + (size_t)n * sizeof(EmitMeta) + 64);
+    EmitMeta *meta_out = reinterpret_cast<EmitMeta *>(h->emit_out.get());
+    Tag *tags_out = reinterpret_cast<Tag *>(h->emit_out.get() + (size_t)n * sizeof(EmitMeta) + 64);
     if (wave) {
         WavePlanArgs A;
         A.net = h->d_wnet;
@@ -1251,7 +1133,7 @@ int plan_on_device_launch(mibn_ctx *h, uint32_t flags, int64_t b0, int64_t b1, c
         A.tag_cap = (uint32_t)tag_cap;
         A.perm = nullptr;
         if (h->wave_sort && n > 4 * kWaveWG * (int64_t)h->n_cu) {  // (fewer requests than waves in flight: nothing to order)
-            if ((rc = ensure(h, h->d_plan_perm, h->plan_perm_cap, 2 * (size_t)n))) return rc;
+            if ((rc = ensure(h, h->d_plan_perm, 2 * (size_t)n))) return rc;
             A.perm = h->d_plan_perm;
         }
         hipLaunchKernelGGL(reset_cursor_kernel, dim3(1), dim3(1), 0, P, h->d_emit_cursor);
@@ -1331,8 +1213,8 @@ int plan_on_device_collect(mibn_ctx *h, int64_t b0, int64_t n, BatchPlan &ck, do
     hipStream_t P = h->search_stream;
     const size_t stride = h->emit_words;
     const size_t tag_cap = (size_t)n * 64;
-    const EmitMeta *meta = reinterpret_cast<const EmitMeta *>(h->emit_out.p);
-    const Tag *tags = reinterpret_cast<const Tag *>(h->emit_out.p + (size_t)n * sizeof(EmitMeta) + 64);
+    const EmitMeta *meta = reinterpret_cast<const EmitMeta *>(h->emit_out.get());
+    const Tag *tags = reinterpret_cast<const Tag *>(h->emit_out.get() + (size_t)n * sizeof(EmitMeta) + 64);
     HIP_TRY(h, hipStreamSynchronize(P));
     {
         float ms = 0;
@@ -1419,12 +1301,11 @@ int expect_run(mibn_t *h, const double *d_results) {
     const size_t o_sp = put(P.slab_part.data(), P.slab_part.size() * 8), o_dc = put(P.dim_card.data(), P.dim_card.size() * 4);
     const size_t o_sb = put(P.slab_begin.data(), P.slab_begin.size() * 4), o_sc = put(P.slab_cells.data(), P.slab_cells.size() * 4);
     const size_t o_bb = put(P.blk_begin.data(), P.blk_begin.size() * 4), o_bs = put(P.blk_slab.data(), P.blk_slab.size() * 4);
-    if ((rc = ensure(h, X.d_meta, X.meta_cap, meta.size() + 16))) return rc;
+    if ((rc = ensure(h, X.d_meta, meta.size() + 16))) return rc;
     const size_t nB = (size_t)X.B, nA = (size_t)X.n_acc;
     const size_t f_acc = 0, f_p = nA, f_w = f_p + nB, f_part = f_w + (X.weight ? nB : 0);
-    if ((rc = ensure(h, X.d_f64, X.f64_cap, f_part + (size_t)P.part_cells + 2))) return rc;
-    for (hipEvent_t &e : X.ev)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    if ((rc = ensure(h, X.d_f64, f_part + (size_t)P.part_cells + 2))) return rc;
+    for (Event &e : X.ev) HIP_TRY(h, e.ensure());
     const hipStream_t S = h->stream;
     HIP_TRY(h, hipMemcpyAsync(X.d_meta, meta.data(), meta.size(), hipMemcpyHostToDevice, S));
     if (nA) HIP_TRY(h, hipMemcpyAsync(X.d_f64 + f_acc, X.acc, nA * 8, hipMemcpyHostToDevice, S));
@@ -1506,13 +1387,13 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     const bool zero_copy = B <= kTinyZeroCopyRequests && h->tiny_zero_copy && !h->expect;  // (expect_kernel reads the results on the device)
     const size_t bad_off = req_bytes, res_off = req_bytes + 16;
     const size_t bytes = res_off + (zero_copy ? res_cells * 8 : 0) + 64;
-    mibn_ctx::Staging &sg = h->tiny_stage;
+    PinnedBuf &sg = h->tiny_stage;
     if ((rc = pinned(h, sg, bytes))) return rc;
     if (!zero_copy) {
-        if ((rc = ensure(h, h->d_tiny_req, h->tiny_req_cap, bytes))) return rc;
-        if ((rc = ensure(h, h->d_results[0], h->results_cap[0], res_cells))) return rc;
+        if ((rc = ensure(h, h->d_tiny_req, bytes))) return rc;
+        if ((rc = ensure(h, h->d_results[0], res_cells))) return rc;
     }
-    char *p = sg.p;
+    char *p = sg.get();
     std::memcpy(p, q_off, off_bytes);
     std::memcpy(p + off_bytes, e_off, off_bytes);
     std::memcpy(p + 2 * off_bytes, out_off, off_bytes);
@@ -1524,7 +1405,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     char *dbase = h->d_tiny_req;  // where the kernel finds the arrays
     if (zero_copy) {
         void *dp = nullptr;
-        HIP_TRY(h, hipHostGetDevicePointer(&dp, sg.p, 0));
+        HIP_TRY(h, hipHostGetDevicePointer(&dp, sg.get(), 0));
         dbase = static_cast<char *>(dp);
         std::memset(p + res_off, 0, res_cells * 8);
     } else {
@@ -1627,12 +1508,9 @@ int cut_wave(mibn_ctx *h, const std::vector<int64_t> &arena_need, int64_t r0, in
 // The arena of `lane` holds need_bytes: grown with headroom (chunks differ by ~10 %: re-allocating tens of GB costs hundreds of ms),
 // after S has drained - earlier launches of the lane still use the old arena.
 int grow_arena(mibn_ctx *h, int lane, size_t need_bytes, int64_t budget_cells, hipStream_t S) {
-    if (need_bytes <= h->arena_bytes[lane]) return MIBN_OK;
+    if (need_bytes <= h->d_arena[lane].cap()) return MIBN_OK;
     HIP_TRY(h, hipStreamSynchronize(S));
-    if (h->d_arena[lane]) { HIP_TRY(h, hipFree(h->d_arena[lane])); h->d_arena[lane] = nullptr; h->arena_bytes[lane] = 0; }
-    const size_t want = std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3));
-    HIP_TRY(h, hipMalloc(&h->d_arena[lane], want));
-    h->arena_bytes[lane] = want;
+    HIP_TRY(h, h->d_arena[lane].reset(std::max(need_bytes, std::min((size_t)((double)budget_cells * 8.0), need_bytes + need_bytes / 3))));
     return MIBN_OK;
 }
 
@@ -1709,13 +1587,13 @@ int query_setup(QueryRun &R) {
     mibn_ctx *h = R.h;
     int rc;
     R.res_cells = (size_t)(R.out_off[R.B] - R.out_off[0]);
-    if ((rc = ensure(h, h->d_results[R.slot], h->results_cap[R.slot], R.res_cells))) return rc;
+    if ((rc = ensure(h, h->d_results[R.slot], R.res_cells))) return rc;
     R.d_results = h->d_results[R.slot];
     R.n_lanes = h->n_streams > 1 ? 2 : 1;
     {
         bool idle = true;
         for (auto &st : h->set) idle = idle && !st.busy;
-        if (!h->epoch) { HIP_TRY(h, hipEventCreate(&h->epoch)); idle = true; }
+        if (!h->epoch) { HIP_TRY(h, h->epoch.ensure()); idle = true; }
         if (idle) {  // (times since the epoch stay small: float milliseconds)
             HIP_TRY(h, hipEventRecord(h->epoch, h->stream));
             h->busy_until = 0;
@@ -1723,13 +1601,13 @@ int query_setup(QueryRun &R) {
     }
     HIP_TRY(h, hipMemsetAsync(R.d_results, 0, R.res_cells * 8, h->stream));
     if (R.n_lanes > 1) {  // lane 1 starts this call's work after the results buffer is zeroed
-        if (!h->zero_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->zero_ev, hipEventDisableTiming));
+        HIP_TRY(h, h->zero_ev.ensure(hipEventDisableTiming));
         HIP_TRY(h, hipEventRecord(h->zero_ev, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->zero_ev, 0));
     }
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
-    R.budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0] + h->arena_bytes[1])) / 8.0) / R.n_lanes;
+    R.budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->d_arena[0].cap() + h->d_arena[1].cap())) / 8.0) / R.n_lanes;
     // order_effort >= 1 (more candidate orders, the byte model's best two both emitted): the wave planner has it, order_kernel / emit_kernel do
     // not - where the wave planner does not cover the network the host plans (never two kinds of plans in one stream)
     bool effort_ok = true;
@@ -1776,15 +1654,15 @@ int search_window(QueryRun &R, int64_t b0, int64_t b1, double t0, const uint8_t 
     if (h->gpu_search == 2) {  // test mode: every chunk searched on the device, synchronously
         if ((rc = search_orders_async(h, R.flags, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars))) return rc;
         if ((rc = search_wait(h))) return rc;
-        orders = reinterpret_cast<const uint8_t *>(h->search_out.p);
-        order_len = reinterpret_cast<const int32_t *>(h->search_out.p + (size_t)(b1 - b0) * 128);
+        orders = reinterpret_cast<const uint8_t *>(h->search_out.get());
+        order_len = reinterpret_cast<const int32_t *>(h->search_out.get() + (size_t)(b1 - b0) * 128);
     } else if (R.n_chunks == 0 && b1 < R.B) {
         if ((rc = search_orders_async(h, R.flags, b1, R.B, R.q_off, R.q_vars, R.e_off, R.e_vars))) return rc;
         R.search_b0 = b1;
     } else if (R.search_b0 >= 0) {
         if (!R.search_done) { if ((rc = search_wait(h))) return rc; R.search_done = true; h->search_ms += now_ms() - t0; }
-        orders = reinterpret_cast<const uint8_t *>(h->search_out.p) + (size_t)(b0 - R.search_b0) * 128;
-        order_len = reinterpret_cast<const int32_t *>(h->search_out.p + (size_t)(R.B - R.search_b0) * 128) + (b0 - R.search_b0);
+        orders = reinterpret_cast<const uint8_t *>(h->search_out.get()) + (size_t)(b0 - R.search_b0) * 128;
+        order_len = reinterpret_cast<const int32_t *>(h->search_out.get() + (size_t)(R.B - R.search_b0) * 128) + (b0 - R.search_b0);
     }
     return MIBN_OK;
 }
@@ -1978,9 +1856,9 @@ int upload_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t n, bool on_device, size
     mibn_ctx *h = R.h;
     const BatchPlan &ck = st.plan;
     int rc;
-    if (!on_device && (rc = ensure(h, st.d_prog, st.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
-    if ((rc = ensure(h, st.d_prog_off, st.prog_off_cap, (size_t)n))) return rc;
-    if ((rc = ensure(h, st.d_arena_off, st.arena_off_cap, (size_t)n))) return rc;
+    if (!on_device && (rc = ensure(h, st.d_prog, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
+    if ((rc = ensure(h, st.d_prog_off, (size_t)n))) return rc;
+    if ((rc = ensure(h, st.d_arena_off, (size_t)n))) return rc;
     const double t0 = now_ms();
     if ((rc = upload_programs(h, st.d_prog, prog_base, st.bufs, ck, h->copy_stream))) return rc;
     if ((rc = upload(h, st.stage[0], st.d_prog_off, ck.prog_off.data(), (size_t)n * 8))) return rc;
@@ -2065,13 +1943,13 @@ int run_wave(QueryRun &R, mibn_ctx::Set &st, int lane, hipStream_t S, int64_t b0
     const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
     if ((rc = grow_arena(h, lane, need_bytes, R.budget_cells, S))) return rc;
     if (r0 > 0) { HIP_TRY(h, hipStreamSynchronize(S)); HIP_TRY(h, hipStreamSynchronize(h->copy_stream)); }
-    if ((rc = ensure(h, st.d_items, st.items_cap, sc.items.size()))) return rc;
-    if ((rc = ensure(h, st.d_wg_item, st.wg_item_cap, sc.wg_item.size()))) return rc;
+    if ((rc = ensure(h, st.d_items, sc.items.size()))) return rc;
+    if ((rc = ensure(h, st.d_wg_item, sc.wg_item.size()))) return rc;
     t0 = now_ms();
     if ((rc = upload(h, st.stage[1], st.d_arena_off, sc.arena_off.data(), (size_t)(r1 - r0) * 8))) return rc;
     if ((rc = upload(h, st.stage[2], st.d_items, sc.items.data(), sc.items.size() * sizeof(Item)))) return rc;
     if ((rc = upload(h, st.stage[3], st.d_wg_item, sc.wg_item.data(), sc.wg_item.size() * sizeof(uint32_t)))) return rc;
-    if (!st.uploaded) HIP_TRY(h, hipEventCreateWithFlags(&st.uploaded, hipEventDisableTiming));
+    HIP_TRY(h, st.uploaded.ensure(hipEventDisableTiming));
     HIP_TRY(h, hipEventRecord(st.uploaded, h->copy_stream));
     HIP_TRY(h, hipStreamWaitEvent(S, st.uploaded, 0));  // the kernels of this wave wait for its uploads only
     h->stats.h2d_ms += now_ms() - t0;
@@ -2080,7 +1958,7 @@ int run_wave(QueryRun &R, mibn_ctx::Set &st, int lane, hipStream_t S, int64_t b0
     A.prog_off = st.d_prog_off + r0;
     A.arena_off = st.d_arena_off;
     A.pool = h->d_pool;
-    A.arena = h->d_arena[lane];
+    A.arena = h->arena(lane);
     A.results = R.d_results + (R.out_off[b0] - R.out_off[0]);
     A.items = st.d_items;
     double n_wg = 0;
@@ -2132,8 +2010,8 @@ int run_wave(QueryRun &R, mibn_ctx::Set &st, int lane, hipStream_t S, int64_t b0
     st.timed.push_back({-1, e_first, e_last, 0.0, (double)(r1 - r0), h->call_id});
     HIP_TRY(h, hipGetLastError());
     if (h->trace) {
-        hipEvent_t &ge = h->gap_ev[h->n_waves & 3];
-        if (!ge) HIP_TRY(h, hipEventCreate(&ge));
+        Event &ge = h->gap_ev[h->n_waves & 3];
+        HIP_TRY(h, ge.ensure());
         HIP_TRY(h, hipEventRecord(ge, S));
     }
     ++h->n_waves;
@@ -2164,7 +2042,7 @@ int query_finish(QueryRun &R, double *out, int32_t *ticket) {
     mibn_ctx *h = R.h;
     int rc;
     if (R.lane1_used) {  // the download (main stream) follows the kernels of both lanes
-        if (!h->lane_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->lane_ev, hipEventDisableTiming));
+        HIP_TRY(h, h->lane_ev.ensure(hipEventDisableTiming));
         HIP_TRY(h, hipEventRecord(h->lane_ev, h->stream2));
         HIP_TRY(h, hipStreamWaitEvent(h->stream, h->lane_ev, 0));
     }
@@ -2176,11 +2054,11 @@ int query_finish(QueryRun &R, double *out, int32_t *ticket) {
     if (h->trace) std::fprintf(stderr, "[mibn plan] call of %lld requests: %.2f ms to the last launch (plan %.2f, h2d %.2f)\n", (long long)R.B, now_ms() - R.t_start, h->stats.plan_ms, h->stats.h2d_ms);
     if (ticket) {
         mibn_ctx::Pending &pd = h->pend[R.slot];
-        mibn_ctx::Staging &sg = h->res_stage[R.slot];
+        PinnedBuf &sg = h->res_stage[R.slot];
         const size_t bytes = R.res_cells * 8;
         if ((rc = pinned(h, sg, bytes))) return rc;
-        if (!pd.done) HIP_TRY(h, hipEventCreateWithFlags(&pd.done, hipEventDisableTiming));
-        HIP_TRY(h, hipMemcpyAsync(sg.p, R.d_results, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, pd.done.ensure(hipEventDisableTiming));
+        HIP_TRY(h, hipMemcpyAsync(sg.get(), R.d_results, bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipEventRecord(pd.done, h->stream));
         pd.active = true;
         pd.out = out + R.out_off[0];
@@ -2326,12 +2204,9 @@ struct ElimRun {  // the call in flight, as the hooks of a payload see it
     std::vector<Timed> timed;  // the launches of the wave in flight
 
     int event(size_t &idx) {
-        if (n_ev == M.ev.size()) {
-            hipEvent_t e;
-            HIP_TRY(h, hipEventCreate(&e));
-            M.ev.push_back(e);
-        }
+        if (n_ev == M.ev.size()) M.ev.emplace_back();
         idx = n_ev++;
+        HIP_TRY(h, M.ev[idx].ensure());
         HIP_TRY(h, hipEventRecord(M.ev[idx], S));
         return MIBN_OK;
     }
@@ -2390,7 +2265,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
     std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: d_m
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
-    const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->arena_bytes[0])) / 8.0);
+    const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->d_arena[0].cap())) / 8.0);
     for (int64_t b0 = 0, b1 = 0; b0 < B; b0 = b1) {
         b1 = std::min(B, b0 + std::max<int64_t>(1, h->chunk));
         const int64_t n = b1 - b0;
@@ -2403,9 +2278,9 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
         h->stats.plan_ms += now_ms() - t0;
         t0 = now_ms();
-        if ((rc = ensure(h, M.d_prog, M.prog_cap, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
-        if ((rc = ensure(h, M.d_prog_off, M.prog_off_cap, (size_t)n))) return rc;
-        if ((rc = ensure(h, M.d_m, M.m_cap, (size_t)n))) return rc;
+        if ((rc = ensure(h, M.d_prog, ck.total_words + kMaxStepWords))) return rc;  // (slack: segment_wave prefetches whole descriptor slots)
+        if ((rc = ensure(h, M.d_prog_off, (size_t)n))) return rc;
+        if ((rc = ensure(h, M.d_m, (size_t)n))) return rc;
         if ((rc = upload_programs(h, M.d_prog, 0, M.bufs, ck, S))) return rc;
         HIP_TRY(h, hipMemcpyAsync(M.d_prog_off, ck.prog_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
         if ((rc = P.prepare(R))) return rc;
@@ -2422,9 +2297,9 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
             const size_t need_bytes = (size_t)std::max<int64_t>(16, sc.arena_cells) * sizeof(double);
             if ((rc = grow_arena(h, 0, need_bytes, budget_cells, S))) return rc;
             t0 = now_ms();
-            if ((rc = ensure(h, M.d_arena_off, M.arena_off_cap, (size_t)(r1 - r0)))) return rc;
-            if ((rc = ensure(h, M.d_items, M.items_cap, std::max<size_t>(1, sc.items.size())))) return rc;
-            if ((rc = ensure(h, M.d_wg_item, M.wg_item_cap, std::max<size_t>(1, sc.wg_item.size())))) return rc;
+            if ((rc = ensure(h, M.d_arena_off, (size_t)(r1 - r0)))) return rc;
+            if ((rc = ensure(h, M.d_items, std::max<size_t>(1, sc.items.size())))) return rc;
+            if ((rc = ensure(h, M.d_wg_item, std::max<size_t>(1, sc.wg_item.size())))) return rc;
             HIP_TRY(h, hipMemcpyAsync(M.d_arena_off, sc.arena_off.data(), (size_t)(r1 - r0) * 8, hipMemcpyHostToDevice, S));
             if (!sc.items.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_items, sc.items.data(), sc.items.size() * sizeof(Item), hipMemcpyHostToDevice, S));
             if (!sc.wg_item.empty()) HIP_TRY(h, hipMemcpyAsync(M.d_wg_item, sc.wg_item.data(), sc.wg_item.size() * sizeof(uint32_t), hipMemcpyHostToDevice, S));
@@ -2434,7 +2309,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
             A.prog_off = M.d_prog_off + r0;
             A.arena_off = M.d_arena_off;
             A.pool = h->d_pool;
-            A.arena = h->d_arena[0];
+            A.arena = h->arena(0);
             A.results = M.d_m;  // (FINAL offsets are chunk-relative: the cell of request b at b - b0)
             A.items = M.d_items;
             // one launch per level: every class of work of such a schedule (segments, GENERIC tiles) is the payload's level kernel's
@@ -2491,8 +2366,8 @@ struct MpePayload {
     int prepare(ElimRun &R) const {
         mibn_ctx *h = R.h;
         int rc;
-        if ((rc = ensure(h, R.M.d_log_p, R.M.log_p_cap, (size_t)R.n))) return rc;
-        if ((rc = ensure(h, R.M.d_codes, R.M.codes_cap, (size_t)R.n * (size_t)std::max(1, h->net.n_vars)))) return rc;
+        if ((rc = ensure(h, R.M.d_log_p, (size_t)R.n))) return rc;
+        if ((rc = ensure(h, R.M.d_codes, (size_t)R.n * (size_t)std::max(1, h->net.n_vars)))) return rc;
         HIP_TRY(h, hipMemsetAsync(R.M.d_m, 0, (size_t)R.n * 8, R.S));  // (skipped requests never write theirs: zero probability)
         return MIBN_OK;
     }
@@ -2503,7 +2378,7 @@ struct MpePayload {
         T.prog = R.M.d_prog;
         T.prog_off = R.M.d_prog_off + R.r0;
         T.arena_off = R.M.d_arena_off;
-        T.arena = h->d_arena[0];
+        T.arena = h->arena(0);
         T.m = R.M.d_m + R.r0;
         T.codes = R.M.d_codes + (size_t)R.r0 * (size_t)nv;
         T.log_p = R.M.d_log_p + R.r0;
@@ -2603,7 +2478,7 @@ struct DrawPayload {
         D.prog = M.d_prog;
         D.prog_off = M.d_prog_off + r0;
         D.arena_off = M.d_arena_off;
-        D.arena = h->d_arena[0];
+        D.arena = h->arena(0);
         D.pool = h->d_pool;
         D.m = M.d_m + r0;
         D.n_vars = nv;
@@ -2627,8 +2502,8 @@ struct DrawPayload {
             }
             if (ditems.empty()) break;
             double t0 = now_ms();
-            if ((rc = ensure(h, M.d_draw_items, M.draw_items_cap, ditems.size()))) return rc;
-            if ((rc = ensure(h, M.d_codes, M.codes_cap, rows * (size_t)std::max(1, nv)))) return rc;
+            if ((rc = ensure(h, M.d_draw_items, ditems.size()))) return rc;
+            if ((rc = ensure(h, M.d_codes, rows * (size_t)std::max(1, nv)))) return rc;
             HIP_TRY(h, hipMemcpyAsync(M.d_draw_items, ditems.data(), ditems.size() * sizeof(DrawItem), hipMemcpyHostToDevice, S));
             h->stats.h2d_ms += now_ms() - t0;
             D.items = M.d_draw_items;
@@ -2766,7 +2641,7 @@ extern "C" int mibn_wait(mibn_t *h, int32_t ticket) {
     HIP_TRY(h, hipSetDevice(h->device));
     const double t0 = now_ms();
     HIP_TRY(h, hipEventSynchronize(pd.done));
-    std::memcpy(pd.out, h->res_stage[ticket].p, pd.cells * 8);
+    std::memcpy(pd.out, h->res_stage[ticket].get(), pd.cells * 8);
     pd.active = false;
     h->stats.d2h_ms += now_ms() - t0;
     h->total.d2h_ms += now_ms() - t0;
@@ -2940,14 +2815,12 @@ extern "C" int mibn_dataset_create(mibn_t *h, int64_t n_rows, int32_t n_cols, co
     HIP_TRY(h, hipSetDevice(h->device));
     mibn_ctx::Dataset ds;
     const size_t code_bytes = (size_t)n_rows * (size_t)n_cols;
-    uint8_t *d_rows = nullptr;
-    hipError_t e = hipMalloc(&ds.d_codes, std::max<size_t>(16, code_bytes));
-    if (e == hipSuccess && row_major && code_bytes) e = hipMalloc(&d_rows, code_bytes);
+    DevBuf<uint8_t> d_rows;
+    hipError_t e = ds.d_codes.reset(std::max<size_t>(16, code_bytes));
+    if (e == hipSuccess && row_major && code_bytes) e = d_rows.reset(code_bytes);
     if (e == hipSuccess) e = count_upload_codes(h->stream, n_rows, n_cols, codes, row_major != 0, ds.d_codes, d_rows);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_rows);
     if (e != hipSuccess) {
-        (void)hipFree(ds.d_codes);
         h->err = std::string("dataset: ") + hipGetErrorString(e);
         return MIBN_E_HIP;
     }
@@ -2955,7 +2828,7 @@ extern "C" int mibn_dataset_create(mibn_t *h, int64_t n_rows, int32_t n_cols, co
     ds.n_cols = n_cols;
     ds.card.assign(card, card + n_cols);
     ds.live = true;
-    if (h->datasets.size() >= 0x7ffffff0u) { (void)hipFree(ds.d_codes); h->err = "dataset: too many data sets"; return MIBN_E_LIMIT; }
+    if (h->datasets.size() >= 0x7ffffff0u) { h->err = "dataset: too many data sets"; return MIBN_E_LIMIT; }
     h->datasets.push_back(std::move(ds));
     *id = (int32_t)h->datasets.size() - 1;
     return MIBN_OK;
@@ -2967,7 +2840,7 @@ extern "C" int mibn_dataset_destroy(mibn_t *h, int32_t id) {
     HIP_TRY(h, hipSetDevice(h->device));
     mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipFree(ds.d_codes));
+    HIP_TRY(h, ds.d_codes.release());
     ds = mibn_ctx::Dataset{};
     return MIBN_OK;
 }
@@ -3074,13 +2947,12 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
     HIP_TRY(h, hipSetDevice(h->device));
     mibn_ctx::Score &X = h->sc;
     int rc;
-    if ((rc = ensure(h, X.d_counts, X.counts_cap, (size_t)max_cells))) return rc;
-    if ((rc = ensure(h, X.d_meta, X.meta_cap, meta.size() + 16))) return rc;
-    if ((rc = ensure(h, X.d_f64, X.f64_cap, (size_t)n_fam + (size_t)max_parts + 2))) return rc;
+    if ((rc = ensure(h, X.d_counts, (size_t)max_cells))) return rc;
+    if ((rc = ensure(h, X.d_meta, meta.size() + 16))) return rc;
+    if ((rc = ensure(h, X.d_f64, (size_t)n_fam + (size_t)max_parts + 2))) return rc;
     while (X.ev.size() < 3 * subs.size()) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(h, hipEventCreate(&e));
-        X.ev.push_back(e);
+        X.ev.emplace_back();
+        HIP_TRY(h, X.ev.back().ensure());
     }
     const hipStream_t S0 = h->stream;
     double t0 = now_ms();
@@ -3233,11 +3105,8 @@ int comm_ready(mibn_ctx *h) {
     return MIBN_OK;
 }
 
-int comm_buf(mibn_ctx *h, void *&ptr, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return MIBN_OK;
-    if (ptr) { HIP_TRY(h, hipFree(ptr)); ptr = nullptr; cap = 0; }
-    HIP_TRY(h, hipMalloc(&ptr, bytes + bytes / 4 + 256));
-    cap = bytes + bytes / 4 + 256;
+int comm_buf(mibn_ctx *h, DevBuf<char> &buf, size_t bytes) {
+    if (bytes > buf.cap()) HIP_TRY(h, buf.reset(bytes + bytes / 4 + 256));
     return MIBN_OK;
 }
 
@@ -3297,7 +3166,7 @@ extern "C" int mibn_comm_init(mibn_t *h, int32_t rank, int32_t world, const void
     HIP_TRY(h, hipSetDevice(h->device));
     ncclUniqueId id;
     std::memcpy(&id, id_in, sizeof(id));
-    if (!h->comm.stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->comm.stream, hipStreamNonBlocking));
+    HIP_TRY(h, h->comm.stream.ensure(hipStreamNonBlocking));
     // The collective init blocks until every rank of `world` has joined - for ever when one of them died or took another id.
     // Bounded: the call runs on a helper thread, and a rank that has waited MIBN_COMM_INIT_TIMEOUT_S seconds (default 180) gives
     // up with an error that names the likely causes instead of hanging the launch (the helper thread is abandoned: the process
@@ -3356,9 +3225,9 @@ extern "C" int mibn_comm_destroy(mibn_t *h) {
         (void)c.CommDestroy(c.comm);
         c.comm = nullptr;
     }
-    if (c.stream) { (void)hipStreamDestroy(c.stream); c.stream = nullptr; }
-    if (c.d_send) { (void)hipFree(c.d_send); c.d_send = nullptr; c.send_cap = 0; }
-    if (c.d_recv) { (void)hipFree(c.d_recv); c.d_recv = nullptr; c.recv_cap = 0; }
+    (void)c.stream.release();
+    (void)c.d_send.release();
+    (void)c.d_recv.release();
     return MIBN_OK;
 }
 
@@ -3369,8 +3238,8 @@ extern "C" int mibn_comm_allgather_f64(mibn_t *h, const double *send, int64_t n,
     if (n == 0) return MIBN_OK;
     mibn_ctx::Comm &c = h->comm;
     const size_t bytes = (size_t)n * 8;
-    if ((rc = comm_buf(h, c.d_send, c.send_cap, bytes))) return rc;
-    if ((rc = comm_buf(h, c.d_recv, c.recv_cap, bytes * (size_t)c.world))) return rc;
+    if ((rc = comm_buf(h, c.d_send, bytes))) return rc;
+    if ((rc = comm_buf(h, c.d_recv, bytes * (size_t)c.world))) return rc;
     HIP_TRY(h, hipMemcpyAsync(c.d_send, send, bytes, hipMemcpyHostToDevice, c.stream));
     NCCL_TRY(h, c.AllGather(c.d_send, c.d_recv, (size_t)n, ncclDouble, c.comm, c.stream));
     HIP_TRY(h, hipMemcpyAsync(recv, c.d_recv, bytes * (size_t)c.world, hipMemcpyDeviceToHost, c.stream));
@@ -3385,8 +3254,8 @@ extern "C" int mibn_comm_reduce_i64(mibn_t *h, int64_t *buf, int64_t n, int32_t 
     if (n < 0 || (n && !buf) || root < 0 || root >= c.world) return MIBN_E_ARG;
     if (n == 0) return MIBN_OK;
     const size_t bytes = (size_t)n * 8;
-    if ((rc = comm_buf(h, c.d_send, c.send_cap, bytes))) return rc;
-    if ((rc = comm_buf(h, c.d_recv, c.recv_cap, bytes))) return rc;
+    if ((rc = comm_buf(h, c.d_send, bytes))) return rc;
+    if ((rc = comm_buf(h, c.d_recv, bytes))) return rc;
     HIP_TRY(h, hipMemcpyAsync(c.d_send, buf, bytes, hipMemcpyHostToDevice, c.stream));
     NCCL_TRY(h, c.Reduce(c.d_send, c.d_recv, (size_t)n, ncclInt64, ncclSum, root, c.comm, c.stream));
     if (c.rank == root) HIP_TRY(h, hipMemcpyAsync(buf, c.d_recv, bytes, hipMemcpyDeviceToHost, c.stream));
@@ -3401,8 +3270,8 @@ extern "C" int mibn_comm_allreduce_max_f64(mibn_t *h, double *buf, int64_t n) {
     if (n == 0) return MIBN_OK;
     mibn_ctx::Comm &c = h->comm;
     const size_t bytes = (size_t)n * 8;
-    if ((rc = comm_buf(h, c.d_send, c.send_cap, bytes))) return rc;
-    if ((rc = comm_buf(h, c.d_recv, c.recv_cap, bytes))) return rc;
+    if ((rc = comm_buf(h, c.d_send, bytes))) return rc;
+    if ((rc = comm_buf(h, c.d_recv, bytes))) return rc;
     HIP_TRY(h, hipMemcpyAsync(c.d_send, buf, bytes, hipMemcpyHostToDevice, c.stream));
     NCCL_TRY(h, c.AllReduce(c.d_send, c.d_recv, (size_t)n, ncclDouble, ncclMax, c.comm, c.stream));
     HIP_TRY(h, hipMemcpyAsync(buf, c.d_recv, bytes, hipMemcpyDeviceToHost, c.stream));

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/mibn.h"
+#include "device_mem.h"
 #include "planner.h"
 
 namespace mibn {
@@ -617,21 +618,22 @@ inline int gibbs_run(const Network &net, const double *d_pool, hipStream_t strea
     const bool prog_lds = fast || (allow_lds && (lds + 15) / 16 * 16 + prog_words * 4 <= 160 * 1024 && (n_chains + 63) / 64 <= 512);
     if (prog_lds) lds = (lds + 15) / 16 * 16 + prog_words * 4;
 
-    GibbsVar *d_vars = nullptr;
-    int32_t *d_i32 = nullptr;
-    unsigned long long *d_counts = nullptr;
-    uint8_t *d_cond_states = nullptr;
-    double *d_cond_out = nullptr;
+    DevBuf<GibbsVar> d_vars;
+    DevBuf<int32_t> d_i32;
+    DevBuf<unsigned long long> d_counts;
+    DevBuf<uint8_t> d_cond_states;
+    DevBuf<double> d_cond_out;
+    Event e0, e1;
     std::vector<int32_t> pack;
     auto put = [&](const std::vector<int32_t> &a) { size_t o = pack.size(); pack.insert(pack.end(), a.begin(), a.end()); return o; };
     const size_t o_sv = put(scope_var), o_ss = put(scope_stride), o_ch = put(children), o_cy = put(cycle);
     const size_t o_q = put(std::vector<int32_t>(q_vars, q_vars + n_q)), o_qs = put(qstride);
     const size_t o_up = put(uprog), o_uo = put(uprog_off);
-    auto fail = [&](hipError_t e) { err = std::string("gibbs: ") + hipGetErrorString(e); hipFree(d_vars); hipFree(d_i32); hipFree(d_counts); hipFree(d_cond_states); hipFree(d_cond_out); return MIBN_E_HIP; };
+    auto fail = [&](hipError_t e) { err = std::string("gibbs: ") + hipGetErrorString(e); return MIBN_E_HIP; };
     hipError_t e;
-    if ((e = hipMalloc(&d_vars, sizeof(GibbsVar) * n)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_i32, 4 * std::max<size_t>(1, pack.size()))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_counts, 8 * (size_t)cells)) != hipSuccess) return fail(e);
+    if ((e = d_vars.reset((size_t)n)) != hipSuccess) return fail(e);
+    if ((e = d_i32.reset(std::max<size_t>(1, pack.size()))) != hipSuccess) return fail(e);
+    if ((e = d_counts.reset((size_t)cells)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(d_vars, vars.data(), sizeof(GibbsVar) * n, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(d_i32, pack.data(), 4 * pack.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
     if ((e = hipMemsetAsync(d_counts, 0, 8 * (size_t)cells, stream)) != hipSuccess) return fail(e);
@@ -663,16 +665,14 @@ inline int gibbs_run(const Network &net, const double *d_pool, hipStream_t strea
     A.cond_pos = 0;
     const size_t cond_cells = cond_var >= 0 ? (size_t)n_chains * (size_t)net.card[cond_var] : 0;
     if (cond_var >= 0) {
-        if ((e = hipMalloc(&d_cond_states, std::max<size_t>(1, (size_t)n_chains * n))) != hipSuccess) return fail(e);
-        if ((e = hipMalloc(&d_cond_out, 8 * std::max<size_t>(1, cond_cells))) != hipSuccess) return fail(e);
+        if ((e = d_cond_states.reset(std::max<size_t>(1, (size_t)n_chains * n))) != hipSuccess) return fail(e);
+        if ((e = d_cond_out.reset(std::max<size_t>(1, cond_cells))) != hipSuccess) return fail(e);
         if ((e = hipMemcpyAsync(d_cond_states, cond_states, (size_t)n_chains * n, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
         A.cond_states = d_cond_states;
         A.cond_out = d_cond_out;
         A.cond_pos = cond_pos;
     }
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
+    if ((e = e0.ensure()) != hipSuccess || (e = e1.ensure()) != hipSuccess) return fail(e);
     const bool fast8 = fast && want8;
     const unsigned blocks = fast8 ? (unsigned)((n_chains + 7) / 8) : (unsigned)((n_chains + 63) / 64);
     auto kernel = fast8 ? gibbs_kernel8<false> : fast ? gibbs_kernel<true, true, true>
@@ -695,18 +695,11 @@ inline int gibbs_run(const Network &net, const double *d_pool, hipStream_t strea
     float ms = 0;
     hipEventElapsedTime(&ms, e0, e1);
     kernel_ms = ms;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     if (counts)
         for (int64_t i = 0; i < cells; ++i) counts[i] = (int64_t)hc[(size_t)i];
     if (cond_var >= 0) {
         if ((e = hipMemcpy(cond_out, d_cond_out, 8 * cond_cells, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e);
-        hipFree(d_cond_states);
-        hipFree(d_cond_out);
     }
-    hipFree(d_vars);
-    hipFree(d_i32);
-    hipFree(d_counts);
     return MIBN_OK;
 }
 

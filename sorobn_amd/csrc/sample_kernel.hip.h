@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/mibn.h"
+#include "device_mem.h"
 #include "gibbs_kernel.hip.h"
 #include "planner.h"
 
@@ -150,9 +151,9 @@ inline int sample_run(const Network &net, const double *d_pool, hipStream_t stre
     const size_t lds = ((size_t)n * 64 + 15) / 16 * 16 + (size_t)cells * 12;
     if (lds > 150 * 1024) { err = "sampling: network/query too large for the LDS-resident state"; return MIBN_E_LIMIT; }
 
-    GibbsVar *d_vars = nullptr;
-    int32_t *d_i32 = nullptr;
-    unsigned char *d_out = nullptr;  // states | wsum + counts
+    DevBuf<GibbsVar> d_vars;
+    DevBuf<int32_t> d_i32;
+    DevBuf<unsigned char> d_out_buf;  // states | wsum + counts
     std::vector<int32_t> pack;
     auto put = [&](const std::vector<int32_t> &a) { size_t o = pack.size(); pack.insert(pack.end(), a.begin(), a.end()); return o; };
     const size_t o_sv = put(scope_var), o_ss = put(scope_stride);
@@ -162,11 +163,12 @@ inline int sample_run(const Network &net, const double *d_pool, hipStream_t stre
     const size_t probe_states = ((size_t)n_samples * n + 7) & ~size_t(7);
     const size_t out_bytes = mode == kSampleMode ? (size_t)n_samples * n
                              : mode == kProbeMode ? probe_states + (size_t)n_samples * 8 * (1 + (size_t)n * cdf_stride) : (size_t)cells * 16;
-    auto fail = [&](hipError_t e) { err = std::string("sampling: ") + hipGetErrorString(e); hipFree(d_vars); hipFree(d_i32); hipFree(d_out); return MIBN_E_HIP; };
+    auto fail = [&](hipError_t e) { err = std::string("sampling: ") + hipGetErrorString(e); return MIBN_E_HIP; };
     hipError_t e;
-    if ((e = hipMalloc(&d_vars, sizeof(GibbsVar) * std::max(1, n))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_i32, 4 * std::max<size_t>(1, pack.size()))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_out, std::max<size_t>(16, out_bytes))) != hipSuccess) return fail(e);
+    if ((e = d_vars.reset((size_t)std::max(1, n))) != hipSuccess) return fail(e);
+    if ((e = d_i32.reset(std::max<size_t>(1, pack.size()))) != hipSuccess) return fail(e);
+    if ((e = d_out_buf.reset(std::max<size_t>(16, out_bytes))) != hipSuccess) return fail(e);
+    unsigned char *const d_out = d_out_buf.get();
     if ((e = hipMemcpyAsync(d_vars, vars.data(), sizeof(GibbsVar) * n, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(d_i32, pack.data(), 4 * pack.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
     if ((e = hipMemsetAsync(d_out, 0, std::max<size_t>(16, out_bytes), stream)) != hipSuccess) return fail(e);
@@ -213,9 +215,6 @@ inline int sample_run(const Network &net, const double *d_pool, hipStream_t stre
         const unsigned long long *cn = (const unsigned long long *)(host.data() + (size_t)cells * 8);
         for (int64_t i = 0; i < cells; ++i) { if (wsum) wsum[i] = ws[i]; counts[i] = (int64_t)cn[i]; }
     }
-    hipFree(d_vars);
-    hipFree(d_i32);
-    hipFree(d_out);
     return MIBN_OK;
 }
 

@@ -1365,6 +1365,61 @@ def test_async_submit_wait_matches_the_blocking_call(amd):
     assert eng.query_fixed(*parts[0]).shape == (3000, 4)  # the blocking call works again once everything is collected
 
 
+def test_engine_lifecycle(amd):
+    """Three engines one after another in one process, each taking every path that creates a buffer, a pinned buffer, an event or a
+    stream on first use - host-planned and device-planned query calls (wave planner and order_kernel + emit_kernel), two lanes, the
+    trace events, an asynchronous call, MPE, posterior sampling, P(e), Gibbs, forward sampling, a data set - and closed twice: nothing
+    raises, and every answer is bit for bit the first engine's."""
+    from sorobn_amd import _capi
+    spec = netspec.grid_spec(4, 4, 2)
+    q, ev, ec = netspec.c3_requests(16, 2, 8, 3, seed=5)
+    rows = np.random.default_rng(3).integers(0, 2, (100, 16)).astype(np.uint8)
+
+    def run_all():
+        bn = netspec.build(spec, amd.BayesNet)
+        eng = bn.backend.engine
+        to_var = np.array([bn.backend.flat.id[f"{i:03d}"] for i in range(16)], np.int32)
+        req = (to_var[q][:, None], to_var[ev], ec)
+        out = [eng.query_fixed(*req).copy()]  # (the small-network kernel: its staging buffer)
+        eng.set_option("tiny", 0)
+        out.append(eng.query_fixed(*req).copy())  # eight host-planned requests
+        eng.set_option("second_on_device", 1)
+        eng.set_option("gpu_emit", 2)
+        for wave_plan in (1, 0):
+            eng.set_option("wave_plan", wave_plan)
+            out.append(eng.query_fixed(*req).copy())
+        eng.set_option("wave_plan", 1)
+        eng.set_option("streams", 2)
+        out.append(eng.query_fixed(*req).copy())
+        eng.set_option("streams", 1)
+        eng.set_option("trace", 1)
+        out.append(eng.query_fixed(*req).copy())
+        eng.set_option("trace", 0)
+        eng.set_option("gpu_emit", 0)
+        out.append(eng.wait(eng.submit_fixed(*req)).copy())
+        eng.drain()
+        out.extend(eng.mpe(to_var[ev], ec))
+        out.extend(eng.posterior_sample(to_var[ev], ec, 4, seed=11))
+        out.append(eng.query_fixed(np.zeros((8, 0), np.int32), to_var[ev], ec, flags=_capi.Q_UNNORMALISED).copy())
+        out.append(eng.gibbs(to_var[q[:1]], to_var[ev[0]], ec[0], 64, 10, seed=7))
+        out.append(eng.sample(64, seed=9))
+        ds = eng.dataset(rows, [2] * 16)
+        out.append(ds.score_families([(0, 1), (1, 4, 5), (15,)]).copy())
+        ds.close()
+        eng.close()
+        eng.close()
+        return out
+
+    first = run_all()
+    for a in first[1:6]:  # every way of planning the eight requests gives the host-planned posteriors
+        assert np.array_equal(a, first[1])
+    for k in (1, 2):
+        again = run_all()
+        assert len(again) == len(first)
+        for i, (a, b) in enumerate(zip(again, first)):
+            assert a.dtype == b.dtype and np.array_equal(a, b), (k, i)
+
+
 def test_engine_argument_errors(amd):
     from sorobn_amd import _capi
     spec = next(n for n in gu.load("examples.json") if n["spec"]["name"] == "asia")["spec"]
