@@ -178,6 +178,38 @@ int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off
 int mibn_posterior_sample_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                 const int64_t *s_off, uint64_t seed, uint32_t flags, int32_t *codes, double *p_e);
 
+/*
+ * Marginal MAP: for each request b, the most probable joint assignment of its MAP variables M_b with every other non-evidence
+ * variable summed out,  m*_b = argmax_m sum_h P(m, h, e_b):
+ *   m_off[B+1], m_vars[]              CSR list of the MAP variables of every request (may be empty: no codes, log_p = log P(e_b))
+ *   e_off[B+1], e_vars[], e_codes[]   CSR evidence, as in mibn_mpe_batch
+ *   codes[m_off[B] - m_off[0]]        codes[m_off[b] - m_off[0] + k] = the label code of m_vars[m_off[b] + k] in m*_b
+ *   log_p[B]                          natural log of max_m sum_h P(m, h, e_b) (unnormalised CPTs: of that mass)
+ *   flags                             MIBN_MAP_PRUNE: every CPT is a complete distribution (the caller's promise) - only M_b, the
+ *                                     evidence and their ancestors take part, a barren summed variable sums to 1.  Without it every
+ *                                     CPT takes part (the rule of mibn_mpe_batch): the path of sparse or unnormalised CPTs
+ * A two-phase elimination in one schedule (csrc/planner.h, "MAP programs"): the hidden variables are summed out first, then M_b is
+ * maximised out - one step per variable, every max step with an argmax table that a traceback kernel decodes on the device.  The
+ * dense joint over M_b is never built, but a step of the max phase holds the MAP variables that interact through the summed ones:
+ * a request whose step would reach 2^31 cells is MIBN_E_LIMIT - inherent to marginal MAP (the maxima cannot move inside the sums).
+ * Ties go to the lowest code; a single-state MAP variable gets code 0.  Zero mass (or a code of -1): log_p = -inf and code -1 for
+ * every MAP variable.  A request with an empty program (M empty, no evidence, MIBN_MAP_PRUNE) has log_p = 0.
+ * The result is a function of (network, request, flags) alone: bit for bit the same for any chunk, threads or arena budget.
+ * Blocking and host-planned, chunked and cut into waves by the arena budget; it changes no option and no state a later query call
+ * reads, and books nothing into the totals.  mibn_last_stats / mibn_last_kernel_stats ("ve_map_kernel", "map_traceback_kernel")
+ * describe it; the rows "ve_map_kernel:sum tiles" / "ve_map_kernel:max tiles" are no kernels but what the level launches held
+ * beside segments: launches = sum / max steps that ran as GENERIC tiles, items = their workgroups (no time and no bytes of their
+ * own: both are booked under "ve_map_kernel", so the rows' alg_bytes add up without counting anything twice).
+ * Errors: MIBN_E_ARG for unknown or duplicate variables, a variable both in M_b and in the evidence, a descending m_off or an
+ * unknown flag; MIBN_E_LIMIT for a MAP variable of more than 65 536 states (argmax entries are 16 bits) and for the planner's cell
+ * limit; MIBN_E_NOMEM as in the other elimination calls.  The 65 536-state limit is checked before the requests are validated: a
+ * call that breaks both returns MIBN_E_LIMIT.
+ */
+#define MIBN_MAP_PRUNE 1u
+int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, const int32_t *m_vars,
+                   const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                   int32_t *codes, double *log_p);
+
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {
     double alg_bytes;      /* sum over steps of 8*(sum input cells + output cells) */

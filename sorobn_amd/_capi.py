@@ -22,13 +22,14 @@ SYMBOLS = [
     "mibn_comm_unique_id", "mibn_comm_init", "mibn_comm_destroy", "mibn_comm_allgather_f64",
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
-    "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch",
+    "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch", "mibn_map_batch",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 Q_NOPRUNE = 1
 Q_UNNORMALISED = 2  # P(q, e) instead of P(q | e); zero query variables allowed: one cell, P(e) (see mibn.h)
 DRAW_PRUNE = 1  # mibn_posterior_sample_batch: every CPT is a complete distribution, prune to the ancestors of the evidence
+MAP_PRUNE = 1  # mibn_map_batch: every CPT is a complete distribution, prune to the ancestors of the MAP variables and the evidence
 COMM_ID_BYTES = 128
 SCORE_KINDS = {"loglik": 0, "bic": 1, "aic": 2, "bdeu": 3, "k2": 4}  # MIBN_SCORE_*
 
@@ -80,6 +81,7 @@ def lib():
         L.mibn_query_batch.argtypes = [vp, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_query_batch_ex.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_mpe_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i32p, f64p]
+        L.mibn_map_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i32p, f64p]
         L.mibn_posterior_sample_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i64p, C.c_uint64, C.c_uint32, i32p, f64p]
         L.mibn_expect_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, i64p, f64p, C.c_int64, f64p, f64p]
         L.mibn_plan_order.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, i32p, i32p]
@@ -393,6 +395,36 @@ class Engine:
         ecodes = _i32(ecodes).reshape(B, -1)
         e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
         return self.mpe_batch(e_off, evars.reshape(-1), ecodes.reshape(-1))
+
+    def map_batch(self, m_off, m_vars, e_off, e_vars, e_codes, flags=0):
+        """CSR MAP variables + CSR evidence -> (codes[m_off[B] - m_off[0]] int32, log_p[B] float64): marginal MAP of every request
+        (mibn_map_batch) - codes[m_off[b] - m_off[0] + k] is the code of m_vars[m_off[b] + k] in argmax_m sum_h P(m, h, e_b), log_p[b] the
+        log of that maximum.  flags: MAP_PRUNE."""
+        m_off, e_off = _i64(m_off), _i64(e_off)
+        B = len(e_off) - 1
+        if len(m_off) != B + 1:
+            raise ValueError("m_off and e_off need one entry per request, plus one")
+        m_vars, e_vars, e_codes = _i32(m_vars), _i32(e_vars), _i32(e_codes)
+        codes = np.empty(max(0, int(m_off[-1] - m_off[0])) if B else 0, np.int32)
+        log_p = np.empty(B, np.float64)
+        if B == 0:
+            return codes, log_p
+        pad32 = np.zeros(1, np.int32)
+        self._check(self._L.mibn_map_batch(self._h, int(flags), B, _p(m_off, C.c_int64), _p(m_vars if len(m_vars) else pad32, C.c_int32),
+                                           _p(e_off, C.c_int64), _p(e_vars if len(e_vars) else pad32, C.c_int32),
+                                           _p(e_codes if len(e_codes) else pad32, C.c_int32), _p(codes if codes.size else pad32, C.c_int32),
+                                           _p(log_p, C.c_double)))
+        return codes, log_p
+
+    def map(self, mvars, evars, ecodes, flags=0):
+        """Fixed-shape batch: mvars[B, nm], evars[B, ne], ecodes[B, ne] -> (codes[B, nm], log_p[B]), like mpe."""
+        mvars, evars, ecodes = _i32(mvars), _i32(evars), _i32(ecodes)
+        B = len(mvars)
+        nm, ne = (mvars.size // B, evars.size // B) if B else (0, 0)  # (either may be 0: no reshape(B, -1) of an empty array)
+        m_off = np.arange(B + 1, dtype=np.int64) * nm
+        e_off = np.arange(B + 1, dtype=np.int64) * ne
+        codes, log_p = self.map_batch(m_off, mvars.reshape(-1), e_off, evars.reshape(-1), ecodes.reshape(-1), flags=flags)
+        return codes.reshape(B, nm), log_p
 
     def submit_fixed(self, qvars, evars, ecodes):
         """Asynchronous query_fixed: returns a handle for wait().  At most two calls in flight."""

@@ -37,7 +37,7 @@ import numpy as np
 import pandas as pd
 
 from . import _capi
-from .events import decode_labels, encode_frame, iter_parts, part_args, pattern_groups
+from .events import decode_labels, encode_frame, iter_parts, label_table, part_args, pattern_groups
 from .flatten import flatten
 
 __all__ = ["BayesNet", "accelerate", "Backend"]
@@ -935,7 +935,8 @@ class BayesNet:
         """Replace the `None` entries of `sample` by the most probable joint assignment
         (bayes_net.py:877-908).  With a single missing variable the reference zips the *scalar*
         `idxmax()` (TypeError for bool labels, character-zip for strings - SURVEY.md section 3.2);
-        here that case simply works."""
+        here that case simply works.  (It builds the dense posterior over the missing variables; `map_query` / `map_frame`
+        answer the same question - also for a sample that names only some of the variables - without that table.)"""
         missing = [k for k, v in sample.items() if v is None]
         event = {k: v for k, v in sample.items() if v is not None}
         posterior = self.query(*missing, event=event, **query_params)
@@ -999,6 +1000,70 @@ class BayesNet:
             out[part], log_p[part] = be.engine.mpe(*part_args(ev_ids, codes, part, on))
         names = self._all_names()
         frame = pd.DataFrame(decode_labels(f, names, out, events), index=events.index, columns=names)
+        return (frame, log_p) if return_log_prob else frame
+
+    # ---- marginal MAP (an extension: sum-then-max elimination on the device, mibn_map_batch) ---------------------------------
+    def _map_backend(self, variables, evidence_names):
+        """The argument checks of `map_query` / `map_frame`, all before any engine exists, with the exception types of `query`."""
+        if len(set(variables)) != len(variables):
+            raise ValueError("A MAP variable is named twice")
+        for q in variables:
+            if q in evidence_names:
+                raise ValueError("A query variable cannot be part of the event")
+        return self._event_backend(list(variables) + list(evidence_names), every_cpt=True)
+
+    def _map_log_z(self, be):
+        """(flags, log Z) of the marginal MAP calls: CPTs that are all distributions prune (Z = 1); otherwise every CPT takes part and
+        log max_m P(m, e) is taken under the normalised joint, as `evidence_proba` does - Z is the mass of the empty request."""
+        if self._cpts_are_distributions(be):
+            return _capi.MAP_PRUNE, 0.0
+        none = np.zeros((1, 0), np.int32)
+        return 0, float(be.engine.map(none, none, none, flags=0)[1][0])
+
+    def map_query(self, *variables, event: dict = None, return_log_prob=False):
+        """Marginal MAP: the most probable joint assignment of `variables` given `event`, every other variable summed out -
+        argmax_m sum_h P(m, h, event).  Unlike `mpe` it does not maximise over the variables the caller did not name, and unlike
+        `query(*variables).idxmax()` it never builds the dense table over `variables`.  Returns a Series of labels indexed by
+        `variables` in the order given; with `return_log_prob`, (series, natural log of max_m P(m, event) under the normalised
+        joint).  Zero-probability or out-of-domain evidence gives None labels and -inf.  Ties go to the lowest label code.  The
+        MAP variables that interact through the summed ones share a table on the device: a request whose table would reach 2^31
+        cells raises (inherent to marginal MAP)."""
+        event = dict(event or {})
+        be = self._map_backend(variables, event)
+        f = be.flat
+        mv = [f.id[name] for name in variables]
+        ev = [f.id[name] for name in event]
+        ecodes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
+        flags, log_z = self._map_log_z(be)
+        codes, log_p = be.engine.map(np.array(mv, np.int32).reshape(1, len(mv)), np.array(ev, np.int32).reshape(1, len(ev)),
+                                     np.array(ecodes, np.int32).reshape(1, len(ev)), flags=flags)
+        labels = [label_table(f, v)[codes[0, k]] for k, v in enumerate(mv)]
+        series = pd.Series(labels, index=pd.Index(list(variables)), dtype=object)
+        lp = float(log_p[0]) - log_z if np.isfinite(log_p[0]) else -np.inf
+        return (series, lp) if return_log_prob else series
+
+    def map_frame(self, *variables, events: pd.DataFrame, return_log_prob=False, sub_batch=32768):
+        """`map_query(*variables)` for every row of `events`, in the convention of `mpe_frame`: the columns are evidence variables,
+        NaN / None = not observed in that row.  Rows are grouped by their pattern of observed columns, one engine call per group
+        (in sub-batches of `sub_batch` rows).  Returns a DataFrame with the index of `events` and one column per MAP variable, in
+        the order given (None where the row's evidence has probability zero); with `return_log_prob`, (frame, log probabilities
+        as a numpy array).  A MAP variable that a row observes raises ValueError."""
+        observed_cols = [c for c in events.columns if c not in variables or events[c].notna().any()]
+        be = self._map_backend(variables, observed_cols)
+        f = be.flat
+        cols = list(observed_cols)
+        ev_ids, codes, observed = encode_frame(be, cols, events)
+        mv = np.array([f.id[name] for name in variables], np.int32)
+        n = len(events)
+        out = np.full((n, len(mv)), -1, np.int32)
+        log_p = np.full(n, -np.inf, np.float64)
+        if n:
+            flags, log_z = self._map_log_z(be)
+            for part, on in iter_parts(pattern_groups(observed), observed, sub_batch):
+                out[part], log_p[part] = be.engine.map(np.broadcast_to(mv, (len(part), len(mv))), *part_args(ev_ids, codes, part, on), flags=flags)
+            log_p = np.where(np.isfinite(log_p), log_p - log_z, -np.inf)
+        data = {name: label_table(f, int(v))[out[:, k]] for k, (name, v) in enumerate(zip(variables, mv))}
+        frame = pd.DataFrame(data, index=events.index, columns=list(variables), dtype=object)
         return (frame, log_p) if return_log_prob else frame
 
     # ---- evidence likelihood P(e) (an extension: sum-product elimination without normalisation, MIBN_Q_UNNORMALISED) --------

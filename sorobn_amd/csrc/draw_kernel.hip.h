@@ -32,7 +32,7 @@ __global__ __launch_bounds__(kWG, 4) void ve_sum_kernel(const LevelArgs A) {
     it.a = (uint32_t)uni((int)A.items[item_idx].a);
     it.b = (uint32_t)uni((int)A.items[item_idx].b);
     if (it.a & kItemSegment) {
-        segment_wave<false>(A, item_idx, (int)it.b, reinterpret_cast<double *>(sh_buf), tid);
+        segment_wave<0>(A, item_idx, (int)it.b, reinterpret_cast<double *>(sh_buf), tid);
         return;
     }
     uint32_t *sh_step = reinterpret_cast<uint32_t *>(sh_buf);

@@ -31,6 +31,7 @@
 #include "ve_kernel.hip.h"
 #include "max_kernel.hip.h"
 #include "draw_kernel.hip.h"
+#include "map_kernel.hip.h"
 #include "expect_kernel.hip.h"
 #include "wave_plan_kernel.hip.h"
 
@@ -182,15 +183,17 @@ __global__ __launch_bounds__(MIBN_PLAN_WG, MIBN_EMIT_WAVES_PER_EU) void emit_ker
 constexpr int kChunkSets = 4;
 // statistics slots: the classes of work (split_kinds: 0 .. kNumKernels - 1, kernel_name), then the kernels of mibn_query_batch as
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
-// mibn_posterior_sample_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
+// steps.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
-    "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel"};
+    "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -353,6 +356,7 @@ struct mibn_ctx {
         DevBuf<double> d_m, d_log_p;  // per request of a chunk: what its FINAL step wrote; (MPE) the logarithm of it
         DevBuf<int32_t> d_codes;      // the decoded assignments of a chunk (MPE) / the rows of a draw launch
         DevBuf<DrawItem> d_draw_items;
+        DevBuf<int64_t> d_m_off;      // (MAP) per request of a chunk: where its codes go in d_codes
         std::vector<Event> ev;
         ~Elim() { for (ProgBuf &b : bufs) b.release(); }
     } elim;
@@ -2168,13 +2172,13 @@ static int run_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off,
 }
 
 // ---------------------------------------------------------------------------------------------- blocking elimination calls
-// run_elim: the one driver of the blocking, host-planned elimination calls - mibn_mpe_batch and mibn_posterior_sample_batch.  It plans
+// run_elim: the one driver of the blocking, host-planned elimination calls - mibn_mpe_batch, mibn_posterior_sample_batch, mibn_map_batch.  It plans
 // a chunk of requests on the workers (plan_batch), uploads the programs, cuts the chunk into waves by the arena budget, runs every
 // wave level by level on the main stream and hands it to the payload for post-processing.  No tiny kernel, no device planner, no
 // plan templates, no adaptive policy; the options are read, never written.  The arena of lane 0 is shared with the query calls
 // (after the streams have drained); the buffers are mibn_ctx::Elim's; the statistics are those of the last call only.
 //
-// A payload supplies the flavour of the programs (kMaxMode / kDrawMode / no_prune: plan_batch), the level kernel with its
+// A payload supplies the flavour of the programs (kMaxMode / kDrawMode / kMapMode - with m_off / m_vars, the MAP variables - / no_prune: plan_batch), the level kernel with its
 // statistics slot (launch_level, kLevelSlot), the limits its network must keep (limits: checked after the statistics reset and the
 // B == 0 return, before the requests are validated - as each entry point always did), and three hooks.  Everything is on the main
 // stream S; the driver owns every buffer of ElimRun::M but d_log_p, d_codes and d_draw_items, which are the payload's.
@@ -2249,7 +2253,15 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         Request rq;
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
-        const std::string e = rq.ne < 0 ? std::string("negative evidence count") : validate_mpe_request(net, rq);
+        std::string e;
+        if constexpr (Payload::kMapMode) {  // (the MAP variables too: unknown ids, duplicates, a variable both in M and in E)
+            rq.nq = (int32_t)(P.m_off[b + 1] - P.m_off[b]);
+            rq.qvars = P.m_vars + P.m_off[b];
+            rq.map_mode = true;
+            e = rq.ne < 0 || rq.nq < 0 ? std::string("negative count") : validate_request(net, rq);
+        } else {
+            e = rq.ne < 0 ? std::string("negative evidence count") : validate_mpe_request(net, rq);
+        }
         if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
         if (evidence_outside_domain(net, rq, e_codes + e_off[b])) skip[(size_t)b] = 1;  // -> zero probability
     }
@@ -2263,6 +2275,9 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
     const hipStream_t S = R.S;
     std::vector<int64_t> q_off((size_t)B + 1, 0), out_off((size_t)B + 1);
     std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: d_m
+    const int64_t *qo = q_off.data();  // (no query variables but a map program's M)
+    const int32_t *qv = nullptr;
+    if constexpr (Payload::kMapMode) { qo = P.m_off; qv = P.m_vars; }
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
     const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->d_arena[0].cap())) / 8.0);
@@ -2273,8 +2288,8 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         R.n = n;
         double t0 = now_ms();
         BatchPlan &ck = M.plan;
-        plan_batch(net, *h->pool, M.bufs, b0, b1, q_off.data(), nullptr, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck, P.no_prune,
-                   nullptr, nullptr, -1, Payload::kMaxMode, false, Payload::kDrawMode);
+        plan_batch(net, *h->pool, M.bufs, b0, b1, qo, qv, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck, P.no_prune,
+                   nullptr, nullptr, -1, Payload::kMaxMode, false, Payload::kDrawMode, Payload::kMapMode);
         if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
         h->stats.plan_ms += now_ms() - t0;
         t0 = now_ms();
@@ -2352,7 +2367,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
 // mibn_mpe_batch: max programs (planner.h) run by ve_max_kernel - the arena of a request holds its intermediates and argmax tables -,
 // decoded wave by wave by mpe_traceback_kernel, downloaded chunk by chunk.
 struct MpePayload {
-    static constexpr bool kMaxMode = true, kDrawMode = false, no_prune = false;
+    static constexpr bool kMaxMode = true, kDrawMode = false, kMapMode = false, no_prune = false;
     static constexpr int kLevelSlot = kStatMax;
     int32_t *codes;
     double *log_p;
@@ -2408,7 +2423,7 @@ struct MpePayload {
 constexpr size_t kDrawCodeWords = size_t(64) << 20;  // 256 MB of codes on the device per draw launch
 
 struct DrawPayload {
-    static constexpr bool kMaxMode = false, kDrawMode = true;
+    static constexpr bool kMaxMode = false, kDrawMode = true, kMapMode = false;
     static constexpr int kLevelSlot = kStatSum;
     const bool no_prune;
     const int64_t *s_off;
@@ -2529,6 +2544,94 @@ struct DrawPayload {
     }
 };
 
+// ---------------------------------------------------------------------------------------------- marginal MAP
+// mibn_map_batch: map programs (planner.h) run by ve_map_kernel - sum steps and max steps in one schedule; the arena of a request holds
+// its intermediates and the argmax tables of its max steps -, decoded wave by wave by map_traceback_kernel into the requests' slices of
+// d_codes, downloaded chunk by chunk.
+struct MapPayload {
+    static constexpr bool kMaxMode = false, kDrawMode = false, kMapMode = true;
+    static constexpr int kLevelSlot = kStatMap;
+    const bool no_prune;
+    const int64_t B;
+    const int64_t *m_off;
+    const int32_t *m_vars;
+    int32_t *codes;
+    double *log_p;
+    std::vector<double> m_init;
+    std::vector<int64_t> rel_off;  // m_off of the chunk, relative to its first request
+
+    int limits(mibn_ctx *h) const {
+        for (int64_t k = m_off[0]; k < m_off[B]; ++k) {
+            const int32_t v = m_vars[k];
+            if (v >= 0 && v < h->net.n_vars && h->net.card[v] > 65536) {
+                h->err = "map: variable " + std::to_string(v) + " has more than 65 536 states (argmax entries are 16 bits)";
+                return MIBN_E_LIMIT;
+            }
+        }
+        return MIBN_OK;
+    }
+    void launch_level(unsigned grid, hipStream_t S, const LevelArgs &A) const { hipLaunchKernelGGL(ve_map_kernel, dim3(grid), dim3(kWG), 0, S, A); }
+    int prepare(ElimRun &R) {
+        mibn_ctx *h = R.h;
+        const mibn_ctx::Elim &M = R.M;
+        const BatchPlan &ck = M.plan;
+        const int64_t n = R.n;
+        int rc;
+        if ((rc = ensure(h, R.M.d_log_p, (size_t)n))) return rc;
+        if ((rc = ensure(h, R.M.d_m_off, (size_t)n + 1))) return rc;
+        if ((rc = ensure(h, R.M.d_codes, (size_t)std::max<int64_t>(1, m_off[R.b0 + n] - m_off[R.b0])))) return rc;
+        // a skipped request never writes its cell: zero probability.  A program without steps (M empty, no evidence, pruned) has the
+        // empty product: 1, written here
+        m_init.assign((size_t)n, 0.0);
+        rel_off.resize((size_t)n + 1);
+        for (int64_t i = 0; i <= n; ++i) rel_off[(size_t)i] = m_off[R.b0 + i] - m_off[R.b0];
+        for (int64_t i = 0; i < n; ++i)
+            if (!R.skip[(size_t)(R.b0 + i)] && M.bufs[(size_t)ck.thread_of[(size_t)i]].data[ck.local_off[(size_t)i]] == 0) m_init[(size_t)i] = 1.0;
+        HIP_TRY(h, hipMemcpyAsync(M.d_m, m_init.data(), (size_t)n * 8, hipMemcpyHostToDevice, R.S));
+        HIP_TRY(h, hipMemcpyAsync(M.d_m_off, rel_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, R.S));
+        HIP_TRY(h, hipStreamSynchronize(R.S));  // (both vectors are rewritten by the next chunk)
+        return MIBN_OK;
+    }
+    int after_levels(ElimRun &R) const {
+        mibn_ctx *h = R.h;
+        const mibn_ctx::Elim &M = R.M;
+        // what the wave's level launches held beside segments: the tiled steps of either kind (statistics only)
+        for (const Item &it : M.sched.items) {
+            if (it.a & kItemSegment) continue;
+            const size_t r = (size_t)R.r0 + it.req;
+            const uint32_t *w = M.bufs[(size_t)M.plan.thread_of[r]].data + M.plan.local_off[r] + it.rel_off;
+            const int th = std::max(1, (int)it.a);
+            book_stat(h, ((w[1] >> 16) & kFlagMax) ? kStatMapMaxTiles : kStatMapSumTiles, 1, 0.0, 0.0,  // (their bytes are ve_map_kernel's)
+                      (double)(((int64_t)w[3] + th - 1) / th), true, false);
+        }
+        MapTracebackArgs T;
+        T.prog = M.d_prog;
+        T.prog_off = M.d_prog_off + R.r0;
+        T.arena_off = M.d_arena_off;
+        T.arena = h->arena(0);
+        T.m = M.d_m + R.r0;
+        T.m_off = M.d_m_off + R.r0;
+        T.codes = M.d_codes;
+        T.log_p = M.d_log_p + R.r0;
+        T.n_req = (uint32_t)(R.r1 - R.r0);
+        T.n_vars = h->net.n_vars;
+        int rc;
+        if ((rc = R.timed_launch(kStatMapTraceback, 0.0, (double)(R.r1 - R.r0), [&] {
+                hipLaunchKernelGGL(map_traceback_kernel, dim3((unsigned)(R.r1 - R.r0)), dim3(kTracebackWG), 0, R.S, T);
+            })))
+            return rc;
+        HIP_TRY(h, hipGetLastError());
+        return MIBN_OK;
+    }
+    int download(ElimRun &R) const {
+        mibn_ctx *h = R.h;
+        const int64_t cells = m_off[R.b0 + R.n] - m_off[R.b0];
+        if (cells > 0) HIP_TRY(h, hipMemcpyAsync(codes + (m_off[R.b0] - m_off[0]), R.M.d_codes, (size_t)cells * 4, hipMemcpyDeviceToHost, R.S));
+        HIP_TRY(h, hipMemcpyAsync(log_p + R.b0, R.M.d_log_p, (size_t)R.n * 8, hipMemcpyDeviceToHost, R.S));
+        return MIBN_OK;
+    }
+};
+
 // The argument checks of each entry point come first, in its own order; then the driver.
 int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes, double *log_p) {
     if (!h || B < 0 || !e_off || (B && (!codes || !log_p))) return MIBN_E_ARG;
@@ -2551,12 +2654,30 @@ int run_draw_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_v
     return run_elim(h, B, e_off, e_vars, e_codes, P);
 }
 
+int run_map_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, const int32_t *m_vars, const int64_t *e_off, const int32_t *e_vars,
+                 const int32_t *e_codes, int32_t *codes, double *log_p) {
+    if (!h || B < 0 || !m_off || !e_off || (B && !log_p)) return MIBN_E_ARG;
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (flags & ~(uint32_t)MIBN_MAP_PRUNE) { h->err = "map: unknown flag"; return MIBN_E_ARG; }
+    for (int64_t b = 0; b < B; ++b)
+        if (m_off[b + 1] < m_off[b] || m_off[b] < 0) { h->err = "map: m_off must be non-negative and ascending"; return MIBN_E_ARG; }
+    if (B && m_off[B] > m_off[0] && (!codes || !m_vars)) return MIBN_E_ARG;
+    MapPayload P{!(flags & MIBN_MAP_PRUNE), B, m_off, m_vars, codes, log_p};
+    return run_elim(h, B, e_off, e_vars, e_codes, P);
+}
+
 }  // namespace
 
 // (nothing of a blocking call may still run on the main stream when the caller sees its error)
 extern "C" int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes,
                               double *log_p) {
     return drained_on_error(h, run_mpe_body(h, B, e_off, e_vars, e_codes, codes, log_p), drain_main_unchecked);
+}
+
+extern "C" int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, const int32_t *m_vars, const int64_t *e_off,
+                              const int32_t *e_vars, const int32_t *e_codes, int32_t *codes, double *log_p) {
+    return drained_on_error(h, run_map_body(h, flags, B, m_off, m_vars, e_off, e_vars, e_codes, codes, log_p), drain_main_unchecked);
 }
 
 extern "C" int mibn_posterior_sample_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,

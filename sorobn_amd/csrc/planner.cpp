@@ -286,7 +286,7 @@ void Network::set_hints(int32_t n_hints, const int32_t *priorities) {
 }
 
 bool request_is_valid(const Network &net, const Request &rq) {
-    if (rq.nq < (rq.raw ? 0 : 1)) return false;
+    if (rq.nq < ((rq.raw || rq.map_mode) ? 0 : 1)) return false;
     uint64_t seen[kWords];  // (only the words the network uses: a batch validates 100 k requests on one thread)
     for (int k = 0; k < net.nw; ++k) seen[k] = 0;
     for (int i = 0; i < rq.nq + rq.ne; ++i) {
@@ -312,7 +312,7 @@ std::string validate_mpe_request(const Network &net, const Request &rq) {
 
 std::string validate_request(const Network &net, const Request &rq) {
     if (request_is_valid(net, rq)) return "";
-    if (rq.nq < (rq.raw ? 0 : 1)) return "At least one query variable has to be specified";  // bayes_net.py:840-841
+    if (rq.nq < ((rq.raw || rq.map_mode) ? 0 : 1)) return "At least one query variable has to be specified";  // bayes_net.py:840-841
     Bits seen;
     for (int i = 0; i < rq.nq; ++i) {
         int v = rq.qvars[i];
@@ -772,6 +772,179 @@ static int emit_run_draw(const Network &net, const EmitNet &en_sum, EmitScratch 
     return 0;
 }
 
+// Map program of one request (planner.h, "MAP programs"): the factors of emit_begin for the query set M, one GENERIC sum step per
+// variable of `order` (the hidden variables; intermediates released as usual), then one GENERIC max step with its argmax table per
+// multi-state variable of M - fewest output cells first, lowest id on a tie -, the final product of the remaining scalars (RAW),
+// the traceback record of the max steps and the gather list (M in the caller's order).  Host only.  Returns 0 or a kEmitErr*.
+static int emit_run_map(const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq, const int32_t *order,
+                        int n_order, int64_t &argmax_cells) {
+    EmitNet en = en_sum;  // every step GENERIC, as in a max program
+    en.big_iters = std::numeric_limits<int64_t>::max();
+    en.outer = en.fuse = en.chain = en.sweep = 0;
+    PF *pool = S.pool;
+    // the max order depends on the scopes alone: found on bit sets first, so that the layout keys of both phases are known before
+    // the first step is emitted (longest-living variable fastest: M after every hidden variable, in its own elimination order)
+    std::vector<int32_t> max_order;
+    {
+        std::vector<Bits> sc;
+        for (int idx = 0; idx < S.n0; ++idx) sc.push_back(pool[idx].scope);
+        std::vector<char> live(sc.size(), 1);
+        auto joined = [&](int x) {  // scope of the step that eliminates x (x itself excluded)
+            Bits u;
+            u.nw = en.nw;
+            for (size_t k = 0; k < sc.size(); ++k)
+                if (live[k] && sc[k].test(x)) u.or_(sc[k]);
+            u.clr(x);
+            return u;
+        };
+        auto eliminate = [&](int x) {
+            const Bits u = joined(x);
+            bool found = false;
+            for (size_t k = 0; k < sc.size(); ++k)
+                if (live[k] && sc[k].test(x)) { live[k] = 0; found = true; }
+            if (found) { sc.push_back(u); live.push_back(1); }
+        };
+        for (int i = 0; i < n_order; ++i) eliminate(order[i]);
+        std::vector<int32_t> left;
+        for (int i = 0; i < rq.nq; ++i)
+            if (en.card[rq.qvars[i]] > 1) left.push_back(rq.qvars[i]);
+        std::sort(left.begin(), left.end());
+        while (!left.empty()) {
+            size_t pick = 0;
+            double best = 0;
+            for (size_t k = 0; k < left.size(); ++k) {
+                double cells = 1;
+                joined(left[k]).for_each([&](int v) { cells *= en.card[v]; });
+                if (k == 0 || cells < best) { best = cells; pick = k; }  // (ascending ids: a tie keeps the lowest)
+            }
+            max_order.push_back(left[pick]);
+            eliminate(left[pick]);
+            left.erase(left.begin() + (ptrdiff_t)pick);
+        }
+    }
+    S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
+    Emitter em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr};
+    for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
+    for (size_t i = 0; i < max_order.size(); ++i) S.key[max_order[i]] = (double)(n_order + (int)i);
+    const size_t count_pos = prog.size;
+    prog.push(0);
+    const double steps0 = st.n_steps;
+    std::vector<char> alive((size_t)S.pool_cap, 0);
+    for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
+    const PF **ins = S.ins;
+    auto limit = [&](int n_in) -> int {  // product-only steps above kMaxIn inputs: unflagged in either phase
+        while (n_in > kMaxIn && !em.err) {
+            if (S.n_pool + 1 > S.pool_cap) { em.err = kEmitErrPool; return 0; }
+            std::stable_sort(ins, ins + n_in, [](const PF *a, const PF *b) { return a->cells < b->cells; });
+            PF &o = pool[S.n_pool++];
+            pf_reset(o);
+            em.emit(ins, kMaxIn, nullptr, 0, false, 0, o, false);
+            for (int k = kMaxIn; k < n_in; ++k) ins[k - kMaxIn] = ins[k];
+            n_in -= kMaxIn;
+            ins[n_in++] = &o;
+        }
+        return n_in;
+    };
+    auto gather = [&](int32_t x) -> int {
+        int n_in = 0;
+        for (int idx = 0; idx < S.n_pool; ++idx)
+            if (alive[(size_t)idx] && pool[idx].scope.test(x)) { ins[n_in++] = &pool[idx]; alive[(size_t)idx] = 0; }
+        return n_in ? limit(n_in) : 0;
+    };
+    // sum phase
+    for (int i = 0; i < n_order; ++i) {
+        const int32_t x = order[i];
+        const int n_in = gather(x);
+        if (em.err) return em.err;
+        if (!n_in) continue;  // (cannot happen: x's own CPT mentions it)
+        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
+        PF &o = pool[S.n_pool++];
+        pf_reset(o);
+        em.emit(ins, n_in, &x, 1, false, 0, o, false);
+        if (em.err) return em.err;
+        alive[(size_t)(S.n_pool - 1)] = 1;
+    }
+    // max phase
+    struct Rec { uint64_t off; int32_t x, n; int32_t vars[kRawAxes]; int64_t strides[kRawAxes]; };
+    std::vector<Rec> recs;
+    recs.reserve(max_order.size());
+    for (const int32_t x : max_order) {
+        const int n_in = gather(x);
+        if (em.err) return em.err;
+        if (!n_in) continue;  // (cannot happen: x's own CPT is relevant)
+        // the argmax table is allocated before the step's output - and before its inputs go back to the arena (emit_run_max)
+        Bits u;
+        u.nw = en.nw;
+        for (int j = 0; j < n_in; ++j) u.or_(ins[j]->scope);
+        u.clr(x);
+        double cells = 1;
+        u.for_each([&](int v) { cells *= en.card[v]; });
+        if (cells >= (double)(1ll << 31)) return kEmitErrCells;
+        const int64_t am_cells = ((int64_t)cells * 2 + 7) / 8;  // uint16 entries, in doubles
+        const int64_t am_off = em.arena.alloc(am_cells);
+        argmax_cells += (am_cells + 15) & ~int64_t(15);
+        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
+        PF &o = pool[S.n_pool++];
+        pf_reset(o);
+        const size_t step_base = prog.size;
+        em.emit(ins, n_in, &x, 1, false, 0, o, false);
+        if (em.err) return em.err;
+        uint32_t *w = prog.data + step_base;
+        w[1] |= kFlagMax << 16;
+        w[7] = (uint32_t)((uint64_t)am_off & 0xffffffffu);
+        w[8] = (uint32_t)((uint64_t)am_off >> 32);
+        w[9] += (uint32_t)(((int64_t)cells + 15) / 16);  // (the argmax bytes, in the step's units of 32 bytes)
+        st.alg_bytes += 2.0 * cells;
+        Rec r;
+        r.off = (uint64_t)am_off;
+        r.x = x;
+        r.n = o.n;
+        for (int a = 0; a < o.n; ++a) { r.vars[a] = o.vars[a]; r.strides[a] = o.strides[a]; }
+        recs.push_back(r);
+        alive[(size_t)(S.n_pool - 1)] = 1;
+    }
+    // m = the product of what is left (all scalars), one cell, never normalised.  Nothing left (M empty, no evidence, pruned): no
+    // step, the empty product
+    st.out_cells = 1;
+    int n_in = 0;
+    for (int idx = 0; idx < S.n_pool; ++idx)
+        if (alive[(size_t)idx]) ins[n_in++] = &pool[idx];
+    if (n_in) {
+        n_in = limit(n_in);
+        if (em.err) return em.err;
+        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
+        PF &o = pool[S.n_pool++];
+        pf_reset(o);
+        const size_t step_base = prog.size;
+        em.emit(ins, n_in, nullptr, 0, true, rq.out_off, o, false);
+        if (em.err) return em.err;
+        prog.data[step_base + 1] |= kFlagRaw << 16;
+    }
+    prog.data[count_pos] = (uint32_t)(st.n_steps - steps0);
+    st.arena_cells = std::max(st.arena_cells, em.arena.top);
+    // traceback record, then the gather list
+    prog.push((uint32_t)recs.size());
+    prog.push((uint32_t)rq.ne);
+    for (int i = 0; i < rq.ne; ++i) {
+        prog.push((uint32_t)rq.evars[i]);
+        prog.push((uint32_t)(rq.ecodes ? rq.ecodes[i] : 0));
+    }
+    for (size_t k = recs.size(); k-- > 0;) {
+        const Rec &r = recs[k];
+        prog.push((uint32_t)(r.off & 0xffffffffu));
+        prog.push((uint32_t)(r.off >> 32));
+        prog.push((uint32_t)r.x);
+        prog.push((uint32_t)r.n);
+        for (int a = 0; a < r.n; ++a) {
+            prog.push((uint32_t)r.vars[a]);
+            prog.push((uint32_t)r.strides[a]);
+        }
+    }
+    prog.push((uint32_t)rq.nq);
+    for (int i = 0; i < rq.nq; ++i) prog.push((uint32_t)rq.qvars[i]);
+    return 0;
+}
+
 // One request on the host: the shared emission (emit_core.h) around the choice of the elimination order.
 static std::string plan_request_rec(const Network &net, const Request &rq, ProgBuf &prog, PlanStats &st, PlanRecord *rec) {
     PROF(0);
@@ -800,7 +973,8 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     // evidence-sliced CPTs of the relevant nodes (768-776)
     // (a max program has no query variable and never prunes: every non-evidence variable is maximised out)
     // (a draw program has no query variable either, and prunes to the ancestors of the evidence unless told not to)
-    const bool mx = rq.max_mode, dr = rq.draw_mode;
+    // (a map program's query set is M: relevant = M | event | ancestors, hidden = what the sum phase eliminates)
+    const bool mx = rq.max_mode, dr = rq.draw_mode, mp = rq.map_mode;
     const int nq = (mx || dr) ? 0 : rq.nq;
     const bool no_prune = mx || rq.no_prune;
     if (int e = emit_begin(en, ES, nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, no_prune)) return emit_error_message(e);
@@ -818,10 +992,10 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
         PROF(1);
         OrderScratch &OS = order_scratch();
         OrderNet on = net.order_view();
-        if (mx || dr) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms max / draw programs do not use)
+        if (mx || dr || mp) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms max / draw programs do not use)
         order_search(on, OS, nq, rq.qvars, rq.ne, rq.evars, no_prune);
         best.assign(OS.best, OS.best + OS.n_best);
-        if (!mx && !dr && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
+        if (!mx && !dr && !mp && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
     } else if (hidden.any()) {
         std::vector<Bits> &scopes = S.scopes;
         std::vector<double> &scells = S.scope_cells;
@@ -893,6 +1067,12 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     }
     if (dr) {
         const int e = emit_run_draw(net, en, ES, eb, es, rq, best.data(), (int)best.size(), st.kept_cells);
+        st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
+        st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
+        return emit_error_message(e);
+    }
+    if (mp) {
+        const int e = emit_run_map(en, ES, eb, es, rq, best.data(), (int)best.size(), st.argmax_cells);
         st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
         st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
         return emit_error_message(e);
@@ -1212,7 +1392,7 @@ PlanCache &plan_cache(const TemplateStore *ts) {
 void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs, int64_t b0, int64_t b1,
                 const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
                 const int32_t *e_codes, const int64_t *out_off, const char *skip, BatchPlan &ck, bool no_prune,
-                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode, bool raw, bool draw_mode) {
+                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode, bool raw, bool draw_mode, bool map_mode) {
     const int64_t n = b1 - b0;
     const int T = pool.size();
     if ((int)bufs.size() < T) bufs.resize(T);
@@ -1232,7 +1412,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
     std::vector<std::string> terr(T);
     // dynamic distribution in blocks of 32 requests: request costs vary 100x and a worker may lose its core to
     // another rank's planner, a static split would wait for the slowest worker
-    TemplateStore *store = (net.plan_cache && !max_mode && !raw && !draw_mode) ? template_store(net) : nullptr;
+    TemplateStore *store = (net.plan_cache && !max_mode && !raw && !draw_mode && !map_mode) ? template_store(net) : nullptr;
     std::atomic<int64_t> next{0};
     constexpr int64_t kBlock = 32;
     const EmitNet en = net.emit_view();
@@ -1253,7 +1433,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             ck.tag_first[i] = (uint32_t)tags.size();
             if (skip && skip[b]) {  // zero steps: result stays all-zero
                 prog.push(0);
-                if (max_mode || draw_mode) {  // (an empty traceback / draw record: m = 0 reads as zero probability)
+                if (max_mode || draw_mode || map_mode) {  // (an empty traceback / draw record: m = 0 reads as zero probability)
                     const int32_t ne = (int32_t)(e_off[b + 1] - e_off[b]);
                     prog.push(0);
                     if (draw_mode) prog.push(0);
@@ -1273,6 +1453,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             rq.max_mode = max_mode;
             rq.raw = raw;
             rq.draw_mode = draw_mode;
+            rq.map_mode = map_mode;
             if (orders) { rq.order = orders + (size_t)i * 128; rq.n_order = order_len[i]; }
             PlanStats st;
             // plan templates (see above): probe at the start of every window, stay on while shapes repeat

@@ -92,6 +92,9 @@ struct Request {
     bool raw = false;                 // MIBN_Q_UNNORMALISED: the FINAL step carries kFlagRaw (P(q, e), not normalised); nq = 0 allowed
     bool draw_mode = false;           // draw program (mibn_posterior_sample_batch): sum elimination with every input kept, nq = 0; prunes
                                       // to the evidence's ancestors unless no_prune
+    bool map_mode = false;            // map program (mibn_map_batch): qvars[0..nq) are the MAP variables M - every other non-evidence variable
+                                      // is summed out first, then M is maximised out; nq = 0 allowed; prunes to the ancestors of M and
+                                      // the evidence unless no_prune
     const uint8_t *order = nullptr;   // elimination order found elsewhere (the device order search), n_order entries
     int32_t n_order = -1;             // -1: search on the host
 };
@@ -217,6 +220,21 @@ struct PlanStats {
 //      every axis variable is eliminated later, so the walk has drawn it already.  Forward entries, ascending id (= topological):
 //      one input, x's whole CPT with its multi-state parents as axes - evidence or drawn before.  A request whose evidence code
 //      lies outside its domain is the program "0" + a record with n_back = n_fwd = 0.
+//
+//   MAP programs (Request::map_mode, mibn_map_batch): marginal MAP, m = max_m sum_h P(m, h, e) over the MAP variables M = qvars.  Two
+//      phases, every step GENERIC with one eliminated variable (product-only steps above kMaxIn inputs, as in a max program).  SUM
+//      phase: the factors and the order of the sum program of (M, e) - pruned to the ancestors of M and the evidence unless
+//      Request::no_prune, order_search with plain section-8(d) bytes - one unflagged step per hidden variable, intermediates released
+//      as usual; the sum path's FINAL joint over M is NOT emitted.  MAX phase, over the factors left over M: the MAP variable whose
+//      elimination step has the fewest output cells goes first (lowest id on a tie); one step per multi-state MAP variable with flag
+//      MAX and its argmax table (allocated before the step's output, never released: PlanStats::argmax_cells).  No unflagged step
+//      eliminates a variable after the first MAX step.  The FINAL step multiplies the remaining scalars into one cell, flagged RAW
+//      (never normalised).  Nothing left at all (M empty, no evidence, pruned): no step, the empty product.  A step over M that
+//      would reach 2^31 cells is kEmitErrCells: inherent to marginal MAP - the max phase cannot start before the sums are done.
+//      After the last step follows the TRACEBACK record in the format of a max program (entries: the MAX steps, last eliminated
+//      first), then the GATHER list:  nq, M in the caller's order - what the decoder returns codes for.  A single-state MAP
+//      variable is never eliminated: code 0.  A request whose evidence code lies outside its domain is the program "0" + a record
+//      with n_rec = 0 (no gather list: every code is -1).
 // Growable word buffer the planner appends programs to.  The engine backs it with pinned host memory
 // (so the upload is a true async DMA) and keeps it across calls; the default backing is malloc.
 struct ProgBuf {
@@ -272,7 +290,8 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
                                           // first requests the device plans
                 bool max_mode = false,    // max programs (mibn_mpe_batch; q_off all zero, no plan templates)
                 bool raw = false,         // MIBN_Q_UNNORMALISED requests (nq = 0 allowed, no plan templates)
-                bool draw_mode = false);  // draw programs (mibn_posterior_sample_batch; q_off all zero, no plan templates; prunes unless no_prune)
+                bool draw_mode = false,   // draw programs (mibn_posterior_sample_batch; q_off all zero, no plan templates; prunes unless no_prune)
+                bool map_mode = false);   // map programs (mibn_map_batch; q_off / q_vars = the MAP variables, no plan templates; prunes unless no_prune)
 
 // Shard-balancing estimate (mibn_estimate_costs): section-8(d) bytes of the cheaper of the two sweep orders of every
 // request of a CSR batch - the byte model only, nothing is emitted.
@@ -321,7 +340,7 @@ void build_schedule(const Network &net, const BatchPlan &bp, const std::vector<P
                     Schedule &out);
 
 // Validate a request (unknown ids, duplicates, overlap) - bayes_net.py:840-845 and the KeyError of 770.  nq = 0 is valid only with
-// Request::raw.
+// Request::raw or Request::map_mode.
 std::string validate_request(const Network &net, const Request &rq);  // "" or the reference's error message
 bool request_is_valid(const Network &net, const Request &rq);          // the same checks without building a message
 std::string validate_mpe_request(const Network &net, const Request &rq);  // evidence only (unknown ids, duplicates): "" or the message

@@ -930,9 +930,10 @@ __device__ __forceinline__ void normalise_wave(double *__restrict__ p, int n, in
 // back, on its own.  A chain of dependent tiny steps is latency, not bandwidth, and a wave is enough for one (< 4 096 output
 // cells per step): four chains per workgroup, twelve per CU, hide four times as much of it as one.  The wave's copy of the
 // step descriptor and its offset table live in its quarter of the first 12 KB of shT (a segment has no T).
-// MAX: the steps of a max program (max_kernel.hip.h) - its FINAL step is not normalised; nor is a FINAL step flagged RAW
-// (MIBN_Q_UNNORMALISED).
-template <bool MAX = false>
+// MODE 1: the steps of a max program (max_kernel.hip.h) - its FINAL step is not normalised; nor is a FINAL step flagged RAW
+// (MIBN_Q_UNNORMALISED).  MODE 2: the steps of a map program (map_kernel.hip.h) - a step flagged kFlagMax runs the max body, every
+// other step the sum body; the choice is wave-uniform and made per step, a segment may hold both kinds.  Never normalised.
+template <int MODE = 0>
 __device__ __forceinline__ void segment_wave(const LevelArgs &A, const uint32_t first, const int n_valid, double *shT, const int tid) {
     const int wave = tid >> 6, lane = tid & 63;
     if (wave >= n_valid) return;
@@ -962,8 +963,13 @@ __device__ __forceinline__ void segment_wave(const LevelArgs &A, const uint32_t 
 #pragma unroll
             for (int k = 0; k < kPre; ++k) nxt[k] = p[words + lane + 64 * k];
         }
-        generic_dispatch<64, MAX>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
-        if (!MAX && ((w_step[1] >> 16) & (kFlagFinal | kFlagRaw)) == kFlagFinal) {  // (RAW: P(q, e) as it is)
+        if constexpr (MODE == 2) {
+            if ((w_step[1] >> 16) & kFlagMax) generic_dispatch<64, true>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
+            else generic_dispatch<64, false>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
+        } else {
+            generic_dispatch<64, MODE == 1>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
+        }
+        if (MODE == 0 && ((w_step[1] >> 16) & (kFlagFinal | kFlagRaw)) == kFlagFinal) {  // (RAW: P(q, e) as it is)
             const uint64_t out_off = (uint64_t)w_step[4] | ((uint64_t)w_step[5] << 32);
             lanes_sync<64>();
             normalise_wave(A.results + out_off, (int)(w_step[2] * w_step[3]), lane);
