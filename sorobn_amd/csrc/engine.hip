@@ -1463,7 +1463,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
         rq.qvars = q_vars + q_off[b];
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
-        rq.raw = (flags & MIBN_Q_UNNORMALISED) != 0;
+        rq.kind = (flags & MIBN_Q_UNNORMALISED) ? ProgramKind::Raw : ProgramKind::Sum;
         std::string why = validate_request(h->net, rq);
         if (why.empty()) why = "out_off does not match the query table size";
         h->err = "request " + std::to_string(b) + ": " + why;
@@ -1572,7 +1572,7 @@ int query_validate(QueryRun &R) {
         rq.qvars = R.q_vars + R.q_off[b];
         rq.ne = (int32_t)(R.e_off[b + 1] - R.e_off[b]);
         rq.evars = R.e_vars + R.e_off[b];
-        rq.raw = R.raw;
+        rq.kind = R.raw ? ProgramKind::Raw : ProgramKind::Sum;
         if (!request_is_valid(h->net, rq)) { h->err = "request " + std::to_string(b) + ": " + validate_request(h->net, rq); return MIBN_E_ARG; }
         int64_t cells = 1;
         for (int i = 0; i < rq.nq; ++i) cells *= h->net.card[rq.qvars[i]];
@@ -1844,7 +1844,7 @@ int plan_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t b0, int64_t b1, bool &on_
     }
     if (on_device && !beyond.empty() && (rc = replan_beyond(R, st, b0, nd, beyond, on_device))) return rc;
     if (!on_device)
-        plan_batch(h->net, *h->pool, st.bufs, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), ck, no_prune, orders, order_len, -1, false, R.raw);
+        plan_batch(h->net, *h->pool, st.bufs, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), ck, no_prune, orders, order_len, -1, R.raw ? ProgramKind::Raw : ProgramKind::Sum);
     if (on_device && h->gpu_emit == 2 && (rc = check_against_host(R, st, b0, b1))) return rc;
     if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
     for (auto &b : st.bufs)
@@ -2178,7 +2178,7 @@ static int run_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off,
 // plan templates, no adaptive policy; the options are read, never written.  The arena of lane 0 is shared with the query calls
 // (after the streams have drained); the buffers are mibn_ctx::Elim's; the statistics are those of the last call only.
 //
-// A payload supplies the flavour of the programs (kMaxMode / kDrawMode / kMapMode - with m_off / m_vars, the MAP variables - / no_prune: plan_batch), the level kernel with its
+// A payload supplies the flavour of the programs (kKind - for ProgramKind::Map with m_off / m_vars, the MAP variables - and no_prune: plan_batch), the level kernel with its
 // statistics slot (launch_level, kLevelSlot), the limits its network must keep (limits: checked after the statistics reset and the
 // B == 0 return, before the requests are validated - as each entry point always did), and three hooks.  Everything is on the main
 // stream S; the driver owns every buffer of ElimRun::M but d_log_p, d_codes and d_draw_items, which are the payload's.
@@ -2254,10 +2254,10 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
         std::string e;
-        if constexpr (Payload::kMapMode) {  // (the MAP variables too: unknown ids, duplicates, a variable both in M and in E)
+        if constexpr (Payload::kKind == ProgramKind::Map) {  // (the MAP variables too: unknown ids, duplicates, a variable both in M and in E)
             rq.nq = (int32_t)(P.m_off[b + 1] - P.m_off[b]);
             rq.qvars = P.m_vars + P.m_off[b];
-            rq.map_mode = true;
+            rq.kind = ProgramKind::Map;
             e = rq.ne < 0 || rq.nq < 0 ? std::string("negative count") : validate_request(net, rq);
         } else {
             e = rq.ne < 0 ? std::string("negative evidence count") : validate_mpe_request(net, rq);
@@ -2277,7 +2277,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
     std::iota(out_off.begin(), out_off.end(), int64_t(0));  // one cell per request: d_m
     const int64_t *qo = q_off.data();  // (no query variables but a map program's M)
     const int32_t *qv = nullptr;
-    if constexpr (Payload::kMapMode) { qo = P.m_off; qv = P.m_vars; }
+    if constexpr (Payload::kKind == ProgramKind::Map) { qo = P.m_off; qv = P.m_vars; }
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
     const int64_t budget_cells = (int64_t)(std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->d_arena[0].cap())) / 8.0);
@@ -2289,7 +2289,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         double t0 = now_ms();
         BatchPlan &ck = M.plan;
         plan_batch(net, *h->pool, M.bufs, b0, b1, qo, qv, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck, P.no_prune,
-                   nullptr, nullptr, -1, Payload::kMaxMode, false, Payload::kDrawMode, Payload::kMapMode);
+                   nullptr, nullptr, -1, Payload::kKind);
         if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
         h->stats.plan_ms += now_ms() - t0;
         t0 = now_ms();
@@ -2367,7 +2367,8 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
 // mibn_mpe_batch: max programs (planner.h) run by ve_max_kernel - the arena of a request holds its intermediates and argmax tables -,
 // decoded wave by wave by mpe_traceback_kernel, downloaded chunk by chunk.
 struct MpePayload {
-    static constexpr bool kMaxMode = true, kDrawMode = false, kMapMode = false, no_prune = false;
+    static constexpr ProgramKind kKind = ProgramKind::Max;
+    static constexpr bool no_prune = false;
     static constexpr int kLevelSlot = kStatMax;
     int32_t *codes;
     double *log_p;
@@ -2423,7 +2424,7 @@ struct MpePayload {
 constexpr size_t kDrawCodeWords = size_t(64) << 20;  // 256 MB of codes on the device per draw launch
 
 struct DrawPayload {
-    static constexpr bool kMaxMode = false, kDrawMode = true, kMapMode = false;
+    static constexpr ProgramKind kKind = ProgramKind::Draw;
     static constexpr int kLevelSlot = kStatSum;
     const bool no_prune;
     const int64_t *s_off;
@@ -2549,7 +2550,7 @@ struct DrawPayload {
 // its intermediates and the argmax tables of its max steps -, decoded wave by wave by map_traceback_kernel into the requests' slices of
 // d_codes, downloaded chunk by chunk.
 struct MapPayload {
-    static constexpr bool kMaxMode = false, kDrawMode = false, kMapMode = true;
+    static constexpr ProgramKind kKind = ProgramKind::Map;
     static constexpr int kLevelSlot = kStatMap;
     const bool no_prune;
     const int64_t B;
@@ -2719,7 +2720,7 @@ extern "C" int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int
         rq.qvars = q_vars + q_off[b];
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
-        rq.raw = true;
+        rq.kind = ProgramKind::Raw;
         if (rq.nq < 0 || rq.ne < 0 || !request_is_valid(h->net, rq)) { h->err = "request " + std::to_string(b) + ": " + (rq.nq < 0 || rq.ne < 0 ? std::string("negative count") : validate_request(h->net, rq)); return MIBN_E_ARG; }
         if (rq.nq && (!acc_base || !acc_stride)) { h->err = "expect: acc_base / acc_stride missing"; return MIBN_E_ARG; }
         int64_t cells = 1;

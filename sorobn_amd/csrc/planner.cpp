@@ -286,7 +286,7 @@ void Network::set_hints(int32_t n_hints, const int32_t *priorities) {
 }
 
 bool request_is_valid(const Network &net, const Request &rq) {
-    if (rq.nq < ((rq.raw || rq.map_mode) ? 0 : 1)) return false;
+    if (rq.nq < (allows_no_query(rq.kind) ? 0 : 1)) return false;
     uint64_t seen[kWords];  // (only the words the network uses: a batch validates 100 k requests on one thread)
     for (int k = 0; k < net.nw; ++k) seen[k] = 0;
     for (int i = 0; i < rq.nq + rq.ne; ++i) {
@@ -312,7 +312,7 @@ std::string validate_mpe_request(const Network &net, const Request &rq) {
 
 std::string validate_request(const Network &net, const Request &rq) {
     if (request_is_valid(net, rq)) return "";
-    if (rq.nq < ((rq.raw || rq.map_mode) ? 0 : 1)) return "At least one query variable has to be specified";  // bayes_net.py:840-841
+    if (rq.nq < (allows_no_query(rq.kind) ? 0 : 1)) return "At least one query variable has to be specified";  // bayes_net.py:840-841
     Bits seen;
     for (int i = 0; i < rq.nq; ++i) {
         int v = rq.qvars[i];
@@ -537,104 +537,39 @@ std::string emit_error_message(int err) {
     return "planner error " + std::to_string(err);
 }
 
-// Max program of one request (planner.h, "MAX programs"): the factors of emit_begin (every CPT, evidence-sliced), one GENERIC step
-// per variable of `order` with its argmax table, the final product of the remaining scalars, then the traceback record.  Host
-// only - the device planner does not emit max programs.  Returns 0 or a kEmitErr*.
-static int emit_run_max(const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq, const int32_t *order,
-                        int n_order, int64_t &argmax_cells) {
-    EmitNet en = en_sum;  // every step GENERIC: no output is ever "big" enough for a streaming form, no fused or swept variables
-    en.big_iters = std::numeric_limits<int64_t>::max();
-    en.outer = en.fuse = en.chain = en.sweep = 0;
-    PF *pool = S.pool;
-    S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
-    Emitter em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr};
-    for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
-    const size_t count_pos = prog.size;
+namespace {
+
+// ------------------------------------------------------------------------------------ step-wise programs
+// Max, draw and map programs (planner.h) are one algorithm: one GENERIC step per eliminated variable, in order, the final product of
+// the scalars that remain, then a record.  Host only - the device planner does not emit them.
+
+// The head of the record that follows the steps: its entry counts, then the evidence.  (ecodes may be null: plan-only statistics.)
+template <class Buf>
+void put_record_head(Buf &prog, std::initializer_list<uint32_t> counts, int32_t ne, const int32_t *evars, const int32_t *ecodes) {
+    for (uint32_t c : counts) prog.push(c);
+    prog.push((uint32_t)ne);
+    for (int32_t i = 0; i < ne; ++i) {
+        prog.push((uint32_t)evars[i]);
+        prog.push((uint32_t)(ecodes ? ecodes[i] : 0));
+    }
+}
+
+// The program of a request that runs nothing (evidence outside its domain): zero steps - the result stays all-zero - and, for a
+// step-wise kind, a record without entries (m = 0 reads as zero probability).
+void put_empty_program(ProgBuf &prog, ProgramKind kind, int32_t ne, const int32_t *evars, const int32_t *ecodes) {
     prog.push(0);
-    const double steps0 = st.n_steps;
-    std::vector<char> alive((size_t)S.pool_cap, 0);
-    for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
-    const PF **ins = S.ins;
-    // pre-multiply the smallest tables while more than kMaxIn remain (product-only steps, no argmax)
-    auto limit = [&](int n_in) -> int {
-        while (n_in > kMaxIn && !em.err) {
-            if (S.n_pool + 1 > S.pool_cap) { em.err = kEmitErrPool; return 0; }
-            std::stable_sort(ins, ins + n_in, [](const PF *a, const PF *b) { return a->cells < b->cells; });
-            PF &o = pool[S.n_pool++];
-            pf_reset(o);
-            em.emit(ins, kMaxIn, nullptr, 0, false, 0, o, false);
-            for (int k = kMaxIn; k < n_in; ++k) ins[k - kMaxIn] = ins[k];
-            n_in -= kMaxIn;
-            ins[n_in++] = &o;
-        }
-        return n_in;
-    };
-    struct Rec { uint64_t off; int32_t x, n; int32_t vars[kRawAxes]; int64_t strides[kRawAxes]; };
-    std::vector<Rec> recs;
-    recs.reserve((size_t)n_order);
-    for (int i = 0; i < n_order; ++i) {
-        const int32_t x = order[i];
-        int n_in = 0;
-        for (int idx = 0; idx < S.n_pool; ++idx)
-            if (alive[(size_t)idx] && pool[idx].scope.test(x)) { ins[n_in++] = &pool[idx]; alive[(size_t)idx] = 0; }
-        if (!n_in) continue;  // (cannot happen: x's own CPT mentions it)
-        n_in = limit(n_in);
-        if (em.err) return em.err;
-        // the argmax table is allocated before the step's output - and before its inputs go back to the arena: the kernel writes it
-        // while it reads them
-        Bits u;
-        u.nw = en.nw;
-        for (int j = 0; j < n_in; ++j) u.or_(ins[j]->scope);
-        u.clr(x);
-        double cells = 1;
-        u.for_each([&](int v) { cells *= en.card[v]; });
-        if (cells >= (double)(1ll << 31)) return kEmitErrCells;
-        const int64_t am_cells = ((int64_t)cells * 2 + 7) / 8;  // uint16 entries, in doubles
-        const int64_t am_off = em.arena.alloc(am_cells);
-        argmax_cells += (am_cells + 15) & ~int64_t(15);
-        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
-        PF &o = pool[S.n_pool++];
-        pf_reset(o);
-        const size_t step_base = prog.size;
-        em.emit(ins, n_in, &x, 1, false, 0, o, false);
-        if (em.err) return em.err;
-        uint32_t *w = prog.data + step_base;
-        w[1] |= kFlagMax << 16;
-        w[7] = (uint32_t)((uint64_t)am_off & 0xffffffffu);
-        w[8] = (uint32_t)((uint64_t)am_off >> 32);
-        w[9] += (uint32_t)(((int64_t)cells + 15) / 16);  // (the argmax bytes, in the step's units of 32 bytes)
-        st.alg_bytes += 2.0 * cells;
-        Rec r;
-        r.off = (uint64_t)am_off;
-        r.x = x;
-        r.n = o.n;
-        for (int a = 0; a < o.n; ++a) { r.vars[a] = o.vars[a]; r.strides[a] = o.strides[a]; }
-        recs.push_back(r);
-        alive[(size_t)(S.n_pool - 1)] = 1;
-    }
-    // m = the product of what is left (all scalars), one cell, not normalised
-    st.out_cells = 1;
-    int n_in = 0;
-    for (int idx = 0; idx < S.n_pool; ++idx)
-        if (alive[(size_t)idx]) ins[n_in++] = &pool[idx];
-    n_in = limit(n_in);
-    if (em.err) return em.err;
-    if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
-    PF &o = pool[S.n_pool++];
-    pf_reset(o);
-    em.emit(ins, n_in, nullptr, 0, true, rq.out_off, o, false);
-    if (em.err) return em.err;
-    prog.data[count_pos] = (uint32_t)(st.n_steps - steps0);
-    st.arena_cells = std::max(st.arena_cells, em.arena.top);
-    // traceback record
-    prog.push((uint32_t)recs.size());
-    prog.push((uint32_t)rq.ne);
-    for (int i = 0; i < rq.ne; ++i) {
-        prog.push((uint32_t)rq.evars[i]);
-        prog.push((uint32_t)(rq.ecodes ? rq.ecodes[i] : 0));
-    }
+    if (kind == ProgramKind::Draw) put_record_head(prog, {0u, 0u}, ne, evars, ecodes);
+    else if (step_wise(kind)) put_record_head(prog, {0u}, ne, evars, ecodes);
+}
+
+// An argmax table and what the reverse walk needs to index it: the output axes of its step.
+struct Trace { uint64_t off; int32_t x, n; int32_t vars[kRawAxes]; int64_t strides[kRawAxes]; };
+
+// TRACEBACK record: per MAX step, last eliminated first.
+void put_traceback(EmitBuf &prog, const std::vector<Trace> &recs, const Request &rq) {
+    put_record_head(prog, {(uint32_t)recs.size()}, rq.ne, rq.evars, rq.ecodes);
     for (size_t k = recs.size(); k-- > 0;) {
-        const Rec &r = recs[k];
+        const Trace &r = recs[k];
         prog.push((uint32_t)(r.off & 0xffffffffu));
         prog.push((uint32_t)(r.off >> 32));
         prog.push((uint32_t)r.x);
@@ -644,98 +579,170 @@ static int emit_run_max(const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, Em
             prog.push((uint32_t)r.strides[a]);
         }
     }
+}
+
+struct StepEmitter {
+    const EmitNet en;  // every step GENERIC: no output is ever "big" enough for a streaming form, no fused or swept variables
+    EmitScratch &S;
+    EmitBuf &prog;
+    EmitStats &st;
+    Emitter em;
+    const bool keep;  // no output ever goes back to the arena (draw programs read every input again)
+    const size_t count_pos;
+    const double steps0;
+    std::vector<char> alive;
+    const PF **const ins;  // the inputs of the step emitted last
+
+    static EmitNet generic_only(EmitNet en) {
+        en.big_iters = std::numeric_limits<int64_t>::max();
+        en.outer = en.fuse = en.chain = en.sweep = 0;
+        return en;
+    }
+    // Layout keys from the order(s) - a later elimination is a faster axis; the second order continues the first - and the count word.
+    StepEmitter(const EmitNet &en_sum, EmitScratch &S_, EmitBuf &prog_, EmitStats &st_, bool keep_, const int32_t *order, int n_order,
+                const int32_t *order2 = nullptr, int n_order2 = 0)
+        : en(generic_only(en_sum)), S(S_), prog(prog_), st(st_), em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr}, keep(keep_),
+          count_pos(prog.size), steps0(st.n_steps), alive((size_t)S.pool_cap, 0), ins(S.ins) {
+        S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
+        for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
+        for (int i = 0; i < n_order2; ++i) S.key[order2[i]] = (double)(n_order + i);
+        prog.push(0);
+        for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
+    }
+    // a fresh pool entry for a step's output, or null (em.err set)
+    PF *new_output() {
+        if (S.n_pool + 1 > S.pool_cap) { em.err = kEmitErrPool; return nullptr; }
+        PF &o = S.pool[S.n_pool++];
+        pf_reset(o);
+        return &o;
+    }
+    // with alloc = 0 the emitter never hands an output's cells back when the table is consumed
+    void emitted(PF &o) { if (keep) o.alloc = 0; }
+    // pre-multiply the smallest tables while more than kMaxIn remain (product-only steps, never flagged)
+    int limit(int n_in) {
+        while (n_in > kMaxIn && !em.err) {
+            PF *o = new_output();
+            if (!o) return 0;
+            std::stable_sort(ins, ins + n_in, [](const PF *a, const PF *b) { return a->cells < b->cells; });
+            em.emit(ins, kMaxIn, nullptr, 0, false, 0, *o, false);
+            emitted(*o);
+            for (int k = kMaxIn; k < n_in; ++k) ins[k - kMaxIn] = ins[k];
+            n_in -= kMaxIn;
+            ins[n_in++] = o;
+        }
+        return n_in;
+    }
+    // the live factors that mention x (all of them: x < 0), consumed
+    int gather(int32_t x) {
+        int n_in = 0;
+        for (int idx = 0; idx < S.n_pool; ++idx)
+            if (alive[(size_t)idx] && (x < 0 || S.pool[idx].scope.test(x))) { ins[n_in++] = &S.pool[idx]; alive[(size_t)idx] = 0; }
+        return n_in;
+    }
+    // The step that eliminates x.  Returns its number of inputs (ins[0 .. n)), or 0: nothing mentions x, or em.err is set.  With
+    // `trace` the step maximises: its argmax table is allocated before the step's output - and before its inputs go back to the arena:
+    // the kernel writes it while it reads them -, the step is flagged MAX and *trace is its traceback entry.
+    int eliminate(int32_t x, Trace *trace = nullptr, int64_t *argmax_cells = nullptr) {
+        int n_in = gather(x);
+        if (!n_in) return 0;  // (cannot happen: x's own CPT mentions it)
+        n_in = limit(n_in);
+        if (em.err) return 0;
+        double cells = 1;
+        int64_t am_off = 0;
+        if (trace) {
+            Bits u;
+            u.nw = en.nw;
+            for (int j = 0; j < n_in; ++j) u.or_(ins[j]->scope);
+            u.clr(x);
+            u.for_each([&](int v) { cells *= en.card[v]; });
+            if (cells >= (double)(1ll << 31)) { em.err = kEmitErrCells; return 0; }
+            const int64_t am_cells = ((int64_t)cells * 2 + 7) / 8;  // uint16 entries, in doubles
+            am_off = em.arena.alloc(am_cells);
+            *argmax_cells += (am_cells + 15) & ~int64_t(15);
+        }
+        PF *o = new_output();
+        if (!o) return 0;
+        const size_t step_base = prog.size;
+        em.emit(ins, n_in, &x, 1, false, 0, *o, false);
+        if (em.err) return 0;
+        emitted(*o);
+        if (trace) {
+            uint32_t *w = prog.data + step_base;
+            w[1] |= kFlagMax << 16;
+            w[7] = (uint32_t)((uint64_t)am_off & 0xffffffffu);
+            w[8] = (uint32_t)((uint64_t)am_off >> 32);
+            w[9] += (uint32_t)(((int64_t)cells + 15) / 16);  // (the argmax bytes, in the step's units of 32 bytes)
+            st.alg_bytes += 2.0 * cells;
+            trace->off = (uint64_t)am_off;
+            trace->x = x;
+            trace->n = o->n;
+            for (int a = 0; a < o->n; ++a) { trace->vars[a] = o->vars[a]; trace->strides[a] = o->strides[a]; }
+        }
+        alive[(size_t)(S.n_pool - 1)] = 1;
+        return n_in;
+    }
+    // The FINAL step - the product of what is left (all scalars), one cell, never normalised by a max kernel and flagged RAW for the
+    // sum kernels - then the count word and the arena need.  `optional`: nothing left, no step (the empty product).  Returns em.err.
+    int finish(int64_t out_off, bool raw, bool optional) {
+        st.out_cells = 1;
+        int n_in = gather(-1);
+        if (n_in || !optional) {
+            n_in = limit(n_in);
+            if (em.err) return em.err;
+            PF *o = new_output();
+            if (!o) return em.err;
+            const size_t step_base = prog.size;
+            em.emit(ins, n_in, nullptr, 0, true, out_off, *o, false);
+            if (em.err) return em.err;
+            if (raw) prog.data[step_base + 1] |= kFlagRaw << 16;
+        }
+        prog.data[count_pos] = (uint32_t)(st.n_steps - steps0);
+        st.arena_cells = std::max(st.arena_cells, em.arena.top);
+        return 0;
+    }
+};
+
+// Max program (planner.h, "MAX programs"): the factors of emit_begin (every CPT, evidence-sliced), one MAX step per variable of
+// `order`, the FINAL step - always, never RAW -, the traceback record.  Returns 0 or a kEmitErr*.
+int emit_run_max(const EmitNet &en, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq, const std::vector<int32_t> &order,
+                 int64_t &argmax_cells) {
+    StepEmitter se(en, S, prog, st, false, order.data(), (int)order.size());
+    std::vector<Trace> recs;
+    recs.reserve(order.size());
+    for (const int32_t x : order) {
+        Trace t;
+        if (se.eliminate(x, &t, &argmax_cells)) recs.push_back(t);
+        if (se.em.err) return se.em.err;
+    }
+    if (int e = se.finish(rq.out_off, false, false)) return e;
+    put_traceback(prog, recs, rq);
     return 0;
 }
 
-// Draw program of one request (planner.h, "DRAW programs"): the factors of emit_begin, one GENERIC sum step per variable of `order`
-// whose inputs all stay in the arena, the final product of the remaining scalars (RAW: the mass of the evidence), then the draw
-// record - backward entries for the eliminated variables, forward entries for the pruned ones.  Host only.  Returns 0 or a kEmitErr*.
-static int emit_run_draw(const Network &net, const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq,
-                         const int32_t *order, int n_order, int64_t &kept_cells) {
-    EmitNet en = en_sum;  // every step GENERIC, as in a max program: the traceback wants one step per variable
-    en.big_iters = std::numeric_limits<int64_t>::max();
-    en.outer = en.fuse = en.chain = en.sweep = 0;
-    PF *pool = S.pool;
-    S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
-    Emitter em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr};
-    for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
-    const size_t count_pos = prog.size;
-    prog.push(0);
-    const double steps0 = st.n_steps;
-    std::vector<char> alive((size_t)S.pool_cap, 0);
-    for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
-    const PF **ins = S.ins;
-    // an output keeps its arena cells for good: with alloc = 0 the emitter never hands them back when the table is consumed
-    auto keep = [&](PF &o) { o.alloc = 0; };
-    auto limit = [&](int n_in) -> int {
-        while (n_in > kMaxIn && !em.err) {
-            if (S.n_pool + 1 > S.pool_cap) { em.err = kEmitErrPool; return 0; }
-            std::stable_sort(ins, ins + n_in, [](const PF *a, const PF *b) { return a->cells < b->cells; });
-            PF &o = pool[S.n_pool++];
-            pf_reset(o);
-            em.emit(ins, kMaxIn, nullptr, 0, false, 0, o, false);
-            keep(o);
-            for (int k = kMaxIn; k < n_in; ++k) ins[k - kMaxIn] = ins[k];
-            n_in -= kMaxIn;
-            ins[n_in++] = &o;
-        }
-        return n_in;
-    };
+// Draw program (planner.h, "DRAW programs"): the factors of emit_begin, one sum step per variable of `order` with every output kept,
+// the FINAL step (RAW: the mass of the evidence) if anything is left, the draw record - backward entries for the eliminated
+// variables, forward entries for the pruned ones.  Returns 0 or a kEmitErr*.
+int emit_run_draw(const Network &net, const EmitNet &en, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq,
+                  const std::vector<int32_t> &order, int64_t &kept_cells) {
+    StepEmitter se(en, S, prog, st, true, order.data(), (int)order.size());
     struct Rec { int32_t x, n_in; const PF *in[kMaxIn]; };
     std::vector<Rec> recs;
-    recs.reserve((size_t)n_order);
-    for (int i = 0; i < n_order; ++i) {
-        const int32_t x = order[i];
-        int n_in = 0;
-        for (int idx = 0; idx < S.n_pool; ++idx)
-            if (alive[(size_t)idx] && pool[idx].scope.test(x)) { ins[n_in++] = &pool[idx]; alive[(size_t)idx] = 0; }
-        if (!n_in) continue;  // (cannot happen: x's own CPT mentions it)
-        n_in = limit(n_in);
-        if (em.err) return em.err;
-        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
-        PF &o = pool[S.n_pool++];
-        pf_reset(o);
-        em.emit(ins, n_in, &x, 1, false, 0, o, false);
-        if (em.err) return em.err;
-        keep(o);
+    recs.reserve(order.size());
+    for (const int32_t x : order) {
         Rec r;
         r.x = x;
-        r.n_in = n_in;
-        for (int j = 0; j < n_in; ++j) r.in[j] = ins[j];
-        recs.push_back(r);
-        alive[(size_t)(S.n_pool - 1)] = 1;
+        if ((r.n_in = se.eliminate(x))) {
+            std::copy(se.ins, se.ins + r.n_in, r.in);
+            recs.push_back(r);
+        }
+        if (se.em.err) return se.em.err;
     }
-    // the mass of the evidence: the product of what is left (all scalars), one cell, not normalised.  Nothing left (pruned, no
-    // evidence): no step, the empty product
-    st.out_cells = 1;
-    int n_in = 0;
-    for (int idx = 0; idx < S.n_pool; ++idx)
-        if (alive[(size_t)idx]) ins[n_in++] = &pool[idx];
-    if (n_in) {
-        n_in = limit(n_in);
-        if (em.err) return em.err;
-        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
-        PF &o = pool[S.n_pool++];
-        pf_reset(o);
-        const size_t step_base = prog.size;
-        em.emit(ins, n_in, nullptr, 0, true, rq.out_off, o, false);
-        if (em.err) return em.err;
-        prog.data[step_base + 1] |= kFlagRaw << 16;
-    }
-    prog.data[count_pos] = (uint32_t)(st.n_steps - steps0);
-    st.arena_cells = std::max(st.arena_cells, em.arena.top);
-    kept_cells += em.arena.top;
-    // draw record
+    if (int e = se.finish(rq.out_off, true, true)) return e;
+    kept_cells += se.em.arena.top;
     std::vector<int32_t> fwd;
     for (int v = 0; v < net.n_vars; ++v)
         if (!S.rel.test(v) && net.card[v] > 1) fwd.push_back(v);
-    prog.push((uint32_t)recs.size());
-    prog.push((uint32_t)fwd.size());
-    prog.push((uint32_t)rq.ne);
-    for (int i = 0; i < rq.ne; ++i) {
-        prog.push((uint32_t)rq.evars[i]);
-        prog.push((uint32_t)(rq.ecodes ? rq.ecodes[i] : 0));
-    }
+    put_record_head(prog, {(uint32_t)recs.size(), (uint32_t)fwd.size()}, rq.ne, rq.evars, rq.ecodes);
     for (size_t k = recs.size(); k-- > 0;) {
         const Rec &r = recs[k];
         prog.push((uint32_t)r.x);
@@ -754,7 +761,7 @@ static int emit_run_draw(const Network &net, const EmitNet &en_sum, EmitScratch 
                 if (f.vars[a] != r.x) { prog.push((uint32_t)f.vars[a]); prog.push((uint32_t)f.strides[a]); }
         }
     }
-    for (int32_t v : fwd) {
+    for (int32_t v : fwd) {  // (from the network, not the pool: a pruned variable has no factor)
         const std::vector<int32_t> &sc = net.scope[v];  // [*parents, v]
         const uint64_t off = (uint64_t)net.pool_off[v] | kConstFlag;
         uint32_t n_ax = 0;
@@ -772,178 +779,74 @@ static int emit_run_draw(const Network &net, const EmitNet &en_sum, EmitScratch 
     return 0;
 }
 
-// Map program of one request (planner.h, "MAP programs"): the factors of emit_begin for the query set M, one GENERIC sum step per
-// variable of `order` (the hidden variables; intermediates released as usual), then one GENERIC max step with its argmax table per
-// multi-state variable of M - fewest output cells first, lowest id on a tie -, the final product of the remaining scalars (RAW),
-// the traceback record of the max steps and the gather list (M in the caller's order).  Host only.  Returns 0 or a kEmitErr*.
-static int emit_run_map(const EmitNet &en_sum, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq, const int32_t *order,
-                        int n_order, int64_t &argmax_cells) {
-    EmitNet en = en_sum;  // every step GENERIC, as in a max program
-    en.big_iters = std::numeric_limits<int64_t>::max();
-    en.outer = en.fuse = en.chain = en.sweep = 0;
-    PF *pool = S.pool;
-    // the max order depends on the scopes alone: found on bit sets first, so that the layout keys of both phases are known before
-    // the first step is emitted (longest-living variable fastest: M after every hidden variable, in its own elimination order)
-    std::vector<int32_t> max_order;
-    {
-        std::vector<Bits> sc;
-        for (int idx = 0; idx < S.n0; ++idx) sc.push_back(pool[idx].scope);
-        std::vector<char> live(sc.size(), 1);
-        auto joined = [&](int x) {  // scope of the step that eliminates x (x itself excluded)
-            Bits u;
-            u.nw = en.nw;
-            for (size_t k = 0; k < sc.size(); ++k)
-                if (live[k] && sc[k].test(x)) u.or_(sc[k]);
-            u.clr(x);
-            return u;
-        };
-        auto eliminate = [&](int x) {
-            const Bits u = joined(x);
-            bool found = false;
-            for (size_t k = 0; k < sc.size(); ++k)
-                if (live[k] && sc[k].test(x)) { live[k] = 0; found = true; }
-            if (found) { sc.push_back(u); live.push_back(1); }
-        };
-        for (int i = 0; i < n_order; ++i) eliminate(order[i]);
-        std::vector<int32_t> left;
-        for (int i = 0; i < rq.nq; ++i)
-            if (en.card[rq.qvars[i]] > 1) left.push_back(rq.qvars[i]);
-        std::sort(left.begin(), left.end());
-        while (!left.empty()) {
-            size_t pick = 0;
-            double best = 0;
-            for (size_t k = 0; k < left.size(); ++k) {
-                double cells = 1;
-                joined(left[k]).for_each([&](int v) { cells *= en.card[v]; });
-                if (k == 0 || cells < best) { best = cells; pick = k; }  // (ascending ids: a tie keeps the lowest)
-            }
-            max_order.push_back(left[pick]);
-            eliminate(left[pick]);
-            left.erase(left.begin() + (ptrdiff_t)pick);
-        }
-    }
-    S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
-    Emitter em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr};
-    for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
-    for (size_t i = 0; i < max_order.size(); ++i) S.key[max_order[i]] = (double)(n_order + (int)i);
-    const size_t count_pos = prog.size;
-    prog.push(0);
-    const double steps0 = st.n_steps;
-    std::vector<char> alive((size_t)S.pool_cap, 0);
-    for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
-    const PF **ins = S.ins;
-    auto limit = [&](int n_in) -> int {  // product-only steps above kMaxIn inputs: unflagged in either phase
-        while (n_in > kMaxIn && !em.err) {
-            if (S.n_pool + 1 > S.pool_cap) { em.err = kEmitErrPool; return 0; }
-            std::stable_sort(ins, ins + n_in, [](const PF *a, const PF *b) { return a->cells < b->cells; });
-            PF &o = pool[S.n_pool++];
-            pf_reset(o);
-            em.emit(ins, kMaxIn, nullptr, 0, false, 0, o, false);
-            for (int k = kMaxIn; k < n_in; ++k) ins[k - kMaxIn] = ins[k];
-            n_in -= kMaxIn;
-            ins[n_in++] = &o;
-        }
-        return n_in;
-    };
-    auto gather = [&](int32_t x) -> int {
-        int n_in = 0;
-        for (int idx = 0; idx < S.n_pool; ++idx)
-            if (alive[(size_t)idx] && pool[idx].scope.test(x)) { ins[n_in++] = &pool[idx]; alive[(size_t)idx] = 0; }
-        return n_in ? limit(n_in) : 0;
-    };
-    // sum phase
-    for (int i = 0; i < n_order; ++i) {
-        const int32_t x = order[i];
-        const int n_in = gather(x);
-        if (em.err) return em.err;
-        if (!n_in) continue;  // (cannot happen: x's own CPT mentions it)
-        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
-        PF &o = pool[S.n_pool++];
-        pf_reset(o);
-        em.emit(ins, n_in, &x, 1, false, 0, o, false);
-        if (em.err) return em.err;
-        alive[(size_t)(S.n_pool - 1)] = 1;
-    }
-    // max phase
-    struct Rec { uint64_t off; int32_t x, n; int32_t vars[kRawAxes]; int64_t strides[kRawAxes]; };
-    std::vector<Rec> recs;
-    recs.reserve(max_order.size());
-    for (const int32_t x : max_order) {
-        const int n_in = gather(x);
-        if (em.err) return em.err;
-        if (!n_in) continue;  // (cannot happen: x's own CPT is relevant)
-        // the argmax table is allocated before the step's output - and before its inputs go back to the arena (emit_run_max)
+// The max phase's order of a map program: after the sum phase over `order`, the multi-state MAP variable whose elimination step has
+// the fewest output cells goes first (lowest id on a tie).  It depends on the scopes alone and is found on bit sets, so that the
+// layout keys of both phases are known before the first step is emitted.
+std::vector<int32_t> map_max_order(const EmitNet &en, const EmitScratch &S, const Request &rq, const std::vector<int32_t> &order) {
+    std::vector<Bits> sc;
+    for (int idx = 0; idx < S.n0; ++idx) sc.push_back(S.pool[idx].scope);
+    std::vector<char> live(sc.size(), 1);
+    auto joined = [&](int x) {  // scope of the step that eliminates x (x itself excluded)
         Bits u;
         u.nw = en.nw;
-        for (int j = 0; j < n_in; ++j) u.or_(ins[j]->scope);
+        for (size_t k = 0; k < sc.size(); ++k)
+            if (live[k] && sc[k].test(x)) u.or_(sc[k]);
         u.clr(x);
-        double cells = 1;
-        u.for_each([&](int v) { cells *= en.card[v]; });
-        if (cells >= (double)(1ll << 31)) return kEmitErrCells;
-        const int64_t am_cells = ((int64_t)cells * 2 + 7) / 8;  // uint16 entries, in doubles
-        const int64_t am_off = em.arena.alloc(am_cells);
-        argmax_cells += (am_cells + 15) & ~int64_t(15);
-        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
-        PF &o = pool[S.n_pool++];
-        pf_reset(o);
-        const size_t step_base = prog.size;
-        em.emit(ins, n_in, &x, 1, false, 0, o, false);
-        if (em.err) return em.err;
-        uint32_t *w = prog.data + step_base;
-        w[1] |= kFlagMax << 16;
-        w[7] = (uint32_t)((uint64_t)am_off & 0xffffffffu);
-        w[8] = (uint32_t)((uint64_t)am_off >> 32);
-        w[9] += (uint32_t)(((int64_t)cells + 15) / 16);  // (the argmax bytes, in the step's units of 32 bytes)
-        st.alg_bytes += 2.0 * cells;
-        Rec r;
-        r.off = (uint64_t)am_off;
-        r.x = x;
-        r.n = o.n;
-        for (int a = 0; a < o.n; ++a) { r.vars[a] = o.vars[a]; r.strides[a] = o.strides[a]; }
-        recs.push_back(r);
-        alive[(size_t)(S.n_pool - 1)] = 1;
-    }
-    // m = the product of what is left (all scalars), one cell, never normalised.  Nothing left (M empty, no evidence, pruned): no
-    // step, the empty product
-    st.out_cells = 1;
-    int n_in = 0;
-    for (int idx = 0; idx < S.n_pool; ++idx)
-        if (alive[(size_t)idx]) ins[n_in++] = &pool[idx];
-    if (n_in) {
-        n_in = limit(n_in);
-        if (em.err) return em.err;
-        if (S.n_pool + 1 > S.pool_cap) return kEmitErrPool;
-        PF &o = pool[S.n_pool++];
-        pf_reset(o);
-        const size_t step_base = prog.size;
-        em.emit(ins, n_in, nullptr, 0, true, rq.out_off, o, false);
-        if (em.err) return em.err;
-        prog.data[step_base + 1] |= kFlagRaw << 16;
-    }
-    prog.data[count_pos] = (uint32_t)(st.n_steps - steps0);
-    st.arena_cells = std::max(st.arena_cells, em.arena.top);
-    // traceback record, then the gather list
-    prog.push((uint32_t)recs.size());
-    prog.push((uint32_t)rq.ne);
-    for (int i = 0; i < rq.ne; ++i) {
-        prog.push((uint32_t)rq.evars[i]);
-        prog.push((uint32_t)(rq.ecodes ? rq.ecodes[i] : 0));
-    }
-    for (size_t k = recs.size(); k-- > 0;) {
-        const Rec &r = recs[k];
-        prog.push((uint32_t)(r.off & 0xffffffffu));
-        prog.push((uint32_t)(r.off >> 32));
-        prog.push((uint32_t)r.x);
-        prog.push((uint32_t)r.n);
-        for (int a = 0; a < r.n; ++a) {
-            prog.push((uint32_t)r.vars[a]);
-            prog.push((uint32_t)r.strides[a]);
+        return u;
+    };
+    auto eliminate = [&](int x) {
+        const Bits u = joined(x);
+        bool found = false;
+        for (size_t k = 0; k < sc.size(); ++k)
+            if (live[k] && sc[k].test(x)) { live[k] = 0; found = true; }
+        if (found) { sc.push_back(u); live.push_back(1); }
+    };
+    for (const int32_t x : order) eliminate(x);
+    std::vector<int32_t> left, max_order;
+    for (int i = 0; i < rq.nq; ++i)
+        if (en.card[rq.qvars[i]] > 1) left.push_back(rq.qvars[i]);
+    std::sort(left.begin(), left.end());
+    while (!left.empty()) {
+        size_t pick = 0;
+        double best = 0;
+        for (size_t k = 0; k < left.size(); ++k) {
+            double cells = 1;
+            joined(left[k]).for_each([&](int v) { cells *= en.card[v]; });
+            if (k == 0 || cells < best) { best = cells; pick = k; }  // (ascending ids: a tie keeps the lowest)
         }
+        max_order.push_back(left[pick]);
+        eliminate(left[pick]);
+        left.erase(left.begin() + (ptrdiff_t)pick);
     }
+    return max_order;
+}
+
+// Map program (planner.h, "MAP programs"): the factors of emit_begin for the query set M, one sum step per variable of `order` (the
+// hidden variables; intermediates released as usual), one MAX step per multi-state variable of M, the FINAL step (RAW) if anything is
+// left, the traceback record of the max steps and the gather list (M in the caller's order).  Returns 0 or a kEmitErr*.
+int emit_run_map(const EmitNet &en, EmitScratch &S, EmitBuf &prog, EmitStats &st, const Request &rq, const std::vector<int32_t> &order,
+                 int64_t &argmax_cells) {
+    const std::vector<int32_t> max_order = map_max_order(en, S, rq, order);
+    StepEmitter se(en, S, prog, st, false, order.data(), (int)order.size(), max_order.data(), (int)max_order.size());
+    for (const int32_t x : order) {
+        se.eliminate(x);
+        if (se.em.err) return se.em.err;
+    }
+    std::vector<Trace> recs;
+    recs.reserve(max_order.size());
+    for (const int32_t x : max_order) {
+        Trace t;
+        if (se.eliminate(x, &t, &argmax_cells)) recs.push_back(t);
+        if (se.em.err) return se.em.err;
+    }
+    if (int e = se.finish(rq.out_off, true, true)) return e;
+    put_traceback(prog, recs, rq);
     prog.push((uint32_t)rq.nq);
     for (int i = 0; i < rq.nq; ++i) prog.push((uint32_t)rq.qvars[i]);
     return 0;
 }
+
+}  // namespace
 
 // One request on the host: the shared emission (emit_core.h) around the choice of the elimination order.
 static std::string plan_request_rec(const Network &net, const Request &rq, ProgBuf &prog, PlanStats &st, PlanRecord *rec) {
@@ -974,9 +877,8 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     // (a max program has no query variable and never prunes: every non-evidence variable is maximised out)
     // (a draw program has no query variable either, and prunes to the ancestors of the evidence unless told not to)
     // (a map program's query set is M: relevant = M | event | ancestors, hidden = what the sum phase eliminates)
-    const bool mx = rq.max_mode, dr = rq.draw_mode, mp = rq.map_mode;
-    const int nq = (mx || dr) ? 0 : rq.nq;
-    const bool no_prune = mx || rq.no_prune;
+    const int nq = takes_query(rq.kind) ? rq.nq : 0;
+    const bool no_prune = never_prunes(rq.kind) || rq.no_prune;
     if (int e = emit_begin(en, ES, nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, no_prune)) return emit_error_message(e);
     const Bits &hidden = ES.hidden;
 
@@ -992,10 +894,10 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
         PROF(1);
         OrderScratch &OS = order_scratch();
         OrderNet on = net.order_view();
-        if (mx || dr || mp) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms max / draw programs do not use)
+        if (step_wise(rq.kind)) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms these programs do not use)
         order_search(on, OS, nq, rq.qvars, rq.ne, rq.evars, no_prune);
         best.assign(OS.best, OS.best + OS.n_best);
-        if (!mx && !dr && !mp && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
+        if (!step_wise(rq.kind) && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
     } else if (hidden.any()) {
         std::vector<Bits> &scopes = S.scopes;
         std::vector<double> &scells = S.scope_cells;
@@ -1059,23 +961,16 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     const size_t start_words = prog.size;
     const EmitStats es0 = es;
     const size_t rec_consts0 = rec ? rec->consts.size() : 0, rec_finals0 = rec ? rec->finals.size() : 0;
-    if (mx) {
-        const int e = emit_run_max(en, ES, eb, es, rq, best.data(), (int)best.size(), st.argmax_cells);
+    auto done = [&](int e) {  // the emission's statistics go back to the caller's
         st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
         st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
         return emit_error_message(e);
-    }
-    if (dr) {
-        const int e = emit_run_draw(net, en, ES, eb, es, rq, best.data(), (int)best.size(), st.kept_cells);
-        st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
-        st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
-        return emit_error_message(e);
-    }
-    if (mp) {
-        const int e = emit_run_map(en, ES, eb, es, rq, best.data(), (int)best.size(), st.argmax_cells);
-        st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
-        st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
-        return emit_error_message(e);
+    };
+    switch (rq.kind) {
+        case ProgramKind::Max: return done(emit_run_max(en, ES, eb, es, rq, best, st.argmax_cells));
+        case ProgramKind::Draw: return done(emit_run_draw(net, en, ES, eb, es, rq, best, st.kept_cells));
+        case ProgramKind::Map: return done(emit_run_map(en, ES, eb, es, rq, best, st.argmax_cells));
+        case ProgramKind::Sum: case ProgramKind::Raw: break;
     }
     int e = emit_run(en, ES, eb, es, rec, rq.nq, rq.qvars, rq.out_off, best.data(), (int)best.size() MIBN_PROF_PASS);
     if (!e && !second.empty()) {
@@ -1110,7 +1005,7 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
             *st.order = second;
         }
     }
-    if (!e && rq.raw) {
+    if (!e && rq.kind == ProgramKind::Raw) {
         // the FINAL step - the program's last - keeps its table as it is: P(q, e), not normalised
         const uint32_t *p0 = prog.data + start_words;
         size_t off = start_words + 1, last = 0;
@@ -1118,9 +1013,7 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
         if (!p0[0] || !((prog.data[last + 1] >> 16) & kFlagFinal)) return "planner error: no FINAL step";
         prog.data[last + 1] |= kFlagRaw << 16;
     }
-    st.alg_bytes = es.alg_bytes; st.alg_flops = es.alg_flops; st.n_steps = es.n_steps; st.max_step_cells = es.max_step_cells;
-    st.arena_cells = es.arena_cells; st.out_cells = es.out_cells;
-    return emit_error_message(e);
+    return done(e);
 }
 
 // ------------------------------------------------------------------------------------ cost estimate
@@ -1392,7 +1285,7 @@ PlanCache &plan_cache(const TemplateStore *ts) {
 void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs, int64_t b0, int64_t b1,
                 const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
                 const int32_t *e_codes, const int64_t *out_off, const char *skip, BatchPlan &ck, bool no_prune,
-                const uint8_t *orders, const int32_t *order_len, int64_t out_first, bool max_mode, bool raw, bool draw_mode, bool map_mode) {
+                const uint8_t *orders, const int32_t *order_len, int64_t out_first, ProgramKind kind) {
     const int64_t n = b1 - b0;
     const int T = pool.size();
     if ((int)bufs.size() < T) bufs.resize(T);
@@ -1412,7 +1305,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
     std::vector<std::string> terr(T);
     // dynamic distribution in blocks of 32 requests: request costs vary 100x and a worker may lose its core to
     // another rank's planner, a static split would wait for the slowest worker
-    TemplateStore *store = (net.plan_cache && !max_mode && !raw && !draw_mode && !map_mode) ? template_store(net) : nullptr;
+    TemplateStore *store = (net.plan_cache && may_use_templates(kind)) ? template_store(net) : nullptr;
     std::atomic<int64_t> next{0};
     constexpr int64_t kBlock = 32;
     const EmitNet en = net.emit_view();
@@ -1431,15 +1324,8 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             ck.local_off[i] = prog.size;
             ck.thread_of[i] = t;
             ck.tag_first[i] = (uint32_t)tags.size();
-            if (skip && skip[b]) {  // zero steps: result stays all-zero
-                prog.push(0);
-                if (max_mode || draw_mode || map_mode) {  // (an empty traceback / draw record: m = 0 reads as zero probability)
-                    const int32_t ne = (int32_t)(e_off[b + 1] - e_off[b]);
-                    prog.push(0);
-                    if (draw_mode) prog.push(0);
-                    prog.push((uint32_t)ne);
-                    for (int32_t k = 0; k < ne; ++k) { prog.push((uint32_t)e_vars[e_off[b] + k]); prog.push((uint32_t)e_codes[e_off[b] + k]); }
-                }
+            if (skip && skip[b]) {
+                put_empty_program(prog, kind, (int32_t)(e_off[b + 1] - e_off[b]), e_vars + e_off[b], e_codes + e_off[b]);
                 continue;
             }
             Request rq;
@@ -1450,10 +1336,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             rq.ecodes = e_codes + e_off[b];
             rq.out_off = out_off[b] - out_off[out_first >= 0 ? out_first : b0];
             rq.no_prune = no_prune;
-            rq.max_mode = max_mode;
-            rq.raw = raw;
-            rq.draw_mode = draw_mode;
-            rq.map_mode = map_mode;
+            rq.kind = kind;
             if (orders) { rq.order = orders + (size_t)i * 128; rq.n_order = order_len[i]; }
             PlanStats st;
             // plan templates (see above): probe at the start of every window, stay on while shapes repeat

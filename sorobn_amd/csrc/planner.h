@@ -81,20 +81,30 @@ struct Network {
     void set_hints(int32_t n_hints, const int32_t *priorities);  // n_hints arrays of n_vars priorities
 };
 
+// What a request's program computes - one choice, made once per call (plan_batch) or per request (plan_request).
+//   Sum   the posterior over the query variables, normalised (the query calls)
+//   Raw   MIBN_Q_UNNORMALISED: the Sum program word for word, its FINAL step flagged kFlagRaw (P(q, e), not normalised); nq = 0 allowed
+//   Max   mibn_mpe_batch: max-product elimination of every non-evidence variable, nq = 0, never pruned
+//   Draw  mibn_posterior_sample_batch: sum elimination with every input kept, nq = 0; prunes to the evidence's ancestors unless no_prune
+//   Map   mibn_map_batch: qvars[0..nq) are the MAP variables M - every other non-evidence variable is summed out first, then M is
+//         maximised out; nq = 0 allowed; prunes to the ancestors of M and the evidence unless no_prune
+enum class ProgramKind : uint8_t { Sum, Raw, Max, Draw, Map };
+// the decisions the planner takes on the kind
+constexpr bool takes_query(ProgramKind k) { return k == ProgramKind::Sum || k == ProgramKind::Raw || k == ProgramKind::Map; }  // else nq = 0
+constexpr bool never_prunes(ProgramKind k) { return k == ProgramKind::Max; }  // (a barren node does not maximise to 1)
+// one GENERIC step per eliminated variable and a record after the steps: orders compared by plain section-8(d) bytes, no second order
+constexpr bool step_wise(ProgramKind k) { return k == ProgramKind::Max || k == ProgramKind::Draw || k == ProgramKind::Map; }
+constexpr bool may_use_templates(ProgramKind k) { return k == ProgramKind::Sum; }
+constexpr bool allows_no_query(ProgramKind k) { return k == ProgramKind::Raw || k == ProgramKind::Map; }  // (validate_request)
+
 struct Request {
     int32_t nq = 0, ne = 0;
     const int32_t *qvars = nullptr;
     const int32_t *evars = nullptr;
     const int32_t *ecodes = nullptr;  // may be null for plan-only statistics
     int64_t out_off = 0;              // offset (doubles) into the batch result buffer
+    ProgramKind kind = ProgramKind::Sum;
     bool no_prune = false;            // MIBN_Q_NOPRUNE: every CPT takes part (full_joint_dist / predict_proba, bayes_net.py:460)
-    bool max_mode = false;            // max program (mibn_mpe_batch): max-product elimination of every non-evidence variable, nq = 0
-    bool raw = false;                 // MIBN_Q_UNNORMALISED: the FINAL step carries kFlagRaw (P(q, e), not normalised); nq = 0 allowed
-    bool draw_mode = false;           // draw program (mibn_posterior_sample_batch): sum elimination with every input kept, nq = 0; prunes
-                                      // to the evidence's ancestors unless no_prune
-    bool map_mode = false;            // map program (mibn_map_batch): qvars[0..nq) are the MAP variables M - every other non-evidence variable
-                                      // is summed out first, then M is maximised out; nq = 0 allowed; prunes to the ancestors of M and
-                                      // the evidence unless no_prune
     const uint8_t *order = nullptr;   // elimination order found elsewhere (the device order search), n_order entries
     int32_t n_order = -1;             // -1: search on the host
 };
@@ -183,7 +193,7 @@ struct PlanStats {
 //      the other free digits in ascending order.
 //      A work item = Network::sweep_iters consecutive tiles; one workgroup of kSweepWG lanes per item.
 //
-//   MAX programs (Request::max_mode, mibn_mpe_batch): max-product elimination of EVERY non-evidence variable (no pruning: a
+//   MAX programs (ProgramKind::Max, mibn_mpe_batch): max-product elimination of EVERY non-evidence variable (no pruning: a
 //      barren node does not maximise to 1), no query variable - the FINAL step multiplies the remaining scalars into one cell,
 //      m = max_x P(x, e), not normalised.  Every step is GENERIC with one eliminated variable (no FIBER / OUTER / CHAIN / SWEEP,
 //      no fused pairs: their kernels only sum), candidate orders compared by plain section-8(d) bytes.  A step that eliminates
@@ -198,13 +208,13 @@ struct PlanStats {
 //      x* = argmax[sum_v code[v] * stride_v]: every output variable of a step is eliminated later, so the reverse walk has
 //      already decoded it.  A request whose evidence code lies outside its domain is the program "0" + a record with n_rec = 0.
 //
-//   UNNORMALISED requests (Request::raw, MIBN_Q_UNNORMALISED): the program of the same request without the flag, word for word,
+//   UNNORMALISED requests (ProgramKind::Raw, MIBN_Q_UNNORMALISED): the program of the same request without the flag, word for word,
 //      except that its FINAL step - always the last step, always GENERIC - carries
 //      flag RAW (kFlagRaw, w1 bit 16 + 6): the kernels write the product sum as it is, P(q, e), with no normalisation.
 //      nq = 0 is allowed: the FINAL step is one cell, P(e).  With pruning and no evidence the relevant set is empty and the FINAL
 //      step has no input at all (n_in = 0): the empty product, 1.0.  Planned by the host only, without plan templates.
 //
-//   DRAW programs (Request::draw_mode, mibn_posterior_sample_batch): forward filtering for exact samples of P(x | e).  The factor
+//   DRAW programs (ProgramKind::Draw, mibn_posterior_sample_batch): forward filtering for exact samples of P(x | e).  The factor
 //      set, the order search (plain section-8(d) bytes) and the step shape are those of a max program - one GENERIC step per
 //      eliminated variable, product-only steps above kMaxIn inputs - but the steps SUM (no MAX flag, no argmax table) and the
 //      FINAL step, one cell = the unnormalised mass of the evidence, carries flag RAW.  No intermediate is released to the arena:
@@ -221,7 +231,7 @@ struct PlanStats {
 //      one input, x's whole CPT with its multi-state parents as axes - evidence or drawn before.  A request whose evidence code
 //      lies outside its domain is the program "0" + a record with n_back = n_fwd = 0.
 //
-//   MAP programs (Request::map_mode, mibn_map_batch): marginal MAP, m = max_m sum_h P(m, h, e) over the MAP variables M = qvars.  Two
+//   MAP programs (ProgramKind::Map, mibn_map_batch): marginal MAP, m = max_m sum_h P(m, h, e) over the MAP variables M = qvars.  Two
 //      phases, every step GENERIC with one eliminated variable (product-only steps above kMaxIn inputs, as in a max program).  SUM
 //      phase: the factors and the order of the sum program of (M, e) - pruned to the ancestors of M and the evidence unless
 //      Request::no_prune, order_search with plain section-8(d) bytes - one unflagged step per hidden variable, intermediates released
@@ -288,10 +298,8 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
                 const uint8_t *orders = nullptr, const int32_t *order_len = nullptr,  // orders[(b - b0) * 128 ..]: device order search
                 int64_t out_first = -1,   // result offsets relative to out_off[out_first] (default: b0) - the host's share of a chunk whose
                                           // first requests the device plans
-                bool max_mode = false,    // max programs (mibn_mpe_batch; q_off all zero, no plan templates)
-                bool raw = false,         // MIBN_Q_UNNORMALISED requests (nq = 0 allowed, no plan templates)
-                bool draw_mode = false,   // draw programs (mibn_posterior_sample_batch; q_off all zero, no plan templates; prunes unless no_prune)
-                bool map_mode = false);   // map programs (mibn_map_batch; q_off / q_vars = the MAP variables, no plan templates; prunes unless no_prune)
+                ProgramKind kind = ProgramKind::Sum);  // Max, Draw: q_off all zero; Map: q_off / q_vars = the MAP variables; plan templates
+                                                       // for Sum only
 
 // Shard-balancing estimate (mibn_estimate_costs): section-8(d) bytes of the cheaper of the two sweep orders of every
 // request of a CSR batch - the byte model only, nothing is emitted.
@@ -340,7 +348,7 @@ void build_schedule(const Network &net, const BatchPlan &bp, const std::vector<P
                     Schedule &out);
 
 // Validate a request (unknown ids, duplicates, overlap) - bayes_net.py:840-845 and the KeyError of 770.  nq = 0 is valid only with
-// Request::raw or Request::map_mode.
+// ProgramKind::Raw or ProgramKind::Map.
 std::string validate_request(const Network &net, const Request &rq);  // "" or the reference's error message
 bool request_is_valid(const Network &net, const Request &rq);          // the same checks without building a message
 std::string validate_mpe_request(const Network &net, const Request &rq);  // evidence only (unknown ids, duplicates): "" or the message

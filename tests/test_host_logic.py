@@ -1099,7 +1099,11 @@ def test_planner_output_is_pinned(tmp_path):
     """The planner's optimisations of rounds 4 and 5 (static slot sets, integer min-fill keys, the small-step shortcut, popcount scope
     sizes) must not move a word: tools/plan_fingerprint.cpp plans seeded request streams on 12 synthetic networks x 6 option sets and
     prints one hash of programs + work items + statistics + schedule per pair; tools/plan_fingerprint.expected.txt is that output for
-    the committed planner.  (A deliberate change of the planner's choices or of the class order re-pins the file.)"""
+    the committed planner.  (A deliberate change of the planner's choices or of the class order re-pins the file.)
+    A second section pins what only the host plans: max, unnormalised, draw and map programs (the last three pruned and not) for 200
+    seeded requests on eight of the networks and a ten-variable star - the program words with their traceback / draw / gather records,
+    the empty record of every sixteenth request (handed over as skipped), cost, arena need, argmax and kept cells per request, the
+    schedule - and, per pair, the number of product-only steps (more than kMaxIn tables in one product): at least one everywhere."""
     import shutil
     if not shutil.which("g++"):
         pytest.skip("no g++")

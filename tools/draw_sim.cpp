@@ -86,7 +86,7 @@ int main(int argc, char **argv) {
         rq.ne = ne;
         rq.evars = ev.data();
         rq.ecodes = ec.data();
-        rq.draw_mode = true;
+        rq.kind = ProgramKind::Draw;
         rq.no_prune = !prune;
         const std::string ve = validate_mpe_request(net, rq);
         if (!ve.empty()) fail(b, ve);

@@ -6,14 +6,14 @@
 // Input (whitespace-separated): n_vars, card[n], scope_off[n + 1], scope_vars[], value_off[n + 1], values[] (any strtod
 // format), B, then per request: no_prune (0 / 1), nq, qvars[nq], ne, evars[ne], ecodes[ne].
 //
-//   run      plans every request with Request::raw and runs its program (GENERIC steps only: the small networks' programs).
+//   run      plans every request with ProgramKind::Raw and runs its program (GENERIC steps only: the small networks' programs).
 //            Output: one line per request, its nq-variable table P(q, e) in C-order (%a each; one cell, P(e), for nq = 0).
 //            Checks, and exits 1 with a message when one fails: every step is GENERIC, the FINAL step is the last one and
 //            carries the RAW flag (and no other step does), every arena access lies inside the request's arena_cells.  A
 //            request with an evidence code outside its domain is not planned (the engine skips it): its table is all zero.
-//   compare  plans every request (nq >= 1) with and without Request::raw: the two programs must be equal word for word but for
+//   compare  plans every request (nq >= 1) as ProgramKind::Raw and as Sum: the two programs must be equal word for word but for
 //            the RAW bit of the FINAL step.  Output: one line per request, "<words> <steps>".
-//   reject   validates every request without Request::raw and prints validate_request's message (or "ok"), one line each.
+//   reject   validates every request as ProgramKind::Sum and prints validate_request's message (or "ok"), one line each.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -55,7 +55,7 @@ int main(int argc, char **argv) {
             std::printf("%s\n", ve.empty() ? "ok" : ve.c_str());
             continue;
         }
-        rq.raw = true;
+        rq.kind = ProgramKind::Raw;
         const std::string ve = validate_request(net, rq);
         if (!ve.empty()) fail(b, ve);
         int64_t qcells = 1;
@@ -67,7 +67,7 @@ int main(int argc, char **argv) {
             PlanStats s1, s2;
             std::string pe = plan_request(net, rq, p_raw, s1);
             if (!pe.empty()) fail(b, pe);
-            rq.raw = false;
+            rq.kind = ProgramKind::Sum;
             pe = plan_request(net, rq, p_norm, s2);
             if (!pe.empty()) fail(b, pe);
             if (p_raw.size() != p_norm.size()) fail(b, "programs of different length");

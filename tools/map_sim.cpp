@@ -54,7 +54,7 @@ int main(int argc, char **argv) {
         rq.ne = ne;
         rq.evars = ev.data();
         rq.ecodes = ec.data();
-        rq.map_mode = true;
+        rq.kind = ProgramKind::Map;
         rq.no_prune = no_prune;
         const std::string ve = validate_request(net, rq);
         if (!ve.empty()) fail(b, ve);

@@ -49,7 +49,7 @@ int main(int argc, char **argv) {
         rq.ne = ne;
         rq.evars = ev.data();
         rq.ecodes = ec.data();
-        rq.max_mode = true;
+        rq.kind = ProgramKind::Max;
         const std::string ve = validate_mpe_request(net, rq);
         if (!ve.empty()) fail(b, ve);
         std::vector<uint32_t> prog;
