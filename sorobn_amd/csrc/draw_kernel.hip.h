@@ -1,8 +1,9 @@
 // CDNA4 (gfx950) kernels of exact posterior sampling (mibn_posterior_sample_batch): forward filtering, backward sampling.
 //
 // A draw program (planner.h, "DRAW programs") is a GENERIC-only sum program whose intermediates all stay in the arena.
-// `ve_sum_kernel` runs one level of its schedule - ve_max_kernel's launch shape around the level kernel's own step code with
-// MAX = false; the FINAL step carries the RAW flag, so segment_wave leaves the mass of the evidence as it is.
+// `ve_sum_kernel` (elim_kernel.hip.h) runs one level of its schedule - the level body of the step-wise kinds around the level
+// kernel's own step code with MAX = false; the FINAL step carries the RAW flag, so segment_wave leaves the mass of the evidence as
+// it is.
 //
 // `posterior_draw_kernel` then walks the request's draw record once per sample: ONE SAMPLE PER LANE.  A request has thousands of
 // samples and the walk is a chain of dependent gathers (the value just drawn addresses the next table), so occupancy is the only
@@ -15,38 +16,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "elim_kernel.hip.h"
 #include "gibbs_kernel.hip.h"
-#include "ve_kernel.hip.h"
 
 namespace mibn {
-
-// One level of a draw schedule: workgroup b runs item wg_item[b] - a group of kSegPerWg segments or a tile of a big GENERIC step.
-__global__ __launch_bounds__(kWG, 4) void ve_sum_kernel(const LevelArgs A) {
-    __shared__ __attribute__((aligned(16))) unsigned char sh_buf[kSegPerWg * (kMaxStepWords * 4 + kMaxIn * kTileMax * 4)];
-    const int tid = threadIdx.x;
-    const uint32_t wg = blockIdx.x + A.wg_base;
-    const uint32_t item_idx = (uint32_t)uni((int)A.wg_item[wg]);
-    Item it;
-    it.req = (uint32_t)uni((int)A.items[item_idx].req);
-    it.rel_off = (uint32_t)uni((int)A.items[item_idx].rel_off);
-    it.a = (uint32_t)uni((int)A.items[item_idx].a);
-    it.b = (uint32_t)uni((int)A.items[item_idx].b);
-    if (it.a & kItemSegment) {
-        segment_wave<0>(A, item_idx, (int)it.b, reinterpret_cast<double *>(sh_buf), tid);
-        return;
-    }
-    uint32_t *sh_step = reinterpret_cast<uint32_t *>(sh_buf);
-    int (*sh_hoff)[kTileMax] = reinterpret_cast<int (*)[kTileMax]>(sh_buf + kMaxStepWords * 4);
-    const uint64_t ao = A.arena_off[it.req], po = A.prog_off[it.req];
-    double *slot = A.arena + (((uint64_t)(uint32_t)uni((int)(ao >> 32)) << 32) | (uint32_t)uni((int)(ao & 0xffffffffu)));
-    const uint32_t *p = A.prog + (((uint64_t)(uint32_t)uni((int)(po >> 32)) << 32) | (uint32_t)uni((int)(po & 0xffffffffu))) + it.rel_off;
-    const int words = (int)p[6];
-    for (int i = tid; i < words; i += kWG) sh_step[i] = p[i];
-    __syncthreads();
-    const int h0 = (int)((wg - it.b) * it.a);
-    const int h1 = min((int)sh_step[3], h0 + (int)it.a);
-    generic_dispatch<kWG, false>((sh_step[0] >> 8) & 0xff, sh_step, sh_hoff, A.pool, slot, A.results, tid, h0, h1);
-}
 
 constexpr int kDrawWG = 256;  // samples per workgroup: four waves share one staging of the evidence and one row write-out
 
@@ -71,7 +44,7 @@ struct DrawArgs {
 };
 
 // w_x = prod_j phi_j[base_j + x * xs_j] in input order, rounded after every product (no contraction: the host twin,
-// tools/draw_sim.cpp, computes the same bits)
+// tools/prog_sim.cpp draw, computes the same bits)
 template <int NIN>
 __device__ __forceinline__ double draw_weight(const double *const (&tab)[kMaxIn], const int64_t (&base)[kMaxIn], const int64_t (&xs)[kMaxIn],
                                               const int n_in, const int x) {
@@ -95,6 +68,8 @@ __global__ __launch_bounds__(kDrawWG) void posterior_draw_kernel(const DrawArgs 
     const DrawItem it = A.items[blockIdx.x];
     const uint32_t r = it.req;
     const uint32_t *p = A.prog + A.prog_off[r];
+    // (record_offset(p), written out: through the helper the compiler orders a few independent instructions of this kernel
+    //  differently, and the kernel is to stay instruction for instruction what the recorded profiles measured)
     const uint32_t n_steps = p[0];
     uint64_t off = 1;
     for (uint32_t s = 0; s < n_steps; ++s) off += p[off + 6];

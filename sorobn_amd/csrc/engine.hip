@@ -29,9 +29,8 @@
 #include "tiny_kernel.hip.h"
 #include "sweep_kernel.hip.h"
 #include "ve_kernel.hip.h"
-#include "max_kernel.hip.h"
 #include "draw_kernel.hip.h"
-#include "map_kernel.hip.h"
+#include "elim_kernel.hip.h"
 #include "expect_kernel.hip.h"
 #include "wave_plan_kernel.hip.h"
 
@@ -2363,6 +2362,35 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
     return MIBN_OK;
 }
 
+// What the payloads share.  The masses a chunk starts from (DrawPayload, MapPayload): a skipped request never writes its cell - zero
+// probability; a program without steps (nothing left after pruning, no evidence) has the empty product: 1, written here.  m_init is
+// the caller's and is rewritten by the next chunk: the caller synchronises the stream before that.
+int upload_initial_mass(ElimRun &R, std::vector<double> &m_init) {
+    const mibn_ctx::Elim &M = R.M;
+    const BatchPlan &ck = M.plan;
+    m_init.assign((size_t)R.n, 0.0);
+    for (int64_t i = 0; i < R.n; ++i)
+        if (!R.skip[(size_t)(R.b0 + i)] && M.bufs[(size_t)ck.thread_of[(size_t)i]].data[ck.local_off[(size_t)i]] == 0) m_init[(size_t)i] = 1.0;
+    HIP_TRY(R.h, hipMemcpyAsync(M.d_m, m_init.data(), (size_t)R.n * 8, hipMemcpyHostToDevice, R.S));
+    return MIBN_OK;
+}
+
+// The traceback of the wave's requests (MpePayload, MapPayload): everything but where the codes go.
+TracebackArgs traceback_args(const ElimRun &R) {
+    TracebackArgs T;
+    T.prog = R.M.d_prog;
+    T.prog_off = R.M.d_prog_off + R.r0;
+    T.arena_off = R.M.d_arena_off;
+    T.arena = R.h->arena(0);
+    T.m = R.M.d_m + R.r0;
+    T.m_off = nullptr;
+    T.codes = nullptr;
+    T.log_p = R.M.d_log_p + R.r0;
+    T.n_req = (uint32_t)(R.r1 - R.r0);
+    T.n_vars = R.h->net.n_vars;
+    return T;
+}
+
 // ---------------------------------------------------------------------------------------------- most probable explanation
 // mibn_mpe_batch: max programs (planner.h) run by ve_max_kernel - the arena of a request holds its intermediates and argmax tables -,
 // decoded wave by wave by mpe_traceback_kernel, downloaded chunk by chunk.
@@ -2389,17 +2417,8 @@ struct MpePayload {
     }
     int after_levels(ElimRun &R) const {
         mibn_ctx *h = R.h;
-        const int nv = h->net.n_vars;
-        TracebackArgs T;
-        T.prog = R.M.d_prog;
-        T.prog_off = R.M.d_prog_off + R.r0;
-        T.arena_off = R.M.d_arena_off;
-        T.arena = h->arena(0);
-        T.m = R.M.d_m + R.r0;
-        T.codes = R.M.d_codes + (size_t)R.r0 * (size_t)nv;
-        T.log_p = R.M.d_log_p + R.r0;
-        T.n_req = (uint32_t)(R.r1 - R.r0);
-        T.n_vars = nv;
+        TracebackArgs T = traceback_args(R);
+        T.codes = R.M.d_codes + (size_t)R.r0 * (size_t)h->net.n_vars;
         int rc;
         if ((rc = R.timed_launch(kStatTraceback, 0.0, (double)(R.r1 - R.r0), [&] {
                 hipLaunchKernelGGL(mpe_traceback_kernel, dim3((unsigned)(R.r1 - R.r0)), dim3(kTracebackWG), 0, R.S, T);
@@ -2452,24 +2471,18 @@ struct DrawPayload {
         const mibn_ctx::Elim &M = R.M;
         const BatchPlan &ck = M.plan;
         const int64_t n = R.n;
+        int rc;
         if (R.b0 == 0 && lds > 64 * 1024) {  // (once per call, before the first draw launch)
             HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             HIP_TRY(h, hipFuncSetAttribute((const void *)posterior_draw_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
-        // a skipped request never writes its mass: zero probability.  A program without steps (pruned, no evidence) has the empty
-        // product: 1
-        m_init.assign((size_t)n, 0.0);
-        for (int64_t i = 0; i < n; ++i)
-            if (!R.skip[(size_t)(R.b0 + i)] && M.bufs[(size_t)ck.thread_of[(size_t)i]].data[ck.local_off[(size_t)i]] == 0) m_init[(size_t)i] = 1.0;
-        HIP_TRY(h, hipMemcpyAsync(M.d_m, m_init.data(), (size_t)n * 8, hipMemcpyHostToDevice, R.S));
+        if ((rc = upload_initial_mass(R, m_init))) return rc;
         HIP_TRY(h, hipStreamSynchronize(R.S));  // (m_init is rewritten by the next chunk)
         // table bytes one sample of each request gathers (the draw kernel's "algorithmic bytes"): 8 per input and state of every entry
         gather.assign((size_t)n, 0.0);
         for (int64_t i = 0; i < n; ++i) {
             const uint32_t *p = M.bufs[(size_t)ck.thread_of[(size_t)i]].data + ck.local_off[(size_t)i];
-            size_t off = 1;
-            for (uint32_t s = 0; s < p[0]; ++s) off += p[off + 6];
-            const uint32_t *rec = p + off;
+            const uint32_t *rec = p + record_offset(p);
             const uint32_t n_ent = rec[0] + rec[1];
             rec += 3 + 2 * rec[2];
             for (uint32_t e = 0; e < n_ent; ++e) {
@@ -2575,20 +2588,14 @@ struct MapPayload {
     int prepare(ElimRun &R) {
         mibn_ctx *h = R.h;
         const mibn_ctx::Elim &M = R.M;
-        const BatchPlan &ck = M.plan;
         const int64_t n = R.n;
         int rc;
         if ((rc = ensure(h, R.M.d_log_p, (size_t)n))) return rc;
         if ((rc = ensure(h, R.M.d_m_off, (size_t)n + 1))) return rc;
         if ((rc = ensure(h, R.M.d_codes, (size_t)std::max<int64_t>(1, m_off[R.b0 + n] - m_off[R.b0])))) return rc;
-        // a skipped request never writes its cell: zero probability.  A program without steps (M empty, no evidence, pruned) has the
-        // empty product: 1, written here
-        m_init.assign((size_t)n, 0.0);
         rel_off.resize((size_t)n + 1);
         for (int64_t i = 0; i <= n; ++i) rel_off[(size_t)i] = m_off[R.b0 + i] - m_off[R.b0];
-        for (int64_t i = 0; i < n; ++i)
-            if (!R.skip[(size_t)(R.b0 + i)] && M.bufs[(size_t)ck.thread_of[(size_t)i]].data[ck.local_off[(size_t)i]] == 0) m_init[(size_t)i] = 1.0;
-        HIP_TRY(h, hipMemcpyAsync(M.d_m, m_init.data(), (size_t)n * 8, hipMemcpyHostToDevice, R.S));
+        if ((rc = upload_initial_mass(R, m_init))) return rc;
         HIP_TRY(h, hipMemcpyAsync(M.d_m_off, rel_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, R.S));
         HIP_TRY(h, hipStreamSynchronize(R.S));  // (both vectors are rewritten by the next chunk)
         return MIBN_OK;
@@ -2605,17 +2612,9 @@ struct MapPayload {
             book_stat(h, ((w[1] >> 16) & kFlagMax) ? kStatMapMaxTiles : kStatMapSumTiles, 1, 0.0, 0.0,  // (their bytes are ve_map_kernel's)
                       (double)(((int64_t)w[3] + th - 1) / th), true, false);
         }
-        MapTracebackArgs T;
-        T.prog = M.d_prog;
-        T.prog_off = M.d_prog_off + R.r0;
-        T.arena_off = M.d_arena_off;
-        T.arena = h->arena(0);
-        T.m = M.d_m + R.r0;
+        TracebackArgs T = traceback_args(R);
         T.m_off = M.d_m_off + R.r0;
         T.codes = M.d_codes;
-        T.log_p = M.d_log_p + R.r0;
-        T.n_req = (uint32_t)(R.r1 - R.r0);
-        T.n_vars = h->net.n_vars;
         int rc;
         if ((rc = R.timed_launch(kStatMapTraceback, 0.0, (double)(R.r1 - R.r0), [&] {
                 hipLaunchKernelGGL(map_traceback_kernel, dim3((unsigned)(R.r1 - R.r0)), dim3(kTracebackWG), 0, R.S, T);

@@ -245,6 +245,15 @@ struct PlanStats {
 //      first), then the GATHER list:  nq, M in the caller's order - what the decoder returns codes for.  A single-state MAP
 //      variable is never eliminated: code 0.  A request whose evidence code lies outside its domain is the program "0" + a record
 //      with n_rec = 0 (no gather list: every code is -1).
+
+// Word offset, inside the program p, of what follows its last step: the record of a Max / Draw / Map program.
+MIBN_HD inline uint64_t record_offset(const uint32_t *p) {
+    const uint32_t n_steps = p[0];
+    uint64_t off = 1;
+    for (uint32_t s = 0; s < n_steps; ++s) off += p[off + 6];
+    return off;
+}
+
 // Growable word buffer the planner appends programs to.  The engine backs it with pinned host memory
 // (so the upload is a true async DMA) and keeps it across calls; the default backing is malloc.
 struct ProgBuf {

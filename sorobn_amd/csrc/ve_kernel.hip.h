@@ -86,7 +86,7 @@ __device__ __forceinline__ void lanes_sync() {
     }
 }
 
-// MAX (max programs, planner.h; max_kernel.hip.h): psi[o] = max_x prod_j phi_j[..] instead of the sum, and a step flagged kFlagMax
+// MAX (max programs, planner.h; elim_kernel.hip.h): psi[o] = max_x prod_j phi_j[..] instead of the sum, and a step flagged kFlagMax
 // stores the lowest maximising x of every output cell in its argmax table (uint16, arena offset w7 / w8).
 template <int NIN, int MAXC, int CX, int LANES, bool MAX = false>
 __device__ __forceinline__ void generic_body(const uint32_t *sw, int (*sh_hoff)[kTileMax], const double *__restrict__ pool,
@@ -926,14 +926,18 @@ __device__ __forceinline__ void normalise_wave(double *__restrict__ p, int n, in
         for (int i = lane; i < n; i += 64) p[i] = p[i] / total;
 }
 
+// What the steps of a program reduce with (the step-wise kinds are run by elim_kernel.hip.h):
+//   Sum  every step sums; a FINAL step is normalised unless it is flagged RAW (MIBN_Q_UNNORMALISED, draw programs)
+//   Max  the steps of a max program: every step runs the max body; its FINAL step is not normalised
+//   Map  the steps of a map program: a step flagged kFlagMax runs the max body, every other step the sum body; the choice is
+//        wave-uniform and made per step, a segment may hold both kinds.  Never normalised.
+enum class ElimMode { Sum, Max, Map };
+
 // A workgroup of SEGMENTS (planner.h kSegPerWg): wave w runs item first + w - the small GENERIC steps of one request, back to
 // back, on its own.  A chain of dependent tiny steps is latency, not bandwidth, and a wave is enough for one (< 4 096 output
 // cells per step): four chains per workgroup, twelve per CU, hide four times as much of it as one.  The wave's copy of the
 // step descriptor and its offset table live in its quarter of the first 12 KB of shT (a segment has no T).
-// MODE 1: the steps of a max program (max_kernel.hip.h) - its FINAL step is not normalised; nor is a FINAL step flagged RAW
-// (MIBN_Q_UNNORMALISED).  MODE 2: the steps of a map program (map_kernel.hip.h) - a step flagged kFlagMax runs the max body, every
-// other step the sum body; the choice is wave-uniform and made per step, a segment may hold both kinds.  Never normalised.
-template <int MODE = 0>
+template <ElimMode M = ElimMode::Sum>
 __device__ __forceinline__ void segment_wave(const LevelArgs &A, const uint32_t first, const int n_valid, double *shT, const int tid) {
     const int wave = tid >> 6, lane = tid & 63;
     if (wave >= n_valid) return;
@@ -963,13 +967,13 @@ __device__ __forceinline__ void segment_wave(const LevelArgs &A, const uint32_t 
 #pragma unroll
             for (int k = 0; k < kPre; ++k) nxt[k] = p[words + lane + 64 * k];
         }
-        if constexpr (MODE == 2) {
+        if constexpr (M == ElimMode::Map) {
             if ((w_step[1] >> 16) & kFlagMax) generic_dispatch<64, true>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
             else generic_dispatch<64, false>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
         } else {
-            generic_dispatch<64, MODE == 1>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
+            generic_dispatch<64, M == ElimMode::Max>((w_step[0] >> 8) & 0xff, w_step, w_hoff, A.pool, slot, A.results, lane, 0, (int)w_step[3]);
         }
-        if (MODE == 0 && ((w_step[1] >> 16) & (kFlagFinal | kFlagRaw)) == kFlagFinal) {  // (RAW: P(q, e) as it is)
+        if (M == ElimMode::Sum && ((w_step[1] >> 16) & (kFlagFinal | kFlagRaw)) == kFlagFinal) {  // (RAW: P(q, e) as it is)
             const uint64_t out_off = (uint64_t)w_step[4] | ((uint64_t)w_step[5] << 32);
             lanes_sync<64>();
             normalise_wave(A.results + out_off, (int)(w_step[2] * w_step[3]), lane);

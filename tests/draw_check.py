@@ -1,6 +1,6 @@
 """Plain numpy checkers of exact posterior sampling (tests/test_posterior_sampling.py, tests/test_posterior_sampling_host.py): the
 dense posterior P(x | e) of a small network, a pooled chi-square test of a sample histogram against it, and the runner of the
-host twin tools/draw_sim.cpp - all over the flattened network (sorobn_amd.flatten), i.e. the tables the engine itself is given."""
+host twin tools/prog_sim.cpp draw - all over the flattened network (sorobn_amd.flatten), i.e. the tables the engine itself is given."""
 import os
 import subprocess
 
@@ -8,6 +8,7 @@ import numpy as np
 from scipy.stats import chi2
 
 import mpe_check as mc
+import sim_tools
 
 ROOT = mc.ROOT
 P_MIN = 1e-6  # false-alarm rate per chi-square check: a few hundred checks fail by chance less than once in a thousand runs
@@ -85,31 +86,25 @@ def check_samples(f, ev, codes, ctx=""):
 
 
 def sim_text(f, seed, prune, requests):
-    """Input of tools/draw_sim.cpp: the network, the seed, the prune flag, then the requests [(evars, ecodes, n, g_first)]."""
-    parts = [str(len(f.card)), " ".join(map(str, f.card)), " ".join(map(str, f.scope_off)), " ".join(map(str, f.scope_vars)),
-             " ".join(map(str, f.value_off)), " ".join(float(x).hex() for x in f.values), str(int(seed)), str(int(bool(prune))),
-             str(len(requests))]
+    """Input of tools/prog_sim.cpp draw: the network, the seed, the prune flag, then the requests [(evars, ecodes, n, g_first)]."""
+    parts = sim_tools.network_prefix(f) + [str(int(seed)), str(int(bool(prune))), str(len(requests))]
     for evs, ecs, n, g in requests:
         parts.append(f"{len(evs)} {' '.join(map(str, evs))} {' '.join(map(str, ecs))} {int(n)} {int(g)}")
     return "\n".join(parts) + "\n"
 
 
 def build_draw_sim(tmp_path):
-    exe = os.path.join(str(tmp_path), "draw_sim")
-    r = subprocess.run(["g++", "-O2", "-mpopcnt", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tools", "draw_sim.cpp"),
-                        os.path.join(ROOT, "sorobn_amd", "csrc", "planner.cpp"), "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return sim_tools.build_prog_sim()
 
 
 def run_draw_sim(exe, tmp_path, f, seed, prune, requests, margins=False):
     """-> list per request of dict(codes [n, n_vars] int32, p_e, n_steps, n_back, n_fwd, kept_cells, min_margin, low = the global
-    rows whose smallest margin is <= 1e-12[, margins [n]]) as tools/draw_sim.cpp computes them."""
+    rows whose smallest margin is <= 1e-12[, margins [n]]) as tools/prog_sim.cpp draw computes them."""
     d = str(tmp_path)
     path, cpath, mpath = os.path.join(d, "draw_net.txt"), os.path.join(d, "draw_codes.bin"), os.path.join(d, "draw_margins.bin")
     with open(path, "w") as fh:
         fh.write(sim_text(f, seed, prune, requests))
-    r = subprocess.run([exe, path, cpath] + ([mpath] if margins else []), capture_output=True, text=True, timeout=1800)
+    r = subprocess.run([exe, "draw", path, cpath] + ([mpath] if margins else []), capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-2000:]
     nv = len(f.card)
     codes = np.fromfile(cpath, np.int32).reshape(-1, max(1, nv))[:, :nv]

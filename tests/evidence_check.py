@@ -1,5 +1,5 @@
 """Plain numpy checkers of the evidence likelihood P(e) (tests/test_evidence.py, tests/test_evidence_host.py): P(q, e) of a small
-network by enumeration of its dense joint, and the host interpreter of MIBN_Q_UNNORMALISED programs (tools/ev_sim.cpp) - all over
+network by enumeration of its dense joint, and the host interpreter of MIBN_Q_UNNORMALISED programs (tools/prog_sim.cpp ev) - all over
 the flattened network (sorobn_amd.flatten), i.e. the tables the engine itself is given."""
 import os
 import subprocess
@@ -9,6 +9,7 @@ import numpy as np
 import golden_util as gu
 import mpe_check as mc
 import netspec
+import sim_tools
 import sorobn_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,28 +89,23 @@ def evidence_sets(f, rng, n_random=3):
 
 
 def net_text(f, requests):
-    """Input of tools/ev_sim.cpp: the network, then the requests [(no_prune, qvars, evars, ecodes)]."""
-    parts = [str(len(f.card)), " ".join(map(str, f.card)), " ".join(map(str, f.scope_off)), " ".join(map(str, f.scope_vars)),
-             " ".join(map(str, f.value_off)), " ".join(float(x).hex() for x in f.values), str(len(requests))]
+    """Input of tools/prog_sim.cpp ev: the network, then the requests [(no_prune, qvars, evars, ecodes)]."""
+    parts = sim_tools.network_prefix(f) + [str(len(requests))]
     for no_prune, qs, evs, ecs in requests:
         parts.append(f"{int(no_prune)} {len(qs)} {' '.join(map(str, qs))} {len(evs)} {' '.join(map(str, evs))} {' '.join(map(str, ecs))}")
     return "\n".join(parts) + "\n"
 
 
 def build_ev_sim(tmp_path):
-    exe = os.path.join(str(tmp_path), "ev_sim")
-    r = subprocess.run(["g++", "-O2", "-mpopcnt", "-std=c++17", os.path.join(ROOT, "tools", "ev_sim.cpp"),
-                        os.path.join(ROOT, "sorobn_amd", "csrc", "planner.cpp"), "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return sim_tools.build_prog_sim()
 
 
 def run_ev_sim(exe, tmp_path, f, requests, mode="run"):
-    """-> the output lines of tools/ev_sim.cpp: "run" - a float64 array per request; else the lines as strings."""
+    """-> the output lines of tools/prog_sim.cpp ev: "run" - a float64 array per request; else the lines as strings."""
     path = os.path.join(str(tmp_path), "net.txt")
     with open(path, "w") as fh:
         fh.write(net_text(f, requests))
-    r = subprocess.run([exe, mode, path], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, "ev", mode, path], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
     assert len(lines) == len(requests)

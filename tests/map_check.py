@@ -1,12 +1,13 @@
 """Plain numpy twin of marginal MAP (tests/test_map.py, tests/test_map_host.py): the dense joint of a small network, sliced by the
 evidence and summed over every axis that is not a MAP variable - over the flattened network (sorobn_amd.flatten), i.e. the tables
-the engine itself is given - plus the builder / runner of the host interpreter tools/map_sim.cpp."""
+the engine itself is given - plus the runner of the host interpreter tools/prog_sim.cpp map."""
 import os
 import subprocess
 
 import numpy as np
 
 import mpe_check as mc
+import sim_tools
 
 ROOT = mc.ROOT
 _joints = {}
@@ -83,27 +84,23 @@ def check(f, mvars, ev, log_p, codes, prune=False, ctx="", tol=1e-12):
 
 
 def net_text(f, requests):
-    """Input of tools/map_sim.cpp: the network, then the requests [(no_prune, mvars, evars, ecodes)]."""
-    parts = [mc.net_text(f, []).rsplit("\n", 2)[0], str(len(requests))]
+    """Input of tools/prog_sim.cpp map: the network, then the requests [(no_prune, mvars, evars, ecodes)]."""
+    parts = sim_tools.network_prefix(f) + [str(len(requests))]
     for no_prune, ms, evs, ecs in requests:
         parts.append(f"{int(no_prune)} {len(ms)} {' '.join(map(str, ms))} {len(evs)} {' '.join(map(str, evs))} {' '.join(map(str, ecs))}")
     return "\n".join(parts) + "\n"
 
 
 def build_map_sim(tmp_path):
-    exe = os.path.join(str(tmp_path), "map_sim")
-    r = subprocess.run(["g++", "-O2", "-mpopcnt", "-std=c++17", os.path.join(ROOT, "tools", "map_sim.cpp"),
-                        os.path.join(ROOT, "sorobn_amd", "csrc", "planner.cpp"), "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return sim_tools.build_prog_sim()
 
 
 def run_map_sim(exe, tmp_path, f, requests, expect_fail=False):
-    """-> (log_p [B], [codes of request b, in the order of its mvars]) as tools/map_sim.cpp computes them from the map programs."""
+    """-> (log_p [B], [codes of request b, in the order of its mvars]) as tools/prog_sim.cpp map computes them from the map programs."""
     path = os.path.join(str(tmp_path), "map_net.txt")
     with open(path, "w") as fh:
         fh.write(net_text(f, requests))
-    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, "map", path], capture_output=True, text=True, timeout=900)
     if expect_fail:
         return r
     assert r.returncode == 0, r.stderr[-2000:]

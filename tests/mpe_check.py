@@ -6,6 +6,7 @@ import subprocess
 
 import numpy as np
 
+import sim_tools
 from sorobn_amd.flatten import flatten
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,28 +89,23 @@ def flat_of(bn):
 
 
 def net_text(f, requests):
-    """Input of tools/max_sim.cpp: the network, then the requests [(evars, ecodes)]."""
-    parts = [str(len(f.card)), " ".join(map(str, f.card)), " ".join(map(str, f.scope_off)), " ".join(map(str, f.scope_vars)),
-             " ".join(map(str, f.value_off)), " ".join(float(x).hex() for x in f.values), str(len(requests))]
+    """Input of tools/prog_sim.cpp max: the network, then the requests [(evars, ecodes)]."""
+    parts = sim_tools.network_prefix(f) + [str(len(requests))]
     for evs, ecs in requests:
         parts.append(f"{len(evs)} {' '.join(map(str, evs))} {' '.join(map(str, ecs))}")
     return "\n".join(parts) + "\n"
 
 
 def build_max_sim(tmp_path):
-    exe = os.path.join(str(tmp_path), "max_sim")
-    r = subprocess.run(["g++", "-O2", "-mpopcnt", "-std=c++17", os.path.join(ROOT, "tools", "max_sim.cpp"),
-                        os.path.join(ROOT, "sorobn_amd", "csrc", "planner.cpp"), "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return sim_tools.build_prog_sim()
 
 
 def run_max_sim(exe, tmp_path, f, requests):
-    """-> (log_p [B], codes [B, n]) as tools/max_sim.cpp computes them from the max programs."""
+    """-> (log_p [B], codes [B, n]) as tools/prog_sim.cpp max computes them from the max programs."""
     path = os.path.join(str(tmp_path), "net.txt")
     with open(path, "w") as fh:
         fh.write(net_text(f, requests))
-    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, "max", path], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lp, codes = [], []
     for line in r.stdout.splitlines():

@@ -1,5 +1,5 @@
 """Evidence likelihood P(e) on the CPU: the MIBN_Q_UNNORMALISED programs the host planner emits, run by a host interpreter
-(tools/ev_sim.cpp, linked against planner.cpp) and checked against numpy enumeration; the programs of flagged requests against the
+(tools/prog_sim.cpp ev, linked against planner.cpp) and checked against numpy enumeration; the programs of flagged requests against the
 unflagged ones word for word; the validation of zero query variables; and the argument errors of BayesNet.evidence_proba, raised
 before any engine exists."""
 import shutil

@@ -1,5 +1,5 @@
 """Marginal MAP on the CPU: the map programs, traceback records and gather lists the planner emits for mibn_map_batch, run by a
-host interpreter (tools/map_sim.cpp, linked against planner.cpp - it also checks the structure of every program it runs) and
+host interpreter (tools/prog_sim.cpp map, linked against planner.cpp - it also checks the structure of every program it runs) and
 checked against a plain numpy twin (tests/map_check.py); plus the argument errors of BayesNet.map_query / map_frame, raised before
 any engine exists, and the C-ABI bookkeeping."""
 import os

@@ -91,6 +91,42 @@ def test_c3_grid(grid, ne):
         assert all(codes[v] == c for v, c in ev.items())
 
 
+def test_tiles_on_a_small_grid():
+    """The tile path of ve_max_kernel at a small size: the 6 x 6 K = 4 grid, 16 rows of one or two evidence values, with the step
+    classes forced as the parity tests force them (big_iters 256, odd tiles of 3 hi iterations) - the big max steps run as GENERIC
+    tiles of the workgroup path, several workgroups each, where the default options keep them in segments.  Both runs give the
+    same codes and log_p bit for bit, and log_p is the log joint of the codes."""
+    bn = netspec.build(netspec.grid_spec(6, 6, 4), sorobn_amd.BayesNet).use_device(0)
+    f = mc.flat_of(bn)
+    eng = bn.backend.engine
+    rng = np.random.default_rng(36)
+    rows = []
+    for r in range(16):
+        vs = sorted(rng.choice(36, size=1 + r % 2, replace=False).tolist())
+        rows.append((vs, [int(rng.integers(0, 4)) for _ in vs]))
+    e_off = np.concatenate([[0], np.cumsum([len(vs) for vs, _ in rows])]).astype(np.int64)
+    ev = np.array([v for vs, _ in rows for v in vs], np.int32)
+    ec = np.array([c for _, cs in rows for c in cs], np.int32)
+    eng.set_option("big_iters", 256)
+    eng.set_option("tile_h", 3)
+    try:
+        codes, lp = eng.mpe_batch(e_off, ev, ec)
+        forced = {k["name"]: k for k in eng.kernel_stats()}
+    finally:
+        eng.set_option("big_iters", 4096)
+        eng.set_option("tile_h", 0)
+    codes2, lp2 = eng.mpe_batch(e_off, ev, ec)
+    default = {k["name"]: k for k in eng.kernel_stats()}
+    assert np.array_equal(codes, codes2) and np.array_equal(lp, lp2)
+    for (vs, cs), c, l in zip(rows, codes, lp):
+        assert abs(mc.log_joint(f, c) - l) <= 1e-12, (vs, cs, l)
+        assert all(c[v] == x for v, x in zip(vs, cs))
+    # the forced run really tiled: a launch per tiled step, and more than one workgroup per launch
+    assert forced["ve_max_kernel"]["launches"] > default["ve_max_kernel"]["launches"], (forced, default)
+    assert forced["ve_max_kernel"]["items"] > forced["ve_max_kernel"]["launches"], forced
+    assert forced["mpe_traceback_kernel"]["items"] == 16
+
+
 def _large_cases():
     yield "mixed", netspec.mixed_grid_spec(4, 5, (2, 3, 5, 4, 7), seed=1)
     for entry in gu.load("huge_cards.json"):

@@ -1,5 +1,5 @@
 """Most probable explanation on the CPU: the max programs and traceback records the planner emits for mibn_mpe_batch, run by a host
-interpreter (tools/max_sim.cpp, linked against planner.cpp) and checked against plain numpy; plus the argument errors of
+interpreter (tools/prog_sim.cpp max, linked against planner.cpp) and checked against plain numpy; plus the argument errors of
 BayesNet.mpe / mpe_frame, raised before any engine exists."""
 import shutil
 

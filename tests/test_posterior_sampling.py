@@ -1,5 +1,5 @@
 """Exact posterior sampling on the device (BayesNet.sample(method="posterior") / sample_frame, mibn_posterior_sample_batch:
-ve_sum_kernel + posterior_draw_kernel) against its host twin tools/draw_sim.cpp row for row, against itself under other chunk /
+ve_sum_kernel + posterior_draw_kernel) against its host twin tools/prog_sim.cpp draw row for row, against itself under other chunk /
 thread / arena settings bit for bit, and against dense posteriors and query_frame marginals by chi-square.
 
 Seeds are the literals 0, 1, 2; the chi-square bound is draw_check.P_MIN (see tests/test_posterior_sampling_host.py)."""
@@ -106,6 +106,37 @@ def test_device_rows_equal_the_host_twin(draw_sim, tmp_path, grid):
     for prune in (0, 1):
         excused += _compare_with_twin(draw_sim, tmp_path, bn, f, reqs, 1, prune, f"C3/prune={prune}")
     assert excused <= 1
+
+
+def test_tiles_on_a_small_grid():
+    """The tile path of ve_sum_kernel at a small size: the 6 x 6 K = 4 grid, 4 requests of 300 samples (not a multiple of the
+    draw kernel's 256: a partial workgroup each), with the step classes forced as the parity tests force them (big_iters 256, odd
+    tiles of 3 hi iterations) - the big sum steps run as GENERIC tiles of the workgroup path, several workgroups each, where the
+    default options keep them in segments.  Both runs give the same rows and p_e bit for bit."""
+    bn = netspec.build(netspec.grid_spec(6, 6, 4), sorobn_amd.BayesNet).use_device(0)
+    eng = bn.backend.engine
+    rng = np.random.default_rng(36)
+    reqs = []
+    for r in range(4):
+        vs = sorted(rng.choice(36, size=1 + r % 2, replace=False).tolist())
+        reqs.append((vs, [int(rng.integers(0, 4)) for _ in vs], 300, 300 * r))
+    eng.set_option("big_iters", 256)
+    eng.set_option("tile_h", 3)
+    try:
+        rows, p_e = _device(bn, reqs, 0, 0)
+        forced = {k["name"]: k for k in eng.kernel_stats()}
+    finally:
+        eng.set_option("big_iters", 4096)
+        eng.set_option("tile_h", 0)
+    rows2, p_e2 = _device(bn, reqs, 0, 0)
+    default = {k["name"]: k for k in eng.kernel_stats()}
+    assert rows.shape == (1200, 36) and np.array_equal(rows, rows2) and np.array_equal(p_e, p_e2)
+    assert (rows >= 0).all() and (rows < 4).all() and (p_e > 0).all()
+    for i, (vs, cs, n, g) in enumerate(reqs):
+        assert (rows[g:g + n][:, vs] == np.array(cs)).all(), i
+    # the forced run really tiled: a launch per tiled step, and more than one workgroup per launch
+    assert forced["ve_sum_kernel"]["launches"] > default["ve_sum_kernel"]["launches"], (forced, default)
+    assert forced["ve_sum_kernel"]["items"] > forced["ve_sum_kernel"]["launches"], forced
 
 
 def test_codes_do_not_depend_on_chunk_threads_or_waves(grid):

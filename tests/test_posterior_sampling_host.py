@@ -1,5 +1,5 @@
 """Exact posterior sampling on the CPU: the draw programs and draw records the planner emits for mibn_posterior_sample_batch, run
-by the host twin (tools/draw_sim.cpp, linked against planner.cpp: same programs, same Philox stream, same arithmetic of the
+by the host twin (tools/prog_sim.cpp draw, linked against planner.cpp: same programs, same Philox stream, same arithmetic of the
 draw) and checked against the dense posterior in plain numpy; plus the argument errors of BayesNet.sample(method="posterior") /
 sample_frame, raised before any engine exists.
 
@@ -153,7 +153,7 @@ def test_stream_is_a_function_of_the_global_row(draw_sim, tmp_path):
 
 def test_mass_of_the_evidence_on_the_c3_grid(draw_sim, tmp_path):
     """Case 4 beyond the dense joint: on the 10 x 10 K = 4 grid p_e equals the P(e) of the evidence path's host interpreter
-    (tools/ev_sim.cpp) within 1e-12 relative, pruned or not, and the samples keep the evidence."""
+    (tools/prog_sim.cpp ev) within 1e-12 relative, pruned or not, and the samples keep the evidence."""
     entry = gu.load("grid10x10.json")
     f = mc.flat_of(netspec.build(gu.grid_spec_from_recipe(entry), sorobn_amd.BayesNet))
     rng = np.random.default_rng(3)
