@@ -26,11 +26,12 @@ using namespace mibn;
 static std::string g_err;
 static int g_order_effort = 0;
 static double g_second_above = 1e7;
-static int g_small_cells = 1024, g_big_iters = 4096, g_tile_h = 0, g_fuse = 1, g_prune = 1, g_chain = 1, g_sweep = 5, g_sweep_min = 2;
+static int g_small_cells = 1024, g_big_iters = 4096, g_tile_h = 0, g_fuse = 1, g_prune = 1, g_chain = 1, g_sweep = 5, g_sweep_min = 2, g_outer = 1;
 extern "C" void plan_sim_set_small_cells(int v) { g_small_cells = v; }
 extern "C" void plan_sim_set_tiling(int big_iters, int tile_h) { g_big_iters = big_iters; g_tile_h = tile_h; }
 extern "C" void plan_sim_set_fuse(int fuse) { g_fuse = fuse; }
 extern "C" void plan_sim_set_chain(int chain) { g_chain = chain; }
+extern "C" void plan_sim_set_outer(int outer) { g_outer = outer; }
 extern "C" void plan_sim_set_sweep(int sweep) { g_sweep = sweep; }
 extern "C" void plan_sim_set_sweep_min(int k) { g_sweep_min = k; }
 extern "C" void plan_sim_set_prune(int prune) { g_prune = prune; }
@@ -446,7 +447,7 @@ extern "C" int plan_sim_query_batch(int32_t n_vars, const int32_t *card, const i
     net.big_iters = g_big_iters;
     net.tile_h = g_tile_h;
     net.fuse = g_fuse;
-    net.chain = g_chain;
+    net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
     net.sweep_min = g_sweep_min;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
@@ -585,7 +586,7 @@ extern "C" int64_t plan_sim_cache_check(int32_t n_vars, const int32_t *card, con
     net.big_iters = g_big_iters;
     net.tile_h = g_tile_h;
     net.fuse = g_fuse;
-    net.chain = g_chain;
+    net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
     net.sweep_min = g_sweep_min;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
@@ -637,7 +638,7 @@ extern "C" int64_t plan_sim_program(int32_t n_vars, const int32_t *card, const i
     net.big_iters = g_big_iters;
     net.tile_h = g_tile_h;
     net.fuse = g_fuse;
-    net.chain = g_chain;
+    net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
     net.sweep_min = g_sweep_min;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
@@ -652,6 +653,41 @@ extern "C" int64_t plan_sim_program(int32_t n_vars, const int32_t *card, const i
     if ((int64_t)prog.size() > cap) return -2;
     std::memcpy(out, prog.data(), prog.size() * 4);
     return (int64_t)prog.size();
+}
+
+// The class of work (kernel_name) that executes every step of a program written by plan_sim_program under the options set now:
+// kernel_id_of_step for a step that is a level of its own (step_is_tiled), "segments" for a GENERIC step that runs in the segment
+// interpreter.  The names go to `out` one per step, each followed by '\n'; returns the number of steps, -1 for a malformed program,
+// -2 when `cap` bytes do not hold the names.  tile_h (may be null) receives step_tile_h of every tiled step - the hi iterations of one
+// workgroup - and 0 for the steps of segments.
+extern "C" int64_t plan_sim_step_classes(const uint32_t *prog, int64_t n_words, char *out, int64_t cap, int32_t *tile_h) {
+    if (n_words < 1) { g_err = "empty program"; return -1; }
+    EmitNet en;
+    en.big_iters = g_big_iters; en.tile_h = g_tile_h;  // (all that step_is_tiled / step_tile_h read of the options set here)
+    std::string names;
+    int64_t off = 1;
+    const int64_t n_steps = prog[0];
+    for (int64_t s = 0; s < n_steps; ++s) {
+        if (off + kHdrWords > n_words || prog[off + 6] < (uint32_t)kHdrWords || off + prog[off + 6] > n_words) { g_err = "step outside the program"; return -1; }
+        const uint32_t *w = prog + off;
+        const bool tiled = step_is_tiled(en, w);
+        names += kernel_name(tiled ? kernel_id_of_step(w) : kKidSeg);
+        if (tile_h) tile_h[s] = tiled ? step_tile_h(en, w) : 0;
+        names += '\n';
+        off += w[6];
+    }
+    if ((int64_t)names.size() + 1 > cap) return -2;
+    std::memcpy(out, names.c_str(), names.size() + 1);
+    return n_steps;
+}
+
+// every class name there is, in id order (kNumKernels of them), in the same form
+extern "C" int64_t plan_sim_class_names(char *out, int64_t cap) {
+    std::string names;
+    for (int k = 0; k < kNumKernels; ++k) { names += kernel_name(k); names += '\n'; }
+    if ((int64_t)names.size() + 1 > cap) return -2;
+    std::memcpy(out, names.c_str(), names.size() + 1);
+    return kNumKernels;
 }
 
 // The wave-cooperative device planner (csrc/wave_plan.h) compiled for the host - one lane runs every iteration of its lane loops
@@ -669,7 +705,7 @@ extern "C" int64_t wave_plan_program(int32_t n_vars, const int32_t *card, const 
     net.big_iters = g_big_iters;
     net.tile_h = g_tile_h;
     net.fuse = g_fuse;
-    net.chain = g_chain;
+    net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
     net.sweep_min = g_sweep_min;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
@@ -702,7 +738,7 @@ extern "C" int64_t plan_sim_program_tags(int32_t n_vars, const int32_t *card, co
     net.big_iters = g_big_iters;
     net.tile_h = g_tile_h;
     net.fuse = g_fuse;
-    net.chain = g_chain;
+    net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
     net.sweep_min = g_sweep_min;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
@@ -731,7 +767,7 @@ extern "C" double plan_sim_bench(int32_t n_vars, const int32_t *card, const int6
     Network net;
     g_err = net.set(n_vars, card, scope_off, scope_vars, value_off, values);
     if (!g_err.empty()) return -1;
-    net.chain = g_chain;
+    net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
     net.sweep_min = g_sweep_min;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
@@ -770,7 +806,7 @@ extern "C" int64_t plan_sim_device_style(int32_t n_vars, const int32_t *card, co
     g_err = net.set(n_vars, card, scope_off, scope_vars, value_off, values);
     if (!g_err.empty()) return -1;
     if (n_vars > 128) { g_err = "the device planner covers networks of up to 128 variables"; return -1; }
-    net.small_cells = g_small_cells; net.big_iters = g_big_iters; net.tile_h = g_tile_h; net.fuse = g_fuse; net.chain = g_chain;
+    net.small_cells = g_small_cells; net.big_iters = g_big_iters; net.tile_h = g_tile_h; net.fuse = g_fuse; net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep; net.sweep_min = g_sweep_min; net.prune = g_prune;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.set_hints(n_hints, hints);

@@ -33,6 +33,12 @@ def lib():
         L.plan_sim_set_tiling.argtypes = [C.c_int, C.c_int]
         L.plan_sim_set_fuse.argtypes = [C.c_int]
         L.plan_sim_set_chain.argtypes = [C.c_int]
+        L.plan_sim_set_outer.argtypes = [C.c_int]
+        L.plan_sim_set_order_effort.argtypes = [C.c_int, C.c_double]
+        L.plan_sim_step_classes.argtypes = [C.POINTER(C.c_uint32), C.c_int64, C.c_char_p, C.c_int64, C.POINTER(C.c_int32)]
+        L.plan_sim_step_classes.restype = C.c_int64
+        L.plan_sim_class_names.argtypes = [C.c_char_p, C.c_int64]
+        L.plan_sim_class_names.restype = C.c_int64
         L.plan_sim_set_sweep.argtypes = [C.c_int]
         L.plan_sim_set_sweep_min.argtypes = [C.c_int]
         L.plan_sim_set_prune.argtypes = [C.c_int]
@@ -49,6 +55,7 @@ class SimEngine:
         self.fuse = fuse                # joint elimination of two variables per FIBER step
         self.prune = 1                  # 0: multiply every CPT (full_joint_dist / predict_proba)
         self.chain = 1                  # CHAIN form (three variables per pass), on by default like the product
+        self.outer = 1                  # OUTER form (fp64 MFMA) for products of two big tables, on by default like the product
         self.sweep_min = 2              # fewest variables of a SWEEP pass (2: pair steps too)
         self.sweep = 5                  # SWEEP form (up to five variables per pass, tile in LDS), on by default like the product
         self.f = flat
@@ -72,6 +79,7 @@ class SimEngine:
         L.plan_sim_set_fuse(int(self.fuse))
         L.plan_sim_set_prune(int(self.prune))
         L.plan_sim_set_chain(int(self.chain))
+        L.plan_sim_set_outer(int(self.outer))
         L.plan_sim_set_sweep(int(self.sweep))
         L.plan_sim_set_sweep_min(int(self.sweep_min))
         rc = L.plan_sim_query(len(f.card), p(f.card, C.c_int32), p(f.scope_off, C.c_int64),
@@ -107,6 +115,7 @@ class SimEngine:
         L.plan_sim_set_fuse(int(self.fuse))
         L.plan_sim_set_prune(int(self.prune))
         L.plan_sim_set_chain(int(self.chain))
+        L.plan_sim_set_outer(int(self.outer))
         L.plan_sim_set_sweep(int(self.sweep))
         L.plan_sim_set_sweep_min(int(self.sweep_min))
         ev_ = evars.reshape(-1) if ne else np.zeros(1, np.int32)
@@ -135,6 +144,8 @@ class SimEngine:
             self.prune = int(value)
         elif name == "chain":
             self.chain = int(value)
+        elif name == "outer":
+            self.outer = int(value)
         elif name == "sweep":
             self.sweep = int(value)
         elif name == "sweep_min":

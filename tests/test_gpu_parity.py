@@ -102,9 +102,12 @@ def test_tiny_kernel_with_non_topological_ids(amd):
 
 
 # small_cells < 1024 forces the FIBER (streaming) step form, normally reserved for > 8 KiB tables, onto the
-# small golden networks: mixed cardinalities, sparse CPTs, every (n_big, cx, NC) kernel specialisation
-# (big_iters, tile_h) below the defaults (4096, auto) turn small steps into tiled levels, so the tile kernels
-# of every shape run on the small golden networks too; fuse = joint elimination of two variables per pass
+# small golden networks: mixed cardinalities, sparse CPTs; (big_iters, tile_h) below the defaults (4096, auto)
+# turn small steps into tiled levels; fuse = joint elimination of two variables per pass.  What that reaches:
+# on these four files the planner emits 18 of its 39 classes of work - segments, generic<2..6>, the NC = 1 FIBER
+# classes of every (n_big, cx), a few nc4 / ncN ones and OUTER (the census printed by
+# tests/test_kernel_classes_host.py) - and no nc16 or MFMA pair class.  Every class by name, with the
+# shapes inside it, is tests/class_cases.py, run on the device by tests/test_kernel_classes.py.
 @pytest.mark.parametrize("small_cells,tiling,fuse", [(1024, (4096, 0), 1), (1, (2, 1), 1), (6, (8, 3), 1), (1, (2, 1), 0)])
 @pytest.mark.parametrize("fname", ["examples.json", "random_dags.json", "wide_cards.json", "many_nodes.json"])
 def test_golden_networks(amd, fname, small_cells, tiling, fuse):
@@ -139,6 +142,10 @@ def test_golden_huge_cardinalities(amd, small_cells, tiling, fuse):
         seen.update(k["name"] for k in eng.kernel_stats())
     assert seen and "tiny_kernel" not in seen, seen
     print(f"huge cardinalities, small_cells {small_cells} tiling {tiling} fuse {fuse}: classes run = {sorted(seen)}")
+    # ... and they are the classes the planner writes for these inputs on the CPU (tests/test_kernel_classes_host.py measures the set)
+    from class_cases import HUGE_CARDS_CLASSES
+    classes = sorted(n for n in seen if n.startswith(("fiber<", "generic<", "ve_sweep")) or n == "segments")
+    assert classes == HUGE_CARDS_CLASSES[(small_cells, tiling, fuse)], classes
 
 
 @pytest.mark.parametrize("mfma_kernel", [1, 0])

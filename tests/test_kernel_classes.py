@@ -1,0 +1,114 @@
+"""The class matrix on the device (pytest -m gpu): every case of tests/class_cases.py - small pinned networks whose programs contain,
+between them, every class of work the planner can emit - against the C oracle, request by request and cell by cell, once with one
+launch per class (the statistics then name the classes that ran) and once in the product's launch shape (ve_mfma_kernel for the
+one-table fp64-MFMA classes, ve_segment_kernel for the segments), plus the level kernel's twin of the MFMA kernel.
+tests/test_kernel_classes_host.py proves on the CPU that the cases contain the classes and the edge shapes they claim."""
+import time
+
+import numpy as np
+import pytest
+
+import class_cases as cc
+import golden_util as gu
+from test_gpu_parity import amd  # noqa: F401  (the fixture of the GPU parity tests)
+
+pytestmark = pytest.mark.gpu
+
+TWIN_TOL = 1e-13  # two forms of one computation (the bound of test_wide_grids_every_request_vs_oracle between SWEEP and CHAIN)
+# the sweep class runs in ve_sweep_dma_kernel unless the engine option sweep_dma is off: the statistics carry the kernel's name
+STAT_NAMES = {cc.SWEEP: ("ve_sweep_kernel", "ve_sweep_dma_kernel")}
+
+_worst = {}   # class name -> largest |error| against the oracle over the requests whose programs contain it
+_ran = []     # (case name, seconds)
+_t0 = time.perf_counter()
+
+
+def _run(eng, flat, requests):
+    qv = cc.flat_ids(flat, [q for q, _, _ in requests])
+    ev = np.concatenate([cc.flat_ids(flat, e) for _, e, _ in requests]) if requests else np.zeros(0, np.int32)
+    ec = np.array([c for _, _, cs in requests for c in cs], np.int32)
+    q_off = np.arange(len(requests) + 1, dtype=np.int64)
+    e_off = np.concatenate([[0], np.cumsum([len(e) for _, e, _ in requests])]).astype(np.int64)
+    out, off = eng.query_batch(q_off, qv, e_off, ev, ec)
+    return [out[a:b] for a, b in zip(off[:-1], off[1:])], {k["name"] for k in eng.kernel_stats()}
+
+
+@pytest.mark.parametrize("case", cc.CASES, ids=[c["name"] for c in cc.CASES])
+def test_class_case_vs_oracle(amd, case):
+    import netspec
+    from oracle.oracle import OracleNet
+    t0 = time.perf_counter()
+    spec = cc.build_spec(case)
+    bn = netspec.build(spec, amd.BayesNet)
+    eng, flat = bn.backend.engine, bn.backend.flat
+    on = OracleNet(spec)
+    opt = cc.options(case)
+    eng.set_option("tiny", 0)       # (the small-network kernel would answer these networks without a program)
+    eng.set_option("adaptive", 0)   # the host plans, with the options of the case and nothing the policy turns
+    eng.set_option("gpu_emit", 0)
+    for name in cc.OPTION_NAMES:
+        eng.set_option(name, opt[name])
+    reqs = case["requests"]
+    want = [cc.oracle_dense(on, int(flat.card[flat.id[f"{q:03d}"]]), q, ev, ec) for q, ev, ec in reqs]
+
+    def vs_oracle(post, tag):
+        errs = [float(np.max(np.abs(p - w))) for p, w in zip(post, want)]
+        print(f"{case['name']} {tag}: max|err| vs oracle {max(errs):.3e}")
+        return errs
+
+    # (a) one launch per class of work: the statistics name the classes
+    eng.set_option("split_kinds", 1)
+    post_a, names_a = _run(eng, flat, reqs)
+    missing = [c for c in case["classes"] if not any(n in names_a for n in STAT_NAMES.get(c, (c,)))]
+    assert not missing, (missing, sorted(names_a))
+    errs_a = vs_oracle(post_a, "split_kinds=1")
+    # (b) the product's launch shape
+    eng.set_option("split_kinds", 0)
+    post_b, names_b = _run(eng, flat, reqs)
+    if any(c in cc.MFMA1 for c in case["classes"]):
+        assert "ve_mfma_kernel" in names_b, sorted(names_b)
+    if cc.SEGMENTS in case["classes"]:
+        assert "ve_segment_kernel" in names_b, sorted(names_b)
+    errs_b = vs_oracle(post_b, "split_kinds=0")
+    ab = max(float(np.max(np.abs(a - b))) for a, b in zip(post_a, post_b))
+    print(f"{case['name']}: max|split_kinds 1 - 0| {ab:.3e}")
+    errs_c, bc = [], 0.0
+    if any(c in cc.MFMA1 for c in case["classes"]):
+        # (c) the twin of ve_mfma_kernel inside ve_level_kernel
+        eng.set_option("mfma_kernel", 0)
+        post_c, names_c = _run(eng, flat, reqs)
+        assert "ve_mfma_kernel" not in names_c, sorted(names_c)
+        errs_c = vs_oracle(post_c, "mfma_kernel=0")
+        bc = max(float(np.max(np.abs(b - c))) for b, c in zip(post_b, post_c))
+        print(f"{case['name']}: max|mfma_kernel 1 - 0| {bc:.3e}")
+    # the figures per class, for the summary below (the simulator names the classes of every request's program)
+    cc.set_sim_options(opt)
+    try:
+        for i, rq in enumerate(reqs):
+            e = max([errs_a[i], errs_b[i]] + errs_c[i:i + 1])
+            for c in cc.planned(flat, [rq])[0]:
+                _worst[c] = max(_worst.get(c, 0.0), e)
+    finally:
+        cc.reset_sim_options()
+    assert max(errs_a) <= gu.TOL, errs_a
+    assert max(errs_b) <= gu.TOL, errs_b
+    assert ab <= TWIN_TOL, ab
+    if errs_c:
+        assert max(errs_c) <= gu.TOL, errs_c
+        assert bc <= TWIN_TOL, bc
+    _ran.append((case["name"], time.perf_counter() - t0))
+
+
+def test_class_matrix_summary():
+    """A reporting step: prints the largest error against the oracle per class, the number of cases and the wall time of this file
+    from what the cases above left in this module - so its assertions hold only when every case ran, and passed, in this process
+    (not under -k, not under xdist).  It writes no file: profiles/class_matrix_gpu.log is the captured output of one
+    `pytest -m gpu -s -v` run of this file, kept by hand, and does not refresh itself."""
+    print(f"class matrix: {len(_ran)} of {len(cc.CASES)} cases, {time.perf_counter() - _t0:.1f} s wall, "
+          f"slowest case {max([s for _, s in _ran] or [0.0]):.2f} s")
+    for c in sorted(_worst):
+        print(f"  {c:28s} max|err| vs oracle {_worst[c]:.3e}")
+    if len(_ran) == len(cc.CASES):
+        want = set().union(*[c["classes"] for c in cc.CASES])
+        assert set(_worst) == want, set(_worst) ^ want
+        assert max(_worst.values()) <= gu.TOL

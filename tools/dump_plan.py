@@ -29,9 +29,35 @@ def program(f, q, ev, codes):
     return out[:n]
 
 
-def decode(w):
-    """Decode a step program (planner.h encoding: 10-word header, GENERIC / FIBER bodies)."""
+def step_classes(w, tiles=False):
+    """The class of work (kernel_name) of every step of `w`, from the planner's own kernel_id_of_step / step_is_tiled under the
+    simulator's current options (oracle/plan_sim.cpp plan_sim_step_classes); a GENERIC step that is no level of its own is "segments".
+    With tiles=True: (names, hi iterations per workgroup of every tiled step - 0 for the steps of segments)."""
+    L = simengine.lib()
+    w = np.ascontiguousarray(w, np.uint32)
+    buf = C.create_string_buffer(64 * (int(w[0]) + 1))
+    th = np.zeros(int(w[0]) + 1, np.int32)
+    n = L.plan_sim_step_classes(w.ctypes.data_as(C.POINTER(C.c_uint32)), len(w), buf, len(buf), th.ctypes.data_as(C.POINTER(C.c_int32)))
+    assert n == int(w[0]), n
+    names = buf.value.decode().split("\n")[:n]
+    return (names, th[:n].tolist()) if tiles else names
+
+
+def class_names():
+    """Every name kernel_name() knows, in id order."""
+    L = simengine.lib()
+    buf = C.create_string_buffer(4096)
+    n = L.plan_sim_class_names(buf, len(buf))
+    assert n > 0, n
+    return buf.value.decode().split("\n")[:n]
+
+
+def decode(w, classes=False):
+    """Decode a step program (planner.h encoding: 10-word header, GENERIC / FIBER bodies) from its words alone.  classes=True adds,
+    from step_classes, `cls` - the step's class of work - and `tile_h`, the hi iterations one workgroup of it takes (0: a step of a
+    segment)."""
     steps = []
+    names, tile_h = step_classes(w, tiles=True) if classes else (None, None)
     n = int(w[0]); p = 1
     for _ in range(n):
         w0 = int(w[p]); kind = w0 & 0xff; n_in = (w0 >> 8) & 0xff; na = (w0 >> 16) & 0xff; nlo = (w0 >> 24) & 0xff
@@ -80,6 +106,8 @@ def decode(w):
                 q += 2 + nd3 + n3s * (2 + nd3)
             d["rax"] = [(int(w[q + 3 * a]), I(q + 3 * a + 1), I(q + 3 * a + 2)) for a in range(na)]; q += 3 * na
             d["bst"] = [[I(q + b * na + a) for a in range(na)] for b in range(nb)]
+        if classes:
+            d["cls"], d["tile_h"] = names[len(steps)], tile_h[len(steps)]
         steps.append(d)
         p += words
     return steps
@@ -92,12 +120,12 @@ if __name__ == "__main__":
     to_var = np.array([f.id[f"{i:03d}"] for i in range(100)], np.int32)
     qs, evs, ecs = netspec.c3_requests(100, 4, 4096, 4, seed=1)
     i = int(sys.argv[1]) if len(sys.argv) > 1 else 0
-    steps = decode(program(f, [to_var[qs[i]]], to_var[evs[i]], ecs[i]))
+    steps = decode(program(f, [to_var[qs[i]]], to_var[evs[i]], ecs[i]), classes=True)
     print("request", i, "q", qs[i], "ev", evs[i], "steps", len(steps))
     for k, s in enumerate(steps):
         if s["lo"] * s["hi"] < int(os.environ.get("MINCELLS", "1")):
             continue
-        head = f"{k:3d} {s['kind']:7s} cx={s['cx']} lo={s['lo']} hi={s['hi']} nlo={s['nlo']} na={s['na']} MB={s['bytes']/1e6:8.3f}"
+        head = f"{k:3d} {s['cls']} {s['kind']:7s} cx={s['cx']} lo={s['lo']} hi={s['hi']} nlo={s['nlo']} na={s['na']} MB={s['bytes']/1e6:8.3f}"
         if s["kind"] == "SWEEP":
             print(head, f"k={s['k']} kout={s['kout']} T={s['T']} stages=" + " ".join(f"[d{g['dig']} out{g['cout']} ns{g['ns']} ctrl{g['ctrl']} loop{g['loop']}]" for g in s["stages"]))
         elif s["kind"] == "GENERIC":
