@@ -681,6 +681,62 @@ extern "C" int64_t plan_sim_step_classes(const uint32_t *prog, int64_t n_words, 
     return n_steps;
 }
 
+// How the engine cuts the schedule of a CSR batch into kernel launches (planner.h level_groups) under the options set now and the four
+// routing options in the bits of `routing` (1 split_kinds, 2 seg_kernel, 4 mfma_kernel, 8 sweep_dma).  launches: per Launch entry of
+// the schedule {level, kid, route_of(kid), grid, wg_level, wg_first, alg_bytes}; groups: per launch group {route, level, stat_kid,
+// wg_level, wg_first, grid, alg_bytes, first_launch, n_launches}.  n_out: the two counts.  Returns 0, -2 when a capacity (in rows) is
+// too small, another negative number with plan_sim_error set.
+extern "C" int plan_sim_level_groups(int32_t n_vars, const int32_t *card, const int64_t *scope_off, const int32_t *scope_vars,
+                                     const int64_t *value_off, const double *values, int32_t n_hints, const int32_t *hints,
+                                     int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
+                                     const int32_t *e_codes, int32_t routing, double *launches, int64_t cap_launches, double *groups,
+                                     int64_t cap_groups, int64_t *n_out) {
+    Network net;
+    g_err = net.set(n_vars, card, scope_off, scope_vars, value_off, values);
+    if (!g_err.empty()) return -1;
+    net.small_cells = g_small_cells;
+    net.big_iters = g_big_iters;
+    net.tile_h = g_tile_h;
+    net.fuse = g_fuse;
+    net.chain = g_chain; net.outer = g_outer;
+    net.sweep = g_sweep;
+    net.sweep_min = g_sweep_min;
+    net.order_effort = g_order_effort; net.second_above = g_second_above;
+    net.prune = g_prune;
+    net.set_hints(n_hints, hints);
+    std::vector<int64_t> out_off((size_t)B + 1, 0);
+    for (int64_t b = 0; b < B; ++b) {
+        int64_t cells = 1;
+        for (int64_t k = q_off[b]; k < q_off[b + 1]; ++k) cells *= card[q_vars[k]];
+        out_off[(size_t)b + 1] = out_off[(size_t)b] + cells;
+    }
+    ThreadPool pool(1);
+    std::vector<ProgBuf> bufs;
+    BatchPlan bp;
+    plan_batch(net, pool, bufs, 0, B, q_off, q_vars, e_off, e_vars, e_codes, out_off.data(), nullptr, bp);
+    g_err = bp.err;
+    Schedule sc;
+    if (g_err.empty()) build_schedule(net, bp, bufs, 0, B, sc);
+    for (auto &b : bufs) b.release();
+    if (!g_err.empty()) return -6;
+    const LevelRouteOpts o{(routing & 1) != 0, (routing & 2) != 0, (routing & 4) != 0, (routing & 8) != 0};
+    std::vector<LaunchGroup> gs;
+    level_groups(sc, o, gs);
+    n_out[0] = (int64_t)sc.launches.size();
+    n_out[1] = (int64_t)gs.size();
+    if (n_out[0] > cap_launches || n_out[1] > cap_groups) return -2;
+    for (const Launch &L : sc.launches) {
+        const double row[7] = {(double)L.level, (double)L.kid, (double)(int)route_of(L.kid, o), (double)L.grid, (double)L.wg_level, (double)L.wg_first, L.alg_bytes};
+        launches = std::copy(row, row + 7, launches);
+    }
+    for (const LaunchGroup &g : gs) {
+        const double row[9] = {(double)(int)g.route, (double)g.level, (double)g.stat_kid, (double)g.wg_level, (double)g.wg_first, (double)g.grid, g.alg_bytes,
+                               (double)g.first_launch, (double)g.n_launches};
+        groups = std::copy(row, row + 9, groups);
+    }
+    return 0;
+}
+
 // every class name there is, in id order (kNumKernels of them), in the same form
 extern "C" int64_t plan_sim_class_names(char *out, int64_t cap) {
     std::string names;

@@ -180,6 +180,8 @@ __global__ __launch_bounds__(MIBN_PLAN_WG, MIBN_EMIT_WAVES_PER_EU) void emit_ker
 // proved erratic end to end (planning wall time doubles, runs between 155 k and 204 k queries/s against a steady
 // 194-204 k with two: profiles/r02_q_chunk_sets.log), so it stays an experiment.
 constexpr int kChunkSets = 4;
+// Streams of a wave's level launches (LevelStreams; the column `stream` of kLevelKernels): the lane's own and its three aux streams.
+constexpr int kLevelStreams = 4;
 // statistics slots: the classes of work (split_kinds: 0 .. kNumKernels - 1, kernel_name), then the kernels of mibn_query_batch as
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
@@ -209,7 +211,7 @@ struct mibn_ctx {
     Stream stream;       // kernels, gibbs, result download
     Stream copy_stream;  // program / schedule uploads: overlap the previous chunk's kernels
     Stream stream2;      // lane 1 (lane 0 = stream)
-    Stream aux[2][3];    // option overlap, per lane: the sweep kernel's, the segment kernel's and the MFMA kernel's launches
+    Stream aux[2][kLevelStreams - 1];  // option overlap, per lane: the sweep kernel's, the segment kernel's and the MFMA kernel's launches
     Stream search_stream;  // the device planner's (plan_stream)
     DevBuf<double> d_pool;
     // Lanes: consecutive chunks of a call alternate between two streams with an arena each and run CONCURRENTLY - requests are
@@ -238,11 +240,17 @@ struct mibn_ctx {
         DevBuf<Item> d_items;
         Event uploaded;                      // the copy stream has delivered this set's programs and schedule
         std::vector<Event> ev;               // launch boundaries of the waves in flight
-        struct Timed {  // kid >= 0: one launch; -1: the wall time of a wave (kernel_ms); -2: the launches of one level on the two streams of
-                        // option overlap, as ONE concurrent launch pair - events (e0, e1) of the level kernel's launch, (e2, e3) of the sweep
-                        // kernel's (kNone: the level has no such launch); its duration is the span from the earlier start to the later end
-            int kid; size_t e0, e1; double bytes, items; uint64_t call; size_t e2 = kNone, e3 = kNone, e4 = kNone, e5 = kNone, e6 = kNone, e7 = kNone;  // (e4, e5: the segment kernel's; e6, e7: the MFMA kernel's)
+        struct Timed {  // kid >= 0: one launch, booked to that statistics slot, between the events e[0]; kWave: the wall time of a wave
+                        // (kernel_ms), e[0] too; kLevelGroup: the launches of one level on the streams of option overlap, as ONE concurrent
+                        // launch group - e[s] brackets the launch on stream s (kNone: the level has none there); its duration is the span
+                        // from the earliest start to the latest end
+            enum Kind : int { kWave = -1, kLevelGroup = -2 };
             static constexpr size_t kNone = ~size_t(0);
+            int kid; size_t e[kLevelStreams][2]; double bytes, items; uint64_t call;
+            Timed(int kid_, size_t e0, size_t e1, double bytes_, double items_, uint64_t call_) : kid(kid_), bytes(bytes_), items(items_), call(call_) {
+                for (auto &p : e) p[0] = p[1] = kNone;
+                e[0][0] = e0; e[0][1] = e1;
+            }
         };
         std::vector<Timed> timed;
         size_t ev_used = 0;
@@ -250,6 +258,7 @@ struct mibn_ctx {
         int gap_from = -1;  // trace: index (in mibn_ctx::gap_ev) of the event that closed the previous wave
         BatchPlan plan;
         Schedule sched;
+        std::vector<LaunchGroup> groups;  // the launches of `sched`
         ~Set() {  // (ProgBuf is planner.h's, shared with the host tools: its backing is freed here)
             for (auto *v : {&bufs, &xbufs})
                 for (ProgBuf &b : *v) {
@@ -348,6 +357,7 @@ struct mibn_ctx {
         std::vector<ProgBuf> bufs;  // malloc-backed program buffers, one per worker
         BatchPlan plan;
         Schedule sched;
+        std::vector<LaunchGroup> groups;  // the launches of `sched`: one per level
         DevBuf<uint32_t> d_prog;
         DevBuf<uint64_t> d_prog_off, d_arena_off;
         DevBuf<Item> d_items;
@@ -848,33 +858,34 @@ int drained_on_error(mibn_ctx *h, int rc, void (*drain)(mibn_ctx *)) {
 
 // wait for a set's launches and book their HIP-event durations per kernel
 int retire(mibn_ctx *h, mibn_ctx::Set &st) {
+    using Timed = mibn_ctx::Set::Timed;
     if (!st.busy) return MIBN_OK;
     HIP_TRY(h, hipEventSynchronize(st.ev[st.ev_used - 1]));
     for (auto &t : st.timed) {
         float ms = 0;
-        if (t.kid != -2) HIP_TRY(h, hipEventElapsedTime(&ms, st.ev[t.e0], st.ev[t.e1]));  // (-2: a level's launch group - any of its event pairs may be absent)
+        if (t.kid != Timed::kLevelGroup) HIP_TRY(h, hipEventElapsedTime(&ms, st.ev[t.e[0][0]], st.ev[t.e[0][1]]));  // (a level's launch group: any of its event pairs may be absent)
         const bool mine = t.call == h->call_id;  // (launches of an earlier asynchronous call only count in the totals)
-        if (t.kid == -1) {
+        if (t.kid == Timed::kWave) {
             h->retired_requests += t.items;  // (the wave's requests)
             // GPU time of a wave, first launch to last.  With two lanes the waves of consecutive chunks overlap: what is
             // booked as kernel_ms is the time the GPU was busy (the union of the intervals, kept as a high-water mark
             // since the epoch event; sets retire in launch order)
             float t0 = 0, t1 = 0;
-            HIP_TRY(h, hipEventElapsedTime(&t0, h->epoch, st.ev[t.e0]));
-            HIP_TRY(h, hipEventElapsedTime(&t1, h->epoch, st.ev[t.e1]));
+            HIP_TRY(h, hipEventElapsedTime(&t0, h->epoch, st.ev[t.e[0][0]]));
+            HIP_TRY(h, hipEventElapsedTime(&t1, h->epoch, st.ev[t.e[0][1]]));
             const double add = std::max(0.0, (double)t1 - std::max((double)t0, h->busy_until));
             h->busy_until = std::max(h->busy_until, (double)t1);
             if (mine) h->stats.kernel_ms += add;
             h->total.kernel_ms += add;
             continue;
         }
-        if (t.kid == -2) {
-            // one level = one concurrent launch pair: from the earlier start to the later end (timestamps against the epoch event)
+        if (t.kid == Timed::kLevelGroup) {
+            // one level = one concurrent launch group: from the earliest start to the latest end (timestamps against the epoch event)
             double lo = 1e300, hi = -1e300;
-            for (size_t e : {t.e0, t.e2, t.e4, t.e6})
-                if (e != mibn_ctx::Set::Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[e])); lo = std::min(lo, (double)x); }
-            for (size_t e : {t.e1, t.e3, t.e5, t.e7})
-                if (e != mibn_ctx::Set::Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[e])); hi = std::max(hi, (double)x); }
+            for (const auto &p : t.e)
+                if (p[0] != Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[p[0]])); lo = std::min(lo, (double)x); }
+            for (const auto &p : t.e)
+                if (p[1] != Timed::kNone) { float x = 0; HIP_TRY(h, hipEventElapsedTime(&x, h->epoch, st.ev[p[1]])); hi = std::max(hi, (double)x); }
             book_stat(h, kStatLevelGroup, 1, std::max(0.0, hi - lo), t.bytes, t.items, mine, true);
             continue;
         }
@@ -1872,13 +1883,28 @@ int upload_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t n, bool on_device, size
 // The launches of a wave on the streams of its lane.  Option overlap: the sweep launch of a level goes to a second stream, next to the
 // level kernel's launch of the same level (their items belong to different requests); level L + 1 starts on either stream when BOTH
 // launches of level L have finished.  The tail of one launch - a sweep workgroup lives ~100 us - then runs under the body of the other.
-// Streams of a wave: 0 = S (the level kernel), 1 = S2 (the sweep kernel), 2 = S3 (the segment kernel, option seg_kernel), 3 = S4 (the MFMA
-// kernel, option mfma_kernel).  The launches of level L run side by side; a launch of level L + 1 waits for ALL launches of level L: the
-// one on its own stream by stream order, the others through their end events (`prev`: the ends of the previous level - not the running
-// `last`, or the launches of one level would serialise: ADVICE r3).  Without the option every launch goes to S and nothing waits.
+// Streams of a wave: 0 = S, 1 .. 3 = the lane's aux streams; kLevelKernels says which kernel launches on which.  The launches of level L
+// run side by side; a launch of level L + 1 waits for ALL launches of level L: the one on its own stream by stream order, the others
+// through their end events (`prev`: the ends of the previous level - not the running `last`, or the launches of one level would
+// serialise: ADVICE r3).  Without the option every launch goes to S and nothing waits.
+//
+// The kernels of a level, one row per LevelRoute (planner.h: route_of sends a class of work to its row, level_groups cuts a level's
+// Launch entries into one launch per row).  A new kernel is one row here, one enumerator and one predicate in route_of, and - if it
+// is to run beside the others - one more stream (kLevelStreams).  `slot`: the statistics slot of its launches; under split_kinds a
+// launch is booked to its class id instead (LaunchGroup::stat_kid), except ve_sweep_dma_kernel's, which keep their slot.
+struct LevelKernel { void (*kernel)(LevelArgs); unsigned block, lds_bytes; int stream, slot; };
+constexpr LevelKernel kLevelKernels[kNumLevelRoutes] = {
+    /* Level    */ {ve_level_kernel, kWG, 0, 0, kStatLevel},
+    /* SweepDma */ {ve_sweep_dma_kernel, kSweepWG, kSweepLdsBytes, 1, kStatSweepDma},
+    /* SweepReg */ {ve_sweep_kernel, kSweepWG, kSweepLdsBytes, 1, kKidSweep},
+    /* Segment  */ {ve_segment_kernel, kWG, 0, 2, kStatSegment},
+    /* Mfma     */ {ve_mfma_kernel, kWG, 0, 3, kStatMfma},
+};
+static_assert((int)LevelRoute::Level == 0 && (int)LevelRoute::SweepDma == 1 && (int)LevelRoute::SweepReg == 2 && (int)LevelRoute::Segment == 3 && (int)LevelRoute::Mfma == 4, "the rows' order");
+
 struct LevelStreams {
     using Timed = mibn_ctx::Set::Timed;
-    static constexpr int kNS = 4;
+    static constexpr int kNS = kLevelStreams;
     mibn_ctx *h;
     mibn_ctx::Set &st;
     const bool two;
@@ -1891,12 +1917,11 @@ struct LevelStreams {
         : h(h_), st(st_), two(h_->overlap != 0), SS{S, h_->aux[lane][0], h_->aux[lane][1], h_->aux[lane][2]}, pair(fresh()) {
         for (int a = 0; a < kNS; ++a) { last[a] = prev[a] = -1; for (int b = 0; b < kNS; ++b) saw[a][b] = -1; }
     }
-    Timed fresh() const { return Timed{-2, Timed::kNone, Timed::kNone, 0.0, 0.0, h->call_id}; }
+    Timed fresh() const { return Timed{Timed::kLevelGroup, Timed::kNone, Timed::kNone, 0.0, 0.0, h->call_id}; }
     void close_pair() {
-        if (pair.e0 != Timed::kNone || pair.e2 != Timed::kNone || pair.e4 != Timed::kNone || pair.e6 != Timed::kNone) st.timed.push_back(pair);
+        if (std::any_of(std::begin(pair.e), std::end(pair.e), [](const size_t (&p)[2]) { return p[0] != Timed::kNone; })) st.timed.push_back(pair);
         pair = fresh();
     }
-    int stream_of(bool sweep, bool seg, bool mf) const { return two ? (sweep ? 1 : (seg ? 2 : (mf ? 3 : 0))) : 0; }
     // the wave's first event (the uploads, the previous wave's kernels: the arena is theirs until then) holds the other streams back
     int begin(size_t e_first) {
         for (int j = 1; two && j < kNS; ++j) HIP_TRY(h, hipStreamWaitEvent(SS[j], st.ev[e_first], 0));
@@ -1915,7 +1940,7 @@ struct LevelStreams {
         if (!two) return;
         last[si] = (long)e1;
         if (h->split_kinds) return;
-        if (si == 1) { pair.e2 = e0; pair.e3 = e1; } else if (si == 2) { pair.e4 = e0; pair.e5 = e1; } else if (si == 3) { pair.e6 = e0; pair.e7 = e1; } else { pair.e0 = e0; pair.e1 = e1; }
+        pair.e[si][0] = e0; pair.e[si][1] = e1;
         pair.bytes += bytes;
         pair.items += grid;
     }
@@ -1972,45 +1997,26 @@ int run_wave(QueryRun &R, mibn_ctx::Set &st, int lane, hipStream_t S, int64_t b0
     if ((rc = next_event(h, st, e_first, S))) return rc;
     LevelStreams LS(h, st, lane, S);
     if ((rc = LS.begin(e_first))) return rc;
-    // (the two classes of ve_mfma_kernel are the last ones of a level in front of the sweep class: planner.cpp ClassOrder)
-    auto is_mfma1 = [&](int kid) { return h->mfma_kernel && !h->split_kinds && (kid == kKidFiber0 + 4 || kid == kKidFiber0 + 6 + 4); };
-    for (size_t li = 0; li < sc.launches.size();) {
-        // one launch of the level kernel per level (all its classes of work together) unless split_kinds, one of the
-        // segment kernel for the level's segments (the first class of a level; option seg_kernel) and one of the sweep kernel
-        // for its SWEEP items (the last class: its own LDS budget)
-        size_t lj = li + 1;
-        const Launch &L = sc.launches[li];
-        const bool sweep = L.kid == kKidSweep;
-        const bool seg = h->seg_kernel && !h->split_kinds && L.kid == kKidSeg;
-        const bool mf = is_mfma1(L.kid);
-        double bytes = L.alg_bytes;
-        size_t grid = L.grid;
-        if (!h->split_kinds && !sweep && !seg)
-            for (; lj < sc.launches.size() && sc.launches[lj].level == L.level && sc.launches[lj].kid != kKidSweep && is_mfma1(sc.launches[lj].kid) == mf; ++lj) {
-                bytes += sc.launches[lj].alg_bytes;
-                grid += sc.launches[lj].grid;
-            }
-        A.wg_item = st.d_wg_item + L.wg_level;
-        A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
+    // one launch per group of a level's classes of work: planner.h level_groups, kLevelKernels
+    level_groups(sc, {h->split_kinds != 0, h->seg_kernel != 0, h->mfma_kernel != 0, h->sweep_dma != 0}, st.groups);
+    for (const LaunchGroup &g : st.groups) {
+        const LevelKernel &K = kLevelKernels[(int)g.route];
+        A.wg_item = st.d_wg_item + g.wg_level;
+        A.wg_base = (uint32_t)(g.wg_first - g.wg_level);
         size_t e0 = 0, e1 = 0;
-        const int si = LS.stream_of(sweep, seg, mf);
+        const int si = LS.two ? K.stream : 0;
         hipStream_t Sx = LS.SS[si];
-        if ((rc = LS.before(L.level, si))) return rc;
+        if ((rc = LS.before(g.level, si))) return rc;
         if ((rc = next_event(h, st, e0, Sx))) return rc;
-        if (sweep && h->sweep_dma) hipLaunchKernelGGL(ve_sweep_dma_kernel, dim3((unsigned)grid), dim3(kSweepWG), kSweepLdsBytes, Sx, A);
-        else if (sweep) hipLaunchKernelGGL(ve_sweep_kernel, dim3((unsigned)grid), dim3(kSweepWG), kSweepLdsBytes, Sx, A);
-        else if (seg) hipLaunchKernelGGL(ve_segment_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
-        else if (mf) hipLaunchKernelGGL(ve_mfma_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
-        else hipLaunchKernelGGL(ve_level_kernel, dim3((unsigned)grid), dim3(kWG), 0, Sx, A);
+        hipLaunchKernelGGL(K.kernel, dim3((unsigned)g.grid), dim3(K.block), K.lds_bytes, Sx, A);
         if ((rc = next_event(h, st, e1, Sx))) return rc;
-        LS.after(si, e0, e1, bytes, (double)grid);
-        st.timed.push_back({sweep ? (h->sweep_dma ? kStatSweepDma : kKidSweep) : (seg ? kStatSegment : (mf ? kStatMfma : (h->split_kinds ? L.kid : kStatLevel))), e0, e1, bytes, (double)grid, h->call_id});
-        n_wg += (double)grid;
-        li = lj;
+        LS.after(si, e0, e1, g.alg_bytes, (double)g.grid);
+        st.timed.push_back({g.stat_kid >= 0 && g.route != LevelRoute::SweepDma ? g.stat_kid : K.slot, e0, e1, g.alg_bytes, (double)g.grid, h->call_id});
+        n_wg += (double)g.grid;
     }
     if ((rc = LS.end())) return rc;
     if ((rc = next_event(h, st, e_last, S))) return rc;
-    st.timed.push_back({-1, e_first, e_last, 0.0, (double)(r1 - r0), h->call_id});
+    st.timed.push_back({mibn_ctx::Set::Timed::kWave, e_first, e_last, 0.0, (double)(r1 - r0), h->call_id});
     HIP_TRY(h, hipGetLastError());
     if (h->trace) {
         Event &ge = h->gap_ev[h->n_waves & 3];
@@ -2327,20 +2333,12 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
             A.results = M.d_m;  // (FINAL offsets are chunk-relative: the cell of request b at b - b0)
             A.items = M.d_items;
             // one launch per level: every class of work of such a schedule (segments, GENERIC tiles) is the payload's level kernel's
-            for (size_t li = 0; li < sc.launches.size();) {
-                size_t lj = li + 1;
-                double bytes = sc.launches[li].alg_bytes;
-                size_t grid = sc.launches[li].grid;
-                for (; lj < sc.launches.size() && sc.launches[lj].level == sc.launches[li].level; ++lj) {
-                    bytes += sc.launches[lj].alg_bytes;
-                    grid += sc.launches[lj].grid;
-                }
-                const Launch &L = sc.launches[li];
-                A.wg_item = M.d_wg_item + L.wg_level;
-                A.wg_base = (uint32_t)(L.wg_first - L.wg_level);
-                if ((rc = R.timed_launch(Payload::kLevelSlot, bytes, (double)grid, [&] { P.launch_level((unsigned)grid, S, A); }))) return rc;
-                h->stats.n_workgroups += (double)grid;
-                li = lj;
+            group_launches(sc, false, [](int) { return LevelRoute::Level; }, M.groups);
+            for (const LaunchGroup &g : M.groups) {
+                A.wg_item = M.d_wg_item + g.wg_level;
+                A.wg_base = (uint32_t)(g.wg_first - g.wg_level);
+                if ((rc = R.timed_launch(Payload::kLevelSlot, g.alg_bytes, (double)g.grid, [&] { P.launch_level((unsigned)g.grid, S, A); }))) return rc;
+                h->stats.n_workgroups += (double)g.grid;
             }
             HIP_TRY(h, hipGetLastError());
             if ((rc = P.after_levels(R))) return rc;

@@ -1470,26 +1470,41 @@ const char *kernel_name(int kid) {
 // workgroups run long and move little - segments, GENERIC tiles, the two-table VALU forms: 80-170 us per workgroup -
 // go first, so that they finish under the streaming classes instead of forming the tail of every level.
 struct ClassOrder {
-    int rank_of[kNumKernels], kid_at[kNumKernels];
-    ClassOrder() {
-        std::vector<int> order;
-        auto add = [&](int kid) { if (std::find(order.begin(), order.end(), kid) == order.end()) order.push_back(kid); };
+    int rank_of[kNumKernels] = {}, kid_at[kNumKernels] = {};
+    constexpr ClassOrder() {
+        int n = 0;
+        bool seen[kNumKernels] = {};
+        auto add = [&](int kid) { if (!seen[kid]) { seen[kid] = true; kid_at[n] = kid; rank_of[kid] = n++; } };
         add(kKidSeg);
         for (int j = 0; j < kMaxIn; ++j) add(kKidGeneric0 + j);
-        for (int n : {3, 1, 2, 0})  // two tables, VALU: ncN, nc4, nc16, nc1
-            for (int c = 2; c >= 0; --c) add(kKidFiber0 + 18 + c * 6 + n);
+        constexpr int two_table_nc[4] = {3, 1, 2, 0};  // two tables, VALU: ncN, nc4, nc16, nc1
+        for (int n2 : two_table_nc)
+            for (int c = 2; c >= 0; --c) add(kKidFiber0 + 18 + c * 6 + n2);
         for (int c = 2; c >= 0; --c) add(kKidFiber0 + c * 6 + 3);                          // one table, ncN
-        for (int n = 0; n < 6; ++n) add(kKidFiber0 + 2 * 6 + n);                            // one table, runtime cx
+        for (int k = 0; k < 6; ++k) add(kKidFiber0 + 2 * 6 + k);                            // one table, runtime cx
         for (int c = 0; c < 2; ++c) add(kKidFiber0 + 18 + c * 6 + 5);                       // OUTER
         for (int kid = 0; kid < kNumKernels; ++kid)                                        // the streaming classes ...
-            if (kid != kKidFiber0 + 4 && kid != kKidFiber0 + 6 + 4 && kid != kKidSweep) add(kid);
-        add(kKidFiber0 + 4);      // ... the one-table fp64-MFMA pair classes last among them (contiguous: engine option mfma_kernel
-        add(kKidFiber0 + 6 + 4);  //     launches the two as ve_mfma_kernel), then the sweep class (a kernel of its own)
+            if (!is_mfma1_class(kid) && kid != kKidSweep) add(kid);
+        add(kKidMfma1Cx4);   // ... the one-table fp64-MFMA pair classes last among them, then the sweep class (a kernel of its own)
+        add(kKidMfma1Cx16);
         add(kKidSweep);
-        for (int r = 0; r < kNumKernels; ++r) { kid_at[r] = order[(size_t)r]; rank_of[order[(size_t)r]] = r; }
+    }
+    // what group_launches relies on: under every setting of the routing options the classes of a route are one run of the order
+    constexpr bool routes_contiguous() const {
+        for (int k = 0; k < 16; ++k) {
+            const LevelRouteOpts o{(k & 1) != 0, (k & 2) != 0, (k & 4) != 0, (k & 8) != 0};
+            bool closed[kNumLevelRoutes] = {};
+            for (int r = 0; r < kNumKernels; ++r) {
+                const int route = (int)route_of(kid_at[r], o);
+                if (closed[route]) return false;
+                if (r + 1 < kNumKernels && (int)route_of(kid_at[r + 1], o) != route) closed[route] = true;
+            }
+        }
+        return true;
     }
 };
-static const ClassOrder kClassOrder;
+constexpr ClassOrder kClassOrder;
+static_assert(kClassOrder.routes_contiguous(), "the classes of a kernel must be contiguous in the class order: level_groups merges neighbours only");
 
 void build_schedule(const Network &net, const BatchPlan &bp, const std::vector<ProgBuf> &bufs, int64_t r0, int64_t r1,
                     Schedule &out) {
@@ -1615,6 +1630,10 @@ void build_schedule(const Network &net, const BatchPlan &bp, const std::vector<P
             out.launches.push_back({level, kid, count[k], count[k + 1] - count[k], wg_first, wg - wg_first, wg_level, bytes[k]});
         }
     out.wg_item.resize(wg);  // (sized for one workgroup per segment above)
+}
+
+void level_groups(const Schedule &sc, const LevelRouteOpts &o, std::vector<LaunchGroup> &out) {
+    group_launches(sc, o.split_kinds, [&](int kid) { return route_of(kid, o); }, out);
 }
 
 }  // namespace mibn

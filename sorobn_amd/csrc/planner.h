@@ -356,6 +356,41 @@ struct Schedule {
 void build_schedule(const Network &net, const BatchPlan &bp, const std::vector<ProgBuf> &bufs, int64_t r0, int64_t r1,
                     Schedule &out);
 
+// Which kernel runs a class of work (the engine's table kLevelKernels has one row per route), and how the Launch entries of a level
+// become kernel launches.  The engine options that decide it:
+struct LevelRouteOpts { bool split_kinds, seg_kernel, mfma_kernel, sweep_dma; };
+enum class LevelRoute { Level, SweepDma, SweepReg, Segment, Mfma };
+constexpr int kNumLevelRoutes = 5;
+constexpr int kKidMfma1Cx4 = kKidFiber0 + 4, kKidMfma1Cx16 = kKidFiber0 + 6 + 4;  // fiber<1,cx4,nc16-mfma>, fiber<1,cx16,nc16-mfma>
+constexpr bool is_mfma1_class(int kid) { return kid == kKidMfma1Cx4 || kid == kKidMfma1Cx16; }  // the one-table fp64-MFMA pair classes
+constexpr LevelRoute route_of(int kid, const LevelRouteOpts &o) {
+    if (kid == kKidSweep) return o.sweep_dma ? LevelRoute::SweepDma : LevelRoute::SweepReg;  // (its own LDS budget: never the level kernel's)
+    if (o.split_kinds) return LevelRoute::Level;  // one launch per class, all of the level kernel
+    if (o.seg_kernel && kid == kKidSeg) return LevelRoute::Segment;
+    if (o.mfma_kernel && is_mfma1_class(kid)) return LevelRoute::Mfma;
+    return LevelRoute::Level;
+}
+// One kernel launch: the consecutive Launch entries [first_launch, first_launch + n_launches) of one level that share a route - every
+// entry on its own where `each_alone`.  The classes of a route are contiguous in the class order of build_schedule (checked where
+// that order is built), so a level has at most one group per route.
+struct LaunchGroup {
+    LevelRoute route; int level, stat_kid;  // stat_kid: the class id where every entry is its own group (split_kinds), else -1
+    size_t wg_level, wg_first, grid; double alg_bytes; size_t first_launch, n_launches;
+};
+template <class RouteOf>
+void group_launches(const Schedule &sc, bool each_alone, RouteOf &&route, std::vector<LaunchGroup> &out) {
+    out.clear();
+    for (size_t li = 0; li < sc.launches.size(); ++li) {
+        const Launch &L = sc.launches[li];
+        const LevelRoute r = route(L.kid);
+        if (each_alone || out.empty() || out.back().level != L.level || out.back().route != r)
+            out.push_back({r, L.level, each_alone ? L.kid : -1, L.wg_level, L.wg_first, 0, 0.0, li, 0});
+        LaunchGroup &g = out.back();
+        g.grid += L.grid; g.alg_bytes += L.alg_bytes; ++g.n_launches;
+    }
+}
+void level_groups(const Schedule &sc, const LevelRouteOpts &o, std::vector<LaunchGroup> &out);
+
 // Validate a request (unknown ids, duplicates, overlap) - bayes_net.py:840-845 and the KeyError of 770.  nq = 0 is valid only with
 // ProgramKind::Raw or ProgramKind::Map.
 std::string validate_request(const Network &net, const Request &rq);  // "" or the reference's error message

@@ -128,6 +128,47 @@ def planned(flat, requests):
     return classes, edges, cells
 
 
+ROUTES = ("level", "sweep_dma", "sweep_reg", "segment", "mfma")  # planner.h LevelRoute, in order: the kernel a launch group goes to
+ROUTING_OPTIONS = ("split_kinds", "seg_kernel", "mfma_kernel", "sweep_dma")  # bit k of a routing setting; the engine's defaults: 0, 1, 1, 1
+ROUTING_DEFAULT = 0b1110
+# the smallest pair of cases whose classes reach all four kernels of a level between them: segments, a level-kernel class and an MFMA1
+# class in the first; segments, level-kernel classes and SWEEP in the second (test_kernel_classes_host.py proves it)
+ROUTING_CASES = ("34-dag84812n9-sc16-bi256x0", "35-dag87864n12-sc256-bi64x2")
+
+
+def level_groups(flat, requests, routing):
+    """(launches, groups) of the schedule of `requests` as one batch under the simulator's options and the routing setting `routing`
+    (bits: ROUTING_OPTIONS) - oracle/plan_sim.cpp plan_sim_level_groups, the planner's own level_groups.  Dictionaries with the fields
+    of planner.h Launch (+ route) and LaunchGroup; routes by name, classes by name (cls; stat_cls: None unless split_kinds)."""
+    import ctypes as C
+    import dump_plan as dp
+    import simengine
+    L = simengine.lib()
+    i32p, i64p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    L.plan_sim_level_groups.argtypes = [C.c_int32, i32p, i64p, i32p, i64p, f64p, C.c_int32, i32p, C.c_int64, i64p, i32p, i64p, i32p, i32p,
+                                        C.c_int32, f64p, C.c_int64, f64p, C.c_int64, i64p]
+    p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    qv = flat_ids(flat, [q for q, _, _ in requests])
+    ev = np.ascontiguousarray(np.concatenate([flat_ids(flat, e) for _, e, _ in requests] + [np.zeros(1, np.int32)]), np.int32)
+    ec = np.array([c for _, _, cs in requests for c in cs] + [0], np.int32)
+    q_off = np.arange(len(requests) + 1, dtype=np.int64)
+    e_off = np.concatenate([[0], np.cumsum([len(e) for _, e, _ in requests])]).astype(np.int64)
+    hints = np.ascontiguousarray(np.stack(flat.hints).reshape(-1) if flat.hints else [0], np.int32)
+    cap = 4096
+    la, gr, n = np.zeros((cap, 7)), np.zeros((cap, 9)), np.zeros(2, np.int64)
+    rc = L.plan_sim_level_groups(len(flat.card), p(flat.card, C.c_int32), p(flat.scope_off, C.c_int64), p(flat.scope_vars, C.c_int32),
+                                 p(flat.value_off, C.c_int64), p(flat.values, C.c_double), len(flat.hints), p(hints, C.c_int32),
+                                 len(requests), p(q_off, C.c_int64), p(qv, C.c_int32), p(e_off, C.c_int64), p(ev, C.c_int32), p(ec, C.c_int32),
+                                 routing, p(la, C.c_double), cap, p(gr, C.c_double), cap, p(n, C.c_int64))
+    assert rc == 0, (rc, L.plan_sim_error().decode())
+    names = dp.class_names()
+    launches = [dict(level=int(r[0]), cls=names[int(r[1])], route=ROUTES[int(r[2])], grid=int(r[3]), wg_level=int(r[4]), wg_first=int(r[5]),
+                     alg_bytes=float(r[6])) for r in la[:n[0]]]
+    groups = [dict(route=ROUTES[int(r[0])], level=int(r[1]), stat_cls=names[int(r[2])] if r[2] >= 0 else None, wg_level=int(r[3]),
+                   wg_first=int(r[4]), grid=int(r[5]), alg_bytes=float(r[6]), first_launch=int(r[7]), n_launches=int(r[8])) for r in gr[:n[1]]]
+    return launches, groups
+
+
 def oracle_dense(on, card, q, ev, ec):
     """The oracle's posterior of one request as a dense vector over the query node's codes."""
     codes, vals = on.query_codes([on.id[f"{q:03d}"]], [on.id[f"{v:03d}"] for v in ev], list(ec))

@@ -99,6 +99,70 @@ def test_class_case_vs_oracle(amd, case):
     _ran.append((case["name"], time.perf_counter() - t0))
 
 
+def test_level_routing_table(amd):
+    """The engine's table of level kernels (engine.hip kLevelKernels, planner.h route_of / level_groups) under every setting of the
+    options that choose a launch's kernel and stream: cc.ROUTING_CASES - segments, level-kernel classes, an MFMA1 class and SWEEP
+    between them - with overlap, seg_kernel, mfma_kernel and sweep_dma each 0 and 1 in the product's launch shape, and the default
+    setting once more with one launch per class.  Posteriors against the oracle and against the default setting's; the statistics
+    rows are the kernels the setting names, and their launches and workgroups add up to the call's.
+    (The "level:" launch-group row is booked per level in the product's launch shape only: with split_kinds 1 it is absent, overlap or not.)"""
+    import netspec
+    from oracle.oracle import OracleNet
+    GROUP, PLANNER = "level:", "order_kernel+emit_kernel"
+    default = dict(overlap=1, seg_kernel=1, mfma_kernel=1, sweep_dma=1, split_kinds=0)
+    settings = [default] + [dict(overlap=o, seg_kernel=s, mfma_kernel=m, sweep_dma=d, split_kinds=0)
+                            for o in (0, 1) for s in (0, 1) for m in (0, 1) for d in (0, 1) if (o, s, m, d) != (1, 1, 1, 1)]
+    settings.append(dict(default, split_kinds=1))
+    assert len(settings) == 17
+    reached = set()
+    for case in [c for c in cc.CASES if c["name"] in cc.ROUTING_CASES]:
+        spec = cc.build_spec(case)
+        bn = netspec.build(spec, amd.BayesNet)
+        eng, flat = bn.backend.engine, bn.backend.flat
+        on = OracleNet(spec)
+        eng.set_option("tiny", 0)
+        eng.set_option("adaptive", 0)
+        eng.set_option("gpu_emit", 0)
+        for name, v in cc.options(case).items():
+            eng.set_option(name, v)
+        reqs, classes = case["requests"], set(case["classes"])
+        want = [cc.oracle_dense(on, int(flat.card[flat.id[f"{q:03d}"]]), q, ev, ec) for q, ev, ec in reqs]
+        base = None
+        for opt in settings:
+            for name, v in opt.items():
+                eng.set_option(name, v)
+            post, _ = _run(eng, flat, reqs)
+            rows, st = eng.kernel_stats(), eng.stats()
+            base = post if base is None else base
+            err = max(float(np.max(np.abs(p - w))) for p, w in zip(post, want))
+            twin = max(float(np.max(np.abs(p - b))) for p, b in zip(post, base))
+            names = {k["name"] for k in rows}
+            kernels = [k for k in rows if not k["name"].startswith(GROUP) and k["name"] != PLANNER]
+            print(f"{case['name']} {opt}: max|err| vs oracle {err:.3e}, vs the default setting {twin:.3e}; {sorted(names)}; "
+                  f"launches {sum(k['launches'] for k in kernels):.0f} / {st['n_launches']:.0f}, workgroups {sum(k['items'] for k in kernels):.0f} / {st['n_workgroups']:.0f}")
+            assert err <= gu.TOL, (opt, err)
+            assert twin <= TWIN_TOL, (opt, twin)
+            assert sum(k["launches"] for k in kernels) == st["n_launches"] > 0, opt
+            assert sum(k["items"] for k in kernels) == st["n_workgroups"] > 0, opt
+            sweep_row = "ve_sweep_dma_kernel" if opt["sweep_dma"] else "ve_sweep_kernel"
+            if opt["split_kinds"]:
+                expect = {sweep_row if c == cc.SWEEP else c for c in classes}
+            else:
+                seg = cc.SEGMENTS in classes and opt["seg_kernel"]
+                mf = bool(classes & set(cc.MFMA1)) and opt["mfma_kernel"]
+                expect = {"ve_segment_kernel"} if seg else set()
+                expect |= {"ve_mfma_kernel"} if mf else set()
+                expect |= {sweep_row} if cc.SWEEP in classes else set()
+                if classes - {cc.SWEEP} - ({cc.SEGMENTS} if seg else set()) - (set(cc.MFMA1) if mf else set()):
+                    expect.add("ve_level_kernel")
+            assert {k["name"] for k in kernels} == expect, (opt, sorted(names), sorted(expect))
+            assert any(n.startswith(GROUP) for n in names) == bool(opt["overlap"] and not opt["split_kinds"]), (opt, sorted(names))
+            reached |= expect
+        for name, v in default.items():
+            eng.set_option(name, v)
+    assert {"ve_level_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_sweep_kernel", "ve_sweep_dma_kernel"} <= reached, sorted(reached)
+
+
 def test_class_matrix_summary():
     """A reporting step: prints the largest error against the oracle per class, the number of cases and the wall time of this file
     from what the cases above left in this module - so its assertions hold only when every case ran, and passed, in this process

@@ -53,6 +53,62 @@ def test_case_holds_its_classes_and_edges_and_matches_the_oracle(case):
     assert worst <= gu.TOL, worst
 
 
+@pytest.mark.parametrize("case", cc.CASES, ids=[c["name"] for c in cc.CASES])
+def test_level_groups_partition_the_launches_by_route(case):
+    """planner.h level_groups - the rule by which the engine turns the Launch entries of a schedule into kernel launches - on the
+    schedule of every case, under all 16 settings of the options that route a class to a kernel."""
+    flat = flatten(netspec.build(cc.build_spec(case), sorobn_amd.BayesNet))
+    cc.set_sim_options(cc.options(case))
+    for routing in range(16):
+        split, seg_kernel, mfma_kernel, sweep_dma = [bool(routing >> k & 1) for k in range(4)]
+        launches, groups = cc.level_groups(flat, case["requests"], routing)
+        assert {la["cls"] for la in launches} == set(case["classes"])
+        # every class goes where the options send it (the tests' notion of the MFMA1 classes is the planner's)
+        for la in launches:
+            want = ("sweep_dma" if sweep_dma else "sweep_reg") if la["cls"] == cc.SWEEP else "level" if split else \
+                "segment" if seg_kernel and la["cls"] == cc.SEGMENTS else "mfma" if mfma_kernel and la["cls"] in cc.MFMA1 else "level"
+            assert la["route"] == want, (routing, la)
+        # the groups partition the launches in order
+        assert [g["first_launch"] for g in groups] == [0] + list(np.cumsum([g["n_launches"] for g in groups])[:-1])
+        assert sum(g["n_launches"] for g in groups) == len(launches) and all(g["n_launches"] >= 1 for g in groups)
+        for g in groups:
+            mine = launches[g["first_launch"]:g["first_launch"] + g["n_launches"]]
+            assert all(la["route"] == g["route"] and la["level"] == g["level"] for la in mine), (routing, g)
+            assert g["grid"] == sum(la["grid"] for la in mine)
+            assert g["alg_bytes"] == sum(la["alg_bytes"] for la in mine)  # (added in the same order: the same double)
+            assert (g["wg_level"], g["wg_first"]) == (mine[0]["wg_level"], mine[0]["wg_first"])
+            assert g["stat_cls"] == (mine[0]["cls"] if split else None)
+        if split:
+            assert len(groups) == len(launches)
+        else:  # contiguity: a level has at most one launch of a kernel
+            keys = [(g["level"], g["route"]) for g in groups]
+            assert len(set(keys)) == len(keys), (routing, keys)
+
+
+def test_the_routing_cases_reach_every_kernel_of_a_level():
+    """cc.ROUTING_CASES (the device test test_level_routing_table runs them under every option setting): segments, a level-kernel
+    class, an MFMA1 class and SWEEP between them, and no smaller pair of the table does."""
+    def reach(case):
+        return {"segment": cc.SEGMENTS in case["classes"], "mfma": bool(set(cc.MFMA1) & set(case["classes"])), "sweep": cc.SWEEP in case["classes"],
+                "level": bool(set(case["classes"]) - {cc.SEGMENTS, cc.SWEEP, *cc.MFMA1})}
+    by_name = {c["name"]: c for c in cc.CASES}
+    pair = [by_name[n] for n in cc.ROUTING_CASES]
+    assert all(any(reach(c)[k] for c in pair) for k in ("segment", "mfma", "sweep", "level"))
+    assert not any(all(reach(c).values()) for c in cc.CASES)  # (no single case does)
+    size = lambda cs: (sum(c["nodes"] for c in cs), sum(c["max_cells"] for c in cs))
+    for i, a in enumerate(cc.CASES):
+        for b in cc.CASES[i + 1:]:
+            if all(reach(a)[k] or reach(b)[k] for k in ("segment", "mfma", "sweep", "level")):
+                assert size(pair) <= size([a, b]), (a["name"], b["name"])
+    # and the schedule says the same: under the engine's defaults the pair's launch groups go to all four kernels
+    routes = set()
+    for case in pair:
+        flat = flatten(netspec.build(cc.build_spec(case), sorobn_amd.BayesNet))
+        cc.set_sim_options(cc.options(case))
+        routes |= {g["route"] for g in cc.level_groups(flat, case["requests"], cc.ROUTING_DEFAULT)[1]}
+    assert routes == {"level", "sweep_dma", "segment", "mfma"}, routes
+
+
 def test_the_table_covers_every_class_the_planner_can_emit():
     """All names of kernel_name() minus the ones proved unreachable: a class added to emit_core.h fails here until it has a case, and
     so does a case removed from the table if it was the only one of a class."""

@@ -5,7 +5,10 @@
 // A second section pins the flavours only the host plans - max, unnormalised (raw), draw and map programs, pruned and not - on
 // eight of these networks and a star: program words with their records, the empty records of skipped requests, per-request costs,
 // arena needs, argmax / kept cells, and the schedule.
-//   plan_fingerprint [B [B2]]   B requests per pair of the first section (default 1500), B2 of the second (200); 0 skips a section
+// A third section pins how the engine cuts every schedule of the first section into kernel launches (planner.h level_groups): per
+// network and per setting of the four options that route a class to a kernel, one hash over the launch groups of the network's six
+// schedules - route, level, statistics class, workgroup ranges, grid, bytes (bit pattern) and the range of Launch entries.
+//   plan_fingerprint [B [B2]]   B requests per pair of the first and third section (default 1500), B2 of the second (200); 0 skips them
 //   g++ -O2 -mpopcnt -std=c++17 tools/plan_fingerprint.cpp sorobn_amd/csrc/planner.cpp -lpthread -o /tmp/plan_fingerprint
 #include <algorithm>
 #include <cstdio>
@@ -204,6 +207,22 @@ static void host_flavours(const std::vector<Spec> &specs, int64_t nb) {
     }
 }
 
+// third section: the launch groups of one schedule into the 16 hashes of its network, one per LevelRouteOpts setting
+static LevelRouteOpts route_setting(int k) { return {(k & 1) != 0, (k & 2) != 0, (k & 4) != 0, (k & 8) != 0}; }
+static void hash_groups(const Schedule &sc, uint64_t *h16) {
+    std::vector<LaunchGroup> groups;
+    for (int k = 0; k < 16; ++k) {
+        level_groups(sc, route_setting(k), groups);
+        uint64_t h = h16[k];
+        for (const LaunchGroup &g : groups) {  // (field by field: the struct has padding)
+            const int route = (int)g.route;
+            h = fnv(h, &route, 4); h = fnv(h, &g.level, 4); h = fnv(h, &g.stat_kid, 4); h = fnv(h, &g.wg_level, 8); h = fnv(h, &g.wg_first, 8);
+            h = fnv(h, &g.grid, 8); h = fnv(h, &g.alg_bytes, 8); h = fnv(h, &g.first_launch, 8); h = fnv(h, &g.n_launches, 8);
+        }
+        h16[k] = fnv(h, "|", 1);  // (a schedule ends here)
+    }
+}
+
 int main(int argc, char **argv) {
     const int64_t B = argc > 1 ? atoll(argv[1]) : 1500, B2 = argc > 2 ? atoll(argv[2]) : 200;
     std::vector<Spec> specs;
@@ -227,6 +246,7 @@ int main(int argc, char **argv) {
         {"no_fuse", 1024, 4096, 2e7, 0, 0, 0, 2, 0, 1, 0},
         {"no_sweep_noprune", 64, 256, 1e5, 1, 1, 0, 2, 1, 0, 1},
     };
+    std::vector<uint64_t> route_hash(specs.size() * 16, 1469598103934665603ull);
     for (const Spec &s : specs) {
         if (B <= 0) break;
         const int n = (int)s.card.size();
@@ -287,6 +307,7 @@ int main(int argc, char **argv) {
                 h = fnv(h, sc.items.data(), sc.items.size() * sizeof(Item));
                 h = fnv(h, sc.wg_item.data(), sc.wg_item.size() * 4);
                 h = fnv(h, sc.arena_off.data(), sc.arena_off.size() * 8);
+                hash_groups(sc, route_hash.data() + (size_t)(&s - specs.data()) * 16);
             }
             std::printf("%-16s %-18s %016llx  words %zu steps %.0f bytes %.6g%s\n", s.name.c_str(), o.name, (unsigned long long)h,
                         bp.total_words, bp.st.n_steps, bp.st.alg_bytes, bp.err.empty() ? "" : (" ERR " + bp.err).c_str());
@@ -300,5 +321,11 @@ int main(int argc, char **argv) {
         host.push_back(star(9, {2, 3, 4}, 13, "star10"));
         host_flavours(host, B2);
     }
+    for (size_t i = 0; B > 0 && i < specs.size(); ++i)
+        for (int k = 0; k < 16; ++k) {
+            const LevelRouteOpts o = route_setting(k);
+            std::printf("%-16s groups split_kinds=%d seg_kernel=%d mfma_kernel=%d sweep_dma=%d  %016llx\n", specs[i].name.c_str(), (int)o.split_kinds,
+                        (int)o.seg_kernel, (int)o.mfma_kernel, (int)o.sweep_dma, (unsigned long long)route_hash[i * 16 + (size_t)k]);
+        }
     return 0;
 }
