@@ -655,6 +655,55 @@ extern "C" int64_t plan_sim_program(int32_t n_vars, const int32_t *card, const i
     return (int64_t)prog.size();
 }
 
+// The program of one request of any ProgramKind (`kind`: its integer value - 0 Sum, 1 Raw, 2 Max, 3 Draw, 4 Map; qvars: the query
+// variables, a map program's M, none for Max and Draw) under the options set now, with what follows the steps (traceback / draw
+// record, gather list).  tile_h (may be null, cap_steps entries) receives per step what the schedule does with it: step_tile_h - the hi
+// iterations one workgroup takes - where step_is_tiled makes it a level of its own, 0 where it stays in a segment.  Returns the words,
+// -1 / -6 with plan_sim_error set, -2 when a capacity is too small.
+static double g_minfill_above = -1;  // < 0: the Network's own
+extern "C" void plan_sim_set_minfill_above(double v) { g_minfill_above = v; }
+extern "C" int64_t plan_sim_program_kind(int32_t n_vars, const int32_t *card, const int64_t *scope_off, const int32_t *scope_vars,
+                                         const int64_t *value_off, const double *values, int32_t n_hints, const int32_t *hints,
+                                         int32_t kind, int32_t no_prune, int32_t nq, const int32_t *qvars, int32_t ne, const int32_t *evars,
+                                         const int32_t *ecodes, uint32_t *out, int64_t cap, int32_t *tile_h, int64_t cap_steps) {
+    Network net;
+    g_err = net.set(n_vars, card, scope_off, scope_vars, value_off, values);
+    if (!g_err.empty()) return -1;
+    if (kind < 0 || kind > (int)ProgramKind::Map) { g_err = "unknown program kind"; return -1; }
+    net.small_cells = g_small_cells;
+    net.big_iters = g_big_iters;
+    net.tile_h = g_tile_h;
+    net.fuse = g_fuse;
+    net.chain = g_chain; net.outer = g_outer;
+    net.sweep = g_sweep;
+    net.sweep_min = g_sweep_min;
+    net.order_effort = g_order_effort; net.second_above = g_second_above;
+    if (g_minfill_above >= 0) net.minfill_above = g_minfill_above;
+    net.prune = g_prune;
+    net.set_hints(n_hints, hints);
+    Request rq;
+    rq.kind = (ProgramKind)kind;
+    rq.nq = takes_query(rq.kind) ? nq : 0; rq.qvars = qvars; rq.ne = ne; rq.evars = evars; rq.ecodes = ecodes; rq.out_off = 0; rq.no_prune = no_prune != 0;
+    g_err = takes_query(rq.kind) ? validate_request(net, rq) : validate_mpe_request(net, rq);
+    if (!g_err.empty()) return -1;
+    std::vector<uint32_t> prog;
+    PlanStats st;
+    g_err = plan_request(net, rq, prog, st);
+    if (!g_err.empty()) return -6;
+    if ((int64_t)prog.size() > cap || (tile_h && (int64_t)prog[0] > cap_steps)) return -2;
+    std::memcpy(out, prog.data(), prog.size() * 4);
+    if (tile_h) {
+        const EmitNet en = net.emit_view();
+        size_t off = 1;
+        for (uint32_t s = 0; s < prog[0]; ++s) {
+            const uint32_t *w = prog.data() + off;
+            tile_h[s] = step_is_tiled(en, w) ? step_tile_h(en, w) : 0;
+            off += w[6];
+        }
+    }
+    return (int64_t)prog.size();
+}
+
 // The class of work (kernel_name) that executes every step of a program written by plan_sim_program under the options set now:
 // kernel_id_of_step for a step that is a level of its own (step_is_tiled), "segments" for a GENERIC step that runs in the segment
 // interpreter.  The names go to `out` one per step, each followed by '\n'; returns the number of steps, -1 for a malformed program,

@@ -97,14 +97,16 @@ def build_draw_sim(tmp_path):
     return sim_tools.build_prog_sim()
 
 
-def run_draw_sim(exe, tmp_path, f, seed, prune, requests, margins=False):
-    """-> list per request of dict(codes [n, n_vars] int32, p_e, n_steps, n_back, n_fwd, kept_cells, min_margin, low = the global
+def run_draw_sim(exe, tmp_path, f, seed, prune, requests, margins=False, options=None):
+    """(options: None - planned by a bare Network - or the set_option values of the engine whose programs these are, sim_tools.sim_args)
+    -> list per request of dict(codes [n, n_vars] int32, p_e, n_steps, n_back, n_fwd, kept_cells, min_margin, low = the global
     rows whose smallest margin is <= 1e-12[, margins [n]]) as tools/prog_sim.cpp draw computes them."""
     d = str(tmp_path)
     path, cpath, mpath = os.path.join(d, "draw_net.txt"), os.path.join(d, "draw_codes.bin"), os.path.join(d, "draw_margins.bin")
     with open(path, "w") as fh:
         fh.write(sim_text(f, seed, prune, requests))
-    r = subprocess.run([exe, "draw", path, cpath] + ([mpath] if margins else []), capture_output=True, text=True, timeout=1800)
+    r = subprocess.run([exe, "draw", path, cpath] + ([mpath] if margins else []) + sim_tools.sim_args(f, tmp_path, options), capture_output=True,
+                       text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-2000:]
     nv = len(f.card)
     codes = np.fromfile(cpath, np.int32).reshape(-1, max(1, nv))[:, :nv]

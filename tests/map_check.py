@@ -95,12 +95,14 @@ def build_map_sim(tmp_path):
     return sim_tools.build_prog_sim()
 
 
-def run_map_sim(exe, tmp_path, f, requests, expect_fail=False):
-    """-> (log_p [B], [codes of request b, in the order of its mvars]) as tools/prog_sim.cpp map computes them from the map programs."""
+def run_map_sim(exe, tmp_path, f, requests, expect_fail=False, options=None, ties=False):
+    """-> (log_p [B], [codes of request b, in the order of its mvars]) as tools/prog_sim.cpp map computes them from the map programs -
+    planned by a bare Network, or with `options` as an engine with these set_option values plans them (sim_tools.sim_args).  ties: a
+    third result, sim_tools.parse_ties."""
     path = os.path.join(str(tmp_path), "map_net.txt")
     with open(path, "w") as fh:
         fh.write(net_text(f, requests))
-    r = subprocess.run([exe, "map", path], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, "map", path] + sim_tools.sim_args(f, tmp_path, options, ties), capture_output=True, text=True, timeout=900)
     if expect_fail:
         return r
     assert r.returncode == 0, r.stderr[-2000:]
@@ -110,4 +112,4 @@ def run_map_sim(exe, tmp_path, f, requests, expect_fail=False):
         lp.append(-np.inf if t[0] == "-inf" else float.fromhex(t[0]))
         codes.append([int(x) for x in t[1:]])
     assert len(lp) == len(requests)
-    return np.array(lp), codes
+    return (np.array(lp), codes, sim_tools.parse_ties(r.stderr)) if ties else (np.array(lp), codes)

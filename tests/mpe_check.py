@@ -100,19 +100,21 @@ def build_max_sim(tmp_path):
     return sim_tools.build_prog_sim()
 
 
-def run_max_sim(exe, tmp_path, f, requests):
-    """-> (log_p [B], codes [B, n]) as tools/prog_sim.cpp max computes them from the max programs."""
+def run_max_sim(exe, tmp_path, f, requests, options=None, ties=False):
+    """-> (log_p [B], codes [B, n]) as tools/prog_sim.cpp max computes them from the max programs - planned by a bare Network, or
+    with `options` as an engine with these set_option values plans them (sim_tools.sim_args).  ties: a third result, sim_tools.parse_ties."""
     path = os.path.join(str(tmp_path), "net.txt")
     with open(path, "w") as fh:
         fh.write(net_text(f, requests))
-    r = subprocess.run([exe, "max", path], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, "max", path] + sim_tools.sim_args(f, tmp_path, options, ties), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lp, codes = [], []
     for line in r.stdout.splitlines():
         t = line.split()
         lp.append(-np.inf if t[0] == "-inf" else float.fromhex(t[0]))
         codes.append([int(x) for x in t[1:]])
-    return np.array(lp), np.array(codes, np.int64).reshape(len(requests), len(f.card))
+    out = np.array(lp), np.array(codes, np.int64).reshape(len(requests), len(f.card))
+    return out + (sim_tools.parse_ties(r.stderr),) if ties else out
 
 
 def check_against_brute(f, ev, log_p, codes, ctx=""):

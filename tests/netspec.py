@@ -186,6 +186,54 @@ def random_dag_spec(seed, n_nodes=None, max_parents=3, cards=(2, 3, 4, 5), p_zer
     return {"name": f"dag{seed}", "hashed_names": True, "nodes": names, "edges": edges, "cpts": cpts}
 
 
+def _dag_spec(name, card, parents, row):
+    """Nodes "000", "001", .. in topological order with cardinalities card[i] and parent lists parents[i] (earlier nodes); row(i) is
+    the distribution of node i for one parent configuration, drawn in C order of the configurations."""
+    names = [f"{i:03d}" for i in range(len(card))]
+    edges = [[names[p], names[i]] for i in range(len(card)) for p in parents[i]]
+    cpts = {}
+    for i in range(len(card)):
+        rows = []
+        for cfg in itertools.product(*[range(card[p]) for p in parents[i]]):
+            rows += [[*cfg, j, float(v)] for j, v in enumerate(row(i))]
+        cpts[names[i]] = {"names": [names[p] for p in parents[i]] + [names[i]], "rows": rows}
+    return {"name": name, "hashed_names": True, "nodes": names, "edges": edges, "cpts": cpts}
+
+
+def hub_spec(seed, hub_card, parent_cards, child_cards):
+    """A hub: roots 000 .. (parent_cards), all of them parents of the hub (hub_card states - hundreds are fine, the hub's CPT has
+    hub_card x prod(parent_cards) cells), and children of the hub alone (child_cards).  Dirichlet(1) rows.  The hub is in
+    1 + len(child_cards) factors: eliminating it is a step of that many inputs, over the product of its neighbours."""
+    rng = np.random.default_rng(seed)
+    np_, card = len(parent_cards), [*parent_cards, hub_card, *child_cards]
+    parents = [[] for _ in parent_cards] + [list(range(np_))] + [[np_] for _ in child_cards]
+    return _dag_spec(f"hub{seed}", card, parents, lambda i: rng.dirichlet(np.ones(card[i])))
+
+
+def chain_spec(n, cards, seed):
+    """A chain 000 -> 001 -> .. of n nodes, cardinalities cards cycled, Dirichlet(1) rows."""
+    rng = np.random.default_rng(seed)
+    card = [cards[i % len(cards)] for i in range(n)]
+    return _dag_spec(f"chain{n}s{seed}", card, [[i - 1] if i else [] for i in range(n)], lambda i: rng.dirichlet(np.ones(card[i])))
+
+
+def dyadic_dag_spec(seed, n_nodes, max_parents, cards, denom=8):
+    """A random DAG whose every CPT entry is a multiple of 1 / denom (denom a power of two, at least max(cards)): rows are uniform
+    random compositions of denom into card positive parts.  Products of a dozen such entries and sums of such products are exact
+    in binary64, so two assignments of equal probability have bitwise equal products - the networks of the exact-tie cases."""
+    rng = np.random.default_rng(seed)
+    card = [int(rng.choice(cards)) for _ in range(n_nodes)]
+    parents = []
+    for i in range(n_nodes):
+        k = int(rng.integers(0, min(i, max_parents) + 1))
+        parents.append(sorted(rng.choice(i, size=k, replace=False).tolist()) if k else [])
+
+    def row(i):
+        cuts = np.sort(rng.choice(np.arange(1, denom), size=card[i] - 1, replace=False))
+        return np.diff(np.concatenate([[0], cuts, [denom]])) / denom
+    return _dag_spec(f"dyadic{seed}", card, parents, row)
+
+
 def domains(spec):
     """node -> sorted list of labels (union over every CPT that mentions the node)."""
     dom = {n: set() for n in spec["nodes"]}

@@ -29,6 +29,30 @@ def program(f, q, ev, codes):
     return out[:n]
 
 
+KINDS = {"sum": 0, "raw": 1, "max": 2, "draw": 3, "map": 4}  # planner.h ProgramKind
+
+
+def program_kind(f, kind, q, ev, codes, no_prune=False):
+    """(words, tile_h) of the program of one request of ProgramKind `kind` (a name of KINDS; q: the query variables - a map
+    program's M, nothing for max and draw) under the simulator's options (oracle/plan_sim.cpp plan_sim_program_kind): the steps and
+    the record behind them, and per step the hi iterations one workgroup of the schedule takes - 0 for a step of a segment."""
+    L = simengine.lib()
+    i32p, i64p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    L.plan_sim_program_kind.restype = C.c_int64
+    L.plan_sim_program_kind.argtypes = [C.c_int32, i32p, i64p, i32p, i64p, f64p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, i32p,
+                                        C.c_int32, i32p, i32p, C.POINTER(C.c_uint32), C.c_int64, i32p, C.c_int64]
+    p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    arr = lambda a: np.ascontiguousarray(np.concatenate([np.asarray(a, np.int32).reshape(-1), np.zeros(1, np.int32)]), np.int32)
+    hints = np.ascontiguousarray(np.stack(f.hints).reshape(-1) if f.hints else [0], np.int32)
+    out = np.zeros(1 << 20, np.uint32)
+    th = np.zeros(4096, np.int32)
+    n = L.plan_sim_program_kind(len(f.card), p(f.card, C.c_int32), p(f.scope_off, C.c_int64), p(f.scope_vars, C.c_int32), p(f.value_off, C.c_int64),
+                                p(f.values, C.c_double), len(f.hints), p(hints, C.c_int32), KINDS[kind], int(bool(no_prune)), len(q), p(arr(q), C.c_int32),
+                                len(ev), p(arr(ev), C.c_int32), p(arr(codes), C.c_int32), p(out, C.c_uint32), len(out), p(th, C.c_int32), len(th))
+    assert n > 0, (n, L.plan_sim_error().decode())
+    return out[:n], th[:int(out[0])].tolist()
+
+
 def step_classes(w, tiles=False):
     """The class of work (kernel_name) of every step of `w`, from the planner's own kernel_id_of_step / step_is_tiled under the
     simulator's current options (oracle/plan_sim.cpp plan_sim_step_classes); a GENERIC step that is no level of its own is "segments".
@@ -53,7 +77,8 @@ def class_names():
 
 
 def decode(w, classes=False):
-    """Decode a step program (planner.h encoding: 10-word header, GENERIC / FIBER bodies) from its words alone.  classes=True adds,
+    """Decode a step program (planner.h encoding: 10-word header, GENERIC / FIBER bodies) from its words alone; `max` and `raw` are
+    the MAX and RAW flags of a step (a MAX step's argmax table: `am_off`).  classes=True adds,
     from step_classes, `cls` - the step's class of work - and `tile_h`, the hi iterations one workgroup of it takes (0: a step of a
     segment)."""
     steps = []
@@ -64,7 +89,7 @@ def decode(w, classes=False):
         cx = int(w[p + 1]) & 0xffff; fin = (int(w[p + 1]) >> 16) & 1
         lo, hi, words = int(w[p + 2]), int(w[p + 3]), int(w[p + 6])
         d = dict(w1=int(w[p + 1]), kind={0: "GENERIC", 1: "FIBER", 2: "SWEEP"}[kind], n_in=n_in, na=na, nlo=nlo, fin=fin, cx=cx, lo=lo, hi=hi,
-                 bytes=32 * int(w[p + 9]), words=words)
+                 bytes=32 * int(w[p + 9]), words=words, max=(int(w[p + 1]) >> 21) & 1, raw=(int(w[p + 1]) >> 22) & 1)  # (kFlagMax, kFlagRaw)
         q = p + 10
         I = lambda k: int(np.int32(w[k]))
         if kind == 2:  # SWEEP: k variables per pass, tile in LDS (planner.h)
@@ -79,6 +104,8 @@ def decode(w, classes=False):
                                         ctrl=[int(w[q + 4 + 5 * j + c]) & 0xff for c in range(nc)], t_cells=s1 >> 16))
                 sq += 7 * ns
         elif kind == 0:
+            if d["max"]:
+                d["am_off"] = int(w[p + 7]) | (int(w[p + 8]) << 32)
             d["ins"] = [("C" if int(w[q + 3 * j + 1]) >> 31 else "A", I(q + 3 * j + 2)) for j in range(n_in)]
             q += 3 * n_in
             d["card"] = [int(x) for x in w[q:q + na]]; q += na

@@ -6,6 +6,12 @@
 //
 //   g++ -O2 -mpopcnt -std=c++17 -ffp-contract=off tools/prog_sim.cpp sorobn_amd/csrc/planner.cpp -lpthread -o prog_sim
 //   ./prog_sim max net.txt | map net.txt | draw net.txt codes.bin [margins.bin] | ev run|compare|reject net.txt
+//   options, anywhere on the command line (none: a bare Network, as before): --small_cells N --big_iters N --tile_h N
+//   --order_effort N --second_above X --minfill_above X --hints FILE (n_hints, then n_hints x n_vars priorities) - the planner
+//   options of an engine, so that the program run here is the engine's word for word (the order search reads them, and the order
+//   decides which of two equal maxima a traceback meets first); --ties (max, map): one line per planned request on standard
+//   error, "ties <request> <cells> <on_path>" - the output cells of MAX steps whose maximum two or more x attain with bitwise equal
+//   positive products, and how many of them the traceback reads.
 //
 // (-ffp-contract=off: `draw` is the CPU twin of the draw kernel - same programs, same Philox4x32-10 stream, same arithmetic.)
 // tools/max_sim.cpp, map_sim.cpp, draw_sim.cpp and ev_sim.cpp are three lines each: this file with the kind fixed (PROG_SIM_KIND),
@@ -216,8 +222,9 @@ struct Run {
     std::vector<double> final_;  // the cells of the FINAL step (empty: no such step ran)
     struct Table { int64_t off, cells; int written, last_read; };
     std::vector<Table> tabs;     // the intermediates
-    struct Argmax { int64_t off, cells; int step, cx; };
-    std::vector<Argmax> am;      // the argmax tables (off, cells in doubles) of the MAX steps, in step order
+    struct Argmax { int64_t off, cells; int step, cx; std::vector<char> tie; };
+    std::vector<Argmax> am;      // the argmax tables (off, cells in doubles) of the MAX steps, in step order; tie[o]: two or more x attain the (positive) maximum of cell o
+    int64_t tie_cells = 0, tie_on_path = 0;  // cells with tie set over all MAX steps; those of them a traceback read (--ties)
 
     Run(const Network &net, int64_t b_, const Request &rq) : b(b_) {
         const std::string pe = plan_request(net, rq, prog, st);
@@ -255,22 +262,27 @@ struct Run {
                 const int64_t am_cells = (g.cells * 2 + 7) / 8;
                 for (const Argmax &r : am)
                     if (g.am_off < r.off + r.cells && r.off < g.am_off + am_cells) fail(b, "argmax tables overlap");
-                am.push_back({g.am_off, am_cells, (int)s, g.cx});
+                am.push_back({g.am_off, am_cells, (int)s, g.cx, std::vector<char>((size_t)g.cells, 0)});
                 at(g.am_off + am_cells - 1);
             }
+            char *tie = mx ? am.back().tie.data() : nullptr;
             if (!fin) tabs.push_back({g.out_off, g.cells, (int)s, (int)s});
             std::vector<double> outv((size_t)g.cells, 0.0);
             std::vector<uint16_t> arg((size_t)g.cells);
             g.visit(net, [&](int64_t i) -> double & { return at(i); }, [&](int64_t o, int x, double prod) {
                 if (mx) {  // max over x, the lowest x that attains it
-                    if (x == 0 || prod > outv[(size_t)o]) { outv[(size_t)o] = prod; arg[(size_t)o] = (uint16_t)x; }
+                    if (x == 0 || prod > outv[(size_t)o]) { outv[(size_t)o] = prod; arg[(size_t)o] = (uint16_t)x; tie[o] = 0; }
+                    else if (prod == outv[(size_t)o] && prod > 0) tie[o] = 1;
                 } else {   // the sum body: 0.0 + the terms in ascending x
                     outv[(size_t)o] += prod;
                 }
             });
             if (fin) final_ = outv;
             else for (int64_t o = 0; o < g.cells; ++o) at(g.out_off + o) = outv[(size_t)o];
-            if (mx) std::memcpy(reinterpret_cast<char *>(arena.data() + g.am_off), arg.data(), (size_t)g.cells * 2);
+            if (mx) {
+                std::memcpy(reinterpret_cast<char *>(arena.data() + g.am_off), arg.data(), (size_t)g.cells * 2);
+                for (int64_t o = 0; o < g.cells; ++o) tie_cells += tie[o];
+            }
             off += g.words;
         }
     }
@@ -304,13 +316,22 @@ struct Run {
                 if (!known[v]) fail(b, "traceback reads variable " + std::to_string(v) + " before it is decoded");
                 idx += (int64_t)code[v] * (int64_t)rec[5 + 2 * a];
             }
-            if (read) code[x] = argmax_at(aoff, idx);
+            if (read) {
+                code[x] = argmax_at(aoff, idx);
+                for (const Argmax &r : am)
+                    if (r.off == aoff && idx >= 0 && idx < (int64_t)r.tie.size()) tie_on_path += r.tie[(size_t)idx];
+            }
             known[x] = 1;
             rec += 4 + 2 * n_out;
         }
         return rec;
     }
 };
+
+static bool g_report_ties = false;
+static void report_ties(const Run &R) {
+    if (g_report_ties) std::fprintf(stderr, "ties %lld %lld %lld\n", (long long)R.b, (long long)R.tie_cells, (long long)R.tie_on_path);
+}
 
 static void one_cell_final(int64_t b, const GenericStep &g) {
     if ((g.flags & kFlagFinal) && (g.cells != 1 || g.out_off != 0)) fail(b, "FINAL step of more than one cell");
@@ -349,13 +370,14 @@ static void run_max(const Network &net, int64_t b, const Query &q) {
     rec += 2;
     for (uint32_t i = 0; i < n_ev; ++i) code[rec[2 * i]] = (int32_t)rec[2 * i + 1];
     rec += 2 * n_ev;
-    if (!(m > 0)) { print_zero(); return; }
+    if (!(m > 0)) { report_ties(R); print_zero(); return; }
     std::vector<char> known(n, 1);  // (evidence, single-state variables: everything no entry decodes)
     {
         const uint32_t *r2 = rec;
         for (uint32_t i = 0; i < n_rec; ++i) { known[r2[2]] = 0; r2 += 4 + 2 * r2[3]; }
     }
     R.decode(rec, n_rec, true, code, known, [](uint32_t, int64_t, int) {}, [](uint32_t) {});
+    report_ties(R);
     std::printf("%a", std::log(m));
     print_codes();
 }
@@ -412,6 +434,7 @@ static void run_map(const Network &net, int64_t b, const Query &q) {
         if ((int32_t)rec[1 + k] != mv[k]) fail(b, "gather list entry " + std::to_string(k) + " is not the caller's");
         if (!known[mv[k]]) fail(b, "MAP variable " + std::to_string(mv[k]) + " is never decoded");
     }
+    report_ties(R);
     if (!(m > 0)) { print_zero(); return; }
     std::printf("%a", std::log(m));
     for (int k = 0; k < nm; ++k) std::printf(" %d", code[rec[1 + k]]);
@@ -620,10 +643,34 @@ int main(int argc, char **argv) {
     argc = (int)args.size();
     argv = args.data();
 #endif
+    // the options, taken out of the command line: what stays is the command line of before
+    struct { long small_cells = -1, big_iters = -1, tile_h = -1, order_effort = -1; double second_above = -1, minfill_above = -1; const char *hints = nullptr; } opt;
+    std::vector<char *> pos;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (i > 0 && a == "--ties") { g_report_ties = true; continue; }
+        if (i > 0 && a.rfind("--", 0) == 0) {
+            if (i + 1 >= argc) { std::fprintf(stderr, "option %s without a value\n", argv[i]); return 2; }
+            const char *v = argv[++i];
+            if (a == "--small_cells") opt.small_cells = std::strtol(v, nullptr, 10);
+            else if (a == "--big_iters") opt.big_iters = std::strtol(v, nullptr, 10);
+            else if (a == "--tile_h") opt.tile_h = std::strtol(v, nullptr, 10);
+            else if (a == "--order_effort") opt.order_effort = std::strtol(v, nullptr, 10);
+            else if (a == "--second_above") opt.second_above = std::strtod(v, nullptr);
+            else if (a == "--minfill_above") opt.minfill_above = std::strtod(v, nullptr);
+            else if (a == "--hints") opt.hints = v;
+            else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+            continue;
+        }
+        pos.push_back(argv[i]);
+    }
+    argc = (int)pos.size();
+    argv = pos.data();
     const std::string kind_name = argc > 1 ? argv[1] : "";
     const bool is_ev = kind_name == "ev", is_draw = kind_name == "draw";
     if (!(kind_name == "max" || kind_name == "map" || is_draw || is_ev) || argc < (is_ev || is_draw ? 4 : 3)) {
-        std::fprintf(stderr, "usage: prog_sim max net.txt | map net.txt | draw net.txt codes.bin [margins.bin] | ev run|compare|reject net.txt\n");
+        std::fprintf(stderr, "usage: prog_sim max net.txt | map net.txt | draw net.txt codes.bin [margins.bin] | ev run|compare|reject net.txt\n"
+                             "       [--small_cells N] [--big_iters N] [--tile_h N] [--order_effort N] [--second_above X] [--minfill_above X] [--hints FILE] [--ties]\n");
         return 2;
     }
     const Kind kind = is_ev ? Kind::Ev : is_draw ? Kind::Draw : kind_name == "map" ? Kind::Map : Kind::Max;
@@ -639,6 +686,23 @@ int main(int argc, char **argv) {
     }
     Network net;
     read_network(net);
+    if (opt.small_cells >= 0) net.small_cells = (int)opt.small_cells;
+    if (opt.big_iters >= 0) net.big_iters = opt.big_iters;
+    if (opt.tile_h >= 0) net.tile_h = (int)opt.tile_h;
+    if (opt.order_effort >= 0) net.order_effort = (int)opt.order_effort;
+    if (opt.second_above >= 0) net.second_above = opt.second_above;
+    if (opt.minfill_above >= 0) net.minfill_above = opt.minfill_above;
+    if (opt.hints) {
+        FILE *fh = std::fopen(opt.hints, "rb");
+        if (!fh) { std::perror(opt.hints); return 2; }
+        long n_hints = 0, v = 0;
+        std::vector<int32_t> pri;
+        if (std::fscanf(fh, "%ld", &n_hints) != 1 || n_hints < 0) { std::fprintf(stderr, "%s: no hint count\n", opt.hints); return 2; }
+        while (std::fscanf(fh, "%ld", &v) == 1) pri.push_back((int32_t)v);
+        std::fclose(fh);
+        if ((long)pri.size() != n_hints * net.n_vars) { std::fprintf(stderr, "%s: %zu priorities for %ld hints of %d variables\n", opt.hints, pri.size(), n_hints, net.n_vars); return 2; }
+        net.set_hints((int32_t)n_hints, pri.data());
+    }
     uint64_t seed = 0;
     bool no_prune = false;
     if (is_draw) { seed = getu(); no_prune = geti() == 0; }
