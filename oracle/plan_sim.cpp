@@ -27,6 +27,7 @@ static std::string g_err;
 static int g_order_effort = 0;
 static double g_second_above = 1e7;
 static int g_small_cells = 1024, g_big_iters = 4096, g_tile_h = 0, g_fuse = 1, g_prune = 1, g_chain = 1, g_sweep = 5, g_sweep_min = 2, g_outer = 1;
+static int g_sweep_iters = kSweepItersDefault, g_sweep_canon = 1, g_sweep_adapt = 4096;  // (planner.h Network: sweep_iters, sweep_canon, sweep_adapt)
 extern "C" void plan_sim_set_small_cells(int v) { g_small_cells = v; }
 extern "C" void plan_sim_set_tiling(int big_iters, int tile_h) { g_big_iters = big_iters; g_tile_h = tile_h; }
 extern "C" void plan_sim_set_fuse(int fuse) { g_fuse = fuse; }
@@ -34,6 +35,9 @@ extern "C" void plan_sim_set_chain(int chain) { g_chain = chain; }
 extern "C" void plan_sim_set_outer(int outer) { g_outer = outer; }
 extern "C" void plan_sim_set_sweep(int sweep) { g_sweep = sweep; }
 extern "C" void plan_sim_set_sweep_min(int k) { g_sweep_min = k; }
+extern "C" void plan_sim_set_sweep_iters(int tiles) { g_sweep_iters = std::max(1, std::min(kTileMax, tiles)); }  // (the engine's clamp)
+extern "C" void plan_sim_set_sweep_canon(int canon) { g_sweep_canon = canon != 0; }
+extern "C" void plan_sim_set_sweep_adapt(int workgroups) { g_sweep_adapt = std::max(0, workgroups); }
 extern "C" void plan_sim_set_prune(int prune) { g_prune = prune; }
 extern "C" void plan_sim_set_order_effort(int effort, double second_above) { g_order_effort = effort; g_second_above = second_above; }
 
@@ -449,7 +453,7 @@ extern "C" int plan_sim_query_batch(int32_t n_vars, const int32_t *card, const i
     net.fuse = g_fuse;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.prune = g_prune;
     net.stagger = stagger;
@@ -588,7 +592,7 @@ extern "C" int64_t plan_sim_cache_check(int32_t n_vars, const int32_t *card, con
     net.fuse = g_fuse;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.prune = g_prune;
     std::vector<int64_t> out_off(B + 1, 0);
@@ -640,7 +644,7 @@ extern "C" int64_t plan_sim_program(int32_t n_vars, const int32_t *card, const i
     net.fuse = g_fuse;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.prune = g_prune;
     net.set_hints(n_hints, hints);
@@ -676,7 +680,7 @@ extern "C" int64_t plan_sim_program_kind(int32_t n_vars, const int32_t *card, co
     net.fuse = g_fuse;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     if (g_minfill_above >= 0) net.minfill_above = g_minfill_above;
     net.prune = g_prune;
@@ -712,7 +716,7 @@ extern "C" int64_t plan_sim_program_kind(int32_t n_vars, const int32_t *card, co
 extern "C" int64_t plan_sim_step_classes(const uint32_t *prog, int64_t n_words, char *out, int64_t cap, int32_t *tile_h) {
     if (n_words < 1) { g_err = "empty program"; return -1; }
     EmitNet en;
-    en.big_iters = g_big_iters; en.tile_h = g_tile_h;  // (all that step_is_tiled / step_tile_h read of the options set here)
+    en.big_iters = g_big_iters; en.tile_h = g_tile_h; en.sweep_iters = g_sweep_iters;  // (all that step_is_tiled / step_tile_h read of the options set here)
     std::string names;
     int64_t off = 1;
     const int64_t n_steps = prog[0];
@@ -749,7 +753,7 @@ extern "C" int plan_sim_level_groups(int32_t n_vars, const int32_t *card, const 
     net.fuse = g_fuse;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.prune = g_prune;
     net.set_hints(n_hints, hints);
@@ -812,7 +816,7 @@ extern "C" int64_t wave_plan_program(int32_t n_vars, const int32_t *card, const 
     net.fuse = g_fuse;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.prune = g_prune;
     net.set_hints(n_hints, hints);
@@ -845,7 +849,7 @@ extern "C" int64_t plan_sim_program_tags(int32_t n_vars, const int32_t *card, co
     net.fuse = g_fuse;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.prune = g_prune;
     net.set_hints(n_hints, hints);
@@ -874,7 +878,7 @@ extern "C" double plan_sim_bench(int32_t n_vars, const int32_t *card, const int6
     if (!g_err.empty()) return -1;
     net.chain = g_chain; net.outer = g_outer;
     net.sweep = g_sweep;
-    net.sweep_min = g_sweep_min;
+    net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.set_hints(n_hints, hints);
     net.plan_cache = 0;  // PLANNING is what is timed: the second pass over the same requests must not be answered from templates of the first
@@ -912,7 +916,7 @@ extern "C" int64_t plan_sim_device_style(int32_t n_vars, const int32_t *card, co
     if (!g_err.empty()) return -1;
     if (n_vars > 128) { g_err = "the device planner covers networks of up to 128 variables"; return -1; }
     net.small_cells = g_small_cells; net.big_iters = g_big_iters; net.tile_h = g_tile_h; net.fuse = g_fuse; net.chain = g_chain; net.outer = g_outer;
-    net.sweep = g_sweep; net.sweep_min = g_sweep_min; net.prune = g_prune;
+    net.sweep = g_sweep; net.sweep_min = g_sweep_min; net.sweep_iters = g_sweep_iters; net.sweep_canon = g_sweep_canon; net.sweep_adapt = g_sweep_adapt; net.prune = g_prune;
     net.order_effort = g_order_effort; net.second_above = g_second_above;
     net.set_hints(n_hints, hints);
     const EmitNet en = net.emit_view();

@@ -8,11 +8,22 @@ A case is
     options   the engine options that shape the programs (OPTION_NAMES); the same values go to the simulator and to the engine
     requests  [(query node, [evidence nodes], [evidence codes])] - nodes by the integer of their name ("007" -> 7)
     nodes, max_cells   the size of the network and of the largest step (output cells x eliminated combinations) - the table stays
-              at networks of at most 30 nodes and steps of at most 2^16 cells
+              at networks of at most 30 nodes and steps of at most 2^16 cells (MAX_NODES, MAX_CELLS); the cases of the sweep matrix
+              (a sweep_iters or sweep_canon option, or the roof_grid_spec recipe) at 37 nodes and 2^20 cells = 8 MiB (SWEEP_MAX_NODES,
+              SWEEP_MAX_CELLS): a wave-owned tail wants a table over seven four-state variables, several work items of several
+              tiles one over eight, and whole work items of eight tiles one over nine
     classes   the class names the programs of those requests contain, all of them
     edges     the edge tags (see step_edges) those programs contain, all of them
 The cases are the cheapest witnesses a random search over netspec recipes and option sets found, chosen greedily so that every class
 and every (family, edge) pair is covered, plus a second witness per class; the host test proves each, whatever found it.
+
+The sweep matrix (the cases from 39 on, and sweep_edges): the paths of ve_sweep_dma_kernel and ve_sweep_kernel by name.  A grid small
+enough for the table is eliminated along its short side and never carries the frontier of seven or more four-state variables the
+wave-owned tails need, so these cases use netspec.roof_grid_spec - a grid whose first row is tied together by one more node, which
+is always in the evidence - at 7, 8 and 9 columns (2, 8 and 32 tiles per step).  Each base (recipe, request) comes with sweep_iters
+3 (work items of three tiles and a shorter last one) and 1 (work items of one tile: no next-tile fetch), one of them again with
+sweep_canon 0 (the kernel's general path on the same programs), one with the engine's eight tiles per work item on 32-tile steps.
+Two more have a two- and a three-state column: steps of three tiles, run as work items of two tiles and one.
 """
 import os
 import sys
@@ -25,8 +36,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if os.path.join(ROOT, "tools") not in sys.path:
     sys.path.insert(0, os.path.join(ROOT, "tools"))  # dump_plan
 
-OPTION_NAMES = ("small_cells", "big_iters", "tile_h", "fuse", "chain", "sweep", "sweep_min", "outer", "order_effort")
-DEFAULTS = dict(small_cells=1024, big_iters=4096, tile_h=0, fuse=1, chain=1, sweep=5, sweep_min=2, outer=1, order_effort=0)
+OPTION_NAMES = ("small_cells", "big_iters", "tile_h", "fuse", "chain", "sweep", "sweep_min", "outer", "order_effort", "sweep_iters", "sweep_canon")
+DEFAULTS = dict(small_cells=1024, big_iters=4096, tile_h=0, fuse=1, chain=1, sweep=5, sweep_min=2, outer=1, order_effort=0, sweep_iters=8, sweep_canon=1)
+# Not an option of a case: build_schedule halves the work items of a small sweep launch (sweep_adapt, 4096 workgroups by default), down to
+# two tiles and, from three, to one - every launch of this table is small.  The matrix runs with it off, on the simulator and on the
+# device, so that a SWEEP step's work items are the sweep_iters tiles its case names.
+MATRIX_SWEEP_ADAPT, PRODUCT_SWEEP_ADAPT = 0, 4096
+# The two thresholds of the order search, in modelled bytes: the simulator plans with these (a bare Network's minfill_above, and the
+# second_above set_sim_options passes), the engine's own defaults are 5e6 and 2e7 - the device tests set them, so that the engine
+# writes the programs the host test proved.
+MATRIX_MINFILL_ABOVE, MATRIX_SECOND_ABOVE = 2e7, 1e7
+
+MAX_NODES, MAX_CELLS = 30, 1 << 16
+SWEEP_MAX_NODES, SWEEP_MAX_CELLS = 37, 1 << 20
 
 MFMA1 = ("fiber<1,cx4,nc16-mfma>", "fiber<1,cx16,nc16-mfma>")  # the classes ve_mfma_kernel takes in the product's launch shape
 CHAIN = "fiber<1,cx64,chain-mfma>"
@@ -55,13 +77,7 @@ def step_edges(s):
     fam, out = family(s["cls"]), set()
     add = lambda e: out.add(f"{fam}:{e}")
     if s["kind"] == "SWEEP":
-        # hi = tiles of 8192 cells, tile_h = tiles per workgroup (sweep_iters): the last (or only) workgroup takes fewer; k variables
-        # per pass, kout of them surviving as new axes
-        if s["hi"] % s["tile_h"]:
-            add("partial_tile")
-        add(f"k{s['k']}")
-        add("kout0" if s["kout"] == 0 else "kout+")
-        return out
+        return sweep_edges(s)
     if s["hi"] % s["tile_h"]:
         add("partial_tile")           # the last workgroup of the step takes fewer hi iterations than the others
     if s["lo"] % 64 or s["lo"] < 64:
@@ -85,11 +101,108 @@ def step_edges(s):
     return out
 
 
+SWEEP_DEAD_PACKS = {0x4321: 0, 0x4320: 1, 0x4310: 2, 0x4210: 3, 0x3210: 4}  # w8 of a five-variable pass in which digit d alone dies
+SWEEP_SHAPES = ("own5", "dead0", "dead1", "dead2", "dead3", "dead4", "readout5", "own4", "readout4", "k3", "k2", "any")
+SWEEP_ITEMS = ("items2+", "multi_tile", "one_tile_item", "partial_tile", "one_tile_step")
+SWEEP_STAGES = ("par", "par_tail", "rbits", "nctrl2+", "ns2+")
+SWEEP_STEP = ("odd_tiles",)
+SWEEP_TAILS = ("own5", "dead0", "dead1", "dead2", "dead3", "dead4")  # the wave-owned tails the ragged shapes of the tile loop are crossed with
+
+
+def sweep_shape(s):
+    """The specialisation of sweep_tiles_dma that ve_sweep_dma_kernel (sweep_kernel.hip.h) sends a decoded SWEEP step to - its
+    dispatch restated on the step's header: the canonical flag (w1), k, kout (w7) and the surviving digits (w8)."""
+    k, kout, surv = s["k"], s["kout"], s["surv"]
+    if not s["canon"]:
+        return "any"                                     # <0,false>: runtime strides
+    if k == 5 and kout == 5 and surv == 0x43210:
+        return "own5"                                    # <5,true>: the wave-owned tail
+    if k == 5 and kout == 4 and surv in SWEEP_DEAD_PACKS:
+        return f"dead{SWEEP_DEAD_PACKS[surv]}"           # <5,true,true>: the wave-owned tail with one dying digit
+    if k == 5:
+        return "readout5"                                # <5,false>
+    if k == 4:
+        return "own4" if kout == 4 and surv == 0x3210 else "readout4"  # <4,true> / <4,false>
+    return f"k{k}"                                       # <3,false> / <2,false>
+
+
+def sweep_edges(s):
+    """Edge tags of one decoded SWEEP step.  hi = tiles of 8192 cells, tile_h = tiles per work item (the option sweep_iters; the
+    matrix runs with sweep_adapt 0, so the schedule does not change it): work item i takes the tiles [i tile_h, min(hi, (i + 1) tile_h)).
+      k<k>, kout0 / kout+      variables per pass; none / some of them replaced by a new axis
+      the shape                one of SWEEP_SHAPES (sweep_shape)
+      par, rbits               a stage whose T offset takes a ctrl value from bits 0-1 of r (source 8 + 0: the PAR form of a stage,
+                               two T columns per lane pair) / from any bits of r (source >= 8)
+      par_tail                 the LAST stage of a wave-owned tail (own5, dead<d>, own4) is of the PAR form: sweep_last_stage_out<K, true>
+      nctrl2+, ns2+            a stage with two or three ctrl values / with two or more small inputs
+      odd_tiles                an odd number of tiles: the R cells of the table - the stride between the tile's combinations in
+                               memory - are no power of two (a two- or three-state axis among them)
+      items2+                  more than one work item
+      multi_tile               a work item of two or more tiles: the next tile is fetched while the current one is finished
+      one_tile_item            a work item of exactly one tile: no next-tile fetch behind the (only, or last) tail
+      partial_tile             the last work item takes fewer tiles than the others
+      one_tile_step            a step of one tile (the planner emits none: IMPOSSIBLE_EDGES)
+      <shape>+<item tag>       both on the same step, for the wave-owned tails (SWEEP_TAILS)"""
+    out = set()
+    add = lambda e: out.add(f"sweep:{e}")
+    hi, th = s["hi"], s["tile_h"]
+    add(f"k{s['k']}")
+    add("kout0" if s["kout"] == 0 else "kout+")
+    shape = sweep_shape(s)
+    add(shape)
+    srcs = [c for g in s["stages"] for c in g["ctrl"]]
+    if 8 in srcs:
+        add("par")
+    if any(c >= 8 for c in srcs):
+        add("rbits")
+    if shape in SWEEP_TAILS + ("own4",) and 8 in s["stages"][-1]["ctrl"]:
+        add("par_tail")
+    if any(len(g["ctrl"]) >= 2 for g in s["stages"]):
+        add("nctrl2+")
+    if any(g["ns"] >= 2 for g in s["stages"]):
+        add("ns2+")
+    if hi % 2:
+        add("odd_tiles")
+    items = set()
+    if hi > th:
+        items.add("items2+")
+    if min(hi, th) >= 2:
+        items.add("multi_tile")
+    if th == 1 or hi % th == 1:
+        items.add("one_tile_item")
+    if hi % th:
+        items.add("partial_tile")
+    if hi == 1:
+        items.add("one_tile_step")
+    for e in items:
+        add(e)
+        if shape in SWEEP_TAILS:
+            add(f"{shape}+{e}")
+    return out
+
+
+def in_sweep_matrix(case):
+    """A case of the sweep matrix: the larger size cap holds for these alone."""
+    return case["recipe"][0] == "roof_grid_spec" or "sweep_iters" in case["options"] or "sweep_canon" in case["options"]
+
+
+def size_cap(case):
+    return (SWEEP_MAX_NODES, SWEEP_MAX_CELLS) if in_sweep_matrix(case) else (MAX_NODES, MAX_CELLS)
+
+
+_roof_specs = {}  # (the roof's CPT has up to 2 x 4^9 rows, and a base of the sweep matrix is used by two or three cases: built once, read only)
+
+
 def build_spec(case):
     fn, kw = case["recipe"]
     kw = dict(kw)
     if fn == "random_dag_spec":
         kw.update(p_zero=0.0, p_missing=0.0)
+    if fn == "roof_grid_spec":
+        key = repr(sorted(kw.items()))
+        if key not in _roof_specs:
+            _roof_specs[key] = netspec.roof_grid_spec(**kw)
+        return _roof_specs[key]
     return getattr(netspec, fn)(**kw)
 
 
@@ -97,18 +210,19 @@ def options(case):
     return {**DEFAULTS, **case["options"]}
 
 
-def set_sim_options(opt):
+def set_sim_options(opt, sweep_adapt=MATRIX_SWEEP_ADAPT):
     """The case's options on the simulator (process-wide)."""
     import simengine
     L = simengine.lib()
     L.plan_sim_set_small_cells(opt["small_cells"]); L.plan_sim_set_tiling(opt["big_iters"], opt["tile_h"]); L.plan_sim_set_fuse(opt["fuse"])
     L.plan_sim_set_chain(opt["chain"]); L.plan_sim_set_sweep(opt["sweep"]); L.plan_sim_set_sweep_min(opt["sweep_min"])
-    L.plan_sim_set_outer(opt["outer"]); L.plan_sim_set_prune(1); L.plan_sim_set_order_effort(opt["order_effort"], 1e7)
+    L.plan_sim_set_outer(opt["outer"]); L.plan_sim_set_prune(1); L.plan_sim_set_order_effort(opt["order_effort"], MATRIX_SECOND_ABOVE)
+    L.plan_sim_set_sweep_iters(opt["sweep_iters"]); L.plan_sim_set_sweep_canon(opt["sweep_canon"]); L.plan_sim_set_sweep_adapt(sweep_adapt)
 
 
 def reset_sim_options():
     """The product's defaults (a bare Network's: order_effort 0)."""
-    set_sim_options(DEFAULTS)
+    set_sim_options(DEFAULTS, PRODUCT_SWEEP_ADAPT)
 
 
 def flat_ids(flat, nodes):
@@ -126,6 +240,18 @@ def planned(flat, requests):
             edges |= step_edges(s)
             cells = max(cells, s["lo"] * s["hi"] * (s["cx"] if s["kind"] != "SWEEP" else 1) * s.get("NC", 1))
     return classes, edges, cells
+
+
+def c3_sweep_steps(n_requests=300):
+    """The decoded SWEEP steps (with cls and tile_h) of the first requests of the C3 stream - the 10 x 10 grid of four-state nodes, four
+    evidence nodes per request - under the simulator's options."""
+    import dump_plan as dp
+    import sorobn_amd
+    from sorobn_amd.flatten import flatten
+    flat = flatten(netspec.build(netspec.grid_spec(10, 10, 4, seed=0), sorobn_amd.BayesNet))
+    to_var = np.array([flat.id[f"{i:03d}"] for i in range(100)], np.int32)
+    q, ev, ec = netspec.c3_requests(100, 4, n_requests, 4, seed=1)
+    return [s for i in range(n_requests) for s in dp.decode(dp.program(flat, [to_var[q[i]]], to_var[ev[i]], ec[i]), classes=True) if s["kind"] == "SWEEP"]
 
 
 ROUTES = ("level", "sweep_dma", "sweep_reg", "segment", "mfma")  # planner.h LevelRoute, in order: the kernel a launch group goes to
@@ -378,7 +504,7 @@ CASES = [
          classes=['fiber<1,cx16,nc1>', 'fiber<1,cx4,nc1>', 'fiber<2,cx16,nc1>', 'generic<1>', 'generic<4>', 'generic<5>', 'segments',
                   've_sweep_kernel'],
          edges=['generic:lane_ragged', 'nc1:big_in_consts', 'nc1:lane_ragged', 'nc1:nctrl0', 'nc1:ns0', 'nc1:ns1', 'sweep:k2', 'sweep:kout0',
-                'sweep:partial_tile']),
+                'sweep:multi_tile', 'sweep:partial_tile', 'sweep:rbits']),
     dict(name='22-dag253604n23-sc32-bi8x3',
          recipe=('random_dag_spec', {'seed': 253604, 'n_nodes': 23, 'max_parents': 3, 'cards': (4, 4, 4, 4, 16, 2, 3), 'max_cells': 4096}),
          options={'big_iters': 8, 'fuse': 0, 'outer': 0, 'small_cells': 32, 'sweep': 0, 'tile_h': 3},
@@ -487,7 +613,8 @@ CASES = [
          requests=[(10, [], [])],
          nodes=12, max_cells=65536,
          classes=['fiber<1,cx4,nc4>', 'generic<4>', 'segments', 've_sweep_kernel'],
-         edges=['nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:k5', 'sweep:kout+', 'sweep:partial_tile']),
+         edges=['nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:k5', 'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+',
+                'sweep:partial_tile', 'sweep:rbits', 'sweep:readout5']),
     dict(name='36-mixed5x5s664334-sc32-bi2x1',
          recipe=('mixed_grid_spec', {'R': 5, 'C': 5, 'cards': [4, 2, 4, 4, 4], 'seed': 664334}),
          options={'small_cells': 32, 'big_iters': 2, 'tile_h': 1, 'sweep': 0, 'outer': 0},
@@ -515,6 +642,190 @@ CASES = [
          edges=['fiber<2,cx4,nc16-mfma>:rs4', 'nc16-mfma:big_in_consts', 'nc16-mfma:lane_ragged', 'nc16-mfma:nctrl+', 'nc16-mfma:ns2+',
                 'nc16-mfma:partial_tile', 'nc1:big_in_consts', 'nc1:lane_ragged', 'nc1:nctrl+', 'nc1:nctrl0', 'nc1:ns0', 'nc1:ns1',
                 'nc1:partial_tile']),
+    # the sweep matrix (see the module docstring): roofed grids, sweep_iters and sweep_canon set
+    dict(name='39-roof2x7s12857-sc256-bi1024x0-si8',
+         recipe=('roof_grid_spec', {'R': 2, 'C': 7, 'cards': [4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 12857}),
+         options={'small_cells': 256, 'big_iters': 1024, 'chain': 0, 'outer': 0, 'order_effort': 1},
+         requests=[(12, [14], [1])],
+         nodes=15, max_cells=65536,
+         classes=['fiber<1,cx16,ncN>', 'fiber<1,cx4,ncN>', 'segments', 've_sweep_kernel'],
+         edges=['ncN:big_in_consts', 'ncN:nctrl+', 'ncN:ns2+', 'ncN:partial_tile', 'sweep:k3', 'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+',
+                'sweep:ns2+', 'sweep:partial_tile', 'sweep:rbits']),
+    dict(name='40-roof3x8s54579-sc1024-bi512x0-si1',
+         recipe=('roof_grid_spec', {'R': 3, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 54579}),
+         options={'big_iters': 512, 'sweep_iters': 1},
+         requests=[(22, [24, 18, 10], [1, 1, 3])],
+         nodes=25, max_cells=262144,
+         classes=['fiber<1,cx16,nc16-mfma>', 'fiber<1,cx16,nc4>', 'fiber<1,cx4,nc4>', 'segments', 've_sweep_kernel'],
+         edges=['fiber<1,cx16,nc16-mfma>:rs1', 'nc16-mfma:nctrl+', 'nc16-mfma:ns2+', 'nc16-mfma:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+',
+                'nc4:ns1', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:dead3', 'sweep:dead3+items2+', 'sweep:dead3+one_tile_item', 'sweep:items2+',
+                'sweep:k5', 'sweep:kout+', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:one_tile_item', 'sweep:par', 'sweep:rbits']),
+    dict(name='41-roof3x8s54579-sc1024-bi512x0-si3',
+         recipe=('roof_grid_spec', {'R': 3, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 54579}),
+         options={'big_iters': 512, 'sweep_iters': 3},
+         requests=[(22, [24, 18, 10], [1, 1, 3])],
+         nodes=25, max_cells=262144,
+         classes=['fiber<1,cx16,nc16-mfma>', 'fiber<1,cx16,nc4>', 'fiber<1,cx4,nc4>', 'segments', 've_sweep_kernel'],
+         edges=['fiber<1,cx16,nc16-mfma>:rs1', 'nc16-mfma:nctrl+', 'nc16-mfma:ns2+', 'nc16-mfma:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+',
+                'nc4:ns1', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:dead3', 'sweep:dead3+items2+', 'sweep:dead3+multi_tile', 'sweep:dead3+partial_tile',
+                'sweep:items2+', 'sweep:k5', 'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:par', 'sweep:partial_tile',
+                'sweep:rbits']),
+    dict(name='42-roof3x8s74180-sc64-bi64x2-si1',
+         recipe=('roof_grid_spec', {'R': 3, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 74180}),
+         options={'small_cells': 64, 'big_iters': 64, 'tile_h': 2, 'sweep_iters': 1},
+         requests=[(16, [24, 18, 23], [0, 1, 1])],
+         nodes=25, max_cells=262144,
+         classes=['fiber<1,cx16,nc1>', 'fiber<1,cx4,nc4>', 'segments', 've_sweep_kernel'],
+         edges=['nc1:nctrl+', 'nc1:nctrl0', 'nc1:ns0', 'nc1:ns1', 'nc1:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'sweep:dead4',
+                'sweep:dead4+items2+', 'sweep:dead4+one_tile_item', 'sweep:items2+', 'sweep:k4', 'sweep:k5', 'sweep:kout+', 'sweep:nctrl2+',
+                'sweep:ns2+', 'sweep:one_tile_item', 'sweep:own4', 'sweep:own5', 'sweep:own5+items2+', 'sweep:own5+one_tile_item', 'sweep:par',
+                'sweep:rbits']),
+    dict(name='43-roof3x8s74180-sc64-bi64x2-si2-any',
+         recipe=('roof_grid_spec', {'R': 3, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 74180}),
+         options={'small_cells': 64, 'big_iters': 64, 'tile_h': 2, 'sweep_iters': 2, 'sweep_canon': 0},
+         requests=[(16, [24, 18, 23], [0, 1, 1])],
+         nodes=25, max_cells=262144,
+         classes=['fiber<1,cx16,nc1>', 'fiber<1,cx4,nc4>', 'segments', 've_sweep_kernel'],
+         edges=['nc1:nctrl+', 'nc1:nctrl0', 'nc1:ns0', 'nc1:ns1', 'nc1:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'sweep:any',
+                'sweep:items2+', 'sweep:k4', 'sweep:k5', 'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:par', 'sweep:rbits']),
+    dict(name='44-roof3x8s74180-sc64-bi64x2-si3',
+         recipe=('roof_grid_spec', {'R': 3, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 74180}),
+         options={'small_cells': 64, 'big_iters': 64, 'tile_h': 2, 'sweep_iters': 3},
+         requests=[(16, [24, 18, 23], [0, 1, 1])],
+         nodes=25, max_cells=262144,
+         classes=['fiber<1,cx16,nc1>', 'fiber<1,cx4,nc4>', 'segments', 've_sweep_kernel'],
+         edges=['nc1:nctrl+', 'nc1:nctrl0', 'nc1:ns0', 'nc1:ns1', 'nc1:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'sweep:dead4',
+                'sweep:dead4+items2+', 'sweep:dead4+multi_tile', 'sweep:dead4+partial_tile', 'sweep:items2+', 'sweep:k4', 'sweep:k5', 'sweep:kout+',
+                'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:own4', 'sweep:own5', 'sweep:own5+items2+', 'sweep:own5+multi_tile',
+                'sweep:own5+partial_tile', 'sweep:par', 'sweep:partial_tile', 'sweep:rbits']),
+    dict(name='45-roof3x8s84521-sc1024-bi64x0-si1',
+         recipe=('roof_grid_spec', {'R': 3, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 84521}),
+         options={'big_iters': 64, 'outer': 0, 'sweep_iters': 1},
+         requests=[(21, [24, 12, 22], [0, 0, 2])],
+         nodes=25, max_cells=262144,
+         classes=['fiber<1,cx4,nc1>', 'fiber<1,cx4,nc4>', 'fiber<1,cx64,chain-mfma>', 'generic<1>', 'segments', 've_sweep_kernel'],
+         edges=['chain:nctrl+', 'chain:ns2+', 'chain:partial_tile', 'fiber<1,cx64,chain-mfma>:rs1', 'generic:partial_tile', 'nc1:nctrl0', 'nc1:ns0',
+                'nc1:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:dead1', 'sweep:dead1+items2+',
+                'sweep:dead1+one_tile_item', 'sweep:dead3', 'sweep:dead3+items2+', 'sweep:dead3+one_tile_item', 'sweep:items2+', 'sweep:k5',
+                'sweep:kout+', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:one_tile_item', 'sweep:par', 'sweep:rbits']),
+    dict(name='46-roof3x8s84521-sc1024-bi64x0-si3',
+         recipe=('roof_grid_spec', {'R': 3, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 84521}),
+         options={'big_iters': 64, 'outer': 0, 'sweep_iters': 3},
+         requests=[(21, [24, 12, 22], [0, 0, 2])],
+         nodes=25, max_cells=262144,
+         classes=['fiber<1,cx4,nc1>', 'fiber<1,cx4,nc4>', 'fiber<1,cx64,chain-mfma>', 'generic<1>', 'segments', 've_sweep_kernel'],
+         edges=['chain:nctrl+', 'chain:ns2+', 'chain:partial_tile', 'fiber<1,cx64,chain-mfma>:rs1', 'generic:partial_tile', 'nc1:nctrl0', 'nc1:ns0',
+                'nc1:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:dead1', 'sweep:dead1+items2+',
+                'sweep:dead1+multi_tile', 'sweep:dead1+partial_tile', 'sweep:dead3', 'sweep:dead3+multi_tile', 'sweep:dead3+partial_tile',
+                'sweep:items2+', 'sweep:k5', 'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:par', 'sweep:partial_tile',
+                'sweep:rbits']),
+    dict(name='47-roof4x7s74590-sc16-bi64x2-si8',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 7, 'cards': [4, 4, 4, 4, 4, 4, 3], 'roof_card': 4, 'seed': 74590}),
+         options={'small_cells': 16, 'big_iters': 64, 'tile_h': 2, 'sweep': 3},
+         requests=[(24, [28, 10, 16], [2, 1, 2])],
+         nodes=29, max_cells=65536,
+         classes=['fiber<1,cx4,nc1>', 'fiber<1,cx4,nc4>', 'fiber<1,cxN,nc1>', 'fiber<2,cx16,nc1>', 'fiber<2,cx16,ncN>', 'generic<3>', 'segments',
+                  've_sweep_kernel'],
+         edges=['nc1:big_in_consts', 'nc1:c1_ne_c2', 'nc1:nctrl+', 'nc1:ns1', 'nc1:ns2+', 'nc1:partial_tile', 'nc4:big_in_consts', 'nc4:lane_ragged',
+                'nc4:nctrl0', 'nc4:ns1', 'nc4:partial_tile', 'ncN:big_in_consts', 'ncN:nctrl+', 'ncN:ns2+', 'ncN:partial_tile', 'sweep:k2',
+                'sweep:kout0', 'sweep:multi_tile', 'sweep:partial_tile', 'sweep:rbits']),
+    dict(name='48-roof4x8s4165-sc64-bi1024x0-si2',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 8, 'cards': [4, 4, 4, 4, 3, 2, 4, 4], 'roof_card': 2, 'seed': 4165}),
+         options={'big_iters': 1024, 'small_cells': 64, 'order_effort': 1, 'chain': 0, 'outer': 0, 'sweep_iters': 2},
+         requests=[(30, [32, 26], [1, 0])],
+         nodes=33, max_cells=294912,
+         classes=['fiber<1,cx16,nc16>', 'fiber<1,cx16,nc4>', 'fiber<1,cx4,nc4>', 'fiber<1,cxN,ncN>', 'segments', 've_sweep_kernel'],
+         edges=['nc16:lane_ragged', 'nc16:nctrl+', 'nc16:ns2+', 'nc16:partial_tile', 'nc4:big_in_consts', 'nc4:lane_ragged', 'nc4:nctrl+', 'nc4:ns2+',
+                'nc4:partial_tile', 'ncN:c1_ne_c2', 'ncN:cx_not_mult4', 'ncN:nc_not_pow2', 'ncN:nctrl+', 'ncN:nctrl0', 'ncN:ns2+', 'ncN:partial_tile',
+                'sweep:dead4', 'sweep:dead4+items2+', 'sweep:dead4+multi_tile', 'sweep:dead4+one_tile_item', 'sweep:dead4+partial_tile',
+                'sweep:items2+', 'sweep:k5', 'sweep:kout+', 'sweep:multi_tile', 'sweep:odd_tiles', 'sweep:one_tile_item', 'sweep:partial_tile']),
+    dict(name='49-roof4x8s4187-sc256-bi256x0-si2',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 8, 'cards': [4, 2, 3, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 4187}),
+         options={'big_iters': 256, 'small_cells': 256, 'order_effort': 1, 'chain': 0, 'outer': 0, 'sweep_iters': 2},
+         requests=[(25, [32, 31], [1, 3])],
+         nodes=33, max_cells=393216,
+         classes=['fiber<1,cx16,nc16>', 'fiber<1,cx16,ncN>', 'fiber<1,cx4,nc4>', 'fiber<1,cxN,nc1>', 'fiber<1,cxN,ncN>', 'segments', 've_sweep_kernel'],
+         edges=['nc16:lane_ragged', 'nc16:nctrl+', 'nc16:ns2+', 'nc16:partial_tile', 'nc1:cx_not_mult4', 'nc1:nctrl0', 'nc1:ns0', 'nc1:partial_tile',
+                'nc4:big_in_consts', 'nc4:lane_ragged', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'ncN:c1_ne_c2', 'ncN:cx_not_mult4',
+                'ncN:lane_ragged', 'ncN:nc_not_pow2', 'ncN:nctrl+', 'ncN:ns2+', 'ncN:partial_tile', 'sweep:items2+', 'sweep:k4', 'sweep:k5',
+                'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:odd_tiles', 'sweep:one_tile_item', 'sweep:own4',
+                'sweep:own5', 'sweep:own5+items2+', 'sweep:own5+multi_tile', 'sweep:own5+one_tile_item', 'sweep:own5+partial_tile', 'sweep:par',
+                'sweep:partial_tile', 'sweep:rbits', 'sweep:readout4']),
+    dict(name='50-roof4x8s6089-sc1024-bi64x0-si1',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 4, 'seed': 6089}),
+         options={'big_iters': 64, 'chain': 0, 'outer': 0, 'order_effort': 1, 'sweep_iters': 1},
+         requests=[(30, [32, 11], [2, 3])],
+         nodes=33, max_cells=262144,
+         classes=['fiber<1,cx16,nc16-mfma>', 'fiber<1,cx4,nc4>', 'generic<1>', 'segments', 've_sweep_kernel'],
+         edges=['fiber<1,cx16,nc16-mfma>:rs1', 'generic:partial_tile', 'nc16-mfma:nctrl+', 'nc16-mfma:ns2+', 'nc16-mfma:partial_tile',
+                'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:dead2', 'sweep:dead2+items2+', 'sweep:dead2+one_tile_item',
+                'sweep:dead3', 'sweep:dead3+items2+', 'sweep:dead3+one_tile_item', 'sweep:items2+', 'sweep:k5', 'sweep:kout+', 'sweep:nctrl2+',
+                'sweep:ns2+', 'sweep:one_tile_item', 'sweep:own5', 'sweep:own5+items2+', 'sweep:own5+one_tile_item', 'sweep:par', 'sweep:rbits',
+                'sweep:readout5']),
+    dict(name='51-roof4x8s6089-sc1024-bi64x0-si3',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 8, 'cards': [4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 4, 'seed': 6089}),
+         options={'big_iters': 64, 'chain': 0, 'outer': 0, 'order_effort': 1, 'sweep_iters': 3},
+         requests=[(30, [32, 11], [2, 3])],
+         nodes=33, max_cells=262144,
+         classes=['fiber<1,cx16,nc16-mfma>', 'fiber<1,cx4,nc4>', 'generic<1>', 'segments', 've_sweep_kernel'],
+         edges=['fiber<1,cx16,nc16-mfma>:rs1', 'generic:partial_tile', 'nc16-mfma:nctrl+', 'nc16-mfma:ns2+', 'nc16-mfma:partial_tile',
+                'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:dead2', 'sweep:dead2+items2+', 'sweep:dead2+multi_tile',
+                'sweep:dead2+partial_tile', 'sweep:dead3', 'sweep:dead3+multi_tile', 'sweep:dead3+partial_tile', 'sweep:items2+', 'sweep:k5',
+                'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:own5', 'sweep:own5+multi_tile', 'sweep:own5+partial_tile',
+                'sweep:par', 'sweep:partial_tile', 'sweep:rbits', 'sweep:readout5']),
+    dict(name='52-roof5x7s3039-sc1024-bi1024x0-si1',
+         recipe=('roof_grid_spec', {'R': 5, 'C': 7, 'cards': [4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 3039}),
+         options={'big_iters': 1024, 'sweep_iters': 1},
+         requests=[(34, [35], [1])],
+         nodes=36, max_cells=65536,
+         classes=['fiber<1,cx16,nc16-mfma>', 'fiber<1,cx16,nc4>', 'fiber<1,cx4,ncN>', 'fiber<1,cx64,chain-mfma>', 'generic<2>', 'segments',
+                  've_sweep_kernel'],
+         edges=['chain:nctrl+', 'chain:nctrl0', 'chain:ns2+', 'fiber<1,cx16,nc16-mfma>:rs16', 'fiber<1,cx64,chain-mfma>:rs1',
+                'fiber<1,cx64,chain-mfma>:rs16', 'generic:partial_tile', 'nc16-mfma:nctrl+', 'nc16-mfma:ns2+', 'nc16-mfma:partial_tile', 'nc4:nctrl0',
+                'nc4:ns1', 'nc4:partial_tile', 'ncN:big_in_consts', 'ncN:nctrl+', 'ncN:ns2+', 'ncN:partial_tile', 'sweep:dead1',
+                'sweep:dead1+items2+', 'sweep:dead1+one_tile_item', 'sweep:items2+', 'sweep:k5', 'sweep:kout+', 'sweep:nctrl2+', 'sweep:ns2+',
+                'sweep:one_tile_item', 'sweep:par', 'sweep:par_tail', 'sweep:rbits']),
+    dict(name='53-roof5x7s3039-sc1024-bi1024x0-si2',
+         recipe=('roof_grid_spec', {'R': 5, 'C': 7, 'cards': [4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 3039}),
+         options={'big_iters': 1024, 'sweep_iters': 2},
+         requests=[(34, [35], [1])],
+         nodes=36, max_cells=65536,
+         classes=['fiber<1,cx16,nc16-mfma>', 'fiber<1,cx16,nc4>', 'fiber<1,cx4,ncN>', 'fiber<1,cx64,chain-mfma>', 'generic<2>', 'segments',
+                  've_sweep_kernel'],
+         edges=['chain:nctrl+', 'chain:nctrl0', 'chain:ns2+', 'fiber<1,cx16,nc16-mfma>:rs16', 'fiber<1,cx64,chain-mfma>:rs1',
+                'fiber<1,cx64,chain-mfma>:rs16', 'generic:partial_tile', 'nc16-mfma:nctrl+', 'nc16-mfma:ns2+', 'nc16-mfma:partial_tile', 'nc4:nctrl0',
+                'nc4:ns1', 'nc4:partial_tile', 'ncN:big_in_consts', 'ncN:nctrl+', 'ncN:ns2+', 'ncN:partial_tile', 'sweep:dead1',
+                'sweep:dead1+multi_tile', 'sweep:k5', 'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:par', 'sweep:par_tail',
+                'sweep:rbits']),
+    dict(name='54-roof4x9s2002-sc1024-bi512x0-si8',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 9, 'cards': [4, 4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 2002}),
+         options={'big_iters': 512, 'order_effort': 1},
+         requests=[(27, [36, 35], [0, 1])],
+         nodes=37, max_cells=1048576,
+         classes=['fiber<1,cx16,nc1>', 'fiber<1,cx4,nc1>', 'fiber<1,cx4,nc4>', 'segments', 've_sweep_kernel'],
+         edges=['nc1:nctrl0', 'nc1:ns0', 'nc1:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns2+', 'nc4:partial_tile', 'sweep:items2+',
+                'sweep:k2', 'sweep:k4', 'sweep:k5', 'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:own4', 'sweep:own5',
+                'sweep:own5+items2+', 'sweep:own5+multi_tile', 'sweep:par', 'sweep:rbits']),
+    dict(name='55-roof4x9s2002-sc256-bi64x0-si1',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 9, 'cards': [4, 4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 2002}),
+         options={'big_iters': 64, 'small_cells': 256, 'sweep_iters': 1},
+         requests=[(31, [36, 5], [1, 2])],
+         nodes=37, max_cells=262144,
+         classes=['fiber<1,cx16,nc4>', 'fiber<1,cx4,nc4>', 'fiber<1,cx64,chain-mfma>', 'generic<1>', 'segments', 've_sweep_kernel'],
+         edges=['chain:lane_ragged', 'chain:nctrl+', 'chain:ns2+', 'chain:partial_tile', 'fiber<1,cx64,chain-mfma>:rs1',
+                'fiber<1,cx64,chain-mfma>:rs4', 'generic:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns1', 'nc4:ns2+', 'nc4:partial_tile',
+                'sweep:dead0', 'sweep:dead0+items2+', 'sweep:dead0+one_tile_item', 'sweep:items2+', 'sweep:k5', 'sweep:kout+', 'sweep:nctrl2+',
+                'sweep:ns2+', 'sweep:one_tile_item', 'sweep:par', 'sweep:rbits', 'sweep:readout5']),
+    dict(name='56-roof4x9s2002-sc256-bi64x0-si3',
+         recipe=('roof_grid_spec', {'R': 4, 'C': 9, 'cards': [4, 4, 4, 4, 4, 4, 4, 4, 4], 'roof_card': 2, 'seed': 2002}),
+         options={'big_iters': 64, 'small_cells': 256, 'sweep_iters': 3},
+         requests=[(31, [36, 5], [1, 2])],
+         nodes=37, max_cells=262144,
+         classes=['fiber<1,cx16,nc4>', 'fiber<1,cx4,nc4>', 'fiber<1,cx64,chain-mfma>', 'generic<1>', 'segments', 've_sweep_kernel'],
+         edges=['chain:lane_ragged', 'chain:nctrl+', 'chain:ns2+', 'chain:partial_tile', 'fiber<1,cx64,chain-mfma>:rs1',
+                'fiber<1,cx64,chain-mfma>:rs4', 'generic:partial_tile', 'nc4:big_in_consts', 'nc4:nctrl+', 'nc4:ns1', 'nc4:ns2+', 'nc4:partial_tile',
+                'sweep:dead0', 'sweep:dead0+items2+', 'sweep:dead0+multi_tile', 'sweep:dead0+partial_tile', 'sweep:items2+', 'sweep:k5',
+                'sweep:kout+', 'sweep:multi_tile', 'sweep:nctrl2+', 'sweep:ns2+', 'sweep:par', 'sweep:partial_tile', 'sweep:rbits', 'sweep:readout5']),
 ]
 
 # The edges of step_edges every family of tiled FIBER classes must show somewhere in the table ...
@@ -528,16 +839,20 @@ REQUIRED_EDGES = {
     "nc16-mfma": ["big_in_consts", "lane_ragged", "nctrl+", "nctrl0", "ns1", "ns2+", "partial_tile"],
     "outer-mfma": ["big_in_consts", "lane_ragged", "nctrl+", "nctrl0", "ns0", "ns1", "ns2+", "partial_tile"],
     "chain": ["big_in_consts", "lane_ragged", "nctrl+", "nctrl0", "ns1", "ns2+", "partial_tile"],
-    # SWEEP: a tile is 8192 cells, so a step within the table's 2^16 cells has at most 8 tiles - one workgroup of sweep_iters = 8.  Both
-    # witnesses are two-tile steps (a workgroup that takes fewer tiles than sweep_iters), the shortest pass (k = 2, no surviving digit)
-    # and the longest (k = 5, one survivor).  Full workgroups, many of them, and every dying digit of a five-variable pass are what the
-    # C3 tests run (test_sweep_kernels_agree_bit_for_bit, test_the_gpu_parity_streams_exercise_every_shape_of_the_sweep_tail).
-    "sweep": ["k2", "k5", "kout0", "kout+", "partial_tile"],
+    # SWEEP: the sweep matrix.  Every specialisation ve_sweep_dma_kernel dispatches to (SWEEP_SHAPES), every form of a stage
+    # (SWEEP_STAGES) and every shape of the tile loop (SWEEP_ITEMS), and each wave-owned tail (SWEEP_TAILS) crossed with the shapes of
+    # the tile loop: work items of one, two and three tiles, several of them, the last one shorter.  The C3 tests run most of the
+    # shapes as well, on whole work items only (test_the_c3_census_of_sweep_shapes).
+    "sweep": ["k4", "k5", "kout0", "kout+", *SWEEP_SHAPES, *SWEEP_STAGES, *SWEEP_STEP, *[e for e in SWEEP_ITEMS if e != "one_tile_step"],
+              *[f"{t}+{e}" for t in SWEEP_TAILS for e in SWEEP_ITEMS if e != "one_tile_step"]],
 }
+SWEEP_EDGES = ("k4", "k5", "kout0", "kout+", *SWEEP_SHAPES, *SWEEP_STAGES, *SWEEP_STEP, *SWEEP_ITEMS, *[f"{t}+{e}" for t in SWEEP_TAILS for e in SWEEP_ITEMS])
 # ... and why a family lacks the others (the condition of emit_core.h that excludes the shape)
 _NO_NS0 = "N axes are output axes no big input depends on, so only a small input brings them: ns = 0 means nN = 0 and NC = 1 (emit_fiber)"
 _CX_4_16 = "fiber_cx_class(w) < 2 / `if (!((cx == 4 && c1 == 4) || (cx == 16 && c1 == 4))) return false;`: cx is 4 or 4 x 4"
 _POW2 = "NC is 1, 4 or 16 by the definition of the class (fiber_nc_class)"
+_TWO_TILES = ("emit_core.h, the SWEEP candidates of emit_program: `if (nbig == 1 && !(bigf->off & kConstFlag) && bigf->cells >= 16 * (int64_t)net.big_iters && "
+              "bigf->cells >= 2 * kSweepTileCells) {` - the big input of a SWEEP step has at least two tiles")
 IMPOSSIBLE_EDGES = {
     "nc1": {"nc_not_pow2": _POW2},
     "nc4": {"ns0": _NO_NS0, "nc_not_pow2": _POW2},
@@ -548,6 +863,7 @@ IMPOSSIBLE_EDGES = {
     "chain": {"ns0": "emit_chain_as: `if (nn12 != 2 || nax3 < 0) return false;` - the two N axes of the pair table are axes a pair-group small input depends on",
               "cx_not_mult4": "emit_chain_as: `if (net.card[out.vars[a]] != 4) return false;` and three 4-state variables: cx = 64",
               "c1_ne_c2": "the same: all three eliminated variables have four states", "nc_not_pow2": "NC = 16 (x 4 in registers)"},
+    "sweep": {e: _TWO_TILES for e in ("one_tile_step", *[f"{t}+one_tile_step" for t in SWEEP_TAILS])},
 }
 # The row stride of the MFMA forms (w1 bits 20..27): both classes of ve_mfma_kernel, CHAIN, both two-table pair classes and both
 # OUTER classes at 1, 4 and 16.

@@ -137,6 +137,23 @@ def mixed_grid_spec(R, C, cards, seed):
     return {"name": f"mixed{R}x{C}s{seed}", "hashed_names": True, "nodes": order, "edges": edges, "cpts": cpts}
 
 
+def roof_grid_spec(R, C, cards, roof_card, seed):
+    """netspec.mixed_grid_spec plus a "roof": one more node (id R * C, roof_card states) whose parents are the whole first row.
+    Evidence on the roof ties the C variables of a row together, so every elimination order of the grid below it carries a table
+    over C of them - the row sweeps of a wide grid (a frontier of C variables, each eliminated one bringing in its successor in the
+    next row) on a network of R * C + 1 nodes.  The roof's CPT has roof_card * prod(cards) cells."""
+    spec = mixed_grid_spec(R, C, cards, seed)
+    roof, top = f"{R * C:03d}", [f"{c:03d}" for c in range(C)]
+    rng = np.random.default_rng([seed, R, C])
+    p = rng.dirichlet(np.ones(roof_card), size=int(np.prod(cards))).reshape(-1)
+    doms = [range(k) for k in cards] + [range(roof_card)]
+    spec["name"] = f"roof{R}x{C}s{seed}"
+    spec["nodes"] = spec["nodes"] + [roof]
+    spec["edges"] = spec["edges"] + [[t, roof] for t in top]
+    spec["cpts"][roof] = {"names": top + [roof], "rows": [list(cfg) + [float(v)] for cfg, v in zip(itertools.product(*doms), p)]}
+    return spec
+
+
 def random_dag_spec(seed, n_nodes=None, max_parents=3, cards=(2, 3, 4, 5), p_zero=0.08,
                     p_missing=0.05, labels="int", max_cells=None):
     """Random DAG with mixed cardinalities, Dirichlet CPTs, some exact zeros and missing rows.  `max_cells` (cardinalities in the

@@ -41,6 +41,9 @@ def lib():
         L.plan_sim_class_names.restype = C.c_int64
         L.plan_sim_set_sweep.argtypes = [C.c_int]
         L.plan_sim_set_sweep_min.argtypes = [C.c_int]
+        L.plan_sim_set_sweep_iters.argtypes = [C.c_int]
+        L.plan_sim_set_sweep_canon.argtypes = [C.c_int]
+        L.plan_sim_set_sweep_adapt.argtypes = [C.c_int]
         L.plan_sim_set_prune.argtypes = [C.c_int]
         _lib = L
     return _lib
@@ -58,6 +61,9 @@ class SimEngine:
         self.outer = 1                  # OUTER form (fp64 MFMA) for products of two big tables, on by default like the product
         self.sweep_min = 2              # fewest variables of a SWEEP pass (2: pair steps too)
         self.sweep = 5                  # SWEEP form (up to five variables per pass, tile in LDS), on by default like the product
+        self.sweep_iters = 8            # tiles per work item of a SWEEP step
+        self.sweep_canon = 1            # 0 (the engine's test hook): no SWEEP step is flagged canonical
+        self.sweep_adapt = 4096         # build_schedule: fewer tiles per work item in small sweep launches (0: off)
         self.f = flat
         self.card = flat.card
         self.last_stats = None
@@ -82,6 +88,9 @@ class SimEngine:
         L.plan_sim_set_outer(int(self.outer))
         L.plan_sim_set_sweep(int(self.sweep))
         L.plan_sim_set_sweep_min(int(self.sweep_min))
+        L.plan_sim_set_sweep_iters(int(self.sweep_iters))
+        L.plan_sim_set_sweep_canon(int(self.sweep_canon))
+        L.plan_sim_set_sweep_adapt(int(self.sweep_adapt))
         rc = L.plan_sim_query(len(f.card), p(f.card, C.c_int32), p(f.scope_off, C.c_int64),
                               p(f.scope_vars, C.c_int32), p(f.value_off, C.c_int64),
                               p(f.values, C.c_double), self.hints.shape[0], p(hints, C.c_int32),
@@ -118,6 +127,9 @@ class SimEngine:
         L.plan_sim_set_outer(int(self.outer))
         L.plan_sim_set_sweep(int(self.sweep))
         L.plan_sim_set_sweep_min(int(self.sweep_min))
+        L.plan_sim_set_sweep_iters(int(self.sweep_iters))
+        L.plan_sim_set_sweep_canon(int(self.sweep_canon))
+        L.plan_sim_set_sweep_adapt(int(self.sweep_adapt))
         ev_ = evars.reshape(-1) if ne else np.zeros(1, np.int32)
         ec_ = ecodes.reshape(-1) if ne else np.zeros(1, np.int32)
         rc = L.plan_sim_query_batch(len(f.card), p(f.card, C.c_int32), p(f.scope_off, C.c_int64), p(f.scope_vars, C.c_int32),
@@ -150,6 +162,8 @@ class SimEngine:
             self.sweep = int(value)
         elif name == "sweep_min":
             self.sweep_min = int(value)
+        elif name in ("sweep_iters", "sweep_canon", "sweep_adapt"):
+            setattr(self, name, int(value))
         elif name == "tiny":
             pass  # (the small-network kernel exists on the device only)
         else:

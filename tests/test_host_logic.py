@@ -976,35 +976,32 @@ def test_the_gpu_parity_streams_exercise_every_shape_of_the_sweep_tail():
     sweep_last_stage_out_dead): the digit of any of the five stages.  The GPU tests that hold that code against the register-staged
     kernel bit for bit and against the reference run the first requests of the C3 stream - this checks, on the planner's programs,
     that those requests contain canonical five-variable passes with EACH of the five digits dying, the all-survive form and the
-    shapes that stay on the readout path (two dead digits)."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import dump_plan as dp
-    L = simengine.lib()  # (the simulator's planner options are process-wide: the product's defaults, whatever an earlier test left)
-    L.plan_sim_set_small_cells(1024); L.plan_sim_set_tiling(4096, 0); L.plan_sim_set_fuse(1); L.plan_sim_set_chain(1)
-    L.plan_sim_set_sweep(5); L.plan_sim_set_sweep_min(2); L.plan_sim_set_prune(1)
-    f = flatten(netspec.build(netspec.grid_spec(10, 10, 4, seed=0), sorobn_amd.BayesNet))
-    to_var = np.array([f.id[f"{i:03d}"] for i in range(100)], np.int32)
-    q, ev, ec = netspec.c3_requests(100, 4, 300, 4, seed=1)
-    own, dead, two_dead = 0, set(), 0
-    packs = {0x4321: 0, 0x4320: 1, 0x4310: 2, 0x4210: 3, 0x3210: 4}
-    for i in range(300):
-        w = dp.program(f, [to_var[q[i]]], to_var[ev[i]], ec[i])
-        p = 1
-        for s in dp.decode(w):
-            if s["kind"] == "SWEEP" and s["k"] == 5 and (int(w[p + 1]) >> 16) & 16:  # canonical five-variable pass
-                surv = int(w[p + 8])
-                died = [4 - j for j, g in enumerate(s["stages"]) if g["cout"] == 1]
-                if s["kout"] == 5:
-                    assert surv == 0x43210 and not died
-                    own += 1
-                elif s["kout"] == 4:
-                    assert len(died) == 1 and packs[surv] == died[0], (hex(surv), died)  # the survivors stay in place, ascending
-                    dead.add(died[0])
-                elif s["kout"] == 3:
-                    two_dead += 1
-            p += s["words"]
+    shapes that stay on the readout path (two dead digits) - and, by the tags of the sweep matrix (tests/class_cases.py sweep_edges),
+    every other specialisation of ve_sweep_dma_kernel, stage form and whole-work-item shape of the tile loop the matrix pins."""
+    import class_cases as cc  # (the tagger of the sweep matrix: sweep_shape restates the dispatch of ve_sweep_dma_kernel)
+    cc.reset_sim_options()  # (the simulator's planner options are process-wide: the product's defaults, whatever an earlier test left)
+    own, dead, two_dead, tags = 0, set(), 0, set()
+    for s in cc.c3_sweep_steps(300):
+        shape = cc.sweep_shape(s)
+        tags |= cc.sweep_edges(s)
+        if s["k"] == 5 and s["canon"]:  # canonical five-variable pass
+            died = [4 - j for j, g in enumerate(s["stages"]) if g["cout"] == 1]
+            if s["kout"] == 5:
+                assert s["surv"] == 0x43210 and not died and shape == "own5"
+                own += 1
+            elif s["kout"] == 4:
+                assert len(died) == 1 and cc.SWEEP_DEAD_PACKS[s["surv"]] == died[0], (hex(s["surv"]), died)  # the survivors stay in place, ascending
+                assert shape == f"dead{died[0]}"
+                dead.add(died[0])
+            else:
+                assert shape == "readout5"
+                two_dead += s["kout"] == 3
     assert own > 100 and dead == {0, 1, 2, 3, 4} and two_dead > 0, (own, dead, two_dead)
+    # every shape of the sweep matrix but the ragged ones of the tile loop (a last work item shorter than the others, a work item of one
+    # tile, an odd number of tiles: C3's steps are whole work items of 8, 32 or 128 tiles) and the PAR form of a tail's last stage (one step in 300 requests with order_effort 1, none here)
+    want = {f"sweep:{e}" for e in cc.REQUIRED_EDGES["sweep"] if "partial_tile" not in e and "one_tile_item" not in e and e not in ("par_tail", "odd_tiles")}
+    assert len(want) == 34 and {f"sweep:{e}" for e in (*cc.SWEEP_SHAPES, "par", "rbits", "nctrl2+", "ns2+", "items2+", "multi_tile")} <= want
+    assert want <= tags, sorted(want - tags)
 
 
 # ------------------------------------------------------------------------------------ round 5: the pandas boundary, vectorised

@@ -1,8 +1,11 @@
 """The class matrix on the device (pytest -m gpu): every case of tests/class_cases.py - small pinned networks whose programs contain,
 between them, every class of work the planner can emit - against the C oracle, request by request and cell by cell, once with one
 launch per class (the statistics then name the classes that ran) and once in the product's launch shape (ve_mfma_kernel for the
-one-table fp64-MFMA classes, ve_segment_kernel for the segments), plus the level kernel's twin of the MFMA kernel.
-tests/test_kernel_classes_host.py proves on the CPU that the cases contain the classes and the edge shapes they claim."""
+one-table fp64-MFMA classes, ve_segment_kernel for the segments), plus the level kernel's twin of the MFMA kernel.  The cases with a
+SWEEP step - the sweep matrix: every path of ve_sweep_dma_kernel by name - run once more under each of the two sweep kernels, alone
+and as a batch of three, bit for bit equal (test_sweep_case_under_both_kernels).  The engine plans with the simulator's settings
+(_setup), so the programs on the device are the ones tests/test_kernel_classes_host.py proves on the CPU: that the cases contain
+the classes and the edge shapes they claim."""
 import time
 
 import numpy as np
@@ -19,7 +22,12 @@ TWIN_TOL = 1e-13  # two forms of one computation (the bound of test_wide_grids_e
 STAT_NAMES = {cc.SWEEP: ("ve_sweep_kernel", "ve_sweep_dma_kernel")}
 
 _worst = {}   # class name -> largest |error| against the oracle over the requests whose programs contain it
+_worst_sweep = {}  # sweep tag (class_cases.sweep_edges) -> the same, over both sweep kernels and both launch shapes
+_wants = {}    # (recipe, request) -> the oracle's posterior
+_oracles = {}  # recipe -> OracleNet: a base of the sweep matrix is shared by two or three cases
+SWEEP_CASES = [c for c in cc.CASES if any(e.startswith("sweep:") for e in c["edges"])]
 _ran = []     # (case name, seconds)
+_ran_sweep = []  # the same, of test_sweep_case_under_both_kernels
 _t0 = time.perf_counter()
 
 
@@ -33,23 +41,56 @@ def _run(eng, flat, requests):
     return [out[a:b] for a, b in zip(off[:-1], off[1:])], {k["name"] for k in eng.kernel_stats()}
 
 
-@pytest.mark.parametrize("case", cc.CASES, ids=[c["name"] for c in cc.CASES])
-def test_class_case_vs_oracle(amd, case):
+def _setup(amd, case):
+    """(engine, flat network, oracle network, options) of a case: the host plans, with the options of the case and nothing the policy turns."""
     import netspec
     from oracle.oracle import OracleNet
-    t0 = time.perf_counter()
     spec = cc.build_spec(case)
     bn = netspec.build(spec, amd.BayesNet)
     eng, flat = bn.backend.engine, bn.backend.flat
-    on = OracleNet(spec)
+    key = repr(case["recipe"])
+    if key not in _oracles:
+        _oracles[key] = OracleNet(spec)
     opt = cc.options(case)
     eng.set_option("tiny", 0)       # (the small-network kernel would answer these networks without a program)
-    eng.set_option("adaptive", 0)   # the host plans, with the options of the case and nothing the policy turns
+    eng.set_option("adaptive", 0)
     eng.set_option("gpu_emit", 0)
+    eng.set_option("sweep_adapt", cc.MATRIX_SWEEP_ADAPT)  # a SWEEP step's work items are the sweep_iters tiles of the case
+    eng.set_option("minfill_above", cc.MATRIX_MINFILL_ABOVE)  # the order search of the simulator: the programs the host test proved
+    eng.set_option("second_above", cc.MATRIX_SECOND_ABOVE)
     for name in cc.OPTION_NAMES:
         eng.set_option(name, opt[name])
+    return eng, flat, _oracles[key], opt
+
+
+def _want(case, flat, on, rq):
+    """The oracle's posterior of one request of a case - computed once, shared by the tests and by the cases of one base, left unchanged."""
+    q, ev, ec = rq
+    key = (repr(case["recipe"]), q, tuple(ev), tuple(ec))
+    if key not in _wants:
+        _wants[key] = cc.oracle_dense(on, int(flat.card[flat.id[f"{q:03d}"]]), q, ev, ec)
+        _wants[key].setflags(write=False)
+    return _wants[key]
+
+
+def _note_sweep_tags(flat, opt, reqs, errs):
+    """errs[i] - the largest error of request i - under every sweep tag of its program (the simulator names them)."""
+    cc.set_sim_options(opt)
+    try:
+        for rq, e in zip(reqs, errs):
+            for tag in cc.planned(flat, [rq])[1]:
+                if tag.startswith("sweep:"):
+                    _worst_sweep[tag] = max(_worst_sweep.get(tag, 0.0), e)
+    finally:
+        cc.reset_sim_options()
+
+
+@pytest.mark.parametrize("case", cc.CASES, ids=[c["name"] for c in cc.CASES])
+def test_class_case_vs_oracle(amd, case):
+    t0 = time.perf_counter()
+    eng, flat, on, opt = _setup(amd, case)
     reqs = case["requests"]
-    want = [cc.oracle_dense(on, int(flat.card[flat.id[f"{q:03d}"]]), q, ev, ec) for q, ev, ec in reqs]
+    want = [_want(case, flat, on, rq) for rq in reqs]
 
     def vs_oracle(post, tag):
         errs = [float(np.max(np.abs(p - w))) for p, w in zip(post, want)]
@@ -90,6 +131,7 @@ def test_class_case_vs_oracle(amd, case):
                 _worst[c] = max(_worst.get(c, 0.0), e)
     finally:
         cc.reset_sim_options()
+    _note_sweep_tags(flat, opt, reqs, [max(a, b) for a, b in zip(errs_a, errs_b)])
     assert max(errs_a) <= gu.TOL, errs_a
     assert max(errs_b) <= gu.TOL, errs_b
     assert ab <= TWIN_TOL, ab
@@ -97,6 +139,34 @@ def test_class_case_vs_oracle(amd, case):
         assert max(errs_c) <= gu.TOL, errs_c
         assert bc <= TWIN_TOL, bc
     _ran.append((case["name"], time.perf_counter() - t0))
+
+
+@pytest.mark.parametrize("case", SWEEP_CASES, ids=[c["name"] for c in SWEEP_CASES])
+def test_sweep_case_under_both_kernels(amd, case):
+    """Every case with a SWEEP step under ve_sweep_kernel (sweep_dma 0) and ve_sweep_dma_kernel (1): the case's requests, then three
+    copies of them with different evidence codes as ONE batch, so that work items of several requests share a launch (the codes do not
+    change the shape of a program: the copies carry the case's tags).  Each run against the oracle request by request, the two
+    kernels bit for bit equal (the contract of sweep_kernel.hip.h), the statistics row of the kernel the option names."""
+    t0 = time.perf_counter()
+    eng, flat, on, opt = _setup(amd, case)
+    eng.set_option("split_kinds", 0)
+    card = lambda v: int(flat.card[flat.id[f"{v:03d}"]])
+    batch = [(q, ev, [(c + j) % card(v) for v, c in zip(ev, ec)]) for j in range(3) for q, ev, ec in case["requests"]]
+    for label, reqs in (("requests", case["requests"]), ("batch of 3 copies", batch)):
+        want = [_want(case, flat, on, rq) for rq in reqs]
+        post = {}
+        for dma, row, other in ((0, "ve_sweep_kernel", "ve_sweep_dma_kernel"), (1, "ve_sweep_dma_kernel", "ve_sweep_kernel")):
+            eng.set_option("sweep_dma", dma)
+            post[dma], names = _run(eng, flat, reqs)
+            errs = [float(np.max(np.abs(p - w))) for p, w in zip(post[dma], want)]
+            print(f"{case['name']} {label}, sweep_dma={dma}: max|err| vs oracle {max(errs):.3e}")
+            assert row in names and other not in names, (dma, sorted(names))
+            assert max(errs) <= gu.TOL, (label, dma, errs)
+            _note_sweep_tags(flat, opt, reqs, errs)
+        differ = [i for i, (a, b) in enumerate(zip(post[0], post[1])) if not np.array_equal(a, b)]
+        assert not differ, (label, differ, [float(np.max(np.abs(post[0][i] - post[1][i]))) for i in differ])
+    eng.set_option("sweep_dma", 1)
+    _ran_sweep.append((case["name"], time.perf_counter() - t0))
 
 
 def test_level_routing_table(amd):
@@ -123,6 +193,9 @@ def test_level_routing_table(amd):
         eng.set_option("tiny", 0)
         eng.set_option("adaptive", 0)
         eng.set_option("gpu_emit", 0)
+        eng.set_option("sweep_adapt", cc.MATRIX_SWEEP_ADAPT)
+        eng.set_option("minfill_above", cc.MATRIX_MINFILL_ABOVE)
+        eng.set_option("second_above", cc.MATRIX_SECOND_ABOVE)
         for name, v in cc.options(case).items():
             eng.set_option(name, v)
         reqs, classes = case["requests"], set(case["classes"])
@@ -172,7 +245,14 @@ def test_class_matrix_summary():
           f"slowest case {max([s for _, s in _ran] or [0.0]):.2f} s")
     for c in sorted(_worst):
         print(f"  {c:28s} max|err| vs oracle {_worst[c]:.3e}")
+    print(f"sweep matrix: {len(_ran_sweep)} of {len(SWEEP_CASES)} cases under both kernels, slowest case {max([s for _, s in _ran_sweep] or [0.0]):.2f} s")
+    for e in sorted(_worst_sweep):
+        print(f"  {e:28s} max|err| vs oracle {_worst_sweep[e]:.3e}")
     if len(_ran) == len(cc.CASES):
         want = set().union(*[c["classes"] for c in cc.CASES])
         assert set(_worst) == want, set(_worst) ^ want
         assert max(_worst.values()) <= gu.TOL
+    if len(_ran) == len(cc.CASES) and len(_ran_sweep) == len(SWEEP_CASES):
+        want = {e for c in cc.CASES for e in c["edges"] if e.startswith("sweep:")}
+        assert set(_worst_sweep) == want == {f"sweep:{e}" for e in cc.REQUIRED_EDGES["sweep"]}, set(_worst_sweep) ^ want
+        assert max(_worst_sweep.values()) <= gu.TOL

@@ -30,7 +30,8 @@ def _product_defaults_afterwards():
 def test_case_holds_its_classes_and_edges_and_matches_the_oracle(case):
     from oracle.oracle import OracleNet
     spec = cc.build_spec(case)
-    assert len(spec["nodes"]) == case["nodes"] <= 30
+    max_nodes, max_cells = cc.size_cap(case)
+    assert len(spec["nodes"]) == case["nodes"] <= max_nodes
     flat = flatten(netspec.build(spec, sorobn_amd.BayesNet))
     opt = cc.options(case)
     assert set(case["options"]) <= set(cc.OPTION_NAMES)
@@ -38,11 +39,12 @@ def test_case_holds_its_classes_and_edges_and_matches_the_oracle(case):
     classes, edges, cells = cc.planned(flat, case["requests"])
     assert sorted(classes) == case["classes"], sorted(classes ^ set(case["classes"]))
     assert sorted(edges) == case["edges"], sorted(edges ^ set(case["edges"]))
-    assert cells == case["max_cells"] <= 1 << 16
-    # the same programs, executed: every request, every cell
+    assert cells == case["max_cells"] <= max_cells
+    # the same programs, executed: every request, every cell, work item by work item of the schedule
     eng = simengine.SimEngine(flat, opt["small_cells"], (opt["big_iters"], opt["tile_h"]), opt["fuse"])
-    for name in ("chain", "sweep", "sweep_min", "outer"):
+    for name in ("chain", "sweep", "sweep_min", "outer", "sweep_iters", "sweep_canon"):
         eng.set_option(name, opt[name])
+    eng.set_option("sweep_adapt", cc.MATRIX_SWEEP_ADAPT)
     on = OracleNet(spec)
     worst = 0.0
     for q, ev, ec in case["requests"]:
@@ -94,8 +96,10 @@ def test_the_routing_cases_reach_every_kernel_of_a_level():
     by_name = {c["name"]: c for c in cc.CASES}
     pair = [by_name[n] for n in cc.ROUTING_CASES]
     assert all(any(reach(c)[k] for c in pair) for k in ("segment", "mfma", "sweep", "level"))
-    assert not any(all(reach(c).values()) for c in cc.CASES)  # (no single case does)
     size = lambda cs: (sum(c["nodes"] for c in cs), sum(c["max_cells"] for c in cs))
+    for c in cc.CASES:  # (no single case of the small table does; the ones of the sweep matrix that do are larger than the pair)
+        if all(reach(c).values()):
+            assert cc.in_sweep_matrix(c) and size(pair) <= size([c]), c["name"]
     for i, a in enumerate(cc.CASES):
         for b in cc.CASES[i + 1:]:
             if all(reach(a)[k] or reach(b)[k] for k in ("segment", "mfma", "sweep", "level")):
@@ -133,6 +137,41 @@ def test_the_table_covers_every_edge_in_every_family_where_it_can_occur():
     assert fams == set(cc.REQUIRED_EDGES), fams ^ set(cc.REQUIRED_EDGES)
     for fam in fams - {"generic", "sweep"}:
         assert set(cc.REQUIRED_EDGES[fam]) | set(cc.IMPOSSIBLE_EDGES.get(fam, {})) == set(cc.FIBER_EDGES), fam
+    # the sweep matrix: every tag of sweep_edges is required or accounted for, and nothing is both
+    assert set(cc.REQUIRED_EDGES["sweep"]) | set(cc.IMPOSSIBLE_EDGES["sweep"]) == set(cc.SWEEP_EDGES)
+    assert not set(cc.REQUIRED_EDGES["sweep"]) & set(cc.IMPOSSIBLE_EDGES["sweep"]) and all(cc.IMPOSSIBLE_EDGES["sweep"].values())
+    assert len(cc.REQUIRED_EDGES["sweep"]) == len(set(cc.REQUIRED_EDGES["sweep"])) == 50 and len(set(cc.SWEEP_EDGES)) == 57
+    assert not {e for e in have if e.startswith("sweep:")} - {f"sweep:{e}" for e in cc.SWEEP_EDGES}  # (no tag outside the list)
+    # k2 and k3 name the pass length AND the canonical specialisations <2,false> / <3,false>: a witness of each that is not on the general path
+    for k in ("sweep:k2", "sweep:k3"):
+        assert any(k in c["edges"] and "sweep:any" not in c["edges"] for c in cc.CASES), k
+    # each wave-owned tail with a last work item shorter than the others, with work items of one tile and with several tiles per item
+    for t in cc.SWEEP_TAILS:
+        assert {f"sweep:{t}+{e}" for e in ("partial_tile", "one_tile_item", "multi_tile", "items2+")} <= have, t
+    assert sum(cc.in_sweep_matrix(c) for c in cc.CASES) == 18
+
+
+def test_the_c3_census_of_sweep_shapes():
+    """The sweep shapes the flagship workload runs - the first 300 requests of the C3 stream under the engine's defaults (order_effort 1,
+    second_above 2e7, eight tiles per work item) - are all in the sweep matrix: a shape the workload runs and the table lacks fails
+    here.  And why the matrix is the only place the ragged shapes of the tile loop run: every SWEEP step of C3 has 8, 32 or 128 tiles,
+    whole work items at sweep_iters = 8 and at the 4 and 2 that build_schedule's sweep_adapt may halve it to - no work item of one
+    tile, no shorter last one."""
+    cc.set_sim_options(cc.DEFAULTS, cc.PRODUCT_SWEEP_ADAPT)
+    simengine.lib().plan_sim_set_order_effort(1, 2e7)
+    steps = cc.c3_sweep_steps(300)
+    assert len(steps) > 500 and {s["cls"] for s in steps} == {cc.SWEEP} and {s["tile_h"] for s in steps} == {8}
+    census = {}
+    for s in steps:
+        for e in cc.sweep_edges(s):
+            census[e] = census.get(e, 0) + 1
+    for e in sorted(census):
+        print(f"  {e:28s} {census[e]:4d} steps")
+    table = {e for c in cc.CASES for e in c["edges"] if e.startswith("sweep:")}
+    print("C3 never runs:", sorted(table - set(census)))
+    assert set(census) <= table, sorted(set(census) - table)
+    assert not [e for e in census if "partial_tile" in e or "one_tile_item" in e or "one_tile_step" in e or "odd_tiles" in e]
+    assert {s["hi"] for s in steps} <= {8, 32, 128}  # (so a halved work item - 4 or 2 tiles - divides the step too)
 
 
 def _census_of(flat, reqs):

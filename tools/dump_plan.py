@@ -94,7 +94,7 @@ def decode(w, classes=False):
         I = lambda k: int(np.int32(w[k]))
         if kind == 2:  # SWEEP: k variables per pass, tile in LDS (planner.h)
             k = na
-            d.update(k=k, rb=nlo, kout=int(w[p + 7]) & 0xffff, T=int(w[p + 7]) >> 16, stages=[])
+            d.update(k=k, rb=nlo, kout=int(w[p + 7]) & 0xffff, T=int(w[p + 7]) >> 16, surv=int(w[p + 8]), canon=(int(w[p + 1]) >> 20) & 1, stages=[])  # (kFlagSweepCanon)
             sq = q + 2 + 5 * k
             for j in range(k):
                 s0, s1 = int(w[q + 2 + 5 * j]), int(w[q + 3 + 5 * j])
