@@ -412,6 +412,26 @@ int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t
                         const int32_t *scope_cols, double *scores);
 
 /*
+ * Constraint-based structure learning: conditional-independence tests of X and Y given Z_1 .. Z_m on a resident data set (an
+ * extension, as the scores above).  Test t is scope_cols[scope_off[t] .. scope_off[t + 1]): the m >= 0 conditioning columns first,
+ * then X, then Y LAST (at least two columns, none twice).  With q = the product of the conditioning cardinalities (1 without),
+ * N_xyz the count of (x, y) in stratum z, N_xz and N_yz its row and column sums and N_z its total:
+ *   MIBN_CI_G2   stat = 2 * sum over cells with N_xyz > 0 of N_xyz * ln((N_xyz * N_z) / (N_xz * N_yz))
+ *   MIBN_CI_X2   stat = sum over cells with N_xz * N_yz > 0 of (N_xyz * N_z - N_xz * N_yz)^2 / (N_z * N_xz * N_yz)
+ *   adj_dof[t]   = sum over strata with N_z > 0 of (rows with N_xz > 0 - 1) * (columns with N_yz > 0 - 1), an exact integer
+ * (the classic degrees of freedom, q * (card(X) - 1) * (card(Y) - 1), need no device).  Empty strata, rows and columns contribute
+ * exactly 0; an exactly independent table has X2 exactly 0; a data set of zero rows gives stat 0 and adj_dof 0.  A table above 2^28
+ * cells and a data set of 2^31 rows or more are MIBN_E_LIMIT; an unknown kind, id or column, a column twice and a test of fewer than
+ * two columns are MIBN_E_ARG.  Counting, sub-batches (option score_cells), blocking, validation and statistics are those of
+ * mibn_score_families (entries count_kernel and citest_kernel of mibn_last_kernel_stats); the addition order depends on the shape
+ * (q, card(X), card(Y)) of a test's table alone, so the same test on the same rows gives the same bits in any call.
+ */
+#define MIBN_CI_G2 0
+#define MIBN_CI_X2 1
+int mibn_ci_tests(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const int64_t *scope_off, const int32_t *scope_cols,
+                  double *stat, int64_t *adj_dof);
+
+/*
  * Multi-GPU: one process per GPU, requests / chains sharded with no data-path collective; the
  * only communication is the final gather of the posteriors (exact path) or the sum of the histograms (Gibbs).  These
  * entry points sit directly on RCCL (librccl.so is dlopen'ed by mibn_comm_init - a single-GPU process never loads it) and

@@ -23,6 +23,7 @@ SYMBOLS = [
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
     "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch", "mibn_map_batch",
+    "mibn_ci_tests",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
@@ -32,6 +33,7 @@ DRAW_PRUNE = 1  # mibn_posterior_sample_batch: every CPT is a complete distribut
 MAP_PRUNE = 1  # mibn_map_batch: every CPT is a complete distribution, prune to the ancestors of the MAP variables and the evidence
 COMM_ID_BYTES = 128
 SCORE_KINDS = {"loglik": 0, "bic": 1, "aic": 2, "bdeu": 3, "k2": 4}  # MIBN_SCORE_*
+CI_KINDS = {"g2": 0, "x2": 1}  # MIBN_CI_*
 
 
 class MibnError(RuntimeError):
@@ -112,6 +114,7 @@ def lib():
         L.mibn_dataset_create.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, i32p, i32p]
         L.mibn_dataset_destroy.argtypes = [vp, C.c_int32]
         L.mibn_score_families.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, i64p, i32p, f64p]
+        L.mibn_ci_tests.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f64p, i64p]
         L.mibn_last_stats.argtypes = [vp, C.POINTER(Stats)]
         L.mibn_last_kernel_stats.argtypes = [vp, C.c_int32, C.POINTER(KernelStat), C.POINTER(C.c_int32)]
         L.mibn_plan_stats.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, C.POINTER(Stats)]
@@ -164,6 +167,22 @@ class Dataset:
         eng._check(eng._L.mibn_score_families(eng._h, self.id, SCORE_KINDS[kind], float(ess), len(families), _p(scope_off, C.c_int64),
                                               _p(scope_cols, C.c_int32), _p(scores, C.c_double)))
         return scores[:len(families)]
+
+    def ci_tests(self, tests, kind="g2"):
+        """tests: sequences of column indices (*Z, x, y), the conditioning columns first -> (stat float64[n], adj_dof int64[n]):
+        the G2 or X2 statistic (`kind` one of CI_KINDS) of x and y given Z and the degrees of freedom adjusted for empty rows,
+        columns and strata; one call, whatever the number of tests."""
+        if kind not in CI_KINDS:
+            raise ValueError(f"test must be one of {sorted(CI_KINDS)}, not {kind!r}")
+        tests = [tuple(t) for t in tests]
+        scope_off = np.concatenate([[0], np.cumsum([len(t) for t in tests])]).astype(np.int64)
+        scope_cols = _i32([c for t in tests for c in t]) if scope_off[-1] else np.zeros(1, np.int32)
+        stat = np.zeros(max(1, len(tests)), np.float64)
+        dof = np.zeros(max(1, len(tests)), np.int64)
+        eng = self.engine
+        eng._check(eng._L.mibn_ci_tests(eng._h, self.id, CI_KINDS[kind], len(tests), _p(scope_off, C.c_int64), _p(scope_cols, C.c_int32),
+                                        _p(stat, C.c_double), _p(dof, C.c_int64)))
+        return stat[:len(tests)], dof[:len(tests)]
 
     def close(self):
         eng = self.engine

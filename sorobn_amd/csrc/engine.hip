@@ -24,6 +24,7 @@
 #include "sample_kernel.hip.h"
 #include "count_kernel.hip.h"
 #include "score_kernel.hip.h"
+#include "citest_kernel.hip.h"
 #include "planner.h"
 #include "plan_policy.h"
 #include "tiny_kernel.hip.h"
@@ -185,16 +186,16 @@ constexpr int kLevelStreams = 4;
 // statistics slots: the classes of work (split_kinds: 0 .. kNumKernels - 1, kernel_name), then the kernels of mibn_query_batch as
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
-// steps.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together).  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -395,6 +396,7 @@ struct mibn_ctx {
         DevBuf<unsigned long long> d_counts;
         DevBuf<char> d_meta;
         DevBuf<double> d_f64;  // [scores | partials of the chunked tables]
+        DevBuf<long long> d_i64;  // mibn_ci_tests: the degrees of freedom, laid out as d_f64
         std::vector<Event> ev;
     } sc;
     int64_t score_cells = kScoreCellBudget;  // option score_cells (test hook: forces sub-batches)
@@ -2964,12 +2966,151 @@ extern "C" int mibn_dataset_destroy(mibn_t *h, int32_t id) {
     return MIBN_OK;
 }
 
+// ---- what mibn_score_families and mibn_ci_tests share: a batch of tables over a resident data set, checked and packed on the host,
+// counted sub-batch by sub-batch into one buffer and reduced there by the caller's kernels; three events per sub-batch
+struct TableSub {
+    int f0 = 0, f1 = 0;           // tables of the call
+    int64_t cells = 0;
+    std::vector<int64_t> off;     // first cell of every table in the count buffer (a sub-batch starts at cell 0), then the end
+    CountPack pack;
+    size_t o_i32 = 0, o_i64 = 0;  // the pack in the metadata buffer
+    double count_launches = 0, reduce_launches = 0, reduce_bytes = 0;
+};
+
+struct TableBatch {
+    std::vector<int64_t> cells_of;
+    std::vector<TableSub> subs;
+    std::vector<char> meta;  // everything the kernels read but the counts: ONE upload per call
+    int64_t max_cells = 1;
+    size_t put(const void *src, size_t bytes) {
+        const size_t o = meta.size();
+        meta.resize(o + ((bytes + 15) & ~size_t(15)));
+        if (bytes) std::memcpy(meta.data() + o, src, bytes);
+        return o;
+    }
+};
+
+// every table names at least `min_cols` known columns, none twice, and has at most 2^28 cells -> cells_of
+static int tables_check(mibn_ctx *h, const mibn_ctx::Dataset &ds, const std::string &what, int min_cols, const char *too_few, int32_t n,
+                        const int64_t *scope_off, const int32_t *scope_cols, TableBatch &B) {
+    B.cells_of.assign((size_t)n, 0);
+    std::vector<int32_t> seen((size_t)ds.n_cols, -1);
+    for (int f = 0; f < n; ++f) {
+        const int64_t a = scope_off[f], b = scope_off[f + 1];
+        if (b - a < min_cols) { h->err = what + " " + std::to_string(f) + " " + too_few; return MIBN_E_ARG; }
+        int64_t cells = 1;
+        for (int64_t k = a; k < b; ++k) {
+            const int c = scope_cols[k];
+            if (c < 0 || c >= ds.n_cols) { h->err = what + " " + std::to_string(f) + ": unknown column"; return MIBN_E_ARG; }
+            if (seen[(size_t)c] == f) { h->err = what + " " + std::to_string(f) + " names a column twice"; return MIBN_E_ARG; }
+            seen[(size_t)c] = f;
+            cells *= ds.card[(size_t)c];
+            if (cells > (int64_t(1) << 28)) { h->err = what + " " + std::to_string(f) + ": its table has more than " + std::to_string(int64_t(1) << 28) + " cells"; return MIBN_E_LIMIT; }
+        }
+        B.cells_of[(size_t)f] = cells;
+    }
+    return MIBN_OK;
+}
+
+// sub-batches: consecutive tables while they fit the cell budget (a larger table goes alone), each with its count_pack
+static int tables_cut(mibn_ctx *h, const mibn_ctx::Dataset &ds, int32_t n, const int64_t *scope_off, const int32_t *scope_cols, TableBatch &B) {
+    for (int f = 0; f < n;) {
+        TableSub S;
+        S.f0 = f;
+        int64_t run = 0;
+        while (f < n && (f == S.f0 || run + B.cells_of[(size_t)f] <= h->score_cells)) run += B.cells_of[(size_t)f++];
+        S.f1 = f;
+        S.cells = run;
+        B.subs.push_back(std::move(S));
+    }
+    for (TableSub &S : B.subs) {
+        S.off.assign((size_t)(S.f1 - S.f0) + 1, 0);
+        for (int f = S.f0; f < S.f1; ++f) S.off[(size_t)(f - S.f0) + 1] = S.off[(size_t)(f - S.f0)] + B.cells_of[(size_t)f];
+        const int rc = count_pack(ds.n_cols, ds.card.data(), S.f1 - S.f0, scope_off + S.f0, scope_cols, S.off.data(), S.pack, h->err);
+        if (rc != MIBN_OK) return rc;
+        S.o_i64 = B.put(S.pack.i64.data(), S.pack.i64.size() * 8);
+        S.o_i32 = B.put(S.pack.i32.data(), S.pack.i32.size() * 4);
+        B.max_cells = std::max(B.max_cells, S.cells);
+    }
+    return MIBN_OK;
+}
+
+// the first device work of the call: buffers, events, the metadata upload
+static int tables_begin(mibn_ctx *h, const TableBatch &B) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    mibn_ctx::Score &X = h->sc;
+    int rc;
+    if ((rc = ensure(h, X.d_counts, (size_t)B.max_cells))) return rc;
+    if ((rc = ensure(h, X.d_meta, B.meta.size() + 16))) return rc;
+    while (X.ev.size() < 3 * B.subs.size()) {
+        X.ev.emplace_back();
+        HIP_TRY(h, X.ev.back().ensure());
+    }
+    const double t0 = now_ms();
+    HIP_TRY(h, hipMemcpyAsync(X.d_meta, B.meta.data(), B.meta.size(), hipMemcpyHostToDevice, h->stream));
+    h->stats.h2d_ms += now_ms() - t0;
+    return MIBN_OK;
+}
+
+// the two phases of a sub-batch follow each other on the main stream, as do the sub-batches (they share the count buffer and the
+// partials): no host synchronisation before the results are downloaded.  tables_count: events 3 s and 3 s + 1 around the counting;
+// tables_reduced: event 3 s + 2 after the caller's kernels
+static int tables_count(mibn_ctx *h, const mibn_ctx::Dataset &ds, TableBatch &B, size_t s) {
+    mibn_ctx::Score &X = h->sc;
+    TableSub &S = B.subs[s];
+    HIP_TRY(h, hipMemsetAsync(X.d_counts, 0, 8 * (size_t)std::max<int64_t>(1, S.cells), h->stream));
+    HIP_TRY(h, hipEventRecord(X.ev[3 * s], h->stream));
+    HIP_TRY(h, count_launch(h->stream, ds.d_codes, ds.n_rows, S.pack, reinterpret_cast<const int32_t *>(X.d_meta + S.o_i32),
+                            reinterpret_cast<const int64_t *>(X.d_meta + S.o_i64), X.d_counts));
+    S.count_launches = ds.n_rows > 0 ? (S.pack.n_big > 0) + (S.pack.n_small > 0) : 0;
+    HIP_TRY(h, hipEventRecord(X.ev[3 * s + 1], h->stream));
+    return MIBN_OK;
+}
+
+static int tables_reduced(mibn_ctx *h, size_t s) {
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(h->sc.ev[3 * s + 2], h->stream));
+    return MIBN_OK;
+}
+
+// after the stream is synchronised: last-call statistics, the counting under count_kernel and the reduction under `slot`
+static int tables_book(mibn_ctx *h, const mibn_ctx::Dataset &ds, const TableBatch &B, const int64_t *scope_off, int slot, double t_start) {
+    mibn_ctx::Score &X = h->sc;
+    mibn_kernel_stat &kc = h->kstats[kStatCount], &ks = h->kstats[slot];
+    for (size_t s = 0; s < B.subs.size(); ++s) {
+        const TableSub &S = B.subs[s];
+        float ms_c = 0, ms_s = 0;
+        HIP_TRY(h, hipEventElapsedTime(&ms_c, X.ev[3 * s], X.ev[3 * s + 1]));
+        HIP_TRY(h, hipEventElapsedTime(&ms_s, X.ev[3 * s + 1], X.ev[3 * s + 2]));
+        const double n = (double)(S.f1 - S.f0);
+        kc.launches += S.count_launches;
+        kc.ms += ms_c;
+        kc.alg_bytes += (double)ds.n_rows * (double)(scope_off[S.f1] - scope_off[S.f0]) + 8.0 * (double)S.cells;  // codes read per table member + the tables
+        kc.items += n;
+        ks.launches += S.reduce_launches;
+        ks.ms += ms_s;
+        ks.alg_bytes += S.reduce_bytes;
+        ks.items += n;
+        h->stats.kernel_ms += ms_c + ms_s;
+        h->stats.n_launches += S.count_launches + S.reduce_launches;
+    }
+    h->stats.total_ms = now_ms() - t_start;
+    return MIBN_OK;
+}
+
+// state and id checks of both entry points
+static int tables_enter(mibn_ctx *h, int32_t id, const char *what) {
+    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (h->pend[0].active || h->pend[1].active) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if (id < 0 || (size_t)id >= h->datasets.size() || !h->datasets[(size_t)id].live) { h->err = std::string(what) + ": unknown or destroyed data set id"; return MIBN_E_ARG; }
+    return MIBN_OK;
+}
+
 extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off, const int32_t *scope_cols,
                                    double *scores) {
     if (!h || n_fam < 0 || !scope_off || (n_fam && (!scope_cols || !scores))) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (h->pend[0].active || h->pend[1].active) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
-    if (id < 0 || (size_t)id >= h->datasets.size() || !h->datasets[(size_t)id].live) { h->err = "score: unknown or destroyed data set id"; return MIBN_E_ARG; }
+    int rc;
+    if ((rc = tables_enter(h, id, "score"))) return rc;
     if (kind < MIBN_SCORE_LOGLIK || kind > MIBN_SCORE_K2) { h->err = "score: unknown kind"; return MIBN_E_ARG; }
     if (kind == MIBN_SCORE_BDEU && !(ess > 0 && ess < 1e300)) { h->err = "score: bdeu needs a finite equivalent sample size above 0"; return MIBN_E_ARG; }
     const mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
@@ -2977,118 +3118,55 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
     reset_last_stats(h);
     if (n_fam == 0) return MIBN_OK;
     // ---- everything is checked and packed on the host before anything is launched
-    std::vector<int64_t> cells_of((size_t)n_fam, 0);
-    std::vector<int32_t> fam_r((size_t)n_fam);
-    {
-        std::vector<int32_t> seen((size_t)ds.n_cols, -1);
-        for (int f = 0; f < n_fam; ++f) {
-            const int64_t a = scope_off[f], b = scope_off[f + 1];
-            if (b <= a) { h->err = "score: family " + std::to_string(f) + " is empty (the child comes last)"; return MIBN_E_ARG; }
-            int64_t cells = 1;
-            for (int64_t k = a; k < b; ++k) {
-                const int c = scope_cols[k];
-                if (c < 0 || c >= ds.n_cols) { h->err = "score: family " + std::to_string(f) + ": unknown column"; return MIBN_E_ARG; }
-                if (seen[(size_t)c] == f) { h->err = "score: family " + std::to_string(f) + " names a column twice"; return MIBN_E_ARG; }
-                seen[(size_t)c] = f;
-                cells *= ds.card[(size_t)c];
-                if (cells > (int64_t(1) << 28)) { h->err = "score: a family's table has more than " + std::to_string(int64_t(1) << 28) + " cells"; return MIBN_E_LIMIT; }
-            }
-            fam_r[(size_t)f] = ds.card[(size_t)scope_cols[b - 1]];
-            cells_of[(size_t)f] = cells;
-        }
-    }
-    // sub-batches: consecutive families while their tables fit the cell budget (a larger table goes alone)
+    TableBatch B;
+    if ((rc = tables_check(h, ds, "score: family", 1, "is empty (the child comes last)", n_fam, scope_off, scope_cols, B))) return rc;
+    if ((rc = tables_cut(h, ds, n_fam, scope_off, scope_cols, B))) return rc;
     struct Sub {
-        int f0 = 0, f1 = 0;
-        CountPack pack;
         std::vector<ScoreFam> small, big;
         std::vector<ScoreChunk> chunk;
         std::vector<ScoreBig> big_parts;
-        int64_t cells = 0;
         int32_t n_parts = 0;
-        size_t o_i32 = 0, o_i64 = 0, o_small = 0, o_big = 0, o_chunk = 0, o_bp = 0;  // in the metadata buffer
+        size_t o_small = 0, o_big = 0, o_chunk = 0, o_bp = 0;  // in the metadata buffer
     };
-    std::vector<Sub> subs;
-    int64_t max_cells = 1;
+    std::vector<Sub> subs(B.subs.size());
     int32_t max_parts = 0;
-    for (int f = 0; f < n_fam;) {
-        Sub S;
-        S.f0 = f;
-        int64_t run = 0;
-        while (f < n_fam && (f == S.f0 || run + cells_of[(size_t)f] <= h->score_cells)) run += cells_of[(size_t)f++];
-        S.f1 = f;
-        S.cells = run;
-        subs.push_back(std::move(S));
-    }
-    for (Sub &S : subs) {
-        std::vector<int64_t> off((size_t)(S.f1 - S.f0) + 1, 0);  // every sub-batch starts at cell 0 of the count buffer
-        for (int f = S.f0; f < S.f1; ++f) off[(size_t)(f - S.f0) + 1] = off[(size_t)(f - S.f0)] + cells_of[(size_t)f];
-        const int rc = count_pack(ds.n_cols, ds.card.data(), S.f1 - S.f0, scope_off + S.f0, scope_cols, off.data(), S.pack, h->err);
-        if (rc != MIBN_OK) return rc;
-        for (int f = S.f0; f < S.f1; ++f) {
+    for (size_t s = 0; s < subs.size(); ++s) {
+        const TableSub &T = B.subs[s];
+        Sub &S = subs[s];
+        for (int f = T.f0; f < T.f1; ++f) {
             ScoreFam F;
-            F.off = off[(size_t)(f - S.f0)];
-            F.r = fam_r[(size_t)f];
-            F.q = (off[(size_t)(f - S.f0) + 1] - F.off) / F.r;
+            F.off = T.off[(size_t)(f - T.f0)];
+            F.r = ds.card[(size_t)scope_cols[scope_off[f + 1] - 1]];
+            F.q = B.cells_of[(size_t)f] / F.r;
             F.out = f;
             if (F.q * F.r <= kScoreWaveCells) {
                 S.small.push_back(F);
             } else {
                 const int64_t per = score_chunk_configs(F.r);
-                ScoreBig B;
-                B.part0 = S.n_parts;
-                B.n_parts = (int32_t)((F.q + per - 1) / per);
-                for (int32_t c = 0; c < B.n_parts; ++c) S.chunk.push_back(ScoreChunk{(int32_t)S.big.size(), S.n_parts + c, (int64_t)c * per});
-                S.n_parts += B.n_parts;
+                ScoreBig G;
+                G.part0 = S.n_parts;
+                G.n_parts = (int32_t)((F.q + per - 1) / per);
+                for (int32_t c = 0; c < G.n_parts; ++c) S.chunk.push_back(ScoreChunk{(int32_t)S.big.size(), S.n_parts + c, (int64_t)c * per});
+                S.n_parts += G.n_parts;
                 S.big.push_back(F);
-                S.big_parts.push_back(B);
+                S.big_parts.push_back(G);
             }
         }
-        max_cells = std::max(max_cells, S.cells);
         max_parts = std::max(max_parts, S.n_parts);
-    }
-    std::vector<char> meta;
-    auto put = [&](const void *src, size_t bytes) {
-        const size_t o = meta.size();
-        meta.resize(o + ((bytes + 15) & ~size_t(15)));
-        if (bytes) std::memcpy(meta.data() + o, src, bytes);
-        return o;
-    };
-    for (Sub &S : subs) {
-        S.o_i64 = put(S.pack.i64.data(), S.pack.i64.size() * 8);
-        S.o_small = put(S.small.data(), S.small.size() * sizeof(ScoreFam));
-        S.o_big = put(S.big.data(), S.big.size() * sizeof(ScoreFam));
-        S.o_chunk = put(S.chunk.data(), S.chunk.size() * sizeof(ScoreChunk));
-        S.o_bp = put(S.big_parts.data(), S.big_parts.size() * sizeof(ScoreBig));
-        S.o_i32 = put(S.pack.i32.data(), S.pack.i32.size() * 4);
+        S.o_small = B.put(S.small.data(), S.small.size() * sizeof(ScoreFam));
+        S.o_big = B.put(S.big.data(), S.big.size() * sizeof(ScoreFam));
+        S.o_chunk = B.put(S.chunk.data(), S.chunk.size() * sizeof(ScoreChunk));
+        S.o_bp = B.put(S.big_parts.data(), S.big_parts.size() * sizeof(ScoreBig));
     }
     // ---- device
-    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = tables_begin(h, B))) return rc;
     mibn_ctx::Score &X = h->sc;
-    int rc;
-    if ((rc = ensure(h, X.d_counts, (size_t)max_cells))) return rc;
-    if ((rc = ensure(h, X.d_meta, meta.size() + 16))) return rc;
     if ((rc = ensure(h, X.d_f64, (size_t)n_fam + (size_t)max_parts + 2))) return rc;
-    while (X.ev.size() < 3 * subs.size()) {
-        X.ev.emplace_back();
-        HIP_TRY(h, X.ev.back().ensure());
-    }
     const hipStream_t S0 = h->stream;
-    double t0 = now_ms();
-    HIP_TRY(h, hipMemcpyAsync(X.d_meta, meta.data(), meta.size(), hipMemcpyHostToDevice, S0));
-    h->stats.h2d_ms += now_ms() - t0;
     double *d_scores = X.d_f64, *d_parts = X.d_f64 + n_fam;
-    std::vector<double> count_launches(subs.size(), 0), score_launches(subs.size(), 0);
     for (size_t s = 0; s < subs.size(); ++s) {
         const Sub &S = subs[s];
-        // the two phases of a sub-batch follow each other on the main stream, as do the sub-batches (they share the count buffer and the
-        // partials): no host synchronisation before the scores are downloaded
-        HIP_TRY(h, hipMemsetAsync(X.d_counts, 0, 8 * (size_t)std::max<int64_t>(1, S.cells), S0));
-        HIP_TRY(h, hipEventRecord(X.ev[3 * s], S0));
-        HIP_TRY(h, count_launch(S0, ds.d_codes, ds.n_rows, S.pack, reinterpret_cast<const int32_t *>(X.d_meta + S.o_i32),
-                                reinterpret_cast<const int64_t *>(X.d_meta + S.o_i64), X.d_counts));
-        count_launches[s] = ds.n_rows > 0 ? (S.pack.n_big > 0) + (S.pack.n_small > 0) : 0;
-        HIP_TRY(h, hipEventRecord(X.ev[3 * s + 1], S0));
+        if ((rc = tables_count(h, ds, B, s))) return rc;
         ScoreArgs A;
         A.counts = X.d_counts;
         A.small = reinterpret_cast<const ScoreFam *>(X.d_meta + S.o_small);
@@ -3103,41 +3181,146 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
         A.n_small = (int32_t)S.small.size();
         A.n_big = (int32_t)S.big.size();
         constexpr int kPerWG = kScoreWG / 64;
+        TableSub &T = B.subs[s];
         if (A.n_small) {
             hipLaunchKernelGGL(score_kernel, dim3((unsigned)((A.n_small + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
-            score_launches[s] += 1;
+            T.reduce_launches += 1;
         }
         if (A.n_big) {
             hipLaunchKernelGGL(score_chunk_kernel, dim3((unsigned)S.chunk.size()), dim3(kScoreWG), 0, S0, A);
             hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((A.n_big + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
-            score_launches[s] += 2;
+            T.reduce_launches += 2;
         }
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipEventRecord(X.ev[3 * s + 2], S0));
+        T.reduce_bytes = 8.0 * ((double)T.cells + (double)(T.f1 - T.f0) + 2.0 * (double)S.n_parts);
+        if ((rc = tables_reduced(h, s))) return rc;
     }
-    t0 = now_ms();
+    const double t0 = now_ms();
     HIP_TRY(h, hipMemcpyAsync(scores, d_scores, (size_t)n_fam * 8, hipMemcpyDeviceToHost, S0));
     HIP_TRY(h, hipStreamSynchronize(S0));
     h->stats.d2h_ms += now_ms() - t0;
-    mibn_kernel_stat &kc = h->kstats[kStatCount], &ks = h->kstats[kStatScore];
+    return tables_book(h, ds, B, scope_off, kStatScore, t_start);
+}
+
+extern "C" int mibn_ci_tests(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const int64_t *scope_off, const int32_t *scope_cols, double *stat,
+                             int64_t *adj_dof) {
+    if (!h || n_tests < 0 || !scope_off || (n_tests && (!scope_cols || !stat || !adj_dof))) return MIBN_E_ARG;
+    int rc;
+    if ((rc = tables_enter(h, id, "ci"))) return rc;
+    if (kind != MIBN_CI_G2 && kind != MIBN_CI_X2) { h->err = "ci: unknown kind"; return MIBN_E_ARG; }
+    const mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
+    if (ds.n_rows >= (int64_t(1) << 31)) { h->err = "ci: the data set has 2^31 rows or more (the statistics' products are 64-bit integers)"; return MIBN_E_LIMIT; }
+    const double t_start = now_ms();
+    reset_last_stats(h);
+    if (n_tests == 0) return MIBN_OK;
+    // ---- everything is checked and packed on the host before anything is launched
+    TableBatch B;
+    if ((rc = tables_check(h, ds, "ci: test", 2, "names fewer than two columns (conditioning columns, then X, then Y)", n_tests, scope_off, scope_cols, B))) return rc;
+    if ((rc = tables_cut(h, ds, n_tests, scope_off, scope_cols, B))) return rc;
+    struct Sub {
+        std::vector<CiItem> lane, wave;  // lane: by group size, 64 first
+        std::vector<CiBig> big;
+        int32_t lane0[kCiClasses + 1] = {}, item0[kCiClasses + 1] = {};
+        int32_t n_parts = 0;
+        size_t o_lane = 0, o_wave = 0, o_big = 0;
+    };
+    std::vector<Sub> subs(B.subs.size());
+    int32_t max_parts = 0;
     for (size_t s = 0; s < subs.size(); ++s) {
-        float ms_c = 0, ms_s = 0;
-        HIP_TRY(h, hipEventElapsedTime(&ms_c, X.ev[3 * s], X.ev[3 * s + 1]));
-        HIP_TRY(h, hipEventElapsedTime(&ms_s, X.ev[3 * s + 1], X.ev[3 * s + 2]));
-        const double fams = (double)(subs[s].f1 - subs[s].f0);
-        kc.launches += count_launches[s];
-        kc.ms += ms_c;
-        kc.alg_bytes += (double)ds.n_rows * (double)(scope_off[subs[s].f1] - scope_off[subs[s].f0]) + 8.0 * (double)subs[s].cells;  // codes read per family member + the tables
-        kc.items += fams;
-        ks.launches += score_launches[s];
-        ks.ms += ms_s;
-        ks.alg_bytes += 8.0 * ((double)subs[s].cells + fams + 2.0 * (double)subs[s].n_parts);
-        ks.items += fams;
-        h->stats.kernel_ms += ms_c + ms_s;
-        h->stats.n_launches += count_launches[s] + score_launches[s];
+        const TableSub &T = B.subs[s];
+        Sub &S = subs[s];
+        std::vector<CiItem> by_class[kCiClasses];
+        auto add = [&](const CiItem &I, int64_t strata_of_table) {
+            if (I.rx * I.ry > kCiLaneCells) return S.wave.push_back(I);
+            int k = 0;  // group of 64 >> k lanes
+            for (const int32_t g = ci_group(strata_of_table); (64 >> k) > g;) ++k;
+            by_class[k].push_back(I);
+        };
+        for (int f = T.f0; f < T.f1; ++f) {
+            CiItem I;
+            I.off = T.off[(size_t)(f - T.f0)];
+            I.rx = ds.card[(size_t)scope_cols[scope_off[f + 1] - 2]];
+            I.ry = ds.card[(size_t)scope_cols[scope_off[f + 1] - 1]];
+            const int64_t cells = B.cells_of[(size_t)f], sz = (int64_t)I.rx * I.ry, q = cells / sz;
+            if (cells <= kCiWaveCells) {
+                I.nz = (int32_t)q;
+                I.out = f;
+                add(I, q);
+                continue;
+            }
+            const int64_t per = ci_chunk_strata(sz);
+            CiBig G;
+            G.part0 = n_tests + S.n_parts;
+            G.n_parts = (int32_t)((q + per - 1) / per);
+            G.out = f;
+            for (int32_t c = 0; c < G.n_parts; ++c) {
+                CiItem P = I;
+                P.off = I.off + (int64_t)c * per * sz;
+                P.nz = (int32_t)std::min<int64_t>(per, q - (int64_t)c * per);
+                P.out = G.part0 + c;
+                add(P, 64);  // (a chunk of the lane form: always a whole wave)
+            }
+            S.n_parts += G.n_parts;
+            S.big.push_back(G);
+        }
+        int64_t lanes = 0;
+        for (int k = 0; k < kCiClasses; ++k) {
+            S.lane0[k] = (int32_t)lanes;
+            S.item0[k] = (int32_t)S.lane.size();
+            lanes += (int64_t)by_class[k].size() * (64 >> k);
+            S.lane.insert(S.lane.end(), by_class[k].begin(), by_class[k].end());
+        }
+        if (lanes >= (int64_t(1) << 31)) { h->err = "ci: a sub-batch needs 2^31 lanes or more (lower the option score_cells)"; return MIBN_E_LIMIT; }
+        S.lane0[kCiClasses] = (int32_t)lanes;
+        S.item0[kCiClasses] = (int32_t)S.lane.size();
+        max_parts = std::max(max_parts, S.n_parts);
+        S.o_lane = B.put(S.lane.data(), S.lane.size() * sizeof(CiItem));
+        S.o_wave = B.put(S.wave.data(), S.wave.size() * sizeof(CiItem));
+        S.o_big = B.put(S.big.data(), S.big.size() * sizeof(CiBig));
     }
-    h->stats.total_ms = now_ms() - t_start;
-    return MIBN_OK;
+    // ---- device
+    if ((rc = tables_begin(h, B))) return rc;
+    mibn_ctx::Score &X = h->sc;
+    if ((rc = ensure(h, X.d_f64, (size_t)n_tests + (size_t)max_parts + 2))) return rc;
+    if ((rc = ensure(h, X.d_i64, (size_t)n_tests + (size_t)max_parts + 2))) return rc;
+    const hipStream_t S0 = h->stream;
+    for (size_t s = 0; s < subs.size(); ++s) {
+        const Sub &S = subs[s];
+        if ((rc = tables_count(h, ds, B, s))) return rc;
+        CiArgs A;
+        A.counts = X.d_counts;
+        A.lane_items = reinterpret_cast<const CiItem *>(X.d_meta + S.o_lane);
+        A.wave_items = reinterpret_cast<const CiItem *>(X.d_meta + S.o_wave);
+        A.big = reinterpret_cast<const CiBig *>(X.d_meta + S.o_big);
+        A.stat = X.d_f64;
+        A.dof = X.d_i64;
+        A.kind = kind;
+        A.n_wave = (int32_t)S.wave.size();
+        A.n_big = (int32_t)S.big.size();
+        std::copy(S.lane0, S.lane0 + kCiClasses + 1, A.lane0);
+        std::copy(S.item0, S.item0 + kCiClasses + 1, A.item0);
+        TableSub &T = B.subs[s];
+        if (!S.lane.empty()) {
+            hipLaunchKernelGGL(ci_lane_kernel, dim3((unsigned)((S.lane0[kCiClasses] + kCiWG - 1) / kCiWG)), dim3(kCiWG), 0, S0, A);
+            T.reduce_launches += 1;
+        }
+        if (A.n_wave) {
+            hipLaunchKernelGGL(ci_wave_kernel, dim3((unsigned)A.n_wave), dim3(64), 0, S0, A);
+            T.reduce_launches += 1;
+        }
+        if (A.n_big) {
+            constexpr int kPerWG = kCiWG / 64;
+            hipLaunchKernelGGL(ci_finish_kernel, dim3((unsigned)((A.n_big + kPerWG - 1) / kPerWG)), dim3(kCiWG), 0, S0, A);
+            T.reduce_launches += 1;
+        }
+        T.reduce_bytes = 8.0 * (double)T.cells + 16.0 * ((double)(T.f1 - T.f0) + 2.0 * (double)S.n_parts);
+        if ((rc = tables_reduced(h, s))) return rc;
+    }
+    const double t0 = now_ms();
+    HIP_TRY(h, hipMemcpyAsync(stat, X.d_f64, (size_t)n_tests * 8, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipMemcpyAsync(adj_dof, X.d_i64, (size_t)n_tests * 8, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipStreamSynchronize(S0));
+    h->stats.d2h_ms += now_ms() - t0;
+    return tables_book(h, ds, B, scope_off, kStatCiTest, t_start);
 }
 
 extern "C" int mibn_plan_order(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,

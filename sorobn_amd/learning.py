@@ -726,3 +726,269 @@ def net_score(bn, X, score="bic", ess=1.0):
     """The sum of the family scores of the net's own structure on the rows of X (`BayesNet.score`)."""
     fams = [(node, list(bn.parents.get(node, []))) for node in bn.nodes]
     return math.fsum(family_scores(X, fams, score=score, ess=ess, device=getattr(bn, "_device", None)).tolist())
+
+
+# ------------------------------------------------------ constraint-based structure learning: CI tests and PC-stable
+# An extension, like the score-based search above.  PC in its order-independent form freezes the adjacency sets at the start
+# of a level, so every conditional-independence test of a level is known before any runs: a level is ONE batch of tables
+# over the resident rows (csrc/citest_kernel.hip.h, `mibn_ci_tests`); the search itself runs on the host.
+CI_TESTS = ("g2", "x2", "mi")  # "mi": the G2 test, reported as the conditional mutual information G2 / (2 N) in nats
+CI_DOFS = ("classic", "adjusted")
+
+
+def _gamma_q(a, x):
+    """The regularised upper incomplete gamma function Q(a, x), a > 0, x >= 0: the series of P below a + 1, Lentz's
+    evaluation of the continued fraction of Q above it."""
+    if x <= 0.0:
+        return 1.0
+    log_front = a * math.log(x) - x - math.lgamma(a)
+    if x < a + 1.0:
+        term = total = 1.0 / a
+        k = a
+        for _ in range(100_000):
+            k += 1.0
+            term *= x / k
+            total += term
+            if term < total * 1e-17:
+                break
+        return max(0.0, 1.0 - total * math.exp(log_front))
+    tiny = 1e-300
+    b = x + 1.0 - a
+    c = 1.0 / tiny
+    d = 1.0 / b
+    h = d
+    for i in range(1, 100_000):
+        an = -i * (i - a)
+        b += 2.0
+        d = an * d + b
+        d = tiny if abs(d) < tiny else d
+        c = b + an / c
+        c = tiny if abs(c) < tiny else c
+        d = 1.0 / d
+        delta = d * c
+        h *= delta
+        if abs(delta - 1.0) < 1e-16:
+            break
+    return h * math.exp(log_front) if log_front > -745.0 else 0.0
+
+
+def chi2_sf(stat, dof):
+    """P(chi-square with `dof` degrees of freedom > stat); 1.0 for dof == 0 (nothing to test)."""
+    if dof <= 0:
+        return 1.0
+    return _gamma_q(0.5 * float(dof), 0.5 * max(float(stat), 0.0))
+
+
+def _check_ci(test, dof):
+    if test not in CI_TESTS:
+        raise ValueError(f"test must be one of {CI_TESTS}, not {test!r}")
+    if dof not in CI_DOFS:
+        raise ValueError(f"dof must be one of {CI_DOFS}, not {dof!r}")
+
+
+def _ci_batch(ds, cards, n_rows, batch, test, dof):
+    """batch: (x, y, Z) column positions -> (stat, dof, p_value) arrays through ONE `Dataset.ci_tests` call."""
+    stat, adj = ds.ci_tests([(*Z, x, y) for x, y, Z in batch], "g2" if test == "mi" else test)
+    if dof == "classic":
+        d = np.array([math.prod(int(cards[z]) for z in Z) * (int(cards[x]) - 1) * (int(cards[y]) - 1) for x, y, Z in batch], np.int64)
+    else:
+        d = np.asarray(adj, np.int64)
+    p = np.array([chi2_sf(s, k) for s, k in zip(stat.tolist(), d.tolist())], np.float64)
+    if test == "mi":
+        stat = stat / (2.0 * n_rows) if n_rows else stat
+    return np.asarray(stat, np.float64), d.reshape(-1), p
+
+
+def ci_tests(X, tests, test="g2", dof="classic", device=None):
+    """Conditional-independence tests on the rows of X: `tests` is a list of (x, y, given) names (`given` a name or a
+    sequence of names, possibly empty) -> DataFrame with one row per test: `stat`, `dof`, `p_value`.  test: "g2" (the
+    likelihood-ratio statistic), "x2" (Pearson's) or "mi" (G2 / (2 N) as `stat`, the p-value of G2).  dof: "classic" =
+    q (rx - 1)(ry - 1) over the cardinalities of the encoded columns, "adjusted" = summed over the strata that occur, from
+    the rows and columns that occur in each.  dof == 0 gives p_value 1.  One launch pair for all tests; complete data only."""
+    _check_ci(test, dof)
+    asked = []
+    for t in tests:
+        if not (isinstance(t, (tuple, list)) and len(t) == 3):
+            raise ValueError(f"{t!r} is not an (x, y, given) triple")
+        x, y, given = t
+        given = [given] if isinstance(given, str) or not hasattr(given, "__iter__") else list(given)
+        for c in [x, y, *given]:
+            if c not in X.columns:
+                raise ValueError(f"unknown column {c!r}")
+        if len({x, y, *given}) != 2 + len(given):
+            raise ValueError(f"the test {t!r} names a column twice")
+        asked.append((x, y, given))
+    order = list(X.columns)
+    used = sorted({c for x, y, given in asked for c in [x, y, *given]}, key=order.index)
+    codes, _, cards = encode_complete(X, used)
+    out = pd.DataFrame({"stat": np.zeros(len(asked)), "dof": np.zeros(len(asked), np.int64), "p_value": np.ones(len(asked))})
+    if not asked:
+        return out
+    pos = {c: j for j, c in enumerate(used)}
+    with counting_engine(device).dataset(codes, cards) as ds:
+        batch = [(pos[x], pos[y], tuple(sorted(pos[z] for z in given))) for x, y, given in asked]
+        out["stat"], out["dof"], out["p_value"] = _ci_batch(ds, cards, len(X), batch, test, dof)
+    return out
+
+
+def _meek(n, adj, arrow):
+    """Meek's rules 1 to 3 to closure on the partially directed graph (adj: adjacency sets; arrow: the set of (u, v) with
+    u -> v).  Passes over the ordered pairs (a, b) in ascending order, a rule that fires orients a -> b at once; the
+    passes repeat until one changes nothing."""
+    def undirected(a, b):
+        return b in adj[a] and (a, b) not in arrow and (b, a) not in arrow
+
+    changed = True
+    while changed:
+        changed = False
+        for a in range(n):
+            for b in sorted(adj[a]):
+                if not undirected(a, b):
+                    continue
+                r1 = any((c, a) in arrow and b not in adj[c] for c in adj[a] if c != b)
+                r2 = any((a, c) in arrow and (c, b) in arrow for c in adj[a] if c != b)
+                into_b = [c for c in adj[a] if c != b and undirected(a, c) and (c, b) in arrow]
+                r3 = any(d not in adj[c] for c, d in itertools.combinations(into_b, 2))
+                if r1 or r2 or r3:
+                    arrow.add((a, b))
+                    changed = True
+
+
+def _pc_search(n, tester, alpha, max_cond=3, required=(), forbidden=()):
+    """PC-stable over the columns 0 .. n - 1.  tester: a list of (x, y, S) with x < y and S an ascending tuple -> their
+    p-values; it is called ONCE per level.  required / forbidden: (u, v) position pairs for u -> v.  A pair forbidden in both
+    directions is never adjacent; a required edge is never tested and starts directed; an edge forbidden one way is directed
+    the other way if it survives.  -> dict(adj, arrow, sepsets, levels, trace)."""
+    required, forbidden = list(required), set(forbidden)
+    adj = [{v for v in range(n) if v != u and not ((u, v) in forbidden and (v, u) in forbidden)} for u in range(n)]
+    fixed = {frozenset(e) for e in required}
+    for u, v in required:
+        adj[u].add(v)
+        adj[v].add(u)
+    sepsets, levels, trace = {}, [], []
+    level = 0
+    while level <= max_cond:
+        frozen = [sorted(a) for a in adj]  # the adjacency of the whole level
+        batch, index, per_pair = [], {}, {}
+        for x in range(n):
+            for y in frozen[x]:
+                if frozenset((x, y)) in fixed:
+                    continue
+                others = [z for z in frozen[x] if z != y]
+                pair = (min(x, y), max(x, y))
+                for S in itertools.combinations(others, level):
+                    key = (*pair, S)
+                    if key not in index:  # (already asked from the other side)
+                        index[key] = len(batch)
+                        batch.append(key)
+                        per_pair.setdefault(pair, []).append(index[key])
+        if not batch:
+            break
+        p = [float(v) for v in tester(batch)]
+        levels.append(len(batch))
+        trace += [(level, x, y, S, pv) for (x, y, S), pv in zip(batch, p)]
+        for (x, y), asked in per_pair.items():
+            hit = next((i for i in asked if p[i] > alpha), None)
+            if hit is not None:  # the first separating set in enumeration order
+                adj[x].discard(y)
+                adj[y].discard(x)
+                sepsets[(x, y)] = batch[hit][2]
+        level += 1
+    # ---- orientation: background knowledge, v-structures in column order (the first orientation of an edge stays), Meek
+    arrow = set()
+
+    def orient(u, v):
+        if v in adj[u] and (v, u) not in arrow and (u, v) not in forbidden:
+            arrow.add((u, v))
+
+    for u, v in required:
+        orient(u, v)
+    for u, v in sorted(forbidden):
+        orient(v, u)
+    for x in range(n):
+        for y in range(x + 1, n):
+            if y in adj[x] or (x, y) not in sepsets:
+                continue
+            for z in sorted(adj[x] & adj[y]):
+                if z not in sepsets[(x, y)]:
+                    orient(x, z)
+                    orient(y, z)
+    _meek(n, adj, arrow)
+    return {"adj": adj, "arrow": arrow, "sepsets": sepsets, "levels": levels, "trace": trace}
+
+
+class PCResult:
+    """What `pc` learned: `directed` [(u, v) for u -> v] and `undirected` [(u, v), u before v in X.columns] - together the
+    partially directed graph -, `sepsets` {(u, v): the tuple of columns that separated them}, `tests_per_level`, and `trace`
+    ([(level, x, y, given, p_value)] of every test, with return_trace)."""
+
+    def __init__(self, columns, found, keep_trace):
+        name = columns.__getitem__
+        n = len(columns)
+        adj, arrow = found["adj"], found["arrow"]
+        self.columns = list(columns)
+        self.directed = [(name(u), name(v)) for u, v in sorted(arrow)]
+        self.undirected = [(name(u), name(v)) for u in range(n) for v in sorted(adj[u]) if u < v and (u, v) not in arrow and (v, u) not in arrow]
+        self.sepsets = {(name(x), name(y)): tuple(name(z) for z in S) for (x, y), S in found["sepsets"].items()}
+        self.tests_per_level = list(found["levels"])
+        self.trace = [(lv, name(x), name(y), tuple(name(z) for z in S), p) for lv, x, y, S, p in found["trace"]] if keep_trace else None
+
+    def dag(self):
+        """A DAG of the learned equivalence class - a consistent extension by Dor and Tarsi's algorithm - as `BayesNet(*edges)`
+        takes it: (parent, child) tuples plus the bare names of isolated columns.  ValueError where the partially directed
+        graph has none (conflicting test results can produce such a graph)."""
+        pos = {c: j for j, c in enumerate(self.columns)}
+        arrow = {(pos[u], pos[v]) for u, v in self.directed}
+        und = {frozenset((pos[u], pos[v])) for u, v in self.undirected}
+        out = set(arrow)
+        alive = set(range(len(self.columns)))
+        while alive:
+            for x in sorted(alive):
+                nb = {y for y in alive if frozenset((x, y)) in und}
+                adjacent = nb | {y for y in alive if (y, x) in arrow or (x, y) in arrow}
+                if any((x, y) in arrow for y in alive):
+                    continue  # not a sink
+                if all(frozenset((y, z)) in und or (y, z) in arrow or (z, y) in arrow for y in nb for z in adjacent if z != y):
+                    break
+            else:
+                raise ValueError("the partially directed graph has no consistent extension to a DAG")
+            out |= {(y, x) for y in nb}
+            alive.discard(x)
+            und = {e for e in und if x not in e}
+            arrow = {(u, v) for u, v in arrow if x not in (u, v)}
+        name = self.columns.__getitem__
+        result = [(name(u), name(v)) for u, v in sorted(out, key=lambda e: (e[1], e[0]))]
+        linked = {c for e in result for c in e}
+        return result + [c for c in self.columns if c not in linked]
+
+
+def pc(X, alpha=0.01, test="g2", dof="classic", max_cond=3, required=(), forbidden=(), device=None, return_trace=False):
+    """The PC algorithm in its order-independent ("stable") form.  Skeleton: from the complete graph, level l = 0, 1, ...,
+    max_cond tests every pair still adjacent given every l-subset of either end's other neighbours - the adjacency frozen at
+    the start of the level, so ALL tests of a level go to the device as one batch - and drops an edge as soon as one of its
+    tests has p > alpha; the separating set is the first such subset (pairs in column order, subsets lexicographic).
+    Orientation: v-structures from the separating sets in column order (the first orientation of an edge stays, no
+    bidirected edges), then Meek's rules 1 to 3 to closure.  `required` / `forbidden` are (parent, child) pairs: a required
+    edge is kept and directed, a forbidden one never directed that way (forbidden both ways: never adjacent).
+
+    test, dof: see `ci_tests`.  Returns a `PCResult`; `PCResult.dag()` gives `BayesNet(*edges).fit(X)` a member of the class.
+    Complete data only; the rows are uploaded once."""
+    _check_ci(test, dof)
+    if not 0.0 < float(alpha) < 1.0:
+        raise ValueError("alpha must lie strictly between 0 and 1")
+    if int(max_cond) < 0:
+        raise ValueError("max_cond must not be negative")
+    columns = list(X.columns)
+    if len(set(columns)) != len(columns):
+        raise ValueError("X has duplicate column names")
+    req = _edge_list(required, columns, "required")
+    forb = _edge_list(forbidden, columns, "forbidden")
+    for u, v in req:
+        if (u, v) in forb:
+            raise ValueError(f"the edge {columns[u]!r} -> {columns[v]!r} is both required and forbidden")
+        if (v, u) in req:
+            raise ValueError(f"{columns[u]!r} and {columns[v]!r} are required in both directions")
+    codes, _, cards = encode_complete(X, columns)
+    with counting_engine(device).dataset(codes, cards) as ds:
+        found = _pc_search(len(columns), lambda batch: _ci_batch(ds, cards, len(X), batch, test, dof)[2], float(alpha), int(max_cond), req, forb)
+    return PCResult(columns, found, return_trace)
