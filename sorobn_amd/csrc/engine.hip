@@ -506,6 +506,15 @@ static int upload_emit_net(mibn_ctx *h) {
     return MIBN_OK;
 }
 
+// The state an entry point needs, checked in this order: no asynchronous call in flight, a HIP device, a network.
+enum : unsigned { kNeedIdle = 1, kNeedDevice = 2, kNeedNet = 4 };
+static int check_state(mibn_ctx *h, unsigned need) {
+    if ((need & kNeedIdle) && (h->pend[0].active || h->pend[1].active)) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if ((need & kNeedDevice) && h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if ((need & kNeedNet) && !h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    return MIBN_OK;
+}
+
 extern "C" {
 
 const char *mibn_version(void) { return "mibn 0.1 (gfx950)"; }
@@ -679,7 +688,7 @@ int mibn_set_network(mibn_t *h, int32_t n_vars, const int32_t *card, const int64
 
 int mibn_set_order_hints(mibn_t *h, int32_t n_hints, const int32_t *priorities) {
     if (!h || n_hints < 0 || (n_hints && !priorities)) return MIBN_E_ARG;
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedNet)) return rc;
     h->net.set_hints(n_hints, priorities);
     if (!h->planner_only) return upload_order_net(h);
     return MIBN_OK;
@@ -694,7 +703,7 @@ int mibn_last_stats(const mibn_t *h, mibn_stats *out) {
 int mibn_plan_stats(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,
                     mibn_stats *out) {
     if (!h || !out) return MIBN_E_ARG;
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedNet)) return rc;
     Request rq;
     rq.nq = n_q; rq.qvars = q_vars; rq.ne = n_e; rq.evars = e_vars;
     std::string e = validate_request(h->net, rq);
@@ -2097,8 +2106,7 @@ int query_finish(QueryRun &R, double *out, int32_t *ticket) {
 int run_query(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
               const int32_t *e_codes, const int64_t *out_off, double *out, int32_t *ticket) {
     if (!h || B < 0 || !q_off || !e_off || !out_off || (B && !out && !h->expect)) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     QueryRun R{h, flags, (flags & MIBN_Q_UNNORMALISED) != 0, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, now_ms()};
     ++h->call_id;
     h->search_ms = 0;
@@ -2635,8 +2643,7 @@ struct MapPayload {
 // The argument checks of each entry point come first, in its own order; then the driver.
 int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes, double *log_p) {
     if (!h || B < 0 || !e_off || (B && (!codes || !log_p))) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     MpePayload P{codes, log_p};
     return run_elim(h, B, e_off, e_vars, e_codes, P);
 }
@@ -2644,8 +2651,7 @@ int run_mpe_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_va
 int run_draw_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, const int64_t *s_off,
                   uint64_t seed, uint32_t flags, int32_t *codes, double *p_e) {
     if (!h || B < 0 || !e_off || !s_off) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     if (flags & ~(uint32_t)MIBN_DRAW_PRUNE) { h->err = "posterior sampling: unknown flag"; return MIBN_E_ARG; }
     for (int64_t b = 0; b < B; ++b)
         if (s_off[b + 1] < s_off[b] || s_off[b] < 0) { h->err = "posterior sampling: s_off must be non-negative and ascending"; return MIBN_E_ARG; }
@@ -2657,8 +2663,7 @@ int run_draw_body(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_v
 int run_map_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, const int32_t *m_vars, const int64_t *e_off, const int32_t *e_vars,
                  const int32_t *e_codes, int32_t *codes, double *log_p) {
     if (!h || B < 0 || !m_off || !e_off || (B && !log_p)) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     if (flags & ~(uint32_t)MIBN_MAP_PRUNE) { h->err = "map: unknown flag"; return MIBN_E_ARG; }
     for (int64_t b = 0; b < B; ++b)
         if (m_off[b + 1] < m_off[b] || m_off[b] < 0) { h->err = "map: m_off must be non-negative and ascending"; return MIBN_E_ARG; }
@@ -2688,14 +2693,14 @@ extern "C" int mibn_posterior_sample_batch(mibn_t *h, int64_t B, const int64_t *
 extern "C" int mibn_query_batch(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *q_vars,
                                 const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                 const int64_t *out_off, double *out) {
-    if (h && (h->pend[0].active || h->pend[1].active)) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if (h && check_state(h, kNeedIdle)) return MIBN_E_STATE;
     return run_batch(h, 0, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, nullptr);
 }
 
 extern "C" int mibn_query_batch_ex(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars,
                                    const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                    const int64_t *out_off, double *out) {
-    if (h && (h->pend[0].active || h->pend[1].active)) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if (h && check_state(h, kNeedIdle)) return MIBN_E_STATE;
     if (flags & ~(uint32_t)(MIBN_Q_NOPRUNE | MIBN_Q_UNNORMALISED)) { if (h) h->err = "unknown query flag"; return MIBN_E_ARG; }
     return run_batch(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, nullptr);
 }
@@ -2704,10 +2709,9 @@ extern "C" int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int
                                  const int32_t *e_vars, const int32_t *e_codes, const int64_t *acc_base, const int64_t *acc_stride,
                                  const double *weight, int64_t n_acc, double *acc, double *p_out) {
     if (!h || B < 0 || n_acc < 0 || !q_off || !e_off || (n_acc && !acc)) return MIBN_E_ARG;
-    if (h->pend[0].active || h->pend[1].active) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedIdle)) return rc;
     if (flags & ~(uint32_t)(MIBN_Q_NOPRUNE | MIBN_Q_UNNORMALISED)) { h->err = "unknown query flag"; return MIBN_E_ARG; }
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     if (B >= 0x7ffffff0) { h->err = "expect: too many requests in one call"; return MIBN_E_LIMIT; }
     flags |= MIBN_Q_UNNORMALISED;
     // everything the targets depend on is checked here, on the host, before anything is launched: the requests themselves (the query
@@ -2810,18 +2814,12 @@ extern "C" int mibn_gibbs_shard(mibn_t *h, int32_t n_q, const int32_t *q_vars, i
                                 const int32_t *e_codes, const int32_t *cycle, int64_t chain_first, int64_t n_chains,
                                 int64_t n_iterations, uint64_t seed, int64_t *counts) {
     if (!h || !q_vars || !counts || n_chains < 0 || chain_first < 0 || n_iterations < 0) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     Request rq;
     rq.nq = n_q; rq.qvars = q_vars; rq.ne = n_e; rq.evars = e_vars;
     std::string e = validate_request(h->net, rq);
     if (!e.empty()) { h->err = e; return MIBN_E_ARG; }
-    if (n_chains == 0) {  // an empty shard (more ranks than chains)
-        int64_t cells = 1;
-        for (int k = 0; k < n_q; ++k) cells *= h->net.card[q_vars[k]];
-        for (int64_t c = 0; c < cells; ++c) counts[c] = 0;
-        return MIBN_OK;
-    }
+    if (n_chains == 0) return zero_histogram(h->net, n_q, q_vars, kGibbsTooLarge, counts, h->err);  // an empty shard (more ranks than chains)
     HIP_TRY(h, hipSetDevice(h->device));
     return gibbs_run(h->net, h->d_pool, h->stream, h->gibbs_lds, n_q, q_vars, n_e, e_vars, e_codes, cycle, chain_first, n_chains,
                      n_iterations, seed, counts, h->err, h->stats.kernel_ms);
@@ -2830,9 +2828,12 @@ extern "C" int mibn_gibbs_shard(mibn_t *h, int32_t n_q, const int32_t *q_vars, i
 extern "C" int mibn_gibbs_conditional(mibn_t *h, int32_t n_e, const int32_t *e_vars, const int32_t *e_codes, const int32_t *cycle,
                                       int32_t var, int64_t n_rows, const uint8_t *states, double *out) {
     if (!h || n_rows < 0 || (n_rows && (!states || !out)) || (n_e && (!e_vars || !e_codes))) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     if (var < 0 || var >= h->net.n_vars) { h->err = "gibbs conditional: unknown variable"; return MIBN_E_ARG; }
+    Request rq;
+    rq.ne = n_e; rq.evars = e_vars;
+    std::string e = validate_mpe_request(h->net, rq);  // unknown or duplicate evidence ids
+    if (!e.empty()) { h->err = e; return MIBN_E_ARG; }
     for (int64_t r = 0; r < n_rows; ++r)
         for (int v = 0; v < h->net.n_vars; ++v)
             if (states[r * h->net.n_vars + v] >= h->net.card[v]) { h->err = "gibbs conditional: a state code is outside its variable's domain"; return MIBN_E_ARG; }
@@ -2847,8 +2848,7 @@ extern "C" int mibn_gibbs_conditional(mibn_t *h, int32_t n_e, const int32_t *e_v
 extern "C" int mibn_sample(mibn_t *h, int64_t n_samples, int32_t n_init, const int32_t *init_vars, const int32_t *init_codes,
                            uint64_t seed, uint8_t *states) {
     if (!h || n_samples < 0 || !states || (n_init && (!init_vars || !init_codes))) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     if (n_samples == 0) return MIBN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     return sample_run(h->net, h->d_pool, h->stream, kSampleMode, 0, nullptr, n_init, init_vars, init_codes, 0, nullptr, nullptr,
@@ -2857,8 +2857,7 @@ extern "C" int mibn_sample(mibn_t *h, int64_t n_samples, int32_t n_init, const i
 
 extern "C" int mibn_sample_probe(mibn_t *h, int64_t n_rows, const uint8_t *states, int32_t cdf_stride, double *likelihood, double *cdf) {
     if (!h || n_rows < 0 || (n_rows && (!states || !likelihood || !cdf))) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     for (int v = 0; v < h->net.n_vars; ++v)
         if (h->net.card[v] > cdf_stride) { h->err = "sample probe: cdf_stride below a variable's cardinality"; return MIBN_E_ARG; }
     for (int64_t r = 0; r < n_rows; ++r)
@@ -2874,8 +2873,7 @@ extern "C" int mibn_sampling_query(mibn_t *h, int32_t mode, int32_t n_q, const i
                                    const int32_t *e_codes, int64_t n_samples, uint64_t seed, double *weight_sum, int64_t *counts) {
     if (!h || !q_vars || !counts || n_samples < 0 || (mode != MIBN_REJECTION && mode != MIBN_LIKELIHOOD)) return MIBN_E_ARG;
     if (mode == MIBN_LIKELIHOOD && !weight_sum) return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     Request rq;
     rq.nq = n_q; rq.qvars = q_vars; rq.ne = n_e; rq.evars = e_vars;
     std::string e = validate_request(h->net, rq);
@@ -2887,12 +2885,7 @@ extern "C" int mibn_sampling_query(mibn_t *h, int32_t mode, int32_t n_q, const i
     // rejection: nothing is clamped, samples that disagree with the event are dropped (bayes_net.py:604-612);
     // a label outside the domain can never be drawn
     for (int i = 0; i < n_e; ++i)
-        if (e_codes[i] < 0 || e_codes[i] >= h->net.card[e_vars[i]]) {
-            int64_t cells = 1;
-            for (int k = 0; k < n_q; ++k) cells *= h->net.card[q_vars[k]];
-            for (int64_t c = 0; c < cells; ++c) counts[c] = 0;
-            return MIBN_OK;
-        }
+        if (e_codes[i] < 0 || e_codes[i] >= h->net.card[e_vars[i]]) return zero_histogram(h->net, n_q, q_vars, kSamplingTooLarge, counts, h->err);
     return sample_run(h->net, h->d_pool, h->stream, kRejectionMode, n_q, q_vars, 0, nullptr, nullptr, n_e, e_vars, e_codes, n_samples,
                       seed, nullptr, nullptr, counts, h->err);
 }
@@ -2903,7 +2896,7 @@ extern "C" int mibn_count_tables(mibn_t *h, int64_t n_rows, int32_t n_cols, cons
     if (!h || n_rows < 0 || n_cols < 0 || n_tables < 0 || (n_rows && n_cols && !codes) || !card || !scope_off || !scope_cols ||
         !counts_off || !counts || (row_major != 0 && row_major != 1))
         return MIBN_E_ARG;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (int rc = check_state(h, kNeedDevice)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     return count_run(h->stream, n_rows, n_cols, codes, row_major != 0, card, n_tables, scope_off, scope_cols, counts_off, counts, h->err);
 }
@@ -2911,7 +2904,7 @@ extern "C" int mibn_count_tables(mibn_t *h, int64_t n_rows, int32_t n_cols, cons
 extern "C" int mibn_dataset_create(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t *codes, int32_t row_major, const int32_t *card, int32_t *id) {
     if (!h || !id || n_rows < 0 || n_cols < 0 || (n_rows && n_cols && !codes) || (n_cols && !card) || (row_major != 0 && row_major != 1)) return MIBN_E_ARG;
     *id = -1;
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
+    if (int rc = check_state(h, kNeedDevice)) return rc;
     for (int c = 0; c < n_cols; ++c)
         if (card[c] < 1 || card[c] > 256) { h->err = "dataset: cardinality outside 1..256"; return MIBN_E_LIMIT; }
     // a code outside its column's domain would make the count kernels write outside a table: checked here, once
@@ -3100,8 +3093,8 @@ static int tables_book(mibn_ctx *h, const mibn_ctx::Dataset &ds, const TableBatc
 
 // state and id checks of both entry points
 static int tables_enter(mibn_ctx *h, int32_t id, const char *what) {
-    if (h->planner_only) { h->err = "planner-only context: no HIP device bound (there is no CPU fallback)"; return MIBN_E_NODEVICE; }
-    if (h->pend[0].active || h->pend[1].active) { h->err = "asynchronous calls in flight: collect them with mibn_wait first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedDevice)) return rc;
+    if (int rc = check_state(h, kNeedIdle)) return rc;
     if (id < 0 || (size_t)id >= h->datasets.size() || !h->datasets[(size_t)id].live) { h->err = std::string(what) + ": unknown or destroyed data set id"; return MIBN_E_ARG; }
     return MIBN_OK;
 }
@@ -3326,7 +3319,7 @@ extern "C" int mibn_ci_tests(mibn_t *h, int32_t id, int32_t kind, int32_t n_test
 extern "C" int mibn_plan_order(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,
                                int32_t *order, int32_t *n) {
     if (!h || !order || !n) return MIBN_E_ARG;
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedNet)) return rc;
     Request rq;
     rq.nq = n_q; rq.qvars = q_vars; rq.ne = n_e; rq.evars = e_vars;
     std::string e = validate_request(h->net, rq);
@@ -3345,7 +3338,7 @@ extern "C" int mibn_plan_order(mibn_t *h, int32_t n_q, const int32_t *q_vars, in
 extern "C" int mibn_estimate_costs(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off,
                                    const int32_t *e_vars, double *cost) {
     if (!h || B < 0 || !q_off || !e_off || (B && (!q_vars || !cost))) return MIBN_E_ARG;
-    if (!h->has_net) { h->err = "set_network first"; return MIBN_E_STATE; }
+    if (int rc = check_state(h, kNeedNet)) return rc;
     ensure_pool(h);
     estimate_costs(h->net, *h->pool, B, q_off, q_vars, e_off, e_vars, cost);
     return MIBN_OK;

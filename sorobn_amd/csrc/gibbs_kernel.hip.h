@@ -15,6 +15,9 @@
 // together, then all table reads (config 5: 2.38 -> 1.16 us per update, same counts bit for bit).  Random numbers:
 // Philox4x32-10 keyed by (seed, chain), counter = update index; parity with the reference's stream is unpinned (see
 // include/mibn.h), our own stream is pinned by tests/sample_check.py.
+// Which of the six launch forms a call takes, the packed words and the LDS layout are decided in sampler_plan.h (host-only,
+// pinned on a CPU by tests/test_sampler_plan_host.py); the kernels' prologues take their LDS pointers from its gibbs_layout, and
+// gibbs_run at the end of this file is plan, allocate, upload, launch, download.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,12 +27,9 @@
 #include "../../include/mibn.h"
 #include "device_mem.h"
 #include "planner.h"
+#include "sampler_plan.h"
 
 namespace mibn {
-
-struct GibbsVar {
-    int32_t card, table_off, scope_begin, scope_len, child_begin, child_len, is_evidence, ev_code;
-};
 
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
@@ -79,7 +79,6 @@ struct GibbsArgs {
 };
 
 constexpr int kGibbsWaves = 1;  // waves per workgroup (each wave = 64 independent chains)
-constexpr int kFastWords = 28;  // words of one cycle position's update record in the FAST format (gibbs_kernel)
 
 // weight of value x of variable v given the rest of the lane's state
 template <typename PoolPtr>
@@ -119,15 +118,15 @@ template <bool POOL_LDS, bool PROG_LDS, bool FAST = false, bool COND = false>
 __global__ __launch_bounds__(64 * kGibbsWaves) void gibbs_kernel(const GibbsArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
+    const GibbsLayout<int> L = gibbs_layout<int>(A.n_vars, A.hist_cells, POOL_LDS ? A.pool_cells : 0, FAST, A.prog_words);
     uint8_t *st = smem;                                        // n_vars * 64 bytes
-    unsigned int *hist = (unsigned int *)(smem + ((A.n_vars * 64 + 15) & ~15));  // hist_cells
-    double *lds_pool = (double *)(smem + ((((A.n_vars * 64 + 15) & ~15) + A.hist_cells * 4 + 15) & ~15));
+    unsigned int *hist = (unsigned int *)(smem + L.hist);      // hist_cells
+    double *lds_pool = (double *)(smem + L.pool);
     if (POOL_LDS)
         for (int i = threadIdx.x; i < A.pool_cells; i += blockDim.x) lds_pool[i] = A.pool[i];
     if (FAST && threadIdx.x == 0) lds_pool[A.pool_cells] = 1.0;  // the table of an unused factor slot
     // uprog | uprog_off | cycle (FAST: 16-byte aligned records of kFastWords words, one per cycle position, nothing else)
-    int32_t *lds_prog = FAST ? (int32_t *)((unsigned char *)lds_pool + (((size_t)(A.pool_cells + 1) * 8 + 15) & ~size_t(15)))
-                             : (int32_t *)(lds_pool + (POOL_LDS ? A.pool_cells : 0));
+    int32_t *lds_prog = (int32_t *)(smem + L.prog);
     if (PROG_LDS) {
         for (int i = threadIdx.x; i < A.uprog_words; i += blockDim.x) lds_prog[i] = A.uprog[i];
         for (int i = threadIdx.x; i < (FAST ? 0 : A.n_cycle); i += blockDim.x) {
@@ -368,12 +367,13 @@ template <bool COND>
 __global__ __launch_bounds__(64) void gibbs_kernel8(const GibbsArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, g = lane >> 3, x = lane & 7;
+    const GibbsLayout<int> L = gibbs_layout<int>(A.n_vars, A.hist_cells, A.pool_cells, true, A.prog_words);
     uint8_t *st = smem;                                        // state[var * 8 + chain of the wave] (room for n_vars * 64 as in gibbs_kernel)
-    unsigned int *hist = (unsigned int *)(smem + ((A.n_vars * 64 + 15) & ~15));
-    double *lds_pool = (double *)(smem + ((((A.n_vars * 64 + 15) & ~15) + A.hist_cells * 4 + 15) & ~15));
+    unsigned int *hist = (unsigned int *)(smem + L.hist);
+    double *lds_pool = (double *)(smem + L.pool);
     for (int i = threadIdx.x; i < A.pool_cells; i += blockDim.x) lds_pool[i] = A.pool[i];
     if (threadIdx.x == 0) lds_pool[A.pool_cells] = 1.0;  // the table of an unused factor slot
-    int32_t *lds_prog = (int32_t *)((unsigned char *)lds_pool + (((size_t)(A.pool_cells + 1) * 8 + 15) & ~size_t(15)));
+    int32_t *lds_prog = (int32_t *)(smem + L.prog);
     for (int i = threadIdx.x; i < A.uprog_words; i += blockDim.x) lds_prog[i] = A.uprog[i];
     const int64_t local = (int64_t)blockIdx.x * 8 + g;
     const int64_t chain = A.chain_first + local;
@@ -489,180 +489,70 @@ __global__ __launch_bounds__(64) void gibbs_kernel8(const GibbsArgs A) {
         if (hist[i]) atomicAdd(&A.counts[i], (unsigned long long)hist[i]);
 }
 
-// host driver; returns MIBN_* code
+// (GibbsForm, drawing | COND) -> kernel
+typedef void (*GibbsKernel)(const GibbsArgs);
+inline GibbsKernel gibbs_kernel_of(GibbsForm form, bool cond) {
+    static const GibbsKernel table[kGibbsForms][2] = {
+        /* L2          */ {gibbs_kernel<false, false>, gibbs_kernel<false, false, false, true>},
+        /* PoolLds     */ {gibbs_kernel<true, false>, gibbs_kernel<true, false, false, true>},
+        /* ProgLds     */ {gibbs_kernel<false, true>, gibbs_kernel<false, true, false, true>},
+        /* PoolProgLds */ {gibbs_kernel<true, true>, gibbs_kernel<true, true, false, true>},
+        /* Fast        */ {gibbs_kernel<true, true, true>, gibbs_kernel<true, true, true, true>},
+        /* Fast8       */ {gibbs_kernel8<false>, gibbs_kernel8<true>},
+    };
+    return table[(int)form][cond];
+}
+
+// host driver: plan (sampler_plan.h), allocate, upload, launch, download - per-call buffers, blocking; returns MIBN_* code
 // cond_var >= 0 (mibn_gibbs_conditional): n_chains rows of cond_states, the conditional of cond_var into cond_out
 inline int gibbs_run(const Network &net, const double *d_pool, hipStream_t stream, int lds_mode /* 0: tables in L2; 1: LDS; 2: LDS, no 8-lane form */, int32_t n_q, const int32_t *q_vars,
                      int32_t n_e, const int32_t *e_vars, const int32_t *e_codes, const int32_t *cycle_in, int64_t chain_first,
                      int64_t n_chains, int64_t n_iterations, uint64_t seed, int64_t *counts, std::string &err, double &kernel_ms,
                      int32_t cond_var = -1, const uint8_t *cond_states = nullptr, double *cond_out = nullptr) {
-    const int n = net.n_vars;
-    const bool allow_lds = lds_mode != 0;
-    std::vector<GibbsVar> vars(n);
-    std::vector<int32_t> scope_var, scope_stride, children, cycle;
-    std::vector<std::vector<int32_t>> ch(n);
-    for (int v = 0; v < n; ++v)
-        for (size_t k = 0; k + 1 < net.scope[v].size(); ++k) ch[net.scope[v][k]].push_back(v);
-    for (int v = 0; v < n; ++v) {
-        if (net.card[v] > 255) { err = "gibbs: cardinality above 255"; return MIBN_E_LIMIT; }
-        GibbsVar g{};
-        g.card = net.card[v];
-        g.table_off = (int32_t)net.pool_off[v];
-        g.scope_begin = (int32_t)scope_var.size();
-        g.scope_len = (int32_t)net.scope[v].size();
-        for (size_t k = 0; k < net.scope[v].size(); ++k) {
-            scope_var.push_back(net.scope[v][k]);
-            scope_stride.push_back((int32_t)net.cstride[v][k]);
-        }
-        g.child_begin = (int32_t)children.size();
-        g.child_len = (int32_t)ch[v].size();
-        for (int c : ch[v]) children.push_back(c);
-        vars[v] = g;
-    }
-    for (int i = 0; i < n_e; ++i) {
-        if (e_codes[i] < 0 || e_codes[i] >= net.card[e_vars[i]]) { err = "gibbs: evidence label outside the domain"; return MIBN_E_ARG; }
-        vars[e_vars[i]].is_evidence = 1;
-        vars[e_vars[i]].ev_code = e_codes[i];
-    }
-    int n_free = 0;
-    for (int v = 0; v < n; ++v) n_free += !vars[v].is_evidence;
-    if (cycle_in) {  // caller's update order (the reference cycles through sorted(nodes - event), bayes_net.py:697,718)
-        std::vector<char> seen(n, 0);
-        for (int i = 0; i < n_free; ++i) {
-            const int v = cycle_in[i];
-            if (v < 0 || v >= n || vars[v].is_evidence || seen[v]) { err = "gibbs: cycle must list every non-evidence variable once"; return MIBN_E_ARG; }
-            seen[v] = 1;
-            cycle.push_back(v);
-        }
-    } else {
-        for (int v = 0; v < n; ++v)
-            if (!vars[v].is_evidence) cycle.push_back(v);
-    }
-    if (cycle.empty()) { err = "gibbs: every variable is evidence"; return MIBN_E_ARG; }
-    int cond_pos = -1;
-    if (cond_var >= 0) {
-        for (size_t i = 0; i < cycle.size(); ++i)
-            if (cycle[i] == cond_var) cond_pos = (int)i;
-        if (cond_pos < 0) { err = "gibbs conditional: the variable is evidence or unknown"; return MIBN_E_ARG; }
-    }
-    // update programs, one per cycle position
-    std::vector<int32_t> uprog, uprog_off;
-    for (int v : cycle) {
-        uprog_off.push_back((int32_t)uprog.size());
-        uprog.push_back(net.card[v]);
-        uprog.push_back(1 + (int32_t)ch[v].size());
-        auto factor = [&](int c) {  // CPT of c as a function of v's value
-            int32_t sv = 0;
-            std::vector<int32_t> others;
-            for (size_t k = 0; k < net.scope[c].size(); ++k) {
-                const int u = net.scope[c][k];
-                if (u == v) sv = (int32_t)net.cstride[c][k];
-                else { others.push_back(u); others.push_back((int32_t)net.cstride[c][k]); }
-            }
-            uprog.push_back((int32_t)net.pool_off[c]);
-            uprog.push_back(sv);
-            uprog.push_back((int32_t)(others.size() / 2));
-            uprog.insert(uprog.end(), others.begin(), others.end());
-        };
-        factor(v);
-        for (int c : ch[v]) factor(c);
-    }
-    std::vector<int32_t> qstride(n_q);
-    int64_t cells = 1;
-    for (int i = n_q - 1; i >= 0; --i) { qstride[i] = (int32_t)cells; cells *= net.card[q_vars[i]]; }
-    size_t lds = ((size_t)n * 64 + 15) / 16 * 16 + (size_t)cells * 4;
-    if (lds > 150 * 1024) { err = "gibbs: network/query too large for the LDS-resident chain state"; return MIBN_E_LIMIT; }
-    // tables in LDS too when they fit beside the state and the launch is small enough for one workgroup per CU
-    const size_t pool_cells = net.pool.size();
-    const size_t lds_with_pool = (lds + 15) / 16 * 16 + pool_cells * 8;
-    // the 8-lane form (gibbs_kernel8) has eight chains per workgroup: it wins while its workgroups - one per CU, the tables fill the
-    // LDS - need at most two rounds over the 256 CUs (~0.4 us per update against 1.16 us for gibbs_kernel's 64 chains per wave)
-    const bool want8 = lds_mode == 1 && (n_chains + 7) / 8 <= 512;
-    const bool pool_lds = allow_lds && lds_with_pool <= 160 * 1024 && (want8 || (n_chains + 63) / 64 <= 512);
-    if (pool_lds) lds = lds_with_pool;
-    // fixed-size update records (gibbs_kernel<.., FAST>) when every variable of the cycle qualifies and they still fit
-    bool fast = pool_lds;
-    std::vector<int32_t> fprog;
-    for (size_t ci = 0; ci < cycle.size() && fast; ++ci) {
-        const int v = cycle[ci];
-        if (net.card[v] > 8 || 1 + ch[v].size() > 4) { fast = false; break; }
-        int32_t is_query = 0;
-        for (int i = 0; i < n_q; ++i) is_query |= q_vars[i] == v;
-        const int32_t head[4] = {v, net.card[v], 1 + (int32_t)ch[v].size(), is_query};
-        fprog.insert(fprog.end(), head, head + 4);
-        int slots = 0;
-        auto record = [&](int c) {
-            int32_t rec[6] = {(int32_t)net.pool_off[c], 0, 0, 0, 0, 0};
-            int n_other = 0;
-            for (size_t k = 0; k < net.scope[c].size(); ++k) {
-                const int u = net.scope[c][k];
-                if (u == v) rec[1] = (int32_t)net.cstride[c][k];
-                else if (n_other < 2) { rec[2 + 2 * n_other] = u; rec[3 + 2 * n_other] = (int32_t)net.cstride[c][k]; ++n_other; }
-                else fast = false;
-            }
-            fprog.insert(fprog.end(), rec, rec + 6);
-            ++slots;
-        };
-        record(v);
-        for (int c : ch[v]) record(c);
-        for (; slots < 4; ++slots) {  // unused slots: the 1.0 behind the tables, strides 0
-            const int32_t rec[6] = {(int32_t)pool_cells, 0, 0, 0, 0, 0};
-            fprog.insert(fprog.end(), rec, rec + 6);
-        }
-    }
-    if (fast && (lds + 8 + 15) / 16 * 16 + fprog.size() * 4 > 160 * 1024) fast = false;
-    if (fast) {
-        uprog = fprog;
-        lds += 8;
-    }
-    const size_t prog_words = fast ? uprog.size() : uprog.size() + 2 * cycle.size();
-    const bool prog_lds = fast || (allow_lds && (lds + 15) / 16 * 16 + prog_words * 4 <= 160 * 1024 && (n_chains + 63) / 64 <= 512);
-    if (prog_lds) lds = (lds + 15) / 16 * 16 + prog_words * 4;
-
+    GibbsPlan G;
+    if (int rc = gibbs_plan(net, lds_mode, n_q, q_vars, n_e, e_vars, e_codes, cycle_in, n_chains, cond_var, G, err)) return rc;
+    const size_t n = (size_t)net.n_vars, cells = (size_t)G.hist_cells;
+    const std::vector<int32_t> &pack = G.pack.words;
     DevBuf<GibbsVar> d_vars;
     DevBuf<int32_t> d_i32;
     DevBuf<unsigned long long> d_counts;
     DevBuf<uint8_t> d_cond_states;
     DevBuf<double> d_cond_out;
     Event e0, e1;
-    std::vector<int32_t> pack;
-    auto put = [&](const std::vector<int32_t> &a) { size_t o = pack.size(); pack.insert(pack.end(), a.begin(), a.end()); return o; };
-    const size_t o_sv = put(scope_var), o_ss = put(scope_stride), o_ch = put(children), o_cy = put(cycle);
-    const size_t o_q = put(std::vector<int32_t>(q_vars, q_vars + n_q)), o_qs = put(qstride);
-    const size_t o_up = put(uprog), o_uo = put(uprog_off);
     auto fail = [&](hipError_t e) { err = std::string("gibbs: ") + hipGetErrorString(e); return MIBN_E_HIP; };
     hipError_t e;
-    if ((e = d_vars.reset((size_t)n)) != hipSuccess) return fail(e);
+    if ((e = d_vars.reset(n)) != hipSuccess) return fail(e);
     if ((e = d_i32.reset(std::max<size_t>(1, pack.size()))) != hipSuccess) return fail(e);
-    if ((e = d_counts.reset((size_t)cells)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(d_vars, vars.data(), sizeof(GibbsVar) * n, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+    if ((e = d_counts.reset(cells)) != hipSuccess) return fail(e);
+    if ((e = hipMemcpyAsync(d_vars, G.pack.vars.data(), sizeof(GibbsVar) * n, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(d_i32, pack.data(), 4 * pack.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
-    if ((e = hipMemsetAsync(d_counts, 0, 8 * (size_t)cells, stream)) != hipSuccess) return fail(e);
+    if ((e = hipMemsetAsync(d_counts, 0, 8 * cells, stream)) != hipSuccess) return fail(e);
     GibbsArgs A;
     A.pool = d_pool;
     A.vars = d_vars;
-    A.scope_var = d_i32 + o_sv;
-    A.scope_stride = d_i32 + o_ss;
-    A.children = d_i32 + o_ch;
-    A.cycle = d_i32 + o_cy;
-    A.uprog = d_i32 + o_up;
-    A.uprog_off = d_i32 + o_uo;
-    A.qvars = d_i32 + o_q;
-    A.qstride = d_i32 + o_qs;
+    A.scope_var = d_i32 + G.o_sv;
+    A.scope_stride = d_i32 + G.o_ss;
+    A.children = d_i32 + G.o_ch;
+    A.cycle = d_i32 + G.o_cy;
+    A.uprog = d_i32 + G.o_up;
+    A.uprog_off = d_i32 + G.o_uo;
+    A.qvars = d_i32 + G.o_q;
+    A.qstride = d_i32 + G.o_qs;
     A.counts = d_counts;
-    A.n_vars = n;
-    A.pool_cells = (int32_t)pool_cells;
-    A.uprog_words = (int32_t)uprog.size();
-    A.prog_words = prog_lds ? (int32_t)prog_words : 0;
-    A.n_cycle = (int32_t)cycle.size();
+    A.n_vars = net.n_vars;
+    A.pool_cells = G.pool_cells;
+    A.uprog_words = G.uprog_words;
+    A.prog_words = G.prog_words;
+    A.n_cycle = G.n_cycle;
     A.n_q = n_q;
-    A.hist_cells = (int32_t)cells;
+    A.hist_cells = G.hist_cells;
     A.n_chains = n_chains;
     A.chain_first = chain_first;
     A.n_iterations = n_iterations;
     A.seed = seed;
     A.cond_states = nullptr;
     A.cond_out = nullptr;
-    A.cond_pos = 0;
+    A.cond_pos = G.cond_pos;
     const size_t cond_cells = cond_var >= 0 ? (size_t)n_chains * (size_t)net.card[cond_var] : 0;
     if (cond_var >= 0) {
         if ((e = d_cond_states.reset(std::max<size_t>(1, (size_t)n_chains * n))) != hipSuccess) return fail(e);
@@ -670,33 +560,24 @@ inline int gibbs_run(const Network &net, const double *d_pool, hipStream_t strea
         if ((e = hipMemcpyAsync(d_cond_states, cond_states, (size_t)n_chains * n, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
         A.cond_states = d_cond_states;
         A.cond_out = d_cond_out;
-        A.cond_pos = cond_pos;
     }
     if ((e = e0.ensure()) != hipSuccess || (e = e1.ensure()) != hipSuccess) return fail(e);
-    const bool fast8 = fast && want8;
-    const unsigned blocks = fast8 ? (unsigned)((n_chains + 7) / 8) : (unsigned)((n_chains + 63) / 64);
-    auto kernel = fast8 ? gibbs_kernel8<false> : fast ? gibbs_kernel<true, true, true>
-                       : pool_lds ? (prog_lds ? gibbs_kernel<true, true> : gibbs_kernel<true, false>)
-                                  : (prog_lds ? gibbs_kernel<false, true> : gibbs_kernel<false, false>);
-    if (cond_var >= 0)  // the same form, writing the weights instead of drawing from them
-        kernel = fast8 ? gibbs_kernel8<true> : fast ? gibbs_kernel<true, true, true, true>
-                      : pool_lds ? (prog_lds ? gibbs_kernel<true, true, false, true> : gibbs_kernel<true, false, false, true>)
-                                 : (prog_lds ? gibbs_kernel<false, true, false, true> : gibbs_kernel<false, false, false, true>);
-    if (lds > 64 * 1024) {
-        if ((e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return fail(e);
+    const GibbsKernel kernel = gibbs_kernel_of(G.form, cond_var >= 0);
+    if (G.lds.total > 64 * 1024) {
+        if ((e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds.total)) != hipSuccess) return fail(e);
     }
-    hipEventRecord(e0, stream);
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * kGibbsWaves), lds, stream, A);
+    if ((e = hipEventRecord(e0, stream)) != hipSuccess) return fail(e);
+    hipLaunchKernelGGL(kernel, dim3(G.blocks), dim3(64 * kGibbsWaves), G.lds.total, stream, A);
     if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    hipEventRecord(e1, stream);
-    std::vector<unsigned long long> hc((size_t)cells);
-    if ((e = hipMemcpyAsync(hc.data(), d_counts, 8 * (size_t)cells, hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
+    if ((e = hipEventRecord(e1, stream)) != hipSuccess) return fail(e);
+    std::vector<unsigned long long> hc(cells);
+    if ((e = hipMemcpyAsync(hc.data(), d_counts, 8 * cells, hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);
     float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
+    if ((e = hipEventElapsedTime(&ms, e0, e1)) != hipSuccess) return fail(e);
     kernel_ms = ms;
     if (counts)
-        for (int64_t i = 0; i < cells; ++i) counts[i] = (int64_t)hc[(size_t)i];
+        for (size_t i = 0; i < cells; ++i) counts[i] = (int64_t)hc[i];
     if (cond_var >= 0) {
         if ((e = hipMemcpy(cond_out, d_cond_out, 8 * cond_cells, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e);
     }

@@ -10,15 +10,15 @@ The network contract caps a network at 1 024 variables (kMaxVars, the planner's 
 LDS-resident state of sample_kernel is at most 64 KiB and a forward-sampling launch never needs the raised dynamic-LDS limit:
 test_variable_cap_bounds_the_sample_state pins that.  The raised limit, the exact 150 KiB boundary and MIBN_E_LIMIT behind it are
 reached the way the library can reach them - state + histogram of a sampling query."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
-import golden_util as gu
-import netspec
+import gibbs_cases as gc
 import sample_check as sc
-import sorobn_amd
+from gibbs_cases import chain_net as _chain_net, example as _example, grid_net as _grid_net, random_net as _random_net, tables as _tables
 from sorobn_amd import _capi
-from sorobn_amd.flatten import flatten
 
 pytestmark = pytest.mark.gpu
 
@@ -26,52 +26,6 @@ REJECTION, LIKELIHOOD = 1, 2
 
 
 # ----------------------------------------------------------------------------------------------------------- networks
-
-def _tables(rng, card, parents, zeros=True):
-    """Unnormalised positive tables; every third row gets a zero at the start, the middle or the end (in turn), some rows two
-    trailing zeros - never a whole row."""
-    out = []
-    for v, p in enumerate(parents):
-        k = int(card[v])
-        t = rng.random([int(card[u]) for u in p] + [k]) * 2 + 0.05
-        rows = t.reshape(-1, k)
-        if zeros and k > 1:
-            for r in range(0, len(rows), 3):
-                rows[r, (0, k // 2, k - 1)[(r // 3) % 3]] = 0.0
-                if k > 3 and (r // 3) % 4 == 3:
-                    rows[r, -2:] = 0.0
-        assert (rows.sum(axis=1) > 0).all()
-        out.append(t)
-    return out
-
-
-def _random_net(card, parents, seed, zeros=True):
-    return sc.make_net(card, parents, _tables(np.random.default_rng(seed), card, parents, zeros))
-
-
-def _grid_net(R, C, K, seed):
-    """Row-major grid, parents = top and left neighbour."""
-    parents = [([v - C] if v >= C else []) + ([v - 1] if v % C else []) for v in range(R * C)]
-    return _random_net([K] * (R * C), parents, seed)
-
-
-def _chain_net(n, seed):
-    return _random_net([2] * n, [[v - 1] if v else [] for v in range(n)], seed)
-
-
-def _example(name):
-    spec = next(n for n in gu.load("examples.json") if n["spec"]["name"] == name)["spec"]
-    return sc.from_flat(flatten(netspec.build(spec, sorobn_amd.BayesNet)))
-
-
-def _dag():
-    """A network of tests/golden/random_dags.json with a node of five children and nodes of three parents (normalised rows, exact
-    zeros, missing rows = zeros of the dense table)."""
-    spec = next(e["spec"] for e in gu.load("random_dags.json") if e["spec"]["name"] == "dag2")
-    net = sc.from_flat(flatten(netspec.build(spec, sorobn_amd.BayesNet)))
-    assert max(len(c) for c in net.children) >= 4 and max(len(s) for s in net.scope) - 1 >= 3
-    return net
-
 
 MIXED = dict(card=[3, 2, 5, 4, 2, 3], parents=[[], [0], [0, 1], [2], [1, 3], [2, 4]])
 # a zero row of variable 1 behind 0 = 0, a zero in the middle of its other row, a deterministic last variable
@@ -302,37 +256,61 @@ def _gibbs_all_forms(eng, net, q, ev, chains, iters, seed, cycle=None, chain_fir
     return want
 
 
-def _tree_net():
-    """Cards 17 and 255: the `card > 16` update form (variables 0, 1, 3), beside two small ones."""
-    return _random_net([17, 255, 3, 17, 2], [[], [0], [1], [0], [3]], seed=41)
-
-
-GIBBS_CASES = {
-    # name: (network, query, evidence, cycle)
-    "grid3x3k8": (lambda: _grid_net(3, 3, 8, 51), [4, 8], {}, None),                                  # 8-lane / FAST, no evidence
-    "grid4x5k3": (lambda: _grid_net(4, 5, 3, 52), [12], {0: 1, 19: 2, 7: 0}, None),                   # three evidence variables
-    "grid4x5k3-reverse-cycle": (lambda: _grid_net(4, 5, 3, 52), [9, 10], {0: 1}, "reverse"),           # a caller's cycle
-    "dag-5-children-3-parents": (_dag, [4, 9], {1: 1}, None),                                          # generic `card <= 16` form
-    "dag-reverse-cycle": (_dag, [10, 0, 5], {}, "reverse"),
-    "tree-17-255": (_tree_net, [1], {4: 1}, None),                                                     # `card > 16` form, 255 cells
-    "tree-17-255-two-queries": (_tree_net, [3, 0], {}, "reverse"),
-    "asia-five-queries": (lambda: _example("asia"), [0, 2, 4, 5, 7], {}, None),                        # n_q > 4, a deterministic CPT
-    "asia-five-queries-evidence": (lambda: _example("asia"), [6, 1, 3, 0, 5], {2: 1, 4: 0, 7: 1}, "reverse"),
-    "grid-five-queries": (lambda: _grid_net(3, 3, 2, 53), [8, 0, 4, 2, 6], {5: 1}, None),              # n_q > 4 in the 8-lane / FAST forms
-}
-
-
-@pytest.mark.parametrize("name", list(GIBBS_CASES))
+@pytest.mark.parametrize("name", list(gc.GIBBS_CASES))
 def test_gibbs_histograms_equal_the_twin(name):
-    make, q, ev, cycle = GIBBS_CASES[name]
+    """Every case under gibbs_lds 1, 2 and 0: the launch forms its table entry names (tests/test_sampler_plan_host.py holds the plan to them)."""
+    make, q, ev, cycle, _, ((chains, iters), (shard_chains, shard_iters)) = gc.GIBBS_CASES[name]
     net = make()
-    if cycle == "reverse":
-        cycle = [v for v in range(len(net.card) - 1, -1, -1) if v not in ev]
+    cycle = gc.cycle_of(net, ev, cycle)
     eng = _engine(net)
-    counts = _gibbs_all_forms(eng, net, q, ev, 61, 257, seed=(3 << 32) | 9, cycle=cycle)
+    counts = _gibbs_all_forms(eng, net, q, ev, chains, iters, seed=(3 << 32) | 9, cycle=cycle)
     assert (counts > 0).sum() > 1
-    _gibbs_all_forms(eng, net, q, ev, 9, 40, seed=2, cycle=cycle, chain_first=7)
-    _gibbs_all_forms(eng, net, q, ev, 9, 40, seed=2, cycle=cycle, chain_first=(1 << 32) + 5)  # the high word of the chain index
+    _gibbs_all_forms(eng, net, q, ev, shard_chains, shard_iters, seed=2, cycle=cycle, chain_first=7)
+    _gibbs_all_forms(eng, net, q, ev, shard_chains, shard_iters, seed=2, cycle=cycle, chain_first=(1 << 32) + 5)  # the high word of the chain index
+
+
+@pytest.mark.parametrize("name", ["grid3x3k8", "dag-5-children-3-parents", "tree-17-255", "two-255-state-variables", "grid32x32k2"])
+def test_gibbs_conditionals_equal_the_twin(name):
+    """mibn_gibbs_conditional (the COND instantiation of every launch form: gibbs_lds 1, 2 and 0 of cases that between them take all
+    six) on a wave and six lanes of forward samples: the weights of the twin, each divided by their sum in ascending state order -
+    the same products in the same order, one correctly rounded division: EQUAL.  The one-chain-per-lane FAST form alone carries a bound:
+    the compiler contracts its `total += w[x]` into fused multiply-adds, so its sum of at most 8 non-negative terms
+    and the twin's are two differently rounded sums, each within 8 x 2^-53 of the exact one: |got - want| <= 2^-48 x want."""
+    make, q, ev, cycle, forms, _ = gc.GIBBS_CASES[name]
+    net = make()
+    states = sc.forward(net, gc.CONDITIONAL_ROWS, 11, clamp=ev)[0]
+    w = sc.gibbs_weights(net, q[0], states)
+    total = np.zeros(len(w))
+    for x in range(w.shape[1]):
+        total = total + w[:, x]
+    want = np.where(total[:, None] > 0, w / np.where(total > 0, total, 1.0)[:, None], 0.0)
+    eng = _engine(net)
+    try:
+        for mode in gc.LDS_MODES:
+            eng.set_option("gibbs_lds", mode)
+            got = eng.gibbs_conditional(q[0], states, list(ev), list(ev.values()), cycle=gc.cycle_of(net, ev, cycle))
+            diff = np.abs(got - want)
+            print(name, forms[mode], "largest |got - want| / want:", float(np.max(diff[want > 0] / want[want > 0])))
+            assert (diff <= (2.0 ** -48 * want if forms[mode] == "Fast" else 0.0)).all(), (mode, float(diff.max()))
+    finally:
+        eng.set_option("gibbs_lds", 1)
+
+
+def test_gibbs_conditional_refuses_unknown_evidence_ids(asia):
+    """Through the raw library handle (the Python wrapper has checks of its own): an evidence id of n_vars or -1 is MIBN_E_ARG with the
+    planner's message, a duplicate likewise - before anything is launched: the output keeps its fill (a launch overwrites every row)."""
+    net, eng = asia
+    n = len(net.card)
+    i32 = lambda a: np.asarray(a, np.int32).ctypes.data_as(C.POINTER(C.c_int32))
+    states = np.zeros((3, n), np.uint8)
+    for ids, msg in (([n], f"unknown evidence variable id {n}"), ([-1], "unknown evidence variable id -1"), ([2, n], f"unknown evidence variable id {n}"),
+                     ([2, 2], "duplicate evidence variable id 2")):
+        out = np.full((3, 2), -7.0)
+        rc = eng._L.mibn_gibbs_conditional(eng._h, len(ids), i32(ids), i32([0] * len(ids)), None, 0, 3, states.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                           out.ctypes.data_as(C.POINTER(C.c_double)))
+        assert rc == _capi.E_ARG and eng._L.mibn_last_error(eng._h).decode() == msg
+        assert (out == -7.0).all()
+    assert eng.gibbs_conditional(0, states, [2], [0]).shape == (3, 2)  # the handle still works
 
 
 def test_gibbs_updates_without_mass():
