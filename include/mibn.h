@@ -210,6 +210,35 @@ int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, c
                    const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                    int32_t *codes, double *log_p);
 
+/* Likelihood findings (Pearl's virtual evidence, "soft evidence") for the NEXT batch call.
+ * A finding on variable X is one finite, non-negative weight per state of X; every result of the call is computed from the joint
+ * multiplied by the weights of the request's findings:  P(x) * prod_k lambda_k(x_k).  It is what the unmodified reference computes on a
+ * network in which every finding variable has an extra binary child V with P(V = 1 | X = x) = lambda(x) / max lambda, observed at 1.
+ * It expresses a noisy sensor or a classifier's scores, "X is not x" (weight 0 on x, 1 elsewhere), "X is a or b", a partly trusted label.
+ *   Normalised queries: the posterior over the query variables under the weighted joint; scaling a lambda changes nothing.
+ *   MIBN_Q_UNNORMALISED: the weighted mass as it is - the caller's lambda is used as given, never rescaled.
+ *   mibn_mpe_batch / mibn_map_batch: the maximum is over the weighted joint, log_p is its natural logarithm.
+ * A finding variable may be a query or MAP variable; it may not be an evidence variable of the same request, nor be named twice.
+ * Finding variables and their ancestors are relevant exactly as evidence variables are; barren descendants are still pruned.  Weights
+ * that leave no positive mass behave like impossible evidence: an all-zero posterior, log_p = -inf and codes -1, mass 0.  A single-
+ * state variable may carry a finding: a scalar factor, visible in unnormalised and log_p results only.
+ * CSR layout: request b has the findings l_vars[l_off[b] .. l_off[b + 1]); finding k has the weights values[v_off[k] .. v_off[k + 1]),
+ * exactly card(l_vars[k]) of them (v_off has one entry more than l_vars and is indexed like it).
+ * The block is copied.  It belongs to the next batch call and is gone when that call returns, whatever it returns:
+ *   mibn_query_batch, mibn_query_batch_ex, mibn_mpe_batch and mibn_map_batch consume it; their B must be the block's (MIBN_E_ARG);
+ *   mibn_submit_batch and mibn_expect_batch refuse it with MIBN_E_STATE, mibn_posterior_sample_batch with MIBN_E_ARG.
+ * A block without a single finding (B = 0 with a call of no requests, or all rows empty) is legal: the call is bit for bit the call
+ * without a block.  A call with findings is planned by the host's workers only - no plan templates, no device planner, no adaptive
+ * policy -; on the device the weights reach each request's arena through "likelihood_seed_kernel" (a row of its own in
+ * mibn_last_kernel_stats), tiny networks answer through "tiny_lh_kernel".
+ * Errors, all before anything is enqueued and with the request's index in mibn_last_error: MIBN_E_ARG for a descending l_off, an
+ * unknown variable, a variable named twice in a request, a weight vector whose length is not the variable's cardinality, a negative,
+ * NaN or infinite weight (here), and for a finding variable that is also evidence of its request (in the call that consumes the block);
+ * MIBN_E_STATE before mibn_set_network.
+ */
+int mibn_set_likelihoods(mibn_t *h, int64_t B, const int64_t *l_off, const int32_t *l_vars,
+                         const int64_t *v_off, const double *values);
+
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {
     double alg_bytes;      /* sum over steps of 8*(sum input cells + output cells) */

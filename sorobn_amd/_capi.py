@@ -23,7 +23,7 @@ SYMBOLS = [
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
     "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch", "mibn_map_batch",
-    "mibn_ci_tests",
+    "mibn_ci_tests", "mibn_set_likelihoods",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
@@ -84,6 +84,7 @@ def lib():
         L.mibn_query_batch_ex.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, f64p]
         L.mibn_mpe_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i32p, f64p]
         L.mibn_map_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i32p, f64p]
+        L.mibn_set_likelihoods.argtypes = [vp, C.c_int64, i64p, i32p, i64p, f64p]
         L.mibn_posterior_sample_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i64p, C.c_uint64, C.c_uint32, i32p, f64p]
         L.mibn_expect_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, i64p, f64p, C.c_int64, f64p, f64p]
         L.mibn_plan_order.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, i32p, i32p]
@@ -260,8 +261,22 @@ class Engine:
     def set_option(self, name, value):
         self._check(self._L.mibn_set_option(self._h, name.encode(), float(value)))
 
-    def query_batch(self, q_off, q_vars, e_off, e_vars, e_codes, out_off=None, flags=0):
-        """CSR request batch -> flat float64 posteriors (+ out_off).  flags: Q_NOPRUNE, Q_UNNORMALISED (per call, see mibn.h)."""
+    def set_likelihoods(self, likelihoods):
+        """Stages the likelihood findings of the NEXT batch call (mibn_set_likelihoods): likelihoods = (l_off, l_vars, v_off, values),
+        request b's findings are l_vars[l_off[b]:l_off[b + 1]], finding k's weights values[v_off[k]:v_off[k + 1]] - one per state of
+        l_vars[k].  The query, mpe and map calls do this themselves for their `likelihoods=` argument."""
+        l_off, l_vars, v_off, values = likelihoods
+        l_off, v_off, l_vars = _i64(l_off), _i64(v_off), _i32(l_vars)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        if len(l_off) < 1 or len(v_off) != len(l_vars) + 1:
+            raise ValueError("likelihoods: l_off needs one entry per request plus one, v_off one per finding plus one")
+        self._check(self._L.mibn_set_likelihoods(
+            self._h, len(l_off) - 1, _p(l_off, C.c_int64), _p(l_vars if len(l_vars) else np.zeros(1, np.int32), C.c_int32),
+            _p(v_off, C.c_int64), _p(values if len(values) else np.zeros(1, np.float64), C.c_double)))
+
+    def query_batch(self, q_off, q_vars, e_off, e_vars, e_codes, out_off=None, flags=0, likelihoods=None):
+        """CSR request batch -> flat float64 posteriors (+ out_off).  flags: Q_NOPRUNE, Q_UNNORMALISED (per call, see mibn.h).
+        likelihoods: the findings of the requests as (l_off, l_vars, v_off, values), see set_likelihoods."""
         q_off, e_off = _i64(q_off), _i64(e_off)
         q_vars, e_vars, e_codes = _i32(q_vars), _i32(e_vars), _i32(e_codes)
         B = len(q_off) - 1
@@ -281,13 +296,15 @@ class Engine:
         e_codes_ = e_codes if len(e_codes) else np.zeros(1, np.int32)
         q_vars_ = q_vars if len(q_vars) else np.zeros(1, np.int32)
         out_ = out if len(out) else np.zeros(1, np.float64)
+        if likelihoods is not None:
+            self.set_likelihoods(likelihoods)
         self._check(self._L.mibn_query_batch_ex(
             self._h, int(flags), B, _p(q_off, C.c_int64), _p(q_vars_, C.c_int32), _p(e_off, C.c_int64),
             _p(e_vars_, C.c_int32), _p(e_codes_, C.c_int32), _p(out_off, C.c_int64),
             _p(out_, C.c_double)))
         return out, out_off
 
-    def query_one(self, q, ev, codes, flags=0):
+    def query_one(self, q, ev, codes, flags=0, likelihoods=None):
         """One request (lists of variable ids / codes) -> dense posterior [cells].  The latency path of a single `query()`:
         preallocated ctypes arrays per request shape, one C call (query_fixed builds a dozen numpy arrays on the way)."""
         nq, ne = len(q), len(ev)
@@ -311,13 +328,15 @@ class Engine:
             ea[:ne] = ev
             ca[:ne] = codes
         out = np.zeros(max(1, cells), np.float64)
+        if likelihoods is not None:
+            self.set_likelihoods(likelihoods)
         rc = self._L.mibn_query_batch_ex(self._h, int(flags), 1, q_off, qa, e_off, ea, ca, out_off,
                                          out.ctypes.data_as(C.POINTER(C.c_double)))
         if rc != OK:
             self._check(rc)
         return out[:cells]
 
-    def query_fixed(self, qvars, evars, ecodes, flags=0):
+    def query_fixed(self, qvars, evars, ecodes, flags=0, likelihoods=None):
         """Fixed-shape batch: qvars[B, nq], evars[B, ne], ecodes[B, ne] -> posteriors[B, cells]
         (all requests must have the same query-table size).  nq = 0 (flags with Q_UNNORMALISED): one cell per request, P(e)."""
         if len(qvars) == 0:
@@ -330,12 +349,12 @@ class Engine:
         q_off = np.arange(B + 1, dtype=np.int64) * nq
         e_off = np.arange(B + 1, dtype=np.int64) * ne
         out, out_off = self.query_batch(q_off, qvars.reshape(-1), e_off, evars.reshape(-1),
-                                        ecodes.reshape(-1), flags=flags)
+                                        ecodes.reshape(-1), flags=flags, likelihoods=likelihoods)
         return out.reshape(B, -1) if B else out.reshape(0, 0)
 
-    def mpe_batch(self, e_off, e_vars, e_codes):
+    def mpe_batch(self, e_off, e_vars, e_codes, likelihoods=None):
         """CSR evidence -> (codes[B, n_vars] int32, log_p[B] float64): the most probable explanation of every request
-        (mibn_mpe_batch)."""
+        (mibn_mpe_batch).  likelihoods: as in query_batch."""
         n_vars = len(self.card)
         e_off = _i64(e_off)
         B = len(e_off) - 1
@@ -344,6 +363,8 @@ class Engine:
         log_p = np.empty(B, np.float64)
         if B == 0:
             return codes, log_p
+        if likelihoods is not None:
+            self.set_likelihoods(likelihoods)
         self._check(self._L.mibn_mpe_batch(self._h, B, _p(e_off, C.c_int64), _p(e_vars, C.c_int32), _p(e_codes, C.c_int32),
                                            _p(codes, C.c_int32), _p(log_p, C.c_double)))
         return codes, log_p
@@ -406,19 +427,19 @@ class Engine:
             _p(w, C.c_double) if w is not None and B else None, int(acc.size), _p(acc_, C.c_double), _p(p_out, C.c_double)))
         return p_out[:B]
 
-    def mpe(self, evars, ecodes):
+    def mpe(self, evars, ecodes, likelihoods=None):
         """Fixed-shape batch: evars[B, ne], ecodes[B, ne] -> (codes[B, n_vars], log_p[B]), like query_fixed."""
         evars = _i32(evars)
         B = len(evars)
         evars = evars.reshape(B, -1)
         ecodes = _i32(ecodes).reshape(B, -1)
         e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
-        return self.mpe_batch(e_off, evars.reshape(-1), ecodes.reshape(-1))
+        return self.mpe_batch(e_off, evars.reshape(-1), ecodes.reshape(-1), likelihoods=likelihoods)
 
-    def map_batch(self, m_off, m_vars, e_off, e_vars, e_codes, flags=0):
+    def map_batch(self, m_off, m_vars, e_off, e_vars, e_codes, flags=0, likelihoods=None):
         """CSR MAP variables + CSR evidence -> (codes[m_off[B] - m_off[0]] int32, log_p[B] float64): marginal MAP of every request
         (mibn_map_batch) - codes[m_off[b] - m_off[0] + k] is the code of m_vars[m_off[b] + k] in argmax_m sum_h P(m, h, e_b), log_p[b] the
-        log of that maximum.  flags: MAP_PRUNE."""
+        log of that maximum.  flags: MAP_PRUNE.  likelihoods: as in query_batch."""
         m_off, e_off = _i64(m_off), _i64(e_off)
         B = len(e_off) - 1
         if len(m_off) != B + 1:
@@ -429,20 +450,22 @@ class Engine:
         if B == 0:
             return codes, log_p
         pad32 = np.zeros(1, np.int32)
+        if likelihoods is not None:
+            self.set_likelihoods(likelihoods)
         self._check(self._L.mibn_map_batch(self._h, int(flags), B, _p(m_off, C.c_int64), _p(m_vars if len(m_vars) else pad32, C.c_int32),
                                            _p(e_off, C.c_int64), _p(e_vars if len(e_vars) else pad32, C.c_int32),
                                            _p(e_codes if len(e_codes) else pad32, C.c_int32), _p(codes if codes.size else pad32, C.c_int32),
                                            _p(log_p, C.c_double)))
         return codes, log_p
 
-    def map(self, mvars, evars, ecodes, flags=0):
+    def map(self, mvars, evars, ecodes, flags=0, likelihoods=None):
         """Fixed-shape batch: mvars[B, nm], evars[B, ne], ecodes[B, ne] -> (codes[B, nm], log_p[B]), like mpe."""
         mvars, evars, ecodes = _i32(mvars), _i32(evars), _i32(ecodes)
         B = len(mvars)
         nm, ne = (mvars.size // B, evars.size // B) if B else (0, 0)  # (either may be 0: no reshape(B, -1) of an empty array)
         m_off = np.arange(B + 1, dtype=np.int64) * nm
         e_off = np.arange(B + 1, dtype=np.int64) * ne
-        codes, log_p = self.map_batch(m_off, mvars.reshape(-1), e_off, evars.reshape(-1), ecodes.reshape(-1), flags=flags)
+        codes, log_p = self.map_batch(m_off, mvars.reshape(-1), e_off, evars.reshape(-1), ecodes.reshape(-1), flags=flags, likelihoods=likelihoods)
         return codes.reshape(B, nm), log_p
 
     def submit_fixed(self, qvars, evars, ecodes):

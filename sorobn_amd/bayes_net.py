@@ -294,19 +294,55 @@ class Backend:
             self._anc[v] = s
         return self._anc[v]
 
-    def encode(self, query, event):
+    def encode(self, query, event, findings=()):
         """names/labels -> (qvars, evars, ecodes); raises KeyError like the reference when a relevant
-        node is unknown or has no CPT."""
+        node is unknown or has no CPT.  `findings` (encode_likelihood): their variables are relevant too."""
         q = [self.var_id(n) for n in query]
         ev = [self.var_id(n) for n in event]
         codes = [self.flat.code_of(v, lab) for v, lab in zip(ev, event.values())]
         if self.flat.missing:
-            rel = set(q) | set(ev)
+            rel = set(q) | set(ev) | {v for v, _ in findings}
             for v in list(rel):
                 rel |= self._ancestors(v)
             for v in sorted(rel & self.flat.missing):
                 raise KeyError(self.flat.names[v])
         return q, ev, codes
+
+    # ---- likelihood findings (soft evidence) ------------------------------------------------------
+    def encode_likelihood(self, likelihood, event=()):
+        """{variable: mapping or Series label -> weight} -> [(variable id, float64 weights, one per state)].  A label of the domain
+        that is not named gets weight 0 ("X is a or b"); a label outside the domain raises ValueError, an unknown variable the
+        reference's KeyError(name), a variable that is also in `event` ValueError - as do weights that are negative or not finite."""
+        out = []
+        for name, lam in (likelihood or {}).items():
+            v = self.var_id(name)
+            if name in event:
+                raise ValueError("A likelihood variable cannot be part of the event")
+            w = np.zeros(int(self.flat.card[v]), np.float64)
+            for lab, x in lam.items():
+                c = self.flat.code_of(v, lab)
+                if c < 0:
+                    raise ValueError(f"{lab!r} is not a label of {name!r}")
+                x = float(x)
+                if not (0.0 <= x < np.inf):
+                    raise ValueError(f"the weights of a likelihood finding must be finite and non-negative ({name!r}: {x!r})")
+                w[c] = x
+            out.append((v, w))
+        return out
+
+    @staticmethod
+    def likelihood_block(per_request):
+        """The findings of a batch, one encode_likelihood list per request -> the CSR block (l_off, l_vars, v_off, values) of
+        `Engine.*(likelihoods=...)`, or None when no request has a finding."""
+        if not any(per_request):
+            return None
+        l_off = np.zeros(len(per_request) + 1, np.int64)
+        np.cumsum([len(fs) for fs in per_request], out=l_off[1:])
+        flat = [f for fs in per_request for f in fs]
+        v_off = np.zeros(len(flat) + 1, np.int64)
+        np.cumsum([len(w) for _, w in flat], out=v_off[1:])
+        return (l_off, np.array([v for v, _ in flat], np.int32), v_off,
+                np.concatenate([w for _, w in flat]) if flat else np.zeros(0, np.float64))
 
     # ---- result construction --------------------------------------------------------------------
     def posterior_series(self, query, dense):
@@ -371,8 +407,13 @@ class Backend:
         idx = pd.MultiIndex(levels=levels, codes=list(np.unravel_index(keep, shape)), names=names, verify_integrity=False)
         return pd.Series(dense[keep], index=idx, name=name)
 
-    def exact_query(self, query, event):
+    def exact_query(self, query, event, likelihood=None):
         """`query(*query, event=event)` of the exact path, finished: encode, ONE call into the library, the answer Series."""
+        if likelihood:
+            findings = self.encode_likelihood(likelihood, event)
+            q, ev, codes = self.encode(query, event, findings)
+            dense = self.engine.query_fixed([q], [ev], [codes], likelihoods=self.likelihood_block([findings]))[0]
+            return self.finished_series(query, dense)
         q, ev, codes = self.encode(query, event)
         one = getattr(self.engine, "query_one", None)
         dense = one(q, ev, codes) if one is not None else self.engine.query_fixed([q], [ev], [codes])[0]
@@ -465,6 +506,24 @@ class Backend:
         eng = self.engine
         if n == 0:
             return PosteriorBatch(self, [], np.zeros(0), np.zeros(1, np.int64))
+        if any(len(r) == 3 for r in requests):
+            # requests (query, event, likelihood): sub-batch by sub-batch through the blocking call, which takes the findings
+            queries, parts, cells = [], [], []
+            for a in range(0, n, sub_batch):
+                chunk = [(r[0], r[1], r[2] if len(r) == 3 else None) for r in requests[a:a + sub_batch]]
+                plain = checked([(q, e) for q, e, _ in chunk])
+                findings = [self.encode_likelihood(lam, e) for _, e, lam in chunk]
+                if self.flat.missing:
+                    for (q, e), fs in zip(plain, findings):
+                        self.encode(q, e, fs)
+                q_off, qv, e_off, evs, ecs = self.encode_many(plain)
+                out, out_off = eng.query_batch(q_off, qv, e_off, evs, ecs, likelihoods=self.likelihood_block(findings))
+                queries.extend(q for q, _ in plain)
+                parts.append(out)
+                cells.append(np.diff(np.asarray(out_off, np.int64)))
+            out_off = np.zeros(n + 1, np.int64)
+            np.cumsum(np.concatenate(cells), out=out_off[1:])
+            return PosteriorBatch(self, queries, np.concatenate(parts), out_off)
         if not (hasattr(eng, "submit_fixed") and n > sub_batch):
             requests = checked(requests)
             q_off, qv, e_off, evs, ecs = self.encode_many(requests)
@@ -864,14 +923,24 @@ class BayesNet:
             answer = answer.reorder_levels(sorted(answer.index.names))
         return answer.sort_index()
 
-    def query(self, *query, event: dict, algorithm="exact", n_iterations=100, n_chains=1) -> pd.Series:
+    def query(self, *query, event: dict, algorithm="exact", n_iterations=100, n_chains=1, likelihood: dict = None) -> pd.Series:
         """Answer a probabilistic query; same contract as the reference (bayes_net.py:796-875).
+
+        `likelihood` (an extension, algorithm "exact" only): likelihood findings - Pearl's virtual evidence, soft evidence - as
+        {variable: mapping or Series label -> weight}.  The joint is multiplied by the weight of every finding variable's state
+        before it is summed and normalised; a label that is not named weighs 0, so {"X": {"a": 1, "b": 1}} says "X is a or b".
+        A finding variable may be queried; it may not be part of `event`.  The reference computes the same on a network with an
+        extra binary child V of X, P(V = 1 | X = x) = weight(x) / max weight, observed at 1.
 
         `algorithm`: "exact" (variable elimination on the GPU), "gibbs" (GPU chains; `n_chains` is an
         extension, default 1 like the reference), "rejection" or "likelihood" (GPU forward sampling, one sample
         per lane); anything else raises the reference's ValueError.
         """
         self._check_request(query, event)
+        if likelihood is not None:
+            if algorithm != "exact":
+                raise ValueError("likelihood findings need algorithm='exact'")
+            return self.backend.exact_query(query, event, likelihood)
         if algorithm == "exact":
             # (the hook the reference's query() dispatches to, bayes_net.py:848, is honoured: not re-bound on this object - e.g. by
             # accelerate() - and not overridden by a subclass)
@@ -892,7 +961,9 @@ class BayesNet:
 
     def query_many(self, requests, sub_batch=32768):
         """Batched extension: `requests` = iterable of (query tuple, event dict) -> `PosteriorBatch`, a sequence whose item i is
-        the Series `query(*q_i, event=e_i)` returns (identical: name, index, level order, row order, values).  Names and labels are
+        the Series `query(*q_i, event=e_i)` returns (identical: name, index, level order, row order, values).  A request may be a
+        3-tuple (query tuple, event dict, likelihood dict or None), item i then `query(*q_i, event=e_i, likelihood=l_i)`; a batch
+        with such a request goes through blocking calls.  Names and labels are
         encoded in bulk, the device works through sub-batches with two calls in flight, and the Series are built on access;
         `.to_frame()` gives every answer as one pandas object."""
         return self.backend.exact_many(requests if isinstance(requests, list) else list(requests), sub_batch=sub_batch)
@@ -965,17 +1036,19 @@ class BayesNet:
             raise KeyError(be.flat.names[min(be.flat.missing)])
         return be
 
-    def mpe(self, event: dict = None, return_log_prob=False):
+    def mpe(self, event: dict = None, return_log_prob=False, likelihood: dict = None):
         """Most probable explanation: the single most probable completion of `event`, argmax_x P(x, event) over every variable
         not in `event`.  Returns a Series of labels indexed by every variable (sorted names); evidence variables keep their
         labels.  Zero-probability or out-of-domain evidence gives None for the other variables (and a log probability of
-        -inf).  With `return_log_prob`, returns (series, natural log of P(x*, event)).  Ties go to the lowest label code."""
+        -inf).  With `return_log_prob`, returns (series, natural log of P(x*, event)).  Ties go to the lowest label code.
+        `likelihood`: likelihood findings as in `query` - the maximum is over P(x, event) times the weights, and so is the log."""
         event = dict(event or {})
-        be = self._event_backend(event)
+        be = self._event_backend(list(event) + list(likelihood or {}))
         f = be.flat
         ev = [f.id[name] for name in event]
         codes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
-        out, log_p = be.engine.mpe(np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev)))
+        more = {"likelihoods": be.likelihood_block([be.encode_likelihood(likelihood, event)])} if likelihood else {}
+        out, log_p = be.engine.mpe(np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev)), **more)
         names = self._all_names()
         data = decode_labels(f, names, out, event)
         series = pd.Series([data[name][0] for name in names], index=pd.Index(names), dtype=object)
@@ -1020,23 +1093,27 @@ class BayesNet:
         none = np.zeros((1, 0), np.int32)
         return 0, float(be.engine.map(none, none, none, flags=0)[1][0])
 
-    def map_query(self, *variables, event: dict = None, return_log_prob=False):
+    def map_query(self, *variables, event: dict = None, return_log_prob=False, likelihood: dict = None):
         """Marginal MAP: the most probable joint assignment of `variables` given `event`, every other variable summed out -
         argmax_m sum_h P(m, h, event).  Unlike `mpe` it does not maximise over the variables the caller did not name, and unlike
         `query(*variables).idxmax()` it never builds the dense table over `variables`.  Returns a Series of labels indexed by
         `variables` in the order given; with `return_log_prob`, (series, natural log of max_m P(m, event) under the normalised
         joint).  Zero-probability or out-of-domain evidence gives None labels and -inf.  Ties go to the lowest label code.  The
         MAP variables that interact through the summed ones share a table on the device: a request whose table would reach 2^31
-        cells raises (inherent to marginal MAP)."""
+        cells raises (inherent to marginal MAP).  `likelihood`: likelihood findings as in `query`, multiplied into the joint before it
+        is summed and maximised; a MAP variable may carry one."""
         event = dict(event or {})
         be = self._map_backend(variables, event)
+        if likelihood:
+            self._event_backend(likelihood)  # (an unknown name: the reference's KeyError)
         f = be.flat
         mv = [f.id[name] for name in variables]
         ev = [f.id[name] for name in event]
         ecodes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
         flags, log_z = self._map_log_z(be)
+        more = {"likelihoods": be.likelihood_block([be.encode_likelihood(likelihood, event)])} if likelihood else {}
         codes, log_p = be.engine.map(np.array(mv, np.int32).reshape(1, len(mv)), np.array(ev, np.int32).reshape(1, len(ev)),
-                                     np.array(ecodes, np.int32).reshape(1, len(ev)), flags=flags)
+                                     np.array(ecodes, np.int32).reshape(1, len(ev)), flags=flags, **more)
         labels = [label_table(f, v)[codes[0, k]] for k, v in enumerate(mv)]
         series = pd.Series(labels, index=pd.Index(list(variables)), dtype=object)
         lp = float(log_p[0]) - log_z if np.isfinite(log_p[0]) else -np.inf

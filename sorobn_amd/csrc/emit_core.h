@@ -1113,6 +1113,8 @@ struct EmitScratch {
     // filled by emit_begin
     Bits rel, hidden;             // relevant = query | event | ancestors (bayes_net.py:763-765); hidden = relevant - query - event (766)
     int32_t n_pool = 0, n0 = 0;   // factors in the pool; n0 = the evidence-sliced CPTs (the first n0 of them)
+    int32_t n_seed = 0;           // likelihood findings: pool entries n0 .. n0 + n_seed, one-axis tables the engine writes into the arena
+    int64_t seed_cells = 0;       // the first cells of the request's arena, theirs for the whole program (padded to 16 each)
 };
 MIBN_HD inline int emit_pool_cap(int n_vars) { return 3 * n_vars + 64; }
 // bytes of one request's scratch behind a 16-byte aligned base (device: one slice per lane), and the carving of it
@@ -1156,8 +1158,13 @@ MIBN_HD inline void emit_or_ancestors(const EmitNet &net, Bits &b, int v) {
 
 // Relevant / hidden sets and the factors of a request = the evidence-sliced CPTs of the relevant nodes (bayes_net.py:768-776):
 // the evidence axis is not copied away but folded into the base offset.  Returns 0 or a kEmitErr*.
+// Likelihood findings (lvars[0 .. nl)): a finding variable and its ancestors are relevant like an evidence variable's,
+// but the variable stays free (hidden, unless it is a query variable).  Each finding is one more factor behind the CPTs' - scope {X},
+// or empty for a single-state X; stride 1 - at a SEED offset: arena-relative (no kConstFlag), the first cells of the request's arena
+// in the order given, each padded to 16 like every table.  The engine writes the weights there before level 0; the arena of the
+// emission starts above them (S.seed_cells) and never hands them out.
 MIBN_HD inline int emit_begin(const EmitNet &net, EmitScratch &S, int nq, const int32_t *qvars, int ne, const int32_t *evars,
-                              const int32_t *ecodes, bool no_prune) {
+                              const int32_t *ecodes, bool no_prune, int nl = 0, const int32_t *lvars = nullptr) {
     Bits &rel = S.rel, &hidden = S.hidden;
     Bits qb, eb;
     rel = Bits{};
@@ -1169,6 +1176,10 @@ MIBN_HD inline int emit_begin(const EmitNet &net, EmitScratch &S, int nq, const 
     for (int i = 0; i < ne; ++i) {
         eb.set(evars[i]); rel.set(evars[i]);
         emit_or_ancestors(net, rel, evars[i]);
+    }
+    for (int i = 0; i < nl; ++i) {
+        rel.set(lvars[i]);
+        emit_or_ancestors(net, rel, lvars[i]);
     }
     if (!net.prune || no_prune)  // full_joint_dist / predict_proba multiply *all* CPTs (bayes_net.py:460): with sparse or
         for (int v = 0; v < net.n_vars; ++v) rel.set(v);  // unnormalised CPTs a barren node does not sum to 1
@@ -1205,6 +1216,26 @@ MIBN_HD inline int emit_begin(const EmitNet &net, EmitScratch &S, int nq, const 
         f.cells = cells;
     });
     S.n0 = S.n_pool;
+    S.n_seed = 0;
+    S.seed_cells = 0;
+    for (int i = 0; i < nl && !err; ++i) {
+        if (S.n_pool >= S.pool_cap) { err = kEmitErrPool; break; }
+        const int x = lvars[i];
+        PF &f = S.pool[S.n_pool++];
+        pf_reset(f);
+        f.scope.nw = net.nw;
+        for (int k = 0; k < MIBN_BITS_WORDS(net.nw); ++k) f.scope.w[k] = 0;
+        if (net.card[x] > 1) {
+            f.scope.set(x);
+            f.vars[0] = x;
+            f.strides[0] = 1;
+            f.n = 1;
+        }
+        f.cells = net.card[x];
+        f.off = (uint64_t)S.seed_cells;
+        S.seed_cells += ((int64_t)net.card[x] + 15) & ~int64_t(15);
+        ++S.n_seed;
+    }
     // single-state variables carry no information: they are never axes, never eliminated
     const Bits h0 = hidden;
     h0.for_each([&](int v) { if (net.card[v] <= 1) hidden.clr(v); });
@@ -1219,6 +1250,7 @@ MIBN_HD inline int emit_run(const EmitNet &net, EmitScratch &S, EmitBuf &prog, E
     PF *pool = S.pool;
     S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });  // (only relevant variables are axes of anything)
     Emitter em{net, prog, st, Arena{}, S.key, S.pos, 0, rec};
+    em.arena.top = S.seed_cells;  // (the findings' seeds: never handed out, never released)
     for (int i = 0; i < n_best; ++i) S.key[best[i]] = (double)i;
     for (int i = 0; i < nq; ++i) S.key[qvars[i]] = 1e9 + i;
 
@@ -1261,7 +1293,7 @@ MIBN_HD inline int emit_run(const EmitNet &net, EmitScratch &S, EmitBuf &prog, E
         alive[idx >> 6] |= 1ull << (idx & 63);
         pool[idx].scope.for_each([&](int v) { mem[(size_t)v * sw + (idx >> 6)] |= 1ull << (idx & 63); });
     };
-    for (int idx = 0; idx < S.n0; ++idx) add_factor(idx);
+    for (int idx = 0; idx < S.n0 + S.n_seed; ++idx) add_factor(idx);
     MIBN_TICK(1)  // key / pos / slot sets
     // factors alive whose scope contains a (or b, if b >= 0), in slot order; f(idx) returns false to stop early
     auto each_with = [&](int a, int b, auto f) {

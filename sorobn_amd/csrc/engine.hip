@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <numeric>
@@ -33,6 +34,7 @@
 #include "draw_kernel.hip.h"
 #include "elim_kernel.hip.h"
 #include "expect_kernel.hip.h"
+#include "likelihood_kernel.hip.h"
 #include "wave_plan_kernel.hip.h"
 
 using namespace mibn;
@@ -186,21 +188,40 @@ constexpr int kLevelStreams = 4;
 // statistics slots: the classes of work (split_kinds: 0 .. kNumKernels - 1, kernel_name), then the kernels of mibn_query_batch as
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
-// steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together).  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together), and the two kernels of a call with likelihood
+// findings: the seeds of a planned wave, the tiny kernel's twin.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
 // beside the 288 GB of the device.  A single larger table (up to 2^28 cells) gets a sub-batch - and a buffer - of its own.
 constexpr int64_t kScoreCellBudget = int64_t(1) << 22;
+
+// Likelihood findings of a batch (mibn_set_likelihoods): the caller's CSR block, copied.
+struct Findings {
+    int64_t B = 0;
+    std::vector<int64_t> l_off, v_off;  // l_off[B + 1] over l_vars; v_off[n + 1] over values
+    std::vector<int32_t> l_vars;
+    std::vector<double> values;
+    bool any() const { return !l_vars.empty(); }
+};
+// The seeds of one chunk of such a call (likelihood_kernel.hip.h): the records of its requests - none for a request no program runs
+// for - and where each request's begin, host and device.  One per chunk set and one for run_elim: live until the chunk's last wave ran.
+struct ChunkSeeds {
+    std::vector<SeedRec> recs;
+    std::vector<uint32_t> first;  // [n + 1]: the records of request r of the chunk are recs[first[r] .. first[r + 1])
+    DevBuf<SeedRec> d_recs;
+    DevBuf<double> d_values;
+    PinnedBuf stage[2];
+};
 
 struct mibn_ctx {
     Network net;
@@ -260,6 +281,7 @@ struct mibn_ctx {
         BatchPlan plan;
         Schedule sched;
         std::vector<LaunchGroup> groups;  // the launches of `sched`
+        ChunkSeeds seeds;                 // a call with likelihood findings
         ~Set() {  // (ProgBuf is planner.h's, shared with the host tools: its backing is freed here)
             for (auto *v : {&bufs, &xbufs})
                 for (ProgBuf &b : *v) {
@@ -367,6 +389,7 @@ struct mibn_ctx {
         DevBuf<int32_t> d_codes;      // the decoded assignments of a chunk (MPE) / the rows of a draw launch
         DevBuf<DrawItem> d_draw_items;
         DevBuf<int64_t> d_m_off;      // (MAP) per request of a chunk: where its codes go in d_codes
+        ChunkSeeds seeds;             // a call with likelihood findings
         std::vector<Event> ev;
         ~Elim() { for (ProgBuf &b : bufs) b.release(); }
     } elim;
@@ -382,6 +405,11 @@ struct mibn_ctx {
         Event ev[2];
     } ex;
     bool expect = false;
+    // mibn_set_likelihoods: `staged` belongs to the next batch call, which takes it - `lh` points at it while that call runs - or refuses it;
+    // either way it is gone when the call returns
+    Findings staged;
+    bool has_staged = false;
+    const Findings *lh = nullptr;
     // mibn_dataset_create / mibn_score_families: code matrices resident on the device (id = index; a destroyed entry keeps its slot, so an
     // id is never handed out twice) and the buffers of a scoring call.  Nothing a query call reads; last-call statistics only.
     struct Dataset {
@@ -1402,15 +1430,20 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     if (q_off[0] != 0 || e_off[0] != 0) return 1;                    // (offsets relative to a larger array: plan)
     if (res_cells > (size_t)B * kTinyMaxQCells) return 1;
     int rc;
-    // one pinned staging buffer: [q_off | e_off | out_off | q_vars | e_vars | e_codes | bad | results (zero-copy calls only)]
+    // one pinned staging buffer: [q_off | e_off | out_off | q_vars | e_vars | e_codes | findings | bad | results (zero-copy calls only)]
+    // findings (a call with likelihood findings: tiny_lh_kernel): [l_off | v_off | values | l_vars]
     const size_t off_bytes = (size_t)(B + 1) * 8;
     const size_t req_bytes = (3 * off_bytes + (nq + 2 * ne) * 4 + 15) & ~(size_t)15;
+    const Findings *F = h->lh;
+    const size_t nl = F ? F->l_vars.size() : 0, nv = F ? F->values.size() : 0;
+    const size_t lh_bytes = F ? (off_bytes + (nl + 1) * 8 + nv * 8 + nl * 4 + 15) & ~(size_t)15 : 0;
+    if (F && (nv >= (size_t)0x7fffffff || tiny_lds_bytes((int32_t)h->net.pool.size(), h->tiny_meta_words, true) > 65536)) return 1;  // (plan)
     // A call of at most one wave of requests (a single query(): BASELINE config 1) is latency, not bandwidth: the kernel reads the
     // request arrays from - and writes the posteriors and the bad-request flag to - the pinned, device-mapped staging buffer
     // itself.  No H2D / D2H copy, no timing events: one launch and one stream synchronisation (round 4 spent two DMAs each way
     // and two event records around a kernel of a few microseconds).  stats.kernel_ms is 0 for such a call.
     const bool zero_copy = B <= kTinyZeroCopyRequests && h->tiny_zero_copy && !h->expect;  // (expect_kernel reads the results on the device)
-    const size_t bad_off = req_bytes, res_off = req_bytes + 16;
+    const size_t bad_off = req_bytes + lh_bytes, res_off = bad_off + 16;
     const size_t bytes = res_off + (zero_copy ? res_cells * 8 : 0) + 64;
     PinnedBuf &sg = h->tiny_stage;
     if ((rc = pinned(h, sg, bytes))) return rc;
@@ -1426,6 +1459,13 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     std::memcpy(pv, q_vars, nq * 4);
     if (ne) { std::memcpy(pv + nq * 4, e_vars, ne * 4); std::memcpy(pv + (nq + ne) * 4, e_codes, ne * 4); }
     const int32_t none = 0x7fffffff;
+    if (F) {
+        char *pl = p + req_bytes;
+        std::memcpy(pl, F->l_off.data(), off_bytes);
+        std::memcpy(pl + off_bytes, F->v_off.data(), (nl + 1) * 8);
+        std::memcpy(pl + off_bytes + (nl + 1) * 8, F->values.data(), nv * 8);
+        std::memcpy(pl + off_bytes + (nl + 1) * 8 + nv * 8, F->l_vars.data(), nl * 4);
+    }
     std::memcpy(p + bad_off, &none, 4);
     char *dbase = h->d_tiny_req;  // where the kernel finds the arrays
     if (zero_copy) {
@@ -1434,7 +1474,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
         dbase = static_cast<char *>(dp);
         std::memset(p + res_off, 0, res_cells * 8);
     } else {
-        HIP_TRY(h, hipMemcpyAsync(h->d_tiny_req, p, req_bytes + 16, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_tiny_req, p, bad_off + 16, hipMemcpyHostToDevice, h->stream));
     }
     TinyArgs A;
     A.pool = h->d_pool;
@@ -1452,13 +1492,20 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     A.pool_cells = (int32_t)h->net.pool.size();
     A.meta_words = h->tiny_meta_words;
     A.flags = (flags & ~kTinyFlagHostBad) | (zero_copy ? kTinyFlagHostBad : 0u);
-    const size_t lds = tiny_lds_bytes(A.pool_cells, A.meta_words);
+    if (F) {
+        const char *dl = dbase + req_bytes;
+        A.l_off = reinterpret_cast<const int64_t *>(dl);
+        A.v_off = reinterpret_cast<const int64_t *>(dl + off_bytes);
+        A.values = reinterpret_cast<const double *>(dl + off_bytes + (nl + 1) * 8);
+        A.l_vars = reinterpret_cast<const int32_t *>(dl + off_bytes + (nl + 1) * 8 + nv * 8);
+    }
+    const size_t lds = tiny_lds_bytes(A.pool_cells, A.meta_words, F != nullptr);
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((B + 63) / 64, (int64_t)h->n_cu * 16));
     mibn_ctx::Set &st = h->set[0];
     if ((rc = retire(h, st))) return rc;
     size_t e0 = 0, e1 = 0;
     if (!zero_copy && (rc = next_event(h, st, e0))) return rc;
-    hipLaunchKernelGGL(tiny_kernel, dim3(grid), dim3(64), lds, h->stream, A);
+    hipLaunchKernelGGL(F ? tiny_lh_kernel : tiny_kernel, dim3(grid), dim3(64), lds, h->stream, A);
     HIP_TRY(h, hipGetLastError());
     if (!zero_copy && (rc = next_event(h, st, e1))) return rc;
     int32_t bad = none;
@@ -1485,6 +1532,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
         rq.kind = (flags & MIBN_Q_UNNORMALISED) ? ProgramKind::Raw : ProgramKind::Sum;
+        if (F) { rq.nl = (int32_t)(F->l_off[(size_t)b + 1] - F->l_off[(size_t)b]); rq.lvars = F->l_vars.data() + F->l_off[(size_t)b]; }
         std::string why = validate_request(h->net, rq);
         if (why.empty()) why = "out_off does not match the query table size";
         h->err = "request " + std::to_string(b) + ": " + why;
@@ -1501,7 +1549,7 @@ int run_tiny(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const i
     h->total.alg_bytes += io_bytes;
     h->total.total_ms += h->stats.total_ms;
     h->total.d2h_ms += h->stats.d2h_ms;
-    book_stat(h, kStatTiny, 1, ms, io_bytes, grid, true, true);
+    book_stat(h, F ? kStatTinyLh : kStatTiny, 1, ms, io_bytes, grid, true, true);
     if (h->expect) {
         if ((rc = expect_run(h, h->d_results[0]))) return rc;
         h->stats.total_ms = now_ms() - t_start;
@@ -1549,6 +1597,53 @@ int upload_programs(mibn_ctx *h, uint32_t *d_prog, size_t base, const std::vecto
     return MIBN_OK;
 }
 
+// Likelihood findings (h->lh) of chunk [b0, b0 + n), planned into `ck`: the seed records of its requests and the chunk's packed weights
+// -> cs, host and device.  Request r's seeds are the first cells of its arena in the order of its findings, each padded to 16 - what
+// emit_begin gave them; a skipped request runs no program and gets no record.  Enqueued on `stream`, not waited for, out of cs.stage.
+int upload_chunk_seeds(mibn_ctx *h, ChunkSeeds &cs, const BatchPlan &ck, int64_t b0, int64_t n, const char *skip, hipStream_t stream) {
+    const Findings &F = *h->lh;
+    int rc;
+    cs.recs.clear();
+    cs.first.assign((size_t)n + 1, 0);
+    const int64_t v0 = F.v_off[(size_t)F.l_off[(size_t)b0]], v1 = F.v_off[(size_t)F.l_off[(size_t)(b0 + n)]];
+    if (v1 - v0 >= (int64_t(1) << 32) || n >= (int64_t(1) << 31)) { h->err = "likelihood findings: too many weights in one chunk"; return MIBN_E_LIMIT; }
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t b = b0 + r;
+        cs.first[(size_t)r] = (uint32_t)cs.recs.size();
+        if (skip && skip[b]) continue;
+        int64_t seed = 0;
+        for (int64_t k = F.l_off[(size_t)b]; k < F.l_off[(size_t)b + 1]; ++k) {
+            const int64_t cells = F.v_off[(size_t)k + 1] - F.v_off[(size_t)k];
+            cs.recs.push_back({(uint32_t)r, (uint32_t)seed, (uint32_t)(F.v_off[(size_t)k] - v0), (uint32_t)cells});
+            seed += (cells + 15) & ~int64_t(15);
+        }
+        if (seed > ck.arena_need[(size_t)r]) { h->err = "planner error: the seeds of request " + std::to_string(b) + " exceed its arena"; return MIBN_E_LIMIT; }
+    }
+    cs.first[(size_t)n] = (uint32_t)cs.recs.size();
+    if (cs.recs.empty()) return MIBN_OK;
+    if ((rc = ensure(h, cs.d_recs, cs.recs.size()))) return rc;
+    if ((rc = ensure(h, cs.d_values, (size_t)(v1 - v0)))) return rc;
+    const size_t rec_bytes = cs.recs.size() * sizeof(SeedRec), val_bytes = (size_t)(v1 - v0) * 8;
+    if ((rc = pinned(h, cs.stage[0], rec_bytes))) return rc;
+    if ((rc = pinned(h, cs.stage[1], val_bytes))) return rc;
+    std::memcpy(cs.stage[0].get(), cs.recs.data(), rec_bytes);
+    std::memcpy(cs.stage[1].get(), F.values.data() + v0, val_bytes);
+    HIP_TRY(h, hipMemcpyAsync(cs.d_recs, cs.stage[0].get(), rec_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(h, hipMemcpyAsync(cs.d_values, cs.stage[1].get(), val_bytes, hipMemcpyHostToDevice, stream));
+    return MIBN_OK;
+}
+
+// The seed launch of wave [r0, r1) of that chunk: *SA and its grid, or false - the wave has no finding.
+bool wave_seeds(const mibn_ctx *h, const ChunkSeeds &cs, int64_t r0, int64_t r1, double *arena, const uint64_t *d_arena_off, SeedArgs &SA, unsigned &grid, double &bytes) {
+    if (!h->lh || cs.first.size() <= (size_t)r1 || cs.first[(size_t)r1] == cs.first[(size_t)r0]) return false;
+    const uint32_t k0 = cs.first[(size_t)r0], k1 = cs.first[(size_t)r1];
+    SA = SeedArgs{cs.d_recs + k0, cs.d_values, arena, d_arena_off, k1 - k0, (uint32_t)r0};
+    grid = seed_grid(k1 - k0, h->n_cu);
+    bytes = 0;
+    for (uint32_t k = k0; k < k1; ++k) bytes += 16.0 * cs.recs[k].cells + sizeof(SeedRec);  // (weights in, seeds out, the record)
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------- the query driver
 // run_query: the driver behind mibn_query_batch, mibn_query_batch_ex, mibn_submit_batch and mibn_expect_batch - plan, upload and launch a
 // batch.  Synchronous (ticket == nullptr): waits and writes `out`.  Asynchronous: the results land in a pinned buffer, *ticket identifies
@@ -1581,6 +1676,7 @@ struct QueryRun {
     int64_t n_chunks = 0;
     double call_fixed_ms = 0;  // the host's side of this call besides planning (the share rule of wave_plan_kernel)
     double call_plan_ms = 0;   // the workers' planning of the host's shares and the waits for the device planner: what the call's time to the last launch is NOT fixed cost
+    bool host_only = false;    // MIBN_Q_UNNORMALISED or likelihood findings: planned by the host's workers - no device planner, no adaptive policy
 };
 
 // Stage: validation (bayes_net.py:840-845) and the out-of-domain-evidence short cut -> R.skip.  Nothing is enqueued.
@@ -1594,6 +1690,7 @@ int query_validate(QueryRun &R) {
         rq.ne = (int32_t)(R.e_off[b + 1] - R.e_off[b]);
         rq.evars = R.e_vars + R.e_off[b];
         rq.kind = R.raw ? ProgramKind::Raw : ProgramKind::Sum;
+        if (h->lh) { rq.nl = (int32_t)(h->lh->l_off[(size_t)b + 1] - h->lh->l_off[(size_t)b]); rq.lvars = h->lh->l_vars.data() + h->lh->l_off[(size_t)b]; }
         if (!request_is_valid(h->net, rq)) { h->err = "request " + std::to_string(b) + ": " + validate_request(h->net, rq); return MIBN_E_ARG; }
         int64_t cells = 1;
         for (int i = 0; i < rq.nq; ++i) cells *= h->net.card[rq.qvars[i]];
@@ -1601,7 +1698,8 @@ int query_validate(QueryRun &R) {
         if (evidence_outside_domain(h->net, rq, R.e_codes + R.e_off[b])) R.skip[(size_t)b] = 1;  // -> empty posterior
         // P(e) of empty evidence with pruning: the relevant set is empty and the program's FINAL step has no input - the empty
         // product, 1.0, which no kernel form computes: the host writes it after the download
-        if (R.raw && rq.nq == 0 && rq.ne == 0 && h->net.prune && !(R.flags & MIBN_Q_NOPRUNE)) R.skip[(size_t)b] = 2;
+        // (a finding makes its variable relevant: such a request has a program)
+        if (R.raw && rq.nq == 0 && rq.ne == 0 && rq.nl == 0 && h->net.prune && !(R.flags & MIBN_Q_NOPRUNE)) R.skip[(size_t)b] = 2;
     }
     return MIBN_OK;
 }
@@ -1636,16 +1734,16 @@ int query_setup(QueryRun &R) {
     // order_effort >= 1 (more candidate orders, the byte model's best two both emitted): the wave planner has it, order_kernel / emit_kernel do
     // not - where the wave planner does not cover the network the host plans (never two kinds of plans in one stream)
     bool effort_ok = true;
-    if (h->net.order_effort >= 1 && (h->gpu_emit || h->gpu_search) && !R.raw) {
+    if (h->net.order_effort >= 1 && (h->gpu_emit || h->gpu_search) && !R.host_only) {
         std::unique_ptr<WNet> probe(new WNet);
         effort_ok = h->wave_plan && h->net.wave_view(*probe);
     }
-    R.emit_on = !R.raw && h->gpu_emit && h->order_net_ok && h->emit_net_ok && effort_ok;
+    R.emit_on = !R.host_only && h->gpu_emit && h->order_net_ok && h->emit_net_ok && effort_ok;
     // A rank that needs the device planner has no planning time to spare - and on the device the second emission costs more GPU time than
     // the bytes it saves give back (a two-thread rank: 243 against 273 k queries/s, profiles/r06_bh_ab.log): its calls take the extra
     // candidates only, on the host's share and on the device's alike.  (Like minfill_above below: the search effort follows the load.)
     h->net.second_above = (R.emit_on && !h->second_on_device) ? 1e300 : h->pol.base_second_above;
-    R.search_on = !R.raw && !R.emit_on && h->gpu_search && h->order_net_ok && h->net.order_effort < 1;
+    R.search_on = !R.host_only && !R.emit_on && h->gpu_search && h->order_net_ok && h->net.order_effort < 1;
     // a short first chunk gets an idle GPU going while the host plans the first full-size one (first_chunk = 2: also when
     // an earlier asynchronous call still keeps the GPU busy; 0: never)
     for (auto &st : h->set) R.gpu_busy = R.gpu_busy || (st.busy && st.ev_used && hipEventQuery(st.ev[st.ev_used - 1]) == hipErrorNotReady);
@@ -1865,7 +1963,8 @@ int plan_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t b0, int64_t b1, bool &on_
     }
     if (on_device && !beyond.empty() && (rc = replan_beyond(R, st, b0, nd, beyond, on_device))) return rc;
     if (!on_device)
-        plan_batch(h->net, *h->pool, st.bufs, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), ck, no_prune, orders, order_len, -1, R.raw ? ProgramKind::Raw : ProgramKind::Sum);
+        plan_batch(h->net, *h->pool, st.bufs, b0, b1, R.q_off, R.q_vars, R.e_off, R.e_vars, R.e_codes, R.out_off, R.skip.data(), ck, no_prune, orders, order_len, -1, R.raw ? ProgramKind::Raw : ProgramKind::Sum,
+                   h->lh ? h->lh->l_off.data() : nullptr, h->lh ? h->lh->l_vars.data() : nullptr);
     if (on_device && h->gpu_emit == 2 && (rc = check_against_host(R, st, b0, b1))) return rc;
     if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
     for (auto &b : st.bufs)
@@ -1876,8 +1975,9 @@ int plan_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t b0, int64_t b1, bool &on_
 }
 
 // Stage: the programs the host planned and the program offsets of a chunk of n requests -> the set's device buffers.  Enqueued on the
-// copy stream on return, not waited for: the copies out of st.bufs and st.stage[0] (run_wave's `uploaded` event covers them).
-int upload_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t n, bool on_device, size_t prog_base) {
+// copy stream on return, not waited for: the copies out of st.bufs and st.stage[0] - and, for a call with likelihood findings, the
+// chunk's seed records and weights out of st.seeds.stage - (run_wave's `uploaded` event covers them).
+int upload_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t b0, int64_t n, bool on_device, size_t prog_base) {
     mibn_ctx *h = R.h;
     const BatchPlan &ck = st.plan;
     int rc;
@@ -1887,6 +1987,7 @@ int upload_chunk(QueryRun &R, mibn_ctx::Set &st, int64_t n, bool on_device, size
     const double t0 = now_ms();
     if ((rc = upload_programs(h, st.d_prog, prog_base, st.bufs, ck, h->copy_stream))) return rc;
     if ((rc = upload(h, st.stage[0], st.d_prog_off, ck.prog_off.data(), (size_t)n * 8))) return rc;
+    if (h->lh && (rc = upload_chunk_seeds(h, st.seeds, ck, b0, n, R.skip.data(), h->copy_stream))) return rc;
     h->stats.h2d_ms += now_ms() - t0;
     return MIBN_OK;
 }
@@ -2006,8 +2107,23 @@ int run_wave(QueryRun &R, mibn_ctx::Set &st, int lane, hipStream_t S, int64_t b0
     // (retire() books the GPU's busy time from them).
     size_t e_first = 0, e_last = 0;
     if ((rc = next_event(h, st, e_first, S))) return rc;
+    // likelihood findings: the seeds of the wave's requests, before any launch of its first level on any stream
+    size_t e_begin = e_first;
+    {
+        SeedArgs SA;
+        unsigned sgrid = 0;
+        double sbytes = 0;
+        if (wave_seeds(h, st.seeds, r0, r1, A.arena, st.d_arena_off, SA, sgrid, sbytes)) {
+            size_t e0 = 0;
+            if ((rc = next_event(h, st, e0, S))) return rc;
+            hipLaunchKernelGGL(likelihood_seed_kernel, dim3(sgrid), dim3(kSeedWG), 0, S, SA);
+            if ((rc = next_event(h, st, e_begin, S))) return rc;
+            st.timed.push_back({kStatSeed, e0, e_begin, sbytes, (double)sgrid, h->call_id});
+            n_wg += (double)sgrid;
+        }
+    }
     LevelStreams LS(h, st, lane, S);
-    if ((rc = LS.begin(e_first))) return rc;
+    if ((rc = LS.begin(e_begin))) return rc;
     // one launch per group of a level's classes of work: planner.h level_groups, kLevelKernels
     level_groups(sc, {h->split_kinds != 0, h->seg_kernel != 0, h->mfma_kernel != 0, h->sweep_dma != 0}, st.groups);
     for (const LaunchGroup &g : st.groups) {
@@ -2070,7 +2186,7 @@ int query_finish(QueryRun &R, double *out, int32_t *ticket) {
     //  the uploads and some 600 launches: counting validation and schedule alone - 7.7 ms of 20 - left a two-thread rank host-bound once order_effort 1
     //  made its planning dearer, profiles/r06_bi_share.log)
     if (R.call_plan_ms > 0) R.call_fixed_ms = std::max(R.call_fixed_ms, now_ms() - R.t_start - R.call_plan_ms);
-    if (!R.raw) h->pol.call_end(R.B, R.call_fixed_ms);
+    if (!R.host_only) h->pol.call_end(R.B, R.call_fixed_ms);
     if (h->trace) std::fprintf(stderr, "[mibn plan] call of %lld requests: %.2f ms to the last launch (plan %.2f, h2d %.2f)\n", (long long)R.B, now_ms() - R.t_start, h->stats.plan_ms, h->stats.h2d_ms);
     if (ticket) {
         mibn_ctx::Pending &pd = h->pend[R.slot];
@@ -2108,6 +2224,7 @@ int run_query(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const 
     if (!h || B < 0 || !q_off || !e_off || !out_off || (B && !out && !h->expect)) return MIBN_E_ARG;
     if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     QueryRun R{h, flags, (flags & MIBN_Q_UNNORMALISED) != 0, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, now_ms()};
+    R.host_only = R.raw || h->lh;
     ++h->call_id;
     h->search_ms = 0;
     h->emit_ms = 0;
@@ -2121,14 +2238,14 @@ int run_query(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const 
         const int rc_tiny = run_tiny(h, flags | (h->net.prune ? 0u : (uint32_t)MIBN_Q_NOPRUNE), B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, R.t_start);
         if (rc_tiny != 1) return rc_tiny;  // 1: a request does not fit the kernel (query table too large) - plan it
     }
-    // MIBN_Q_UNNORMALISED (P(q, e) / P(e) requests): planned by the host's workers with the options' base search effort - no device
-    // planner, no adaptive policy; the net's policy-tuned fields are restored on every exit
+    // MIBN_Q_UNNORMALISED (P(q, e) / P(e) requests) and calls with likelihood findings: planned by the host's workers with the options'
+    // base search effort - no device planner, no adaptive policy; the net's policy-tuned fields are restored on every exit
     struct NetEffort {
         Network *net = nullptr;
         double second_above = 0, minfill_above = 0;
         ~NetEffort() { if (net) { net->second_above = second_above; net->minfill_above = minfill_above; } }
     } keep_effort;
-    if (R.raw) {
+    if (R.host_only) {
         keep_effort.net = &h->net;
         keep_effort.second_above = h->net.second_above;
         keep_effort.minfill_above = h->net.minfill_above;
@@ -2139,7 +2256,7 @@ int run_query(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const 
     ensure_pool(h);
     if (h->trace) std::fprintf(stderr, "[mibn plan] validation of %lld requests %.2f ms\n", (long long)B, now_ms() - R.t_start);
     R.call_fixed_ms = now_ms() - R.t_start;
-    if (!R.raw) {  // the adaptive policy (plan_policy.h) turns gpu_emit, gpu_search and the network's minfill_above
+    if (!R.host_only) {  // the adaptive policy (plan_policy.h) turns gpu_emit, gpu_search and the network's minfill_above
         const PlanPolicy::Knobs k = h->pol.call_start(h->call_id, (int)h->pool->size(), h->total.plan_ms, h->total.kernel_ms, h->retired_requests, h->order_net_ok,
                                                       h->emit_net_ok, {h->gpu_emit, h->gpu_search, h->net.minfill_above});
         h->gpu_emit = k.gpu_emit;
@@ -2159,7 +2276,7 @@ int run_query(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const 
         bool on_device = false;
         size_t prog_base = 0;
         if ((rc = plan_chunk(R, st, b0, b1, on_device, prog_base))) return rc;
-        if ((rc = upload_chunk(R, st, n, on_device, prog_base))) return rc;
+        if ((rc = upload_chunk(R, st, b0, n, on_device, prog_base))) return rc;
         // waves: consecutive requests whose private arenas fit the scratch budget together
         // (a chunk that does not fit is cut into waves of about EQUAL scratch - ceil(total / budget) of them - not into full
         //  waves and a remainder: round 4 runs chunks of 52 429 requests = 224 GB, close to the budget)
@@ -2269,6 +2386,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
         rq.evars = e_vars + e_off[b];
         std::string e;
+        if (h->lh) { rq.nl = (int32_t)(h->lh->l_off[(size_t)b + 1] - h->lh->l_off[(size_t)b]); rq.lvars = h->lh->l_vars.data() + h->lh->l_off[(size_t)b]; }
         if constexpr (Payload::kKind == ProgramKind::Map) {  // (the MAP variables too: unknown ids, duplicates, a variable both in M and in E)
             rq.nq = (int32_t)(P.m_off[b + 1] - P.m_off[b]);
             rq.qvars = P.m_vars + P.m_off[b];
@@ -2304,7 +2422,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         double t0 = now_ms();
         BatchPlan &ck = M.plan;
         plan_batch(net, *h->pool, M.bufs, b0, b1, qo, qv, e_off, e_vars, e_codes, out_off.data(), skip.data(), ck, P.no_prune,
-                   nullptr, nullptr, -1, Payload::kKind);
+                   nullptr, nullptr, -1, Payload::kKind, h->lh ? h->lh->l_off.data() : nullptr, h->lh ? h->lh->l_vars.data() : nullptr);
         if (!ck.err.empty()) { h->err = ck.err; return MIBN_E_LIMIT; }
         h->stats.plan_ms += now_ms() - t0;
         t0 = now_ms();
@@ -2313,6 +2431,7 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
         if ((rc = ensure(h, M.d_m, (size_t)n))) return rc;
         if ((rc = upload_programs(h, M.d_prog, 0, M.bufs, ck, S))) return rc;
         HIP_TRY(h, hipMemcpyAsync(M.d_prog_off, ck.prog_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, S));
+        if (h->lh && (rc = upload_chunk_seeds(h, M.seeds, ck, b0, n, skip.data(), S))) return rc;
         if ((rc = P.prepare(R))) return rc;
         h->stats.h2d_ms += now_ms() - t0;
         // waves: consecutive requests whose arenas (intermediates + what the payload's programs keep) fit the budget together
@@ -2342,6 +2461,15 @@ int run_elim(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars
             A.arena = h->arena(0);
             A.results = M.d_m;  // (FINAL offsets are chunk-relative: the cell of request b at b - b0)
             A.items = M.d_items;
+            {   // likelihood findings: the seeds of the wave's requests, in stream order before its first level
+                SeedArgs SA;
+                unsigned sgrid = 0;
+                double sbytes = 0;
+                if (wave_seeds(h, M.seeds, r0, r1, A.arena, M.d_arena_off, SA, sgrid, sbytes)) {
+                    if ((rc = R.timed_launch(kStatSeed, sbytes, (double)sgrid, [&] { hipLaunchKernelGGL(likelihood_seed_kernel, dim3(sgrid), dim3(kSeedWG), 0, S, SA); }))) return rc;
+                    h->stats.n_workgroups += (double)sgrid;
+                }
+            }
             // one launch per level: every class of work of such a schedule (segments, GENERIC tiles) is the payload's level kernel's
             group_launches(sc, false, [](int) { return LevelRoute::Level; }, M.groups);
             for (const LaunchGroup &g : M.groups) {
@@ -2674,40 +2802,128 @@ int run_map_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, con
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------- likelihood findings
+// mibn_set_likelihoods stages a block for the NEXT batch call.  The calls that consume it (mibn_query_batch, mibn_query_batch_ex,
+// mibn_mpe_batch, mibn_map_batch) take it for their duration - h->lh, null for a block without a single finding: such a call is the call
+// without a block, bit for bit -; the others refuse it.  Either way it is gone when the call returns, whatever the call returns.
+namespace {
+void drop_findings(mibn_ctx *h) {
+    h->lh = nullptr;
+    h->has_staged = false;
+    h->staged = Findings{};
+}
+struct TakeFindings {
+    mibn_ctx *h;
+    explicit TakeFindings(mibn_ctx *h_) : h(h_) {}
+    ~TakeFindings() { if (h) drop_findings(h); }
+    int take(int64_t B) {
+        if (!h || !h->has_staged) return MIBN_OK;
+        if (h->staged.B != B) {
+            h->err = "likelihood findings were set for " + std::to_string(h->staged.B) + " requests, the call has " + std::to_string(B);
+            return MIBN_E_ARG;
+        }
+        if (h->staged.any()) h->lh = &h->staged;
+        return MIBN_OK;
+    }
+};
+int refuse_findings(mibn_ctx *h, int code, const char *call) {
+    if (!h || !h->has_staged) return MIBN_OK;
+    drop_findings(h);
+    h->err = std::string(call) + " does not take likelihood findings: the block of mibn_set_likelihoods was dropped";
+    return code;
+}
+}  // namespace
+
+extern "C" int mibn_set_likelihoods(mibn_t *h, int64_t B, const int64_t *l_off, const int32_t *l_vars, const int64_t *v_off, const double *values) {
+    if (!h) return MIBN_E_ARG;
+    drop_findings(h);
+    if (B < 0 || (B && !l_off)) { h->err = "likelihood findings: B < 0 or l_off missing"; return MIBN_E_ARG; }
+    if (int rc = check_state(h, kNeedNet)) return rc;
+    const Network &net = h->net;
+    Findings F;
+    F.B = B;
+    F.l_off.assign((size_t)B + 1, 0);
+    const int64_t base = B ? l_off[0] : 0;
+    for (int64_t b = 0; b < B; ++b) {
+        if (l_off[b + 1] < l_off[b]) { h->err = "request " + std::to_string(b) + ": l_off must be ascending"; return MIBN_E_ARG; }
+        F.l_off[(size_t)b + 1] = l_off[b + 1] - base;
+    }
+    const int64_t n = F.l_off[(size_t)B];
+    if (n && (!l_vars || !v_off || !values)) { h->err = "likelihood findings: l_vars, v_off or values missing"; return MIBN_E_ARG; }
+    F.l_vars.reserve((size_t)n);
+    F.v_off.assign((size_t)n + 1, 0);
+    std::vector<char> seen((size_t)net.n_vars, 0);
+    for (int64_t b = 0; b < B; ++b) {
+        const std::string where = "request " + std::to_string(b) + ": ";
+        for (int64_t k = F.l_off[(size_t)b]; k < F.l_off[(size_t)b + 1]; ++k) {
+            const int32_t v = l_vars[base + k];
+            if (v < 0 || v >= net.n_vars) { h->err = where + "unknown likelihood variable id " + std::to_string(v); return MIBN_E_ARG; }
+            if (seen[(size_t)v]) { h->err = where + "duplicate likelihood variable id " + std::to_string(v); return MIBN_E_ARG; }
+            seen[(size_t)v] = 1;
+            const int64_t v0 = v_off[base + k], v1 = v_off[base + k + 1];
+            if (v1 - v0 != net.card[v]) {
+                h->err = where + "the finding on variable " + std::to_string(v) + " has " + std::to_string(v1 - v0) + " weights, the variable " + std::to_string(net.card[v]) + " states";
+                return MIBN_E_ARG;
+            }
+            for (int64_t c = v0; c < v1; ++c) {
+                const double x = values[c];
+                if (!(x >= 0.0) || x > std::numeric_limits<double>::max()) { h->err = where + "the weights of a finding must be finite and non-negative (variable " + std::to_string(v) + ")"; return MIBN_E_ARG; }
+                F.values.push_back(x);
+            }
+            F.l_vars.push_back(v);
+            F.v_off[(size_t)k + 1] = (int64_t)F.values.size();
+        }
+        for (int64_t k = F.l_off[(size_t)b]; k < F.l_off[(size_t)b + 1]; ++k) seen[(size_t)l_vars[base + k]] = 0;
+    }
+    h->staged = std::move(F);
+    h->has_staged = true;
+    return MIBN_OK;
+}
+
 // (nothing of a blocking call may still run on the main stream when the caller sees its error)
 extern "C" int mibn_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t *codes,
                               double *log_p) {
+    TakeFindings lh(h);
+    if (int rc = lh.take(B)) return rc;
     return drained_on_error(h, run_mpe_body(h, B, e_off, e_vars, e_codes, codes, log_p), drain_main_unchecked);
 }
 
 extern "C" int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, const int32_t *m_vars, const int64_t *e_off,
                               const int32_t *e_vars, const int32_t *e_codes, int32_t *codes, double *log_p) {
+    TakeFindings lh(h);
+    if (int rc = lh.take(B)) return rc;
     return drained_on_error(h, run_map_body(h, flags, B, m_off, m_vars, e_off, e_vars, e_codes, codes, log_p), drain_main_unchecked);
 }
 
 extern "C" int mibn_posterior_sample_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                            const int64_t *s_off, uint64_t seed, uint32_t flags, int32_t *codes, double *p_e) {
+    if (int rc = refuse_findings(h, MIBN_E_ARG, "mibn_posterior_sample_batch")) return rc;
     return drained_on_error(h, run_draw_body(h, B, e_off, e_vars, e_codes, s_off, seed, flags, codes, p_e), drain_main_unchecked);
 }
 
 extern "C" int mibn_query_batch(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *q_vars,
                                 const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                 const int64_t *out_off, double *out) {
+    TakeFindings lh(h);
     if (h && check_state(h, kNeedIdle)) return MIBN_E_STATE;
+    if (int rc = lh.take(B)) return rc;
     return run_batch(h, 0, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, nullptr);
 }
 
 extern "C" int mibn_query_batch_ex(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars,
                                    const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                    const int64_t *out_off, double *out) {
+    TakeFindings lh(h);
     if (h && check_state(h, kNeedIdle)) return MIBN_E_STATE;
     if (flags & ~(uint32_t)(MIBN_Q_NOPRUNE | MIBN_Q_UNNORMALISED)) { if (h) h->err = "unknown query flag"; return MIBN_E_ARG; }
+    if (int rc = lh.take(B)) return rc;
     return run_batch(h, flags, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, nullptr);
 }
 
 extern "C" int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off,
                                  const int32_t *e_vars, const int32_t *e_codes, const int64_t *acc_base, const int64_t *acc_stride,
                                  const double *weight, int64_t n_acc, double *acc, double *p_out) {
+    if (int rc = refuse_findings(h, MIBN_E_STATE, "mibn_expect_batch")) return rc;
     if (!h || B < 0 || n_acc < 0 || !q_off || !e_off || (n_acc && !acc)) return MIBN_E_ARG;
     if (int rc = check_state(h, kNeedIdle)) return rc;
     if (flags & ~(uint32_t)(MIBN_Q_NOPRUNE | MIBN_Q_UNNORMALISED)) { h->err = "unknown query flag"; return MIBN_E_ARG; }
@@ -2755,6 +2971,7 @@ extern "C" int mibn_expect_batch(mibn_t *h, uint32_t flags, int64_t B, const int
 extern "C" int mibn_submit_batch(mibn_t *h, int64_t B, const int64_t *q_off, const int32_t *q_vars,
                                  const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                                  const int64_t *out_off, double *out, int32_t *ticket) {
+    if (int rc = refuse_findings(h, MIBN_E_STATE, "mibn_submit_batch")) return rc;
     if (!ticket) return MIBN_E_ARG;
     return run_batch(h, 0, B, q_off, q_vars, e_off, e_vars, e_codes, out_off, out, ticket);
 }

@@ -327,11 +327,13 @@ MIBN_HD inline bool order_greedy(const OrderNet &net, OrderScratch &S, const B2 
 
 // Relevant set, hidden set and the factor scopes (S.f / S.fc of the relevant variables) of one request.
 MIBN_HD inline void order_prepare(const OrderNet &net, OrderScratch &S, int nq, const int32_t *qvars, int ne, const int32_t *evars,
-                                  bool no_prune, B2 &rel, B2 &hidden) {
+                                  bool no_prune, B2 &rel, B2 &hidden, int nl = 0, const int32_t *lvars = nullptr) {
     B2 qb, eb;
     rel = B2{};
     for (int i = 0; i < nq; ++i) { const int v = qvars[i]; qb.set(v); rel.set(v); rel.a |= net.anc[v].a; rel.b |= net.anc[v].b; }
     for (int i = 0; i < ne; ++i) { const int v = evars[i]; eb.set(v); rel.set(v); rel.a |= net.anc[v].a; rel.b |= net.anc[v].b; }
+    // likelihood findings (emit_begin): relevant with their ancestors, but free - a one-axis factor adds no edge to the search
+    for (int i = 0; i < nl; ++i) { const int v = lvars[i]; rel.set(v); rel.a |= net.anc[v].a; rel.b |= net.anc[v].b; }
     if (!net.prune || no_prune)
         for (int v = 0; v < net.n_vars; ++v) rel.set(v);
     hidden.a = rel.a & ~qb.a & ~eb.a;
@@ -374,9 +376,9 @@ MIBN_HD inline void order_sweep(const OrderNet &net, OrderScratch &S, const B2 &
 // modelled cost of that order (infinity when nothing is hidden).  net.effort >= 1: more candidates, and the runner-up in S.second /
 // S.n_second (0: none) with S.best_cost / S.second_cost.
 MIBN_HD inline double order_search(const OrderNet &net, OrderScratch &S, int nq, const int32_t *qvars, int ne, const int32_t *evars,
-                                   bool no_prune) {
+                                   bool no_prune, int nl = 0, const int32_t *lvars = nullptr) {
     B2 rel, hidden;
-    order_prepare(net, S, nq, qvars, ne, evars, no_prune, rel, hidden);
+    order_prepare(net, S, nq, qvars, ne, evars, no_prune, rel, hidden, nl, lvars);
     S.n_best = 0;
     S.n_second = 0;
     S.n_greedy = 0;

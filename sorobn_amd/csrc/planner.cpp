@@ -285,6 +285,21 @@ void Network::set_hints(int32_t n_hints, const int32_t *priorities) {
         }
 }
 
+// "" or what is wrong with the likelihood findings of a request: an unknown id, a variable named twice, a variable that is also evidence
+static std::string validate_findings(const Network &net, const Request &rq) {
+    Bits ev, lh;
+    for (int i = 0; i < rq.ne; ++i)
+        if (rq.evars[i] >= 0 && rq.evars[i] < net.n_vars) ev.set(rq.evars[i]);
+    for (int i = 0; i < rq.nl; ++i) {
+        const int v = rq.lvars[i];
+        if (v < 0 || v >= net.n_vars) return "unknown likelihood variable id " + std::to_string(v);
+        if (lh.test(v)) return "duplicate likelihood variable id " + std::to_string(v);
+        if (ev.test(v)) return "A likelihood variable cannot be part of the event";
+        lh.set(v);
+    }
+    return "";
+}
+
 bool request_is_valid(const Network &net, const Request &rq) {
     if (rq.nq < (allows_no_query(rq.kind) ? 0 : 1)) return false;
     uint64_t seen[kWords];  // (only the words the network uses: a batch validates 100 k requests on one thread)
@@ -296,7 +311,7 @@ bool request_is_valid(const Network &net, const Request &rq) {
         if (seen[v >> 6] & bit) return false;
         seen[v >> 6] |= bit;
     }
-    return true;
+    return rq.nl == 0 || validate_findings(net, rq).empty();
 }
 
 std::string validate_mpe_request(const Network &net, const Request &rq) {
@@ -307,7 +322,7 @@ std::string validate_mpe_request(const Network &net, const Request &rq) {
         if (ev.test(v)) return "duplicate evidence variable id " + std::to_string(v);
         ev.set(v);
     }
-    return "";
+    return validate_findings(net, rq);
 }
 
 std::string validate_request(const Network &net, const Request &rq) {
@@ -328,7 +343,7 @@ std::string validate_request(const Network &net, const Request &rq) {
         if (ev.test(v)) return "duplicate evidence variable id " + std::to_string(v);
         ev.set(v);
     }
-    return "";
+    return validate_findings(net, rq);
 }
 
 // ------------------------------------------------------------------------------------ orders
@@ -603,11 +618,12 @@ struct StepEmitter {
                 const int32_t *order2 = nullptr, int n_order2 = 0)
         : en(generic_only(en_sum)), S(S_), prog(prog_), st(st_), em{en, prog, st, Arena{}, S.key, S.pos, 0, nullptr}, keep(keep_),
           count_pos(prog.size), steps0(st.n_steps), alive((size_t)S.pool_cap, 0), ins(S.ins) {
+        em.arena.top = S.seed_cells;  // (the findings' seeds: never handed out, never released)
         S.rel.for_each([&](int v) { S.key[v] = 0.0; S.pos[v] = -1; });
         for (int i = 0; i < n_order; ++i) S.key[order[i]] = (double)i;
         for (int i = 0; i < n_order2; ++i) S.key[order2[i]] = (double)(n_order + i);
         prog.push(0);
-        for (int idx = 0; idx < S.n0; ++idx) alive[(size_t)idx] = 1;
+        for (int idx = 0; idx < S.n0 + S.n_seed; ++idx) alive[(size_t)idx] = 1;
     }
     // a fresh pool entry for a step's output, or null (em.err set)
     PF *new_output() {
@@ -879,7 +895,7 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
     // (a map program's query set is M: relevant = M | event | ancestors, hidden = what the sum phase eliminates)
     const int nq = takes_query(rq.kind) ? rq.nq : 0;
     const bool no_prune = never_prunes(rq.kind) || rq.no_prune;
-    if (int e = emit_begin(en, ES, nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, no_prune)) return emit_error_message(e);
+    if (int e = emit_begin(en, ES, nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, no_prune, rq.nl, rq.lvars)) return emit_error_message(e);
     const Bits &hidden = ES.hidden;
 
     // candidate elimination orders, cheapest by the byte model wins
@@ -895,7 +911,7 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
         OrderScratch &OS = order_scratch();
         OrderNet on = net.order_view();
         if (step_wise(rq.kind)) on.chain_weight = 1.0;  // (plain section-8(d) bytes: the class weights price forms these programs do not use)
-        order_search(on, OS, nq, rq.qvars, rq.ne, rq.evars, no_prune);
+        order_search(on, OS, nq, rq.qvars, rq.ne, rq.evars, no_prune, rq.nl, rq.lvars);
         best.assign(OS.best, OS.best + OS.n_best);
         if (!step_wise(rq.kind) && net.order_effort >= 1 && OS.n_second > 0 && OS.best_cost >= net.second_above) second.assign(OS.second, OS.second + OS.n_second);
     } else if (hidden.any()) {
@@ -989,7 +1005,7 @@ static std::string plan_request_rec(const Network &net, const Request &rq, ProgB
         prog.size = start_words;
         eb.data = prog.data; eb.size = prog.size; eb.cap = prog.cap;
         es = es0;
-        int e2 = emit_begin(en, ES, rq.nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, rq.no_prune);
+        int e2 = emit_begin(en, ES, rq.nq, rq.qvars, rq.ne, rq.evars, rq.ecodes, rq.no_prune, rq.nl, rq.lvars);
         if (!e2) e2 = emit_run(en, ES, eb, es, rec, rq.nq, rq.qvars, rq.out_off, second.data(), (int)second.size() MIBN_PROF_PASS);
         if (e2 || !(es.alg_bytes - es0.alg_bytes < es_first.alg_bytes - es0.alg_bytes)) {
             prog.size = start_words;
@@ -1285,7 +1301,8 @@ PlanCache &plan_cache(const TemplateStore *ts) {
 void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs, int64_t b0, int64_t b1,
                 const int64_t *q_off, const int32_t *q_vars, const int64_t *e_off, const int32_t *e_vars,
                 const int32_t *e_codes, const int64_t *out_off, const char *skip, BatchPlan &ck, bool no_prune,
-                const uint8_t *orders, const int32_t *order_len, int64_t out_first, ProgramKind kind) {
+                const uint8_t *orders, const int32_t *order_len, int64_t out_first, ProgramKind kind, const int64_t *l_off,
+                const int32_t *l_vars) {
     const int64_t n = b1 - b0;
     const int T = pool.size();
     if ((int)bufs.size() < T) bufs.resize(T);
@@ -1305,7 +1322,8 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
     std::vector<std::string> terr(T);
     // dynamic distribution in blocks of 32 requests: request costs vary 100x and a worker may lose its core to
     // another rank's planner, a static split would wait for the slowest worker
-    TemplateStore *store = (net.plan_cache && may_use_templates(kind)) ? template_store(net) : nullptr;
+    // (a template's key is the query and evidence sets: a call with likelihood findings plans every request)
+    TemplateStore *store = (net.plan_cache && may_use_templates(kind) && !l_off) ? template_store(net) : nullptr;
     std::atomic<int64_t> next{0};
     constexpr int64_t kBlock = 32;
     const EmitNet en = net.emit_view();
@@ -1338,6 +1356,7 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
             rq.no_prune = no_prune;
             rq.kind = kind;
             if (orders) { rq.order = orders + (size_t)i * 128; rq.n_order = order_len[i]; }
+            if (l_off) { rq.nl = (int32_t)(l_off[b + 1] - l_off[b]); rq.lvars = l_vars + l_off[b]; }
             PlanStats st;
             // plan templates (see above): probe at the start of every window, stay on while shapes repeat
             PlanCache *pc = store ? &plan_cache(store) : nullptr;

@@ -107,11 +107,13 @@ struct Request {
     bool no_prune = false;            // MIBN_Q_NOPRUNE: every CPT takes part (full_joint_dist / predict_proba, bayes_net.py:460)
     const uint8_t *order = nullptr;   // elimination order found elsewhere (the device order search), n_order entries
     int32_t n_order = -1;             // -1: search on the host
+    int32_t nl = 0;                   // likelihood findings: one non-negative weight per state of lvars[k], multiplied into the joint.  The
+    const int32_t *lvars = nullptr;   // planner needs the variables only - the weights reach the arena as seeds (emit_begin)
 };
 
 struct PlanStats {
     double alg_bytes = 0, alg_flops = 0, n_steps = 0, max_step_cells = 0;
-    int64_t arena_cells = 0;  // scratch cells this request needs in its arena slot
+    int64_t arena_cells = 0;  // scratch cells this request needs in its arena slot (the seeds of its likelihood findings included)
     int64_t out_cells = 0;
     int64_t argmax_cells = 0;  // max programs: arena cells (doubles) of the argmax tables, included in arena_cells
     int64_t kept_cells = 0;    // draw programs: arena cells of the intermediates, none of them released (= arena_cells of the request)
@@ -207,6 +209,11 @@ struct PlanStats {
 //          per elimination step, last eliminated first:  argmax off lo, off hi, x, n_out, (output variable, stride) x n_out
 //      x* = argmax[sum_v code[v] * stride_v]: every output variable of a step is eliminated later, so the reverse walk has
 //      already decoded it.  A request whose evidence code lies outside its domain is the program "0" + a record with n_rec = 0.
+//
+//   LIKELIHOOD FINDINGS (Request::nl, any kind): finding k is one more initial factor, a one-axis table over lvars[k] (a scalar for a
+//      single-state variable) whose in_off is a SEED offset: arena-relative like every intermediate, but written before level 0 by
+//      likelihood_seed_kernel, not by a step.  Seeds are the first cells of the request's arena, in the order of the findings, each
+//      padded to 16 cells; no step's output ever overlaps them.  A request without findings plans word for word as without the fields.
 //
 //   UNNORMALISED requests (ProgramKind::Raw, MIBN_Q_UNNORMALISED): the program of the same request without the flag, word for word,
 //      except that its FINAL step - always the last step, always GENERIC - carries
@@ -307,8 +314,10 @@ void plan_batch(const Network &net, ThreadPool &pool, std::vector<ProgBuf> &bufs
                 const uint8_t *orders = nullptr, const int32_t *order_len = nullptr,  // orders[(b - b0) * 128 ..]: device order search
                 int64_t out_first = -1,   // result offsets relative to out_off[out_first] (default: b0) - the host's share of a chunk whose
                                           // first requests the device plans
-                ProgramKind kind = ProgramKind::Sum);  // Max, Draw: q_off all zero; Map: q_off / q_vars = the MAP variables; plan templates
-                                                       // for Sum only
+                ProgramKind kind = ProgramKind::Sum,  // Max, Draw: q_off all zero; Map: q_off / q_vars = the MAP variables; plan templates
+                                                      // for Sum only
+                const int64_t *l_off = nullptr, const int32_t *l_vars = nullptr);  // likelihood findings of request b: l_vars[l_off[b] ..
+                                                                                   // l_off[b + 1]); such a call uses no plan templates
 
 // Shard-balancing estimate (mibn_estimate_costs): section-8(d) bytes of the cheaper of the two sweep orders of every
 // request of a CSR batch - the byte model only, nothing is emitted.
@@ -392,7 +401,7 @@ void group_launches(const Schedule &sc, bool each_alone, RouteOf &&route, std::v
 void level_groups(const Schedule &sc, const LevelRouteOpts &o, std::vector<LaunchGroup> &out);
 
 // Validate a request (unknown ids, duplicates, overlap) - bayes_net.py:840-845 and the KeyError of 770.  nq = 0 is valid only with
-// ProgramKind::Raw or ProgramKind::Map.
+// ProgramKind::Raw or ProgramKind::Map.  Likelihood findings: unknown ids, a variable named twice, a variable that is also evidence.
 std::string validate_request(const Network &net, const Request &rq);  // "" or the reference's error message
 bool request_is_valid(const Network &net, const Request &rq);          // the same checks without building a message
 std::string validate_mpe_request(const Network &net, const Request &rq);  // evidence only (unknown ids, duplicates): "" or the message

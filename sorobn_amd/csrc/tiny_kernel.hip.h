@@ -16,6 +16,10 @@
 //   * normalises (790) and writes the dense posterior; zero-probability or out-of-domain evidence gives all zeros
 //     (the reference's empty Series).  MIBN_Q_UNNORMALISED: no normalisation - P(q, e) - and no query variable is allowed: one
 //     cell, P(e) (an empty relevant set is the empty product, 1).
+// Likelihood findings: tiny_lh_kernel is the same body with the compile-time flag LH on.  The lane decodes its
+// findings like its evidence (unknown id, a variable named twice or also observed, a weight vector of the wrong length: malformed),
+// adds them and their ancestors to the relevant set and multiplies lambda_X[state] into the prefix product at X's position; the weights
+// are read from global memory - a few cached doubles per request.  tiny_kernel is the flag-off instantiation: the code it always was.
 // Lanes of a wave run different loop counts (divergence), which is irrelevant next to the host work this removes: the
 // whole 100 k-request Asia batch is microseconds of kernel time.  Not HBM-bound: roofline n/a.
 #pragma once
@@ -59,9 +63,15 @@ struct TinyArgs {
     int64_t B;
     int32_t n_vars, pool_cells, meta_words;
     uint32_t flags;
+    // tiny_lh_kernel only: the findings of request b are l_vars[l_off[b] .. l_off[b + 1]); finding k has the weights
+    // values[v_off[k] .. v_off[k + 1]), one per state of l_vars[k]
+    const int64_t *l_off = nullptr, *v_off = nullptr;
+    const int32_t *l_vars = nullptr;
+    const double *values = nullptr;
 };
 
-__global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
+template <bool LH>
+__device__ __forceinline__ void tiny_body(const TinyArgs &A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tiny_smem[];
     const int lane = threadIdx.x;
     const int n = A.n_vars;
@@ -70,6 +80,7 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
     int32_t *meta = reinterpret_cast<int32_t *>(P + (kTinyMaxVars + 1) * 64);
     uint8_t *st = reinterpret_cast<uint8_t *>(meta + A.meta_words);        // [n][64] current code of every variable
     uint8_t *seq = st + kTinyMaxVars * 64;                                  // [n][64] relevant variables in topological order
+    int32_t *lho = reinterpret_cast<int32_t *>(seq + kTinyMaxVars * 64);    // LH: [n][64] where the weights of a finding variable start
     for (int i = lane; i < A.pool_cells; i += 64) lpool[i] = A.pool[i];
     for (int i = lane; i < A.meta_words; i += 64) meta[i] = A.meta[i];
     __syncthreads();
@@ -81,7 +92,7 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
         const int64_t q0 = A.q_off[b], q1 = A.q_off[b + 1], e0 = A.e_off[b], e1 = A.e_off[b + 1];
         double *out = A.out + (A.out_off[b] - out0);
         const int qcells = (int)(A.out_off[b + 1] - A.out_off[b]);
-        uint32_t qmask = 0, emask = 0, rel = 0;
+        uint32_t qmask = 0, emask = 0, rel = 0, lmask = 0;
         bool valid = true, malformed = q1 <= q0 && !(A.flags & MIBN_Q_UNNORMALISED);  // (P(e): no query variable, one cell)
         int64_t want_cells = 1;
         for (int64_t i = q0; i < q1 && !malformed; ++i) {
@@ -99,6 +110,15 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
             if (c < 0 || c >= card[v]) valid = false;  // label outside the domain: empty posterior
             else st[v * 64 + lane] = (uint8_t)c;
         }
+        if (LH) {
+            for (int64_t i = A.l_off[b]; i < A.l_off[b + 1] && !malformed; ++i) {
+                const int v = A.l_vars[i];
+                if (v < 0 || v >= n || (((emask | lmask) >> v) & 1u) || A.v_off[i + 1] - A.v_off[i] != (int64_t)card[v]) { malformed = true; break; }
+                lmask |= 1u << v;
+                rel |= anc[v];
+                lho[v * 64 + lane] = (int32_t)A.v_off[i];
+            }
+        }
         if (malformed || want_cells != (int64_t)qcells) {
             if (A.flags & kTinyFlagHostBad) {
                 // zero-copy call (engine.hip run_tiny): one wave, request b = lane, `bad` in pinned host memory - no atomic minimum
@@ -110,7 +130,7 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
             }
             continue;
         }
-        rel |= qmask | emask;
+        rel |= qmask | emask | lmask;
         if (A.flags & MIBN_Q_NOPRUNE) rel = n >= 32 ? 0xffffffffu : ((1u << n) - 1u);
         if (!valid) {
             for (int c = 0; c < qcells; ++c) out[c] = 0.0;
@@ -141,7 +161,9 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
                     const int v = seq[i * 64 + lane];
                     int off = pool_off[v];
                     for (int k = scope_begin[v]; k < scope_begin[v + 1]; ++k) off += (int)st[scope[2 * k] * 64 + lane] * scope[2 * k + 1];
-                    P[(i + 1) * 64 + lane] = P[i * 64 + lane] * lpool[off];
+                    double t = lpool[off];
+                    if (LH && ((lmask >> v) & 1u)) t *= A.values[lho[v * 64 + lane] + (int)st[v * 64 + lane]];
+                    P[(i + 1) * 64 + lane] = P[i * 64 + lane] * t;
                 }
                 acc += P[ns * 64 + lane];
                 int j = ns - 1;  // next hidden state: increment the last hidden variable that can still grow
@@ -163,6 +185,9 @@ __global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) {
     }
 }
 
+__global__ __launch_bounds__(64) void tiny_kernel(const TinyArgs A) { tiny_body<false>(A); }
+__global__ __launch_bounds__(64) void tiny_lh_kernel(const TinyArgs A) { tiny_body<true>(A); }
+
 // Device-side description of the network for tiny_kernel, built once per set_network.
 inline std::vector<int32_t> tiny_meta(const Network &net) {
     const int n = net.n_vars;
@@ -179,8 +204,9 @@ inline std::vector<int32_t> tiny_meta(const Network &net) {
     return m;
 }
 
-inline size_t tiny_lds_bytes(int pool_cells, int meta_words) {
-    return (size_t)pool_cells * 8 + (size_t)(kTinyMaxVars + 1) * 64 * 8 + (size_t)meta_words * 4 + 2 * (size_t)kTinyMaxVars * 64;
+inline size_t tiny_lds_bytes(int pool_cells, int meta_words, bool lh = false) {
+    return (size_t)pool_cells * 8 + (size_t)(kTinyMaxVars + 1) * 64 * 8 + (size_t)meta_words * 4 + 2 * (size_t)kTinyMaxVars * 64 +
+           (lh ? (size_t)kTinyMaxVars * 64 * 4 : 0);
 }
 
 }  // namespace mibn

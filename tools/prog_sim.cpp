@@ -12,6 +12,12 @@
 //   decides which of two equal maxima a traceback meets first); --ties (max, map): one line per planned request on standard
 //   error, "ties <request> <cells> <on_path>" - the output cells of MAX steps whose maximum two or more x attain with bitwise equal
 //   positive products, and how many of them the traceback reads.
+//   --lh FILE (max, map, ev run): likelihood findings (planner.h), whitespace-separated - per request of the
+//   input, in order: its number of findings, then for each the variable id and one weight per state of it (any strtod format).  The
+//   request formats on standard input do not change.  The interpreter writes the seeds into its NaN-filled arena before the first
+//   step, where emit_begin put them - a seed read at a wrong offset is a NaN in the result - and fails a request whose step writes
+//   its output or its argmax table over a seed; the seeds are intermediates written "before step 0" in the liveness checks.
+//   --dump: one line per planned request on standard error, "prog <request> <arena_cells> <seed_cells> <word> ..": the program.
 //
 // (-ffp-contract=off: `draw` is the CPU twin of the draw kernel - same programs, same Philox4x32-10 stream, same arithmetic.)
 // tools/max_sim.cpp, map_sim.cpp, draw_sim.cpp and ev_sim.cpp are three lines each: this file with the kind fixed (PROG_SIM_KIND),
@@ -120,6 +126,8 @@ enum class Kind { Max, Map, Draw, Ev };
 struct Query {
     bool no_prune = false;
     std::vector<int32_t> qv, ev, ec;
+    std::vector<int32_t> lv;              // --lh: the finding variables of the request
+    std::vector<std::vector<double>> lw;  // ... and their weights
     int64_t n_samples = 0;
     uint64_t g_first = 0;
 
@@ -144,6 +152,8 @@ struct Query {
         rq.ecodes = ec.data();
         rq.kind = kind;
         rq.no_prune = no_prune;
+        rq.nl = (int32_t)lv.size();
+        rq.lvars = lv.data();
         return rq;
     }
     // (the engine skips such a request: zero probability)
@@ -213,6 +223,8 @@ struct GenericStep {
     }
 };
 
+static bool g_dump = false;
+
 // A planned request and what running it leaves behind.
 struct Run {
     int64_t b;
@@ -225,11 +237,24 @@ struct Run {
     struct Argmax { int64_t off, cells; int step, cx; std::vector<char> tie; };
     std::vector<Argmax> am;      // the argmax tables (off, cells in doubles) of the MAX steps, in step order; tie[o]: two or more x attain the (positive) maximum of cell o
     int64_t tie_cells = 0, tie_on_path = 0;  // cells with tie set over all MAX steps; those of them a traceback read (--ties)
+    int64_t seed_cells = 0;      // the first cells of the arena: the seeds of the request's findings, each padded to 16
 
-    Run(const Network &net, int64_t b_, const Request &rq) : b(b_) {
+    Run(const Network &net, int64_t b_, const Request &rq, const Query &q) : b(b_) {
         const std::string pe = plan_request(net, rq, prog, st);
         if (!pe.empty()) fail(b, pe);
         arena.assign((size_t)std::max<int64_t>(16, st.arena_cells), std::nan(""));
+        for (const std::vector<double> &w : q.lw) {  // what likelihood_seed_kernel writes before level 0
+            const int64_t cells = (int64_t)w.size();
+            if (seed_cells + cells > st.arena_cells) fail(b, "the seeds do not fit arena_cells " + std::to_string(st.arena_cells));
+            for (int64_t c = 0; c < cells; ++c) arena[(size_t)(seed_cells + c)] = w[(size_t)c];
+            tabs.push_back({seed_cells, cells, -1, -1});
+            seed_cells += (cells + 15) & ~int64_t(15);
+        }
+        if (g_dump) {
+            std::fprintf(stderr, "prog %lld %lld %lld", (long long)b, (long long)st.arena_cells, (long long)seed_cells);
+            for (uint32_t w : prog) std::fprintf(stderr, " %x", w);
+            std::fprintf(stderr, "\n");
+        }
     }
     uint32_t n_steps() const { return prog[0]; }
     const uint32_t *record() const { return prog.data() + record_offset(prog.data()); }
@@ -264,7 +289,9 @@ struct Run {
                     if (g.am_off < r.off + r.cells && r.off < g.am_off + am_cells) fail(b, "argmax tables overlap");
                 am.push_back({g.am_off, am_cells, (int)s, g.cx, std::vector<char>((size_t)g.cells, 0)});
                 at(g.am_off + am_cells - 1);
+                if (g.am_off < seed_cells) fail(b, "the argmax table of step " + std::to_string(s) + " overlaps a seed");
             }
+            if (!fin && g.out_off < seed_cells) fail(b, "the output of step " + std::to_string(s) + " overlaps a seed");
             char *tie = mx ? am.back().tie.data() : nullptr;
             if (!fin) tabs.push_back({g.out_off, g.cells, (int)s, (int)s});
             std::vector<double> outv((size_t)g.cells, 0.0);
@@ -355,7 +382,7 @@ static void run_max(const Network &net, int64_t b, const Query &q) {
     const Request rq = q.request(ProgramKind::Max);
     const std::string ve = validate_mpe_request(net, rq);
     if (!ve.empty()) fail(b, ve);
-    Run R(net, b, rq);
+    Run R(net, b, rq, q);
     R.run_steps(net, [&](uint32_t s, const GenericStep &g) {
         const bool mx = g.flags & kFlagMax;
         if (g.cx > 1 && !mx) fail(b, "elimination step " + std::to_string(s) + " without the MAX flag");
@@ -395,7 +422,7 @@ static void run_map(const Network &net, int64_t b, const Query &q) {
     const std::string ve = validate_request(net, rq);
     if (!ve.empty()) fail(b, ve);
     if (q.out_of_domain(net)) { print_zero(); return; }
-    Run R(net, b, rq);
+    Run R(net, b, rq, q);
     std::vector<char> in_m(n, 0);
     for (int32_t v : mv) in_m[v] = 1;
     bool max_phase = false;
@@ -477,7 +504,7 @@ static void run_draw(const Network &net, int64_t b, const Query &q, uint32_t k0,
     const Request rq = q.request(ProgramKind::Draw);
     const std::string ve = validate_mpe_request(net, rq);
     if (!ve.empty()) fail(b, ve);
-    Run R(net, b, rq);
+    Run R(net, b, rq, q);
     const PlanStats &st = R.st;
     if (st.kept_cells != st.arena_cells) fail(b, "kept_cells " + std::to_string(st.kept_cells) + " != arena_cells " + std::to_string(st.arena_cells));
     const uint32_t n_steps = R.n_steps();
@@ -619,7 +646,7 @@ static void run_ev(const Network &net, int64_t b, const Query &q, const std::str
     }
     std::vector<double> result((size_t)qcells, 0.0);
     if (!q.out_of_domain(net)) {
-        Run R(net, b, rq);
+        Run R(net, b, rq, q);
         const uint32_t n_steps = R.n_steps();
         if (!n_steps) fail(b, "empty program");
         R.run_steps(net, [&](uint32_t s, const GenericStep &g) {
@@ -644,11 +671,12 @@ int main(int argc, char **argv) {
     argv = args.data();
 #endif
     // the options, taken out of the command line: what stays is the command line of before
-    struct { long small_cells = -1, big_iters = -1, tile_h = -1, order_effort = -1; double second_above = -1, minfill_above = -1; const char *hints = nullptr; } opt;
+    struct { long small_cells = -1, big_iters = -1, tile_h = -1, order_effort = -1; double second_above = -1, minfill_above = -1; const char *hints = nullptr, *lh = nullptr; } opt;
     std::vector<char *> pos;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
         if (i > 0 && a == "--ties") { g_report_ties = true; continue; }
+        if (i > 0 && a == "--dump") { g_dump = true; continue; }
         if (i > 0 && a.rfind("--", 0) == 0) {
             if (i + 1 >= argc) { std::fprintf(stderr, "option %s without a value\n", argv[i]); return 2; }
             const char *v = argv[++i];
@@ -659,6 +687,7 @@ int main(int argc, char **argv) {
             else if (a == "--second_above") opt.second_above = std::strtod(v, nullptr);
             else if (a == "--minfill_above") opt.minfill_above = std::strtod(v, nullptr);
             else if (a == "--hints") opt.hints = v;
+            else if (a == "--lh") opt.lh = v;
             else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
             continue;
         }
@@ -670,12 +699,13 @@ int main(int argc, char **argv) {
     const bool is_ev = kind_name == "ev", is_draw = kind_name == "draw";
     if (!(kind_name == "max" || kind_name == "map" || is_draw || is_ev) || argc < (is_ev || is_draw ? 4 : 3)) {
         std::fprintf(stderr, "usage: prog_sim max net.txt | map net.txt | draw net.txt codes.bin [margins.bin] | ev run|compare|reject net.txt\n"
-                             "       [--small_cells N] [--big_iters N] [--tile_h N] [--order_effort N] [--second_above X] [--minfill_above X] [--hints FILE] [--ties]\n");
+                             "       [--small_cells N] [--big_iters N] [--tile_h N] [--order_effort N] [--second_above X] [--minfill_above X] [--hints FILE] [--ties] [--lh FILE] [--dump]\n");
         return 2;
     }
     const Kind kind = is_ev ? Kind::Ev : is_draw ? Kind::Draw : kind_name == "map" ? Kind::Map : Kind::Max;
     const std::string mode = is_ev ? argv[2] : "";
     if (is_ev && mode != "run" && mode != "compare" && mode != "reject") { std::fprintf(stderr, "unknown mode %s\n", argv[2]); return 2; }
+    if (opt.lh && (is_draw || (is_ev && mode != "run"))) { std::fprintf(stderr, "--lh: max, map and ev run only\n"); return 2; }
     slurp(argv[is_ev ? 3 : 2]);
     FILE *fc = nullptr, *fm = nullptr;
     if (is_draw) {
@@ -708,8 +738,33 @@ int main(int argc, char **argv) {
     if (is_draw) { seed = getu(); no_prune = geti() == 0; }
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ 0x85EBCA6Bu;  // (the key of mibn_sample)
     const int64_t B = geti();
+    // --lh: the findings of every request, read whole before the first request runs
+    std::vector<std::vector<int32_t>> lh_vars((size_t)B);
+    std::vector<std::vector<std::vector<double>>> lh_w((size_t)B);
+    if (opt.lh) {
+        FILE *fl = std::fopen(opt.lh, "rb");
+        if (!fl) { std::perror(opt.lh); return 2; }
+        char tok[128];
+        auto word = [&]() -> const char * {
+            if (std::fscanf(fl, "%127s", tok) != 1) { std::fprintf(stderr, "%s ends early\n", opt.lh); std::exit(2); }
+            return tok;
+        };
+        for (int64_t b = 0; b < B; ++b) {
+            const long k = std::strtol(word(), nullptr, 10);
+            for (long i = 0; i < k; ++i) {
+                const long v = std::strtol(word(), nullptr, 10);
+                if (v < 0 || v >= net.n_vars) { std::fprintf(stderr, "%s: request %lld names variable %ld\n", opt.lh, (long long)b, v); return 2; }
+                lh_vars[(size_t)b].push_back((int32_t)v);
+                lh_w[(size_t)b].emplace_back();
+                for (int c = 0; c < net.card[v]; ++c) lh_w[(size_t)b].back().push_back(std::strtod(word(), nullptr));
+            }
+        }
+        std::fclose(fl);
+    }
     for (int64_t b = 0; b < B; ++b) {
-        const Query q(kind, no_prune);
+        Query q(kind, no_prune);
+        q.lv = lh_vars[(size_t)b];
+        q.lw = lh_w[(size_t)b];
         switch (kind) {
             case Kind::Max: run_max(net, b, q); break;
             case Kind::Map: run_map(net, b, q); break;
