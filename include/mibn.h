@@ -225,7 +225,7 @@ int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, c
  * CSR layout: request b has the findings l_vars[l_off[b] .. l_off[b + 1]); finding k has the weights values[v_off[k] .. v_off[k + 1]),
  * exactly card(l_vars[k]) of them (v_off has one entry more than l_vars and is indexed like it).
  * The block is copied.  It belongs to the next batch call and is gone when that call returns, whatever it returns:
- *   mibn_query_batch, mibn_query_batch_ex, mibn_mpe_batch and mibn_map_batch consume it; their B must be the block's (MIBN_E_ARG);
+ *   mibn_query_batch, mibn_query_batch_ex, mibn_mpe_batch, mibn_map_batch and mibn_bp_batch consume it; their B must be the block's (MIBN_E_ARG);
  *   mibn_submit_batch and mibn_expect_batch refuse it with MIBN_E_STATE, mibn_posterior_sample_batch with MIBN_E_ARG.
  * A block without a single finding (B = 0 with a call of no requests, or all rows empty) is legal: the call is bit for bit the call
  * without a block.  A call with findings is planned by the host's workers only - no plan templates, no device planner, no adaptive
@@ -238,6 +238,45 @@ int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, c
  */
 int mibn_set_likelihoods(mibn_t *h, int64_t B, const int64_t *l_off, const int32_t *l_vars,
                          const int64_t *v_off, const double *values);
+
+/*
+ * Loopy belief propagation: every single-variable posterior of B requests at once, approximately - sum-product message passing on the
+ * factor graph of the CPTs.  Exact on polytrees; on loopy networks an approximation WITHOUT an error bound and without a guarantee of
+ * convergence (read `residual`).  Its cost is linear in the network, so it answers where every exact call returns MIBN_E_NOMEM or
+ * MIBN_E_LIMIT (a 20 x 20 grid).  Deterministic: no seed, no planner, no per-request program.
+ *   Factor graph: one factor per variable v, its CPT, scope S_v = (parents.., v) as mibn_set_network received it, table in C-order.
+ *     Every CPT takes part (the MIBN_Q_NOPRUNE rule, as in mibn_mpe_batch).
+ *   Edges: e = (f, k) joins factor f and variable u = S_f[k]; numbered by ascending f, then ascending k.  Each carries mu_e (factor ->
+ *     variable) and nu_e (variable -> factor), card(u) doubles each.  N(u): the edges of u in ascending edge number.
+ *   lambda_u: all ones; one-hot for an evidence variable (all zeros for a code outside the domain, -1 included: not an error);
+ *     a likelihood finding's weights as given.
+ *   Start: mu_e(x) = 1 / card(u).  Iteration t = 1 .. max_iterations, everything in step t reads step t - 1 only ("flooding"):
+ *     1. nu_e(x) = lambda_u(x) * prod over e' in N(u), e' != e, ascending, of mu_e'(x) - no division, CPTs hold zeros -; then every cell
+ *        divided by s = the sum over ascending x.
+ *     2. mu^_e(x) = sum over the cells c of f with c_k = x, ascending C-order index, of (f[c] times nu_(f,j)(c_j) for ascending j != k);
+ *        normalised like 1.
+ *     3. mu_e = (1 - damping) * mu^_e + damping * (mu_e of step t - 1); for damping = 0 exactly mu^_e.
+ *     4. r_t = max over e, x of |mu_e(x) - its value of step t - 1|; stop after step t if r_t <= tol or t = max_iterations.
+ *   Beliefs: b_u(x) ~ lambda_u(x) * prod over e in N(u) of mu_e(x), normalised the same way.
+ *   Zero mass - a normalising sum that is 0: impossible evidence, findings that leave nothing -: every belief of the request is 0.0,
+ *     iterations[b] the step in which it was seen (0: lambda alone shows it; beliefs: the last step), residual[b] 0.
+ *   beliefs[b * sum(card) + (sum of card(w), w < v) + x] = b_v(x), evidence variables included (their one-hot); iterations[b] = steps
+ *   executed; residual[b] = the last r_t - the request has converged when it is <= tol.
+ * The result of a request is a function of (network, request, max_iterations, tol, damping) alone: bit for bit the same alone or in
+ * any batch, at any position, under any chunking (options "chunk", "arena_gb") and in either memory form - a request's messages live
+ * in the LDS of its workgroup when they fit in 160 KiB and option "bp_lds" is not 0, else in a slab of the arena; MIBN_E_NOMEM only if
+ * a single slab does not fit.
+ * Blocking; plans on the calling thread; changes no option and nothing a later call reads; books nothing into the totals.
+ * mibn_last_stats / mibn_last_kernel_stats describe it in the row "bp_kernel": launches, HIP-event time, items = requests, and
+ * alg_bytes = the bytes of CPT cells read, 8 * (sum over factors of |S_f| * cells(f)) per executed iteration of every request.
+ * Consumes a pending mibn_set_likelihoods block (its B must be this call's).
+ * Errors, all before anything is enqueued: MIBN_E_ARG for unknown or duplicate evidence variables, a descending e_off, a finding
+ * variable that is also evidence of its request, max_iterations < 1, damping outside [0, 1), a negative or NaN tol; MIBN_E_STATE
+ * before mibn_set_network; MIBN_E_LIMIT for a cardinality above 255 or 2^31 message cells or more.
+ */
+int mibn_bp_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                  int32_t max_iterations, double tol, double damping,
+                  double *beliefs /* B * sum(card) */, int32_t *iterations /* B */, double *residual /* B */);
 
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {
@@ -321,7 +360,8 @@ int mibn_device_synchronize(mibn_t *h);
  * Test and profiling hooks: "sweep_canon" (0: the sweep kernel's general path for every step), "small_cells", "big_iters", "tile_h", "fuse", "chain", "outer" (force the
  * kernels' step forms onto small networks), "split_kinds" (one launch per class of work and level, so that
  * mibn_last_kernel_stats reports per-class rates), "trace" (one stderr line per launch), "gibbs_lds" (0: the Gibbs
- * kernel reads the CPTs through L2 even when they would fit in LDS). */
+ * kernel reads the CPTs through L2 even when they would fit in LDS), "bp_lds" (default 1; 0: mibn_bp_batch keeps the messages in slabs
+ * of the arena even when they would fit in LDS). */
 int mibn_set_option(mibn_t *h, const char *name, double value);
 
 /*

@@ -344,6 +344,19 @@ class Backend:
         return (l_off, np.array([v for v, _ in flat], np.int32), v_off,
                 np.concatenate([w for _, w in flat]) if flat else np.zeros(0, np.float64))
 
+    # ---- loopy belief propagation (mibn_bp_batch) -----------------------------------------------------
+    def lbp(self, event, likelihood=None, n_iterations=100, tol=1e-9, damping=0.0):
+        """One request -> (beliefs [sum(card)] float64 - variable v at sum(card[:v]) -, iterations, residual).  Every CPT takes
+        part: a node without one raises the reference's KeyError."""
+        findings = self.encode_likelihood(likelihood, event)
+        _, ev, codes = self.encode((), event, findings)
+        if self.flat.missing:
+            raise KeyError(self.flat.names[min(self.flat.missing)])
+        more = {"likelihoods": self.likelihood_block([findings])} if findings else {}
+        bel, it, res = self.engine.bp(np.array(ev, np.int32).reshape(1, len(ev)), np.array(codes, np.int32).reshape(1, len(ev)),
+                                      n_iterations, tol, damping, **more)
+        return bel[0], int(it[0]), float(res[0])
+
     # ---- result construction --------------------------------------------------------------------
     def posterior_series(self, query, dense):
         """Dense C-order posterior over `query` (caller order) -> the Series
@@ -934,9 +947,16 @@ class BayesNet:
 
         `algorithm`: "exact" (variable elimination on the GPU), "gibbs" (GPU chains; `n_chains` is an
         extension, default 1 like the reference), "rejection" or "likelihood" (GPU forward sampling, one sample
-        per lane); anything else raises the reference's ValueError.
+        per lane), "lbp" (an extension: loopy belief propagation, `marginals(event)[name]` - one query variable only,
+        approximate on networks with loops, takes `likelihood` too); anything else raises the reference's ValueError.
         """
         self._check_request(query, event)
+        if algorithm == "lbp":
+            # loopy belief propagation (an extension, see `marginals`): single-variable posteriors only
+            if len(query) != 1:
+                raise ValueError("algorithm='lbp' answers one query variable per call: belief propagation yields no joint "
+                                 "over several variables (see marginals())")
+            return self.marginals(event, algorithm="lbp", n_iterations=n_iterations, likelihood=likelihood)[query[0]]
         if likelihood is not None:
             if algorithm != "exact":
                 raise ValueError("likelihood findings need algorithm='exact'")
@@ -1074,6 +1094,82 @@ class BayesNet:
         names = self._all_names()
         frame = pd.DataFrame(decode_labels(f, names, out, events), index=events.index, columns=names)
         return (frame, log_p) if return_log_prob else frame
+
+    # ---- all single-variable posteriors (an extension: loopy belief propagation on the device, mibn_bp_batch) -----------------
+    @staticmethod
+    def _marginals_algorithm(algorithm):
+        if algorithm not in ("lbp", "exact"):
+            raise ValueError("Unknown algorithm, must be one of: lbp, exact")
+
+    def marginals(self, event: dict = None, algorithm="lbp", n_iterations=100, tol=1e-9, damping=0.0, likelihood: dict = None,
+                  return_info=False):
+        """Every single-variable posterior P(X | event) at once: {name: Series} over the variables not in `event`, each Series what
+        `query(name, event=event)` returns - name, index, labels, zero rows absent.
+
+        `algorithm="lbp"` (default): loopy belief propagation on the device, one call for all variables - at most `n_iterations`
+        flooding sweeps, stopped early when no message moves by more than `tol`; `damping` in [0, 1) mixes each new message with
+        its predecessor.  Exact on polytrees.  On a network with loops it is an approximation WITHOUT an error bound and it need
+        not converge: pass `return_info=True` and read `converged`.  Its cost is linear in the network, so it answers networks on
+        which every exact call raises (a 20 x 20 grid).  Every CPT takes part, as in `mpe`.
+        `algorithm="exact"`: one exact `query` per variable through `query_many` - the same spelling, for comparison.
+        `likelihood`: likelihood findings as in `query`.
+        `return_info=True`: (marginals, {"iterations", "residual", "converged"})."""
+        self._marginals_algorithm(algorithm)
+        event = dict(event or {})
+        if algorithm == "exact":
+            names = [n for n in self._all_names() if n not in event]
+            answers = self.query_many([((n,), event, likelihood) if likelihood else ((n,), event) for n in names])
+            out = {n: answers[i] for i, n in enumerate(names)}
+            return (out, {"iterations": 0, "residual": 0.0, "converged": True}) if return_info else out
+        be = self._event_backend(list(event) + list(likelihood or {}), every_cpt=True)
+        f = be.flat
+        names = [n for n in self._all_names() if n not in event]
+        bel, it, res = be.lbp(event, likelihood, n_iterations, tol, damping)
+        off = np.concatenate([[0], np.cumsum(f.card, dtype=np.int64)])
+        out = {n: be.finished_series((n,), bel[off[f.id[n]]:off[f.id[n] + 1]].copy()) for n in names}
+        info = {"iterations": it, "residual": res, "converged": bool(res <= tol)}
+        return (out, info) if return_info else out
+
+    def marginals_frame(self, events: pd.DataFrame, algorithm="lbp", n_iterations=100, tol=1e-9, damping=0.0, return_info=False,
+                        sub_batch=32768):
+        """`marginals` for every row of `events`, in the convention of `mpe_frame`: the columns are evidence variables, NaN / None =
+        not observed in that row.  Returns a DataFrame with the index of `events` and one column per (variable, state) - sorted
+        names, labels in `query()`'s order -, row r holding every posterior given the event of row r (zeros where `query()` drops
+        the row; a variable the row observes holds its one-hot).  `return_info=True` adds the columns ("info", "iterations"),
+        ("info", "residual") and ("info", "converged")."""
+        self._marginals_algorithm(algorithm)
+        cols = list(events.columns)
+        be = self._event_backend(cols, every_cpt=True)
+        f = be.flat
+        ev_ids, codes, observed = encode_frame(be, cols, events)
+        n = len(events)
+        off = np.concatenate([[0], np.cumsum(f.card, dtype=np.int64)])
+        dense = np.zeros((n, int(off[-1])), np.float64)
+        its = np.zeros(n, np.int32)
+        res = np.zeros(n, np.float64)
+        for part, on in iter_parts(pattern_groups(observed), observed, sub_batch):
+            evars, ecodes = part_args(ev_ids, codes, part, on)
+            if algorithm == "lbp":
+                dense[part], its[part], res[part] = be.engine.bp(evars, ecodes, n_iterations, tol, damping)
+                continue
+            seen = set(int(v) for v in ev_ids[on])
+            for v in range(len(f.card)):
+                if v in seen:
+                    continue
+                dense[part, off[v]:off[v + 1]] = be.engine.query_fixed(np.full((len(part), 1), v, np.int32), evars, ecodes)
+            for j in on:  # the observed variables: their one-hot
+                c = codes[part, j]
+                ok = (c >= 0) & (c < f.card[ev_ids[j]])
+                dense[part[ok], off[ev_ids[j]] + c[ok]] = 1.0
+        names = self._all_names()
+        order = np.concatenate([np.arange(off[f.id[name]], off[f.id[name] + 1]) for name in names]) if names else np.zeros(0, np.int64)
+        columns = pd.MultiIndex.from_tuples([(name, lab) for name in names for lab in f.domains[f.id[name]]], names=["variable", "state"])
+        frame = pd.DataFrame(dense[:, order], index=events.index, columns=columns)
+        if return_info:
+            frame[("info", "iterations")] = its
+            frame[("info", "residual")] = res
+            frame[("info", "converged")] = res <= tol
+        return frame
 
     # ---- marginal MAP (an extension: sum-then-max elimination on the device, mibn_map_batch) ---------------------------------
     def _map_backend(self, variables, evidence_names):

@@ -1,0 +1,155 @@
+// Host side of loopy belief propagation (mibn_bp_batch): everything the call decides before its first HIP call, in plain C++17 - no
+// HIP header, so that tools/bp_plan_sim.cpp runs it on a CPU (tests/test_bp_host.py) the way sampler_plan_sim runs sampler_plan.h.
+// bp_layout is the ONE description of a request's message state: bp_kernel takes its pointers from it - into dynamic LDS or into the
+// request's slab of the arena -, the plan takes the launch's LDS size and the slab size from it.
+//
+// The factor graph: one factor per variable v, its CPT, with the scope S_v = (parents.., v) as mibn_set_network received it.  Every CPT
+// takes part.  Edge e = (f, k) joins factor f and variable u = S_f[k]; edges are numbered by ascending factor, then ascending scope
+// position, so the edges of factor f are vars[f].edge_begin .. + scope_len.  Each edge owns card(u) cells at cell offset moff in every
+// message array (mu of the previous step, mu of this step, nu).  N(u): the edges of variable u in ascending edge number.  lambda of
+// variable u: card(u) cells at loff = sum of the cards below u, which is also where u's belief goes in a request's output row.
+//
+// The launch takes one of two forms:
+//     MsgLds      the message arrays and lambda of a request in the LDS of its workgroup     bp_lds != 0 and bp_layout(..).total <= 160 KiB
+//     MsgGlobal   the same arrays in a slab of the arena, one per request of the launch        otherwise
+// Either way the CPTs, the records below and the request's evidence are read from global memory.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/mibn.h"
+#include "planner.h"
+#include "sampler_plan.h"  // MIBN_HD, pack_vars, kSamplerLdsLimit
+
+namespace mibn {
+
+struct BpEdge {
+    int32_t factor, pos, var, card;  // e = (factor, pos); var = S_factor[pos] and its cardinality
+    int32_t moff;                    // first message cell
+    int32_t table_off;               // the factor's CPT in the pool
+    int32_t stride;                  // C-order stride of `pos` in that table
+    int32_t loff;                    // first lambda cell of var
+};
+struct BpVar {
+    int32_t card, loff;
+    int32_t nb_begin, nb_len;        // N(v) in nbr / nbr_moff
+    int32_t edge_begin, scope_len;   // the edges of factor v
+    int32_t table_off, table_cells;  // its CPT
+};
+
+// ------------------------------------------------------------------------------------------------------------ the state of a request
+// mu0[cells] | mu1[cells] | nu[cells] | lambda[lam_cells] f64 | red (byte offsets).  red: the workgroup's reduction slots - always in LDS;
+// a slab has the room and leaves it unused.
+constexpr int kBpMaxWaves = 4;
+constexpr size_t kBpRedBytes = 64;  // kBpMaxWaves doubles (the waves' residual maxima) + as many ints (their zero-mass flags)
+template <typename I>
+struct BpLayout {
+    I mu0, mu1, nu, lam, red, total;
+};
+template <typename I>
+MIBN_HD inline BpLayout<I> bp_layout(I cells, I lam_cells) {
+    BpLayout<I> L;
+    L.mu0 = 0;
+    L.mu1 = cells * 8;
+    L.nu = 2 * cells * 8;
+    L.lam = 3 * cells * 8;
+    L.red = L.lam + lam_cells * 8;
+    L.total = L.red + (I)kBpRedBytes;
+    return L;
+}
+
+enum class BpForm { MsgLds, MsgGlobal };
+inline const char *bp_form_name(BpForm f) { return f == BpForm::MsgLds ? "MsgLds" : "MsgGlobal"; }
+
+// Threads of a workgroup: the work items of both phases are edges, so one lane per edge in whole waves, 64 .. 256.  A small network
+// (Asia: 18 edges) gets one wave - its two barriers an iteration cost nothing and four of its workgroups share a CU's SIMDs -, anything
+// above 192 edges the full 256.
+inline int bp_threads(int64_t n_edges) { return (int)std::min<int64_t>(64 * kBpMaxWaves, std::max<int64_t>(64, (n_edges + 63) / 64 * 64)); }
+
+struct BpPlan {
+    std::vector<BpEdge> edges;
+    std::vector<BpVar> vars;
+    std::vector<int32_t> nbr, nbr_moff;  // flattened N(v): edge numbers, and the moff of each
+    int32_t cells = 0, lam_cells = 0;
+    BpLayout<size_t> lds{};
+    size_t slab_bytes = 0;   // MsgGlobal: stride of a request's slab (16-byte multiple)
+    double iter_bytes = 0;   // bytes of CPT cells one iteration of one request reads: 8 * sum over factors of scope_len * table cells
+    BpForm form = BpForm::MsgLds;
+    int threads = 64;
+};
+
+// max_iterations >= 1, 0 <= damping < 1, tol >= 0 (NaN fails every comparison)
+inline int bp_check_args(int32_t max_iterations, double tol, double damping, std::string &err) {
+    if (max_iterations < 1) { err = "bp: max_iterations must be at least 1"; return MIBN_E_ARG; }
+    if (!(damping >= 0.0 && damping < 1.0)) { err = "bp: damping must be in [0, 1)"; return MIBN_E_ARG; }
+    if (!(tol >= 0.0)) { err = "bp: tol must be a number >= 0"; return MIBN_E_ARG; }
+    return MIBN_OK;
+}
+
+// lds_mode: the bp_lds option (0 forces MsgGlobal)
+inline int bp_plan(const Network &net, int lds_mode, BpPlan &P, std::string &err) {
+    const int n = net.n_vars;
+    SamplerPack pack;
+    size_t o_sv = 0, o_ss = 0, o_ch = 0;
+    if (int rc = pack_vars(net, "bp", false, nullptr, pack, o_sv, o_ss, o_ch, err)) return rc;  // (cardinality above 255: MIBN_E_LIMIT)
+    if (net.pool.size() > (size_t)INT32_MAX) { err = "bp: the CPTs have more than 2^31 cells"; return MIBN_E_LIMIT; }
+    P.edges.clear();
+    P.vars.assign((size_t)n, BpVar{});
+    int64_t cells = 0, lam = 0;
+    std::vector<std::vector<int32_t>> nb((size_t)n);
+    for (int f = 0; f < n; ++f) {
+        const GibbsVar &g = pack.vars[(size_t)f];
+        BpVar &V = P.vars[(size_t)f];
+        V.card = g.card;
+        V.loff = (int32_t)lam;
+        lam += g.card;
+        V.edge_begin = (int32_t)P.edges.size();
+        V.scope_len = g.scope_len;
+        V.table_off = g.table_off;
+        int64_t tc = 1;
+        for (int k = 0; k < g.scope_len; ++k) tc *= net.card[(size_t)pack.words[o_sv + (size_t)g.scope_begin + (size_t)k]];
+        V.table_cells = (int32_t)tc;  // (a part of the pool: below 2^31)
+        P.iter_bytes += 8.0 * (double)g.scope_len * (double)tc;
+        for (int k = 0; k < g.scope_len; ++k) {
+            const int32_t u = pack.words[o_sv + (size_t)g.scope_begin + (size_t)k];
+            if (cells > (int64_t)INT32_MAX - 255) { err = "bp: more than 2^31 message cells"; return MIBN_E_LIMIT; }
+            BpEdge E;
+            E.factor = f; E.pos = k; E.var = u; E.card = net.card[(size_t)u];
+            E.moff = (int32_t)cells;
+            E.table_off = g.table_off;
+            E.stride = pack.words[o_ss + (size_t)g.scope_begin + (size_t)k];
+            E.loff = 0;
+            nb[(size_t)u].push_back((int32_t)P.edges.size());
+            P.edges.push_back(E);
+            cells += E.card;
+        }
+    }
+    for (BpEdge &E : P.edges) E.loff = P.vars[(size_t)E.var].loff;
+    P.nbr.clear();
+    P.nbr_moff.clear();
+    for (int v = 0; v < n; ++v) {
+        P.vars[(size_t)v].nb_begin = (int32_t)P.nbr.size();
+        P.vars[(size_t)v].nb_len = (int32_t)nb[(size_t)v].size();
+        for (int32_t e : nb[(size_t)v]) { P.nbr.push_back(e); P.nbr_moff.push_back(P.edges[(size_t)e].moff); }
+    }
+    P.cells = (int32_t)cells;
+    P.lam_cells = (int32_t)lam;
+    P.lds = bp_layout<size_t>((size_t)cells, (size_t)lam);
+    P.slab_bytes = lds_align16(P.lds.total);
+    P.form = lds_mode != 0 && P.lds.total <= kSamplerLdsLimit ? BpForm::MsgLds : BpForm::MsgGlobal;
+    P.threads = bp_threads((int64_t)P.edges.size());
+    return MIBN_OK;
+}
+
+// Requests of one launch: at most `chunk`, and in the global form as many slabs as the budget holds.  0: one slab does not fit.
+inline int64_t bp_launch_requests(const BpPlan &P, int64_t chunk, double budget_bytes) {
+    chunk = std::max<int64_t>(1, chunk);
+    if (P.form == BpForm::MsgLds) return chunk;
+    const double fit = std::floor(budget_bytes / (double)P.slab_bytes);
+    return fit < 1.0 ? 0 : (int64_t)std::min((double)chunk, fit);
+}
+
+}  // namespace mibn

@@ -22,6 +22,7 @@
 #include "../../include/mibn.h"
 #include "device_mem.h"
 #include "gibbs_kernel.hip.h"
+#include "bp_kernel.hip.h"
 #include "sample_kernel.hip.h"
 #include "count_kernel.hip.h"
 #include "score_kernel.hip.h"
@@ -189,16 +190,16 @@ constexpr int kLevelStreams = 4;
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
 // steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together), and the two kernels of a call with likelihood
-// findings: the seeds of a planned wave, the tiny kernel's twin.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// findings: the seeds of a planned wave, the tiny kernel's twin, and the one kernel of mibn_bp_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -451,6 +452,7 @@ struct mibn_ctx {
                           // wave-owned tail); 0 = round 2's register-staged ve_sweep_kernel (reference for A/B runs and the bit-for-bit test)
     int gibbs_lds = 1;    // Gibbs: 1 = CPTs in LDS when they fit + the eight-lanes-per-chain form for grids (gibbs_kernel8); 2 = LDS, one chain per
                           // lane (round 3's kernel); 0 = always read the tables through L2
+    int bp_lds = 1;       // mibn_bp_batch: 0 = the message arrays in slabs of the arena even where they fit in LDS (test hook, like gibbs_lds)
     int64_t chunk = 32768;  // requests per launch; planning of chunk i+1 overlaps the kernel of chunk i.  Round 3: 32 768 (16 384 before):
                             // half as many, twice as large launches - the tails of the ~150 launches of a chunk cost the same time
                             // whatever their size: 4.13-4.24 -> 4.30-4.38 TB/s over all kernels (profiles/r03_d_chunk.log); the
@@ -629,6 +631,7 @@ int mibn_set_option(mibn_t *h, const char *name, double value) {
     else if (n == "sweep_dma") h->sweep_dma = value != 0;
     else if (n == "seg_kernel") h->seg_kernel = value != 0;
     else if (n == "gibbs_lds") h->gibbs_lds = std::max(0, std::min(2, (int)value));
+    else if (n == "bp_lds") h->bp_lds = value != 0;
     else if (n == "tiny") h->tiny = value != 0;
     else if (n == "tiny_zero_copy") h->tiny_zero_copy = value != 0;
     else if (n == "mfma_kernel") h->mfma_kernel = value != 0;  // (round 6 measured CHAIN and OUTER in ve_mfma_kernel too: at its 128 registers they spill 74 and the
@@ -2804,7 +2807,7 @@ int run_map_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, con
 
 // ---------------------------------------------------------------------------------------------- likelihood findings
 // mibn_set_likelihoods stages a block for the NEXT batch call.  The calls that consume it (mibn_query_batch, mibn_query_batch_ex,
-// mibn_mpe_batch, mibn_map_batch) take it for their duration - h->lh, null for a block without a single finding: such a call is the call
+// mibn_mpe_batch, mibn_map_batch, mibn_bp_batch) take it for their duration - h->lh, null for a block without a single finding: such a call is the call
 // without a block, bit for bit -; the others refuse it.  Either way it is gone when the call returns, whatever the call returns.
 namespace {
 void drop_findings(mibn_ctx *h) {
@@ -3060,6 +3063,157 @@ extern "C" int mibn_gibbs_conditional(mibn_t *h, int32_t n_e, const int32_t *e_v
     double ms = 0;
     return gibbs_run(h->net, h->d_pool, h->stream, h->gibbs_lds, 1, &q0, n_e, e_vars, e_codes, cycle, 0, n_rows, 1, 0, nullptr, h->err, ms,
                      var, states, out);
+}
+
+// ---------------------------------------------------------------------------------------------- loopy belief propagation
+// mibn_bp_batch: plan (bp_plan.h), upload the records once, then launch by launch - at most `chunk` requests, in the global form as
+// many as have slabs in the arena of lane 0 - upload the evidence, run bp_kernel, download.  Blocking, on the main stream, buffers of
+// its own; last-call statistics only, nothing a later call reads.
+namespace {
+int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t max_iterations, double tol,
+            double damping, double *beliefs, int32_t *iterations, double *residual) {
+    const double t_start = now_ms();
+    reset_last_stats(h);
+    const Network &net = h->net;
+    int rc;
+    if ((rc = bp_check_args(max_iterations, tol, damping, h->err))) return rc;
+    const Findings *F = h->lh;
+    for (int64_t b = 0; b < B; ++b) {
+        if (e_off[b + 1] < e_off[b] || e_off[b] < 0) { h->err = "request " + std::to_string(b) + ": e_off must be non-negative and ascending"; return MIBN_E_ARG; }
+        Request rq;
+        rq.ne = (int32_t)(e_off[b + 1] - e_off[b]);
+        if (rq.ne && (!e_vars || !e_codes)) { h->err = "bp: e_vars or e_codes missing"; return MIBN_E_ARG; }
+        rq.evars = rq.ne ? e_vars + e_off[b] : nullptr;
+        if (F) { rq.nl = (int32_t)(F->l_off[(size_t)b + 1] - F->l_off[(size_t)b]); rq.lvars = F->l_vars.data() + F->l_off[(size_t)b]; }
+        const std::string e = validate_mpe_request(net, rq);  // unknown or duplicate evidence ids, a finding variable that is evidence
+        if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
+    }
+    BpPlan P;
+    if ((rc = bp_plan(net, h->bp_lds, P, h->err))) return rc;
+    if (B == 0) return MIBN_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = drain_streams(h))) return rc;  // (the arena of lane 0 is the query calls' too)
+    const hipStream_t S = h->stream;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    const double budget = std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->d_arena[0].cap()));
+    const int64_t per_launch = bp_launch_requests(P, h->chunk, budget);
+    if (per_launch < 1) { h->err = "bp: one request's messages need " + std::to_string((double)P.slab_bytes / 1e9) + " GB, above the arena budget"; return MIBN_E_NOMEM; }
+    const int64_t n_max = std::min(B, per_launch);
+    const size_t lam = (size_t)P.lam_cells;
+    DevBuf<BpEdge> d_edges;
+    DevBuf<BpVar> d_vars;
+    DevBuf<int32_t> d_nbr, d_ev, d_ec, d_lv, d_it;
+    DevBuf<int64_t> d_eoff, d_loff, d_voff;
+    DevBuf<double> d_val, d_bel, d_res;
+    Event ev0, ev1;
+    HIP_TRY(h, d_edges.reset(P.edges.size()));
+    HIP_TRY(h, d_vars.reset(P.vars.size()));
+    HIP_TRY(h, d_nbr.reset(P.nbr_moff.size()));
+    HIP_TRY(h, d_eoff.reset((size_t)n_max + 1));
+    HIP_TRY(h, d_bel.reset((size_t)n_max * lam));
+    HIP_TRY(h, d_it.reset((size_t)n_max));
+    HIP_TRY(h, d_res.reset((size_t)n_max));
+    HIP_TRY(h, ev0.ensure());
+    HIP_TRY(h, ev1.ensure());
+    HIP_TRY(h, hipMemcpyAsync(d_edges, P.edges.data(), P.edges.size() * sizeof(BpEdge), hipMemcpyHostToDevice, S));
+    HIP_TRY(h, hipMemcpyAsync(d_vars, P.vars.data(), P.vars.size() * sizeof(BpVar), hipMemcpyHostToDevice, S));
+    HIP_TRY(h, hipMemcpyAsync(d_nbr, P.nbr_moff.data(), P.nbr_moff.size() * 4, hipMemcpyHostToDevice, S));
+    const BpKernel kernel = bp_kernel_of(P.form);
+    const size_t lds = bp_lds_bytes(P);
+    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (P.form == BpForm::MsgGlobal && (rc = grow_arena(h, 0, (size_t)n_max * P.slab_bytes, (int64_t)(budget / 8.0), S))) return rc;
+    BpArgs A{};
+    A.pool = h->d_pool;
+    A.edges = d_edges;
+    A.vars = d_vars;
+    A.nbr_moff = d_nbr;
+    A.slabs = reinterpret_cast<unsigned char *>(h->d_arena[0].get());
+    A.slab_bytes = P.slab_bytes;
+    A.n_vars = net.n_vars;
+    A.n_edges = (int32_t)P.edges.size();
+    A.cells = P.cells;
+    A.lam_cells = P.lam_cells;
+    A.max_iterations = max_iterations;
+    A.tol = tol;
+    A.damping = damping;
+    std::vector<int64_t> off;
+    for (int64_t b0 = 0; b0 < B; b0 += n_max) {
+        const int64_t n = std::min(n_max, B - b0);
+        double t0 = now_ms();
+        off.assign((size_t)n + 1, 0);
+        for (int64_t r = 0; r <= n; ++r) off[(size_t)r] = e_off[b0 + r] - e_off[b0];
+        const size_t ne = (size_t)off[(size_t)n];
+        HIP_TRY(h, d_ev.ensure(std::max<size_t>(1, ne)));
+        HIP_TRY(h, d_ec.ensure(std::max<size_t>(1, ne)));
+        HIP_TRY(h, hipMemcpyAsync(d_eoff, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, S));
+        if (ne) {
+            HIP_TRY(h, hipMemcpyAsync(d_ev, e_vars + e_off[b0], ne * 4, hipMemcpyHostToDevice, S));
+            HIP_TRY(h, hipMemcpyAsync(d_ec, e_codes + e_off[b0], ne * 4, hipMemcpyHostToDevice, S));
+        }
+        HIP_TRY(h, hipStreamSynchronize(S));  // (`off` is reused below)
+        A.e_off = d_eoff;
+        A.e_vars = d_ev;
+        A.e_codes = d_ec;
+        A.l_off = nullptr;
+        if (F) {  // the findings of requests [b0, b0 + n), offsets relative to the launch
+            const size_t k0 = (size_t)F->l_off[(size_t)b0], k1 = (size_t)F->l_off[(size_t)(b0 + n)], nk = k1 - k0;
+            const size_t w0 = (size_t)F->v_off[k0], nw = (size_t)F->v_off[k1] - w0;
+            std::vector<int64_t> lo((size_t)n + 1), vo(nk + 1);
+            for (int64_t r = 0; r <= n; ++r) lo[(size_t)r] = F->l_off[(size_t)(b0 + r)] - (int64_t)k0;
+            for (size_t k = 0; k <= nk; ++k) vo[k] = F->v_off[k0 + k] - (int64_t)w0;
+            HIP_TRY(h, d_loff.ensure((size_t)n + 1));
+            HIP_TRY(h, d_voff.ensure(nk + 1));
+            HIP_TRY(h, d_lv.ensure(std::max<size_t>(1, nk)));
+            HIP_TRY(h, d_val.ensure(std::max<size_t>(1, nw)));
+            HIP_TRY(h, hipMemcpyAsync(d_loff, lo.data(), lo.size() * 8, hipMemcpyHostToDevice, S));
+            HIP_TRY(h, hipMemcpyAsync(d_voff, vo.data(), vo.size() * 8, hipMemcpyHostToDevice, S));
+            if (nk) HIP_TRY(h, hipMemcpyAsync(d_lv, F->l_vars.data() + k0, nk * 4, hipMemcpyHostToDevice, S));
+            if (nw) HIP_TRY(h, hipMemcpyAsync(d_val, F->values.data() + w0, nw * 8, hipMemcpyHostToDevice, S));
+            HIP_TRY(h, hipStreamSynchronize(S));  // (lo and vo leave scope)
+            A.l_off = d_loff;
+            A.l_vars = d_lv;
+            A.v_off = d_voff;
+            A.values = d_val;
+        }
+        h->stats.h2d_ms += now_ms() - t0;
+        A.beliefs = d_bel;
+        A.iterations = d_it;
+        A.residual = d_res;
+        HIP_TRY(h, hipEventRecord(ev0, S));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3((unsigned)P.threads), lds, S, A);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(ev1, S));
+        t0 = now_ms();
+        HIP_TRY(h, hipMemcpyAsync(beliefs + (size_t)b0 * lam, d_bel, (size_t)n * lam * 8, hipMemcpyDeviceToHost, S));
+        HIP_TRY(h, hipMemcpyAsync(iterations + b0, d_it, (size_t)n * 4, hipMemcpyDeviceToHost, S));
+        HIP_TRY(h, hipMemcpyAsync(residual + b0, d_res, (size_t)n * 8, hipMemcpyDeviceToHost, S));
+        HIP_TRY(h, hipStreamSynchronize(S));
+        h->stats.d2h_ms += now_ms() - t0;
+        float ms = 0;
+        HIP_TRY(h, hipEventElapsedTime(&ms, ev0, ev1));
+        double iters = 0;
+        for (int64_t r = 0; r < n; ++r) iters += iterations[b0 + r];
+        book_stat(h, kStatBp, 1, ms, P.iter_bytes * iters, (double)n, true, false);
+        h->stats.kernel_ms += ms;
+        h->stats.n_launches += 1;
+        h->stats.n_workgroups += (double)n;
+        h->stats.alg_bytes += P.iter_bytes * iters;
+    }
+    if (P.form == BpForm::MsgGlobal) h->stats.arena_bytes = (double)n_max * (double)P.slab_bytes;
+    h->stats.total_ms = now_ms() - t_start;
+    return MIBN_OK;
+}
+}  // namespace
+
+extern "C" int mibn_bp_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t max_iterations,
+                             double tol, double damping, double *beliefs, int32_t *iterations, double *residual) {
+    TakeFindings lh(h);
+    if (!h || B < 0 || (B && (!e_off || !beliefs || !iterations || !residual))) return MIBN_E_ARG;
+    if (int rc = check_state(h, kNeedIdle)) return rc;
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
+    if (int rc = lh.take(B)) return rc;
+    return drained_on_error(h, bp_body(h, B, e_off, e_vars, e_codes, max_iterations, tol, damping, beliefs, iterations, residual), drain_main_unchecked);
 }
 
 extern "C" int mibn_sample(mibn_t *h, int64_t n_samples, int32_t n_init, const int32_t *init_vars, const int32_t *init_codes,
