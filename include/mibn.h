@@ -225,7 +225,7 @@ int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, c
  * CSR layout: request b has the findings l_vars[l_off[b] .. l_off[b + 1]); finding k has the weights values[v_off[k] .. v_off[k + 1]),
  * exactly card(l_vars[k]) of them (v_off has one entry more than l_vars and is indexed like it).
  * The block is copied.  It belongs to the next batch call and is gone when that call returns, whatever it returns:
- *   mibn_query_batch, mibn_query_batch_ex, mibn_mpe_batch, mibn_map_batch and mibn_bp_batch consume it; their B must be the block's (MIBN_E_ARG);
+ *   mibn_query_batch, mibn_query_batch_ex, mibn_mpe_batch, mibn_map_batch, mibn_bp_batch and mibn_bp_mpe_batch consume it; their B must be the block's (MIBN_E_ARG);
  *   mibn_submit_batch and mibn_expect_batch refuse it with MIBN_E_STATE, mibn_posterior_sample_batch with MIBN_E_ARG.
  * A block without a single finding (B = 0 with a call of no requests, or all rows empty) is legal: the call is bit for bit the call
  * without a block.  A call with findings is planned by the host's workers only - no plan templates, no device planner, no adaptive
@@ -277,6 +277,54 @@ int mibn_set_likelihoods(mibn_t *h, int64_t B, const int64_t *l_off, const int32
 int mibn_bp_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
                   int32_t max_iterations, double tol, double damping,
                   double *beliefs /* B * sum(card) */, int32_t *iterations /* B */, double *residual /* B */);
+
+/*
+ * Approximate most probable explanation by max-product belief propagation, for B requests at once: one assignment of every variable
+ * per request and its log-probability, where mibn_mpe_batch returns MIBN_E_NOMEM or MIBN_E_LIMIT (a 20 x 20 grid).  Exact on
+ * polytrees whose maximum is unique; on loopy networks an approximation WITHOUT a bound on the gap to the true maximum and without a
+ * guarantee of convergence.  Three things hold always: log_p[b] is the log-probability of the assignment codes[b] itself (score rule
+ * below); for fixed other arguments the candidate kept after step t never scores below the one kept after step t - 1, and a polish
+ * sweep never lowers the probability of its assignment; when the polish ran fewer than polish_sweeps sweeps, no change of a single
+ * variable gives a more probable assignment.  Deterministic: no seed, no planner, no per-request program.
+ *   Messages: factor graph, edges, lambda, start, flooding, step 1, damping (step 3), residual and stop rule (step 4) and the zero-mass
+ *     rule are word for word those of mibn_bp_batch.  One change, in step 2: mu^_e(x) = the MAXIMUM over the cells c of f with c_k = x,
+ *     ascending C-order index, of (f[c] times nu_(f,j)(c_j) for ascending j != k), each product formed in that order, the maximum
+ *     started at 0; normalised like 1., by the sum over ascending x.
+ *   Max-marginal of u after step t: m_u(x) = lambda_u(x) * prod over e in N(u), ascending, of mu_e(x) (the messages of step t);
+ *     normalised by s = the sum over ascending x, and s = 0 is zero mass, seen in step t.
+ *   Decode after step t: x^t_u = the lowest state of maximal m_u, for EVERY u, compared on the products before the division (dividing
+ *     by s is monotone; it could only merge neighbours).  An evidence variable's lambda is one-hot, so it decodes to its code.
+ *   Score of an assignment x: term_v = log f_v[cell of x] + log lambda_v(x_v) (natural logarithm, log 0 = -inf) for every v;
+ *     partial_l = the sum of term_v over v = l, l + 64, l + 128, .. ascending; score = the sum of partial_l for l = 0 .. 63 ascending.
+ *     The order does not depend on the workgroup size.  -inf is a legal score: the assignment hits a zero of a sparse CPT.
+ *   Best so far: the candidate of step 1 is kept; the candidate of a later step replaces it only when its score is strictly
+ *     greater.  best_iteration = the step of the kept candidate.  The loop ends by the stop rule of mibn_bp_batch.
+ *   Polish (iterated conditional modes) of the kept candidate, after the loop: the moral graph - u and v adjacent when some CPT scope
+ *     holds both - is coloured greedily: ascending v, each the smallest colour no already-coloured neighbour has.  A sweep runs over
+ *     the colours ascending; every variable v of the colour computes, for every x, L(x) = lambda_v(x) * prod over e in N(v), ascending,
+ *     of f_e[the cell of the current assignment with v := x], and moves to the lowest x of maximal L only if L(x) > L(current).
+ *     Variables of one colour share no factor: moving them together is moving them in any order.  An evidence variable never moves
+ *     (its L is 0 off its code).  The polish stops after a sweep without a move or after polish_sweeps sweeps; sweeps run counts the
+ *     last one.  The comparisons are on products, no logarithm: the polish is bit-exact against a host twin.
+ *   Result: codes[b * n_vars + v] = the final assignment; log_p[b] = its score, recomputed by the score rule; iterations[b] and
+ *     residual[b] as in mibn_bp_batch; info[b * 3 ..] = best_iteration, sweeps run, moves made (info may be NULL).
+ *   Zero mass (a normalising sum that is 0, in lambda, a message or a max-marginal): log_p = -inf, code -1 for every non-evidence
+ *     variable - evidence variables keep the code they were given -, iterations[b] the step in which it was seen, residual 0, info 0 0 0;
+ *     as mibn_mpe_batch does.  A single-state non-evidence variable gets code 0.
+ * The result of a request is a function of (network, request, max_iterations, tol, damping, polish_sweeps) alone: bit for bit the same
+ * alone or in any batch, at any position, under any chunking (options "chunk", "arena_gb") and in either memory form - the messages
+ * and the decoder's state (two code rows, the terms, the 64 partials) live in the LDS of the request's workgroup when together they
+ * fit in 160 KiB and option "bp_lds" is not 0, else in a slab of the arena; MIBN_E_NOMEM only if a single slab does not fit.
+ * Blocking; plans on the calling thread; changes no option and nothing a later call reads; books nothing into the totals.
+ * mibn_last_stats / mibn_last_kernel_stats describe it in the row "bp_max_kernel": launches, HIP-event time, items = requests, and
+ * alg_bytes by bp_kernel's rule.  Consumes a pending mibn_set_likelihoods block (its B must be this call's).
+ * Errors, all before anything is enqueued: those of mibn_bp_batch, and MIBN_E_ARG for polish_sweeps < 0.
+ */
+int mibn_bp_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                      int32_t max_iterations, double tol, double damping, int32_t polish_sweeps,
+                      int32_t *codes /* B * n_vars */, double *log_p /* B */,
+                      int32_t *iterations /* B */, double *residual /* B */,
+                      int32_t *info /* B * 3 or NULL: best_iteration, sweeps run, moves made */);
 
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {

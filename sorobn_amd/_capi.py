@@ -23,7 +23,7 @@ SYMBOLS = [
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
     "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch", "mibn_map_batch",
-    "mibn_ci_tests", "mibn_set_likelihoods", "mibn_bp_batch",
+    "mibn_ci_tests", "mibn_set_likelihoods", "mibn_bp_batch", "mibn_bp_mpe_batch",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
@@ -86,6 +86,7 @@ def lib():
         L.mibn_map_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i32p, f64p]
         L.mibn_set_likelihoods.argtypes = [vp, C.c_int64, i64p, i32p, i64p, f64p]
         L.mibn_bp_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, C.c_int32, C.c_double, C.c_double, f64p, i32p, f64p]
+        L.mibn_bp_mpe_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, C.c_int32, C.c_double, C.c_double, C.c_int32, i32p, f64p, i32p, f64p, i32p]
         L.mibn_posterior_sample_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i64p, C.c_uint64, C.c_uint32, i32p, f64p]
         L.mibn_expect_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, i64p, f64p, C.c_int64, f64p, f64p]
         L.mibn_plan_order.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, i32p, i32p]
@@ -398,6 +399,38 @@ class Engine:
         ecodes = _i32(ecodes).reshape(B, -1)
         e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
         return self.bp_batch(e_off, evars.reshape(-1), ecodes.reshape(-1), max_iterations, tol, damping, likelihoods=likelihoods)
+
+    def bp_mpe_batch(self, e_off, e_vars, e_codes, max_iterations=100, tol=1e-9, damping=0.5, polish_sweeps=10, likelihoods=None):
+        """CSR evidence -> (codes[B, n_vars] int32, log_p[B] float64, iterations[B] int32, residual[B] float64, info[B, 3] int32):
+        approximate most probable explanation by max-product belief propagation with an ICM polish (mibn_bp_mpe_batch).  log_p is the
+        log-probability of the returned codes; info holds best_iteration, sweeps run, moves made.  likelihoods: as in query_batch."""
+        e_off = _i64(e_off)
+        B = len(e_off) - 1
+        e_vars, e_codes = _i32(e_vars), _i32(e_codes)
+        n_vars = len(self.card)
+        codes = np.zeros((B, n_vars), np.int32)
+        log_p = np.zeros(B, np.float64)
+        iterations = np.zeros(B, np.int32)
+        residual = np.zeros(B, np.float64)
+        info = np.zeros((B, 3), np.int32)
+        if likelihoods is not None:
+            self.set_likelihoods(likelihoods)
+        pad, padf = np.zeros(1, np.int32), np.zeros(1, np.float64)
+        self._check(self._L.mibn_bp_mpe_batch(
+            self._h, B, _p(e_off, C.c_int64), _p(e_vars if len(e_vars) else pad, C.c_int32), _p(e_codes if len(e_codes) else pad, C.c_int32),
+            int(max_iterations), float(tol), float(damping), int(polish_sweeps), _p(codes if codes.size else pad, C.c_int32),
+            _p(log_p if B else padf, C.c_double), _p(iterations if B else pad, C.c_int32), _p(residual if B else padf, C.c_double),
+            _p(info if B else np.zeros(3, np.int32), C.c_int32)))
+        return codes, log_p, iterations, residual, info
+
+    def bp_mpe(self, evars, ecodes, max_iterations=100, tol=1e-9, damping=0.5, polish_sweeps=10, likelihoods=None):
+        """Fixed-shape batch: evars[B, ne], ecodes[B, ne] -> what bp_mpe_batch returns, like mpe."""
+        evars = _i32(evars)
+        B = len(evars)
+        evars = evars.reshape(B, -1)
+        ecodes = _i32(ecodes).reshape(B, -1)
+        e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
+        return self.bp_mpe_batch(e_off, evars.reshape(-1), ecodes.reshape(-1), max_iterations, tol, damping, polish_sweeps, likelihoods=likelihoods)
 
     def posterior_sample_batch(self, e_off, e_vars, e_codes, s_off, seed=0, flags=0):
         """CSR evidence + sample offsets s_off[B + 1] -> (codes[s_off[B] - s_off[0], n_vars] int32, p_e[B] float64): exact samples of

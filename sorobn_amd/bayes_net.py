@@ -1056,43 +1056,104 @@ class BayesNet:
             raise KeyError(be.flat.names[min(be.flat.missing)])
         return be
 
-    def mpe(self, event: dict = None, return_log_prob=False, likelihood: dict = None):
+    @staticmethod
+    def _mpe_arguments(algorithm, n_iterations, tol, damping, polish):
+        """The argument checks of `mpe` / `mpe_frame`, before any engine exists."""
+        if algorithm not in ("exact", "lbp"):
+            raise ValueError("Unknown algorithm, must be one of: exact, lbp")
+        if algorithm == "exact":
+            return
+        if int(n_iterations) != n_iterations or n_iterations < 1:
+            raise ValueError("n_iterations must be an integer >= 1")
+        if not tol >= 0:
+            raise ValueError("tol must be a number >= 0")
+        if not 0 <= damping < 1:
+            raise ValueError("damping must be in [0, 1)")
+        if int(polish) != polish or polish < 0:
+            raise ValueError("polish must be an integer >= 0")
+
+    def mpe(self, event: dict = None, return_log_prob=False, likelihood: dict = None, algorithm="exact", n_iterations=100, tol=1e-9,
+            damping=0.5, polish=10, return_info=False):
         """Most probable explanation: the single most probable completion of `event`, argmax_x P(x, event) over every variable
         not in `event`.  Returns a Series of labels indexed by every variable (sorted names); evidence variables keep their
         labels.  Zero-probability or out-of-domain evidence gives None for the other variables (and a log probability of
         -inf).  With `return_log_prob`, returns (series, natural log of P(x*, event)).  Ties go to the lowest label code.
-        `likelihood`: likelihood findings as in `query` - the maximum is over P(x, event) times the weights, and so is the log."""
+        `likelihood`: likelihood findings as in `query` - the maximum is over P(x, event) times the weights, and so is the log.
+
+        `algorithm="exact"` (default): max-product elimination on the device.
+        `algorithm="lbp"`: an APPROXIMATION for networks on which the exact call raises (a 20 x 20 grid) - at most `n_iterations`
+        flooding sweeps of max-product belief propagation (stopped when no message moves by more than `tol`), the best decoded
+        assignment seen over the sweeps kept, then at most `polish` sweeps of greedy single-variable moves.  Exact on polytrees;
+        on a network with loops there is no bound on the gap to the true maximum.  What holds: the log probability returned is that
+        of the assignment returned, and when `sweeps < polish` no change of a single variable improves it.  The default `damping`
+        is 0.5, not `marginals`' 0.0: max-product messages oscillate where sum-product ones settle, and undamped decodes are poor.
+        `return_info=True` appends {"iterations", "residual", "converged", "best_iteration", "sweeps", "moves"} to the result
+        (exact: zeros, converged).  Where the assignment found has probability 0 - impossible evidence, or a decode that hit a
+        zero of a sparse CPT and was never bettered - the log probability is -inf and the other variables are None."""
+        self._mpe_arguments(algorithm, n_iterations, tol, damping, polish)
         event = dict(event or {})
-        be = self._event_backend(list(event) + list(likelihood or {}))
+        be = self._event_backend(list(event) + list(likelihood or {}), every_cpt=algorithm == "lbp")
         f = be.flat
         ev = [f.id[name] for name in event]
         codes = [f.code_of(v, lab) for v, lab in zip(ev, event.values())]
         more = {"likelihoods": be.likelihood_block([be.encode_likelihood(likelihood, event)])} if likelihood else {}
-        out, log_p = be.engine.mpe(np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev)), **more)
+        evars, ecodes = np.array([ev], np.int32).reshape(1, len(ev)), np.array([codes], np.int32).reshape(1, len(ev))
+        info = {"iterations": 0, "residual": 0.0, "converged": True, "best_iteration": 0, "sweeps": 0, "moves": 0}
+        if algorithm == "exact":
+            out, log_p = be.engine.mpe(evars, ecodes, **more)
+        else:
+            out, log_p, it, res, extra = be.engine.bp_mpe(evars, ecodes, int(n_iterations), tol, damping, int(polish), **more)
+            out[np.isneginf(log_p)] = -1  # (an assignment of probability 0 is no explanation: None, as for impossible evidence)
+            info = {"iterations": int(it[0]), "residual": float(res[0]), "converged": bool(res[0] <= tol),
+                    "best_iteration": int(extra[0, 0]), "sweeps": int(extra[0, 1]), "moves": int(extra[0, 2])}
         names = self._all_names()
         data = decode_labels(f, names, out, event)
         series = pd.Series([data[name][0] for name in names], index=pd.Index(names), dtype=object)
-        return (series, float(log_p[0])) if return_log_prob else series
+        result = (series, float(log_p[0])) if return_log_prob else (series,)
+        if return_info:
+            result = result + (info,)
+        return result if len(result) > 1 else result[0]
 
-    def mpe_frame(self, events: pd.DataFrame, return_log_prob=False, sub_batch=32768):
+    def mpe_frame(self, events: pd.DataFrame, return_log_prob=False, sub_batch=32768, algorithm="exact", n_iterations=100, tol=1e-9,
+                  damping=0.5, polish=10, return_info=False):
         """`mpe` for every row of `events`, in the convention of `query_frame`: the columns are evidence variables, NaN / None =
         not observed in that row.  Rows are grouped by their pattern of observed columns, one engine call per group (in
         sub-batches of `sub_batch` rows).  Returns a DataFrame with the index of `events` and one column per variable (sorted
         names); with `return_log_prob`, (frame, log probabilities as a numpy array).
 
         A row that names every variable - observed values and missing ones (NaN / None) - gets what `impute` returns for it (up
-        to ties between equally probable assignments), without `impute`'s posterior table of prod(card(missing)) cells."""
+        to ties between equally probable assignments), without `impute`'s posterior table of prod(card(missing)) cells.
+
+        `algorithm`, `n_iterations`, `tol`, `damping`, `polish`: as in `mpe`.  `return_info=True` adds the columns
+        ("info", "iterations"), ("info", "residual"), ("info", "converged"), ("info", "best_iteration"), ("info", "sweeps") and
+        ("info", "moves"), as `marginals_frame` does; the variables' columns keep their plain names."""
+        self._mpe_arguments(algorithm, n_iterations, tol, damping, polish)
         cols = list(events.columns)
-        be = self._event_backend(cols)
+        be = self._event_backend(cols, every_cpt=algorithm == "lbp")
         f = be.flat
         ev_ids, codes, observed = encode_frame(be, cols, events)
         n = len(events)
         out = np.zeros((n, len(f.names)), np.int32)
         log_p = np.zeros(n, np.float64)
+        its = np.zeros(n, np.int32)
+        res = np.zeros(n, np.float64)
+        extra = np.zeros((n, 3), np.int32)
         for part, on in iter_parts(pattern_groups(observed), observed, sub_batch):
-            out[part], log_p[part] = be.engine.mpe(*part_args(ev_ids, codes, part, on))
+            if algorithm == "exact":
+                out[part], log_p[part] = be.engine.mpe(*part_args(ev_ids, codes, part, on))
+            else:
+                out[part], log_p[part], its[part], res[part], extra[part] = be.engine.bp_mpe(
+                    *part_args(ev_ids, codes, part, on), int(n_iterations), tol, damping, int(polish))
+        out[np.isneginf(log_p)] = -1
         names = self._all_names()
         frame = pd.DataFrame(decode_labels(f, names, out, events), index=events.index, columns=names)
+        if return_info:
+            frame[("info", "iterations")] = its
+            frame[("info", "residual")] = res
+            frame[("info", "converged")] = res <= tol
+            frame[("info", "best_iteration")] = extra[:, 0]
+            frame[("info", "sweeps")] = extra[:, 1]
+            frame[("info", "moves")] = extra[:, 2]
         return (frame, log_p) if return_log_prob else frame
 
     # ---- all single-variable posteriors (an extension: loopy belief propagation on the device, mibn_bp_batch) -----------------

@@ -1,4 +1,4 @@
-// Host side of loopy belief propagation (mibn_bp_batch): everything the call decides before its first HIP call, in plain C++17 - no
+// Host side of loopy belief propagation (mibn_bp_batch, mibn_bp_mpe_batch): everything the call decides before its first HIP call, in plain C++17 - no
 // HIP header, so that tools/bp_plan_sim.cpp runs it on a CPU (tests/test_bp_host.py) the way sampler_plan_sim runs sampler_plan.h.
 // bp_layout is the ONE description of a request's message state: bp_kernel takes its pointers from it - into dynamic LDS or into the
 // request's slab of the arena -, the plan takes the launch's LDS size and the slab size from it.
@@ -145,11 +145,100 @@ inline int bp_plan(const Network &net, int lds_mode, BpPlan &P, std::string &err
 }
 
 // Requests of one launch: at most `chunk`, and in the global form as many slabs as the budget holds.  0: one slab does not fit.
-inline int64_t bp_launch_requests(const BpPlan &P, int64_t chunk, double budget_bytes) {
+inline int64_t bp_launch_requests(BpForm form, size_t slab_bytes, int64_t chunk, double budget_bytes) {
     chunk = std::max<int64_t>(1, chunk);
-    if (P.form == BpForm::MsgLds) return chunk;
-    const double fit = std::floor(budget_bytes / (double)P.slab_bytes);
+    if (form == BpForm::MsgLds) return chunk;
+    const double fit = std::floor(budget_bytes / (double)slab_bytes);
     return fit < 1.0 ? 0 : (int64_t)std::min((double)chunk, fit);
+}
+inline int64_t bp_launch_requests(const BpPlan &P, int64_t chunk, double budget_bytes) { return bp_launch_requests(P.form, P.slab_bytes, chunk, budget_bytes); }
+
+// ------------------------------------------------------------------------------------- max-product with a decoder (mibn_bp_mpe_batch)
+// The state of a request: the message arrays and lambda exactly as above, then what the decoder keeps -
+//     term[n_vars] f64 | part[64] f64 | cur[n_vars] i32 | kept[n_vars] i32 | (pad to 8) | red
+// term: the score terms of the assignment being scored; part: the 64 partial sums of the pinned score order; cur: the decode of this
+// step; kept: the best candidate so far, which the polish then moves.  red: the reduction slots of bp_kernel, then as many again for
+// the decoder's own reductions (zero flag, moves of a sweep) and the slot every lane reads the score from - always in LDS.
+constexpr int kBpScoreLanes = 64;
+constexpr size_t kBpMpeRedBytes = 2 * kBpRedBytes;
+template <typename I>
+struct BpMpeLayout {
+    I mu0, mu1, nu, lam, term, part, cur, kept, red, total;
+};
+template <typename I>
+MIBN_HD inline BpMpeLayout<I> bp_mpe_layout(I cells, I lam_cells, I n_vars) {
+    const BpLayout<I> S = bp_layout<I>(cells, lam_cells);
+    BpMpeLayout<I> L;
+    L.mu0 = S.mu0;
+    L.mu1 = S.mu1;
+    L.nu = S.nu;
+    L.lam = S.lam;
+    L.term = S.red;
+    L.part = L.term + n_vars * 8;
+    L.cur = L.part + (I)kBpScoreLanes * 8;
+    L.kept = L.cur + n_vars * 4;
+    L.red = (L.kept + n_vars * 4 + 7) / 8 * 8;
+    L.total = L.red + (I)kBpMpeRedBytes;
+    return L;
+}
+
+// The colouring of the moral graph for the polish: u and v are adjacent when some CPT scope holds both.  Greedy - ascending v, the
+// smallest colour no already-coloured neighbour has -, so a colour's members share no factor.  members: CSR by colour, ascending v.
+struct BpColouring {
+    std::vector<int32_t> colour, off, members;
+    int32_t n_colours = 0;
+};
+inline void bp_colour(const BpPlan &P, BpColouring &C) {
+    const size_t n = P.vars.size();
+    C.colour.assign(n, -1);
+    C.n_colours = 0;
+    std::vector<char> used;
+    for (size_t v = 0; v < n; ++v) {
+        used.assign((size_t)C.n_colours + 1, 0);
+        const BpVar &V = P.vars[v];
+        for (int i = 0; i < V.nb_len; ++i) {  // the factors v is in, and everything in their scopes
+            const BpVar &F = P.vars[(size_t)P.edges[(size_t)P.nbr[(size_t)(V.nb_begin + i)]].factor];
+            for (int j = 0; j < F.scope_len; ++j) {
+                const int32_t c = C.colour[(size_t)P.edges[(size_t)(F.edge_begin + j)].var];
+                if (c >= 0) used[(size_t)c] = 1;
+            }
+        }
+        int32_t c = 0;
+        while (used[(size_t)c]) ++c;
+        C.colour[v] = c;
+        C.n_colours = std::max(C.n_colours, c + 1);
+    }
+    C.off.assign((size_t)C.n_colours + 1, 0);
+    for (size_t v = 0; v < n; ++v) ++C.off[(size_t)C.colour[v] + 1];
+    for (int32_t c = 0; c < C.n_colours; ++c) C.off[(size_t)c + 1] += C.off[(size_t)c];
+    C.members.assign(n, 0);
+    std::vector<int32_t> at(C.off.begin(), C.off.end() - 1);
+    for (size_t v = 0; v < n; ++v) C.members[(size_t)at[(size_t)C.colour[v]]++] = (int32_t)v;
+}
+
+struct BpMpePlan {
+    BpPlan bp;  // the records, threads and iter_bytes; its lds / slab_bytes / form are mibn_bp_batch's and unused here
+    BpColouring col;
+    BpMpeLayout<size_t> lds{};
+    size_t slab_bytes = 0;
+    BpForm form = BpForm::MsgLds;
+};
+
+// bp_check_args, and polish_sweeps >= 0
+inline int bp_mpe_check_args(int32_t max_iterations, double tol, double damping, int32_t polish_sweeps, std::string &err) {
+    if (int rc = bp_check_args(max_iterations, tol, damping, err)) return rc;
+    if (polish_sweeps < 0) { err = "bp: polish_sweeps must be at least 0"; return MIBN_E_ARG; }
+    return MIBN_OK;
+}
+
+// The same rule as bp_plan's on the larger state: in LDS when bp_lds != 0 and the whole of it fits 160 KiB.
+inline int bp_mpe_plan(const Network &net, int lds_mode, BpMpePlan &M, std::string &err) {
+    if (int rc = bp_plan(net, lds_mode, M.bp, err)) return rc;
+    bp_colour(M.bp, M.col);
+    M.lds = bp_mpe_layout<size_t>((size_t)M.bp.cells, (size_t)M.bp.lam_cells, (size_t)net.n_vars);
+    M.slab_bytes = lds_align16(M.lds.total);
+    M.form = lds_mode != 0 && M.lds.total <= kSamplerLdsLimit ? BpForm::MsgLds : BpForm::MsgGlobal;
+    return MIBN_OK;
 }
 
 }  // namespace mibn

@@ -190,16 +190,16 @@ constexpr int kLevelStreams = 4;
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
 // steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together), and the two kernels of a call with likelihood
-// findings: the seeds of a planned wave, the tiny kernel's twin, and the one kernel of mibn_bp_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// findings: the seeds of a planned wave, the tiny kernel's twin, the one kernel of mibn_bp_batch and the one of mibn_bp_mpe_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -2807,7 +2807,7 @@ int run_map_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, con
 
 // ---------------------------------------------------------------------------------------------- likelihood findings
 // mibn_set_likelihoods stages a block for the NEXT batch call.  The calls that consume it (mibn_query_batch, mibn_query_batch_ex,
-// mibn_mpe_batch, mibn_map_batch, mibn_bp_batch) take it for their duration - h->lh, null for a block without a single finding: such a call is the call
+// mibn_mpe_batch, mibn_map_batch, mibn_bp_batch, mibn_bp_mpe_batch) take it for their duration - h->lh, null for a block without a single finding: such a call is the call
 // without a block, bit for bit -; the others refuse it.  Either way it is gone when the call returns, whatever the call returns.
 namespace {
 void drop_findings(mibn_ctx *h) {
@@ -3068,15 +3068,22 @@ extern "C" int mibn_gibbs_conditional(mibn_t *h, int32_t n_e, const int32_t *e_v
 // ---------------------------------------------------------------------------------------------- loopy belief propagation
 // mibn_bp_batch: plan (bp_plan.h), upload the records once, then launch by launch - at most `chunk` requests, in the global form as
 // many as have slabs in the arena of lane 0 - upload the evidence, run bp_kernel, download.  Blocking, on the main stream, buffers of
-// its own; last-call statistics only, nothing a later call reads.
+// its own; last-call statistics only, nothing a later call reads.  mibn_bp_mpe_batch (`mx`) is the same call around bp_max_kernel:
+// the larger state, the colouring next to the records, codes / log_p / info in place of the beliefs.
 namespace {
+struct BpMpeOut {
+    int32_t polish_sweeps;
+    int32_t *codes;
+    double *log_p;
+    int32_t *info;  // or null
+};
 int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t max_iterations, double tol,
-            double damping, double *beliefs, int32_t *iterations, double *residual) {
+            double damping, double *beliefs, int32_t *iterations, double *residual, const BpMpeOut *mx = nullptr) {
     const double t_start = now_ms();
     reset_last_stats(h);
     const Network &net = h->net;
     int rc;
-    if ((rc = bp_check_args(max_iterations, tol, damping, h->err))) return rc;
+    if ((rc = mx ? bp_mpe_check_args(max_iterations, tol, damping, mx->polish_sweeps, h->err) : bp_check_args(max_iterations, tol, damping, h->err))) return rc;
     const Findings *F = h->lh;
     for (int64_t b = 0; b < B; ++b) {
         if (e_off[b + 1] < e_off[b] || e_off[b] < 0) { h->err = "request " + std::to_string(b) + ": e_off must be non-negative and ascending"; return MIBN_E_ARG; }
@@ -3088,8 +3095,11 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
         const std::string e = validate_mpe_request(net, rq);  // unknown or duplicate evidence ids, a finding variable that is evidence
         if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
     }
-    BpPlan P;
-    if ((rc = bp_plan(net, h->bp_lds, P, h->err))) return rc;
+    BpMpePlan M;
+    BpPlan &P = M.bp;
+    if ((rc = mx ? bp_mpe_plan(net, h->bp_lds, M, h->err) : bp_plan(net, h->bp_lds, P, h->err))) return rc;
+    const BpForm form = mx ? M.form : P.form;
+    const size_t slab_bytes = mx ? M.slab_bytes : P.slab_bytes;
     if (B == 0) return MIBN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = drain_streams(h))) return rc;  // (the arena of lane 0 is the query calls' too)
@@ -3097,21 +3107,31 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
     const double budget = std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->d_arena[0].cap()));
-    const int64_t per_launch = bp_launch_requests(P, h->chunk, budget);
-    if (per_launch < 1) { h->err = "bp: one request's messages need " + std::to_string((double)P.slab_bytes / 1e9) + " GB, above the arena budget"; return MIBN_E_NOMEM; }
+    const int64_t per_launch = bp_launch_requests(form, slab_bytes, h->chunk, budget);
+    if (per_launch < 1) { h->err = "bp: one request's messages need " + std::to_string((double)slab_bytes / 1e9) + " GB, above the arena budget"; return MIBN_E_NOMEM; }
     const int64_t n_max = std::min(B, per_launch);
-    const size_t lam = (size_t)P.lam_cells;
+    const size_t lam = (size_t)P.lam_cells, nv = (size_t)net.n_vars;
     DevBuf<BpEdge> d_edges;
     DevBuf<BpVar> d_vars;
-    DevBuf<int32_t> d_nbr, d_ev, d_ec, d_lv, d_it;
+    DevBuf<int32_t> d_nbr, d_ev, d_ec, d_lv, d_it, d_nbre, d_coff, d_cmem, d_codes, d_info;
     DevBuf<int64_t> d_eoff, d_loff, d_voff;
-    DevBuf<double> d_val, d_bel, d_res;
+    DevBuf<double> d_val, d_bel, d_res, d_logp;
+    std::vector<int32_t> info_host;  // (a caller without `info`)
     Event ev0, ev1;
     HIP_TRY(h, d_edges.reset(P.edges.size()));
     HIP_TRY(h, d_vars.reset(P.vars.size()));
     HIP_TRY(h, d_nbr.reset(P.nbr_moff.size()));
     HIP_TRY(h, d_eoff.reset((size_t)n_max + 1));
-    HIP_TRY(h, d_bel.reset((size_t)n_max * lam));
+    if (!mx) HIP_TRY(h, d_bel.reset((size_t)n_max * lam));
+    if (mx) {
+        HIP_TRY(h, d_nbre.reset(P.nbr.size()));
+        HIP_TRY(h, d_coff.reset(M.col.off.size()));
+        HIP_TRY(h, d_cmem.reset(M.col.members.size()));
+        HIP_TRY(h, d_codes.reset((size_t)n_max * nv));
+        HIP_TRY(h, d_logp.reset((size_t)n_max));
+        HIP_TRY(h, d_info.reset((size_t)n_max * 3));
+        if (!mx->info) info_host.resize((size_t)n_max * 3);
+    }
     HIP_TRY(h, d_it.reset((size_t)n_max));
     HIP_TRY(h, d_res.reset((size_t)n_max));
     HIP_TRY(h, ev0.ensure());
@@ -3119,17 +3139,24 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
     HIP_TRY(h, hipMemcpyAsync(d_edges, P.edges.data(), P.edges.size() * sizeof(BpEdge), hipMemcpyHostToDevice, S));
     HIP_TRY(h, hipMemcpyAsync(d_vars, P.vars.data(), P.vars.size() * sizeof(BpVar), hipMemcpyHostToDevice, S));
     HIP_TRY(h, hipMemcpyAsync(d_nbr, P.nbr_moff.data(), P.nbr_moff.size() * 4, hipMemcpyHostToDevice, S));
-    const BpKernel kernel = bp_kernel_of(P.form);
-    const size_t lds = bp_lds_bytes(P);
-    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (P.form == BpForm::MsgGlobal && (rc = grow_arena(h, 0, (size_t)n_max * P.slab_bytes, (int64_t)(budget / 8.0), S))) return rc;
-    BpArgs A{};
+    if (mx) {
+        HIP_TRY(h, hipMemcpyAsync(d_nbre, P.nbr.data(), P.nbr.size() * 4, hipMemcpyHostToDevice, S));
+        HIP_TRY(h, hipMemcpyAsync(d_coff, M.col.off.data(), M.col.off.size() * 4, hipMemcpyHostToDevice, S));
+        HIP_TRY(h, hipMemcpyAsync(d_cmem, M.col.members.data(), M.col.members.size() * 4, hipMemcpyHostToDevice, S));
+    }
+    const BpKernel kernel = bp_kernel_of(form);
+    const BpMaxKernel max_kernel = bp_max_kernel_of(form);
+    const size_t lds = mx ? bp_lds_bytes(M) : bp_lds_bytes(P);
+    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute(mx ? (const void *)max_kernel : (const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (form == BpForm::MsgGlobal && (rc = grow_arena(h, 0, (size_t)n_max * slab_bytes, (int64_t)(budget / 8.0), S))) return rc;
+    BpMaxArgs MA{};
+    BpArgs &A = MA.bp;
     A.pool = h->d_pool;
     A.edges = d_edges;
     A.vars = d_vars;
     A.nbr_moff = d_nbr;
     A.slabs = reinterpret_cast<unsigned char *>(h->d_arena[0].get());
-    A.slab_bytes = P.slab_bytes;
+    A.slab_bytes = slab_bytes;
     A.n_vars = net.n_vars;
     A.n_edges = (int32_t)P.edges.size();
     A.cells = P.cells;
@@ -3137,6 +3164,16 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
     A.max_iterations = max_iterations;
     A.tol = tol;
     A.damping = damping;
+    if (mx) {
+        MA.nbr = d_nbre;
+        MA.col_off = d_coff;
+        MA.col_members = d_cmem;
+        MA.n_colours = M.col.n_colours;
+        MA.polish_sweeps = mx->polish_sweeps;
+        MA.codes = d_codes;
+        MA.log_p = d_logp;
+        MA.info = d_info;
+    }
     std::vector<int64_t> off;
     for (int64_t b0 = 0; b0 < B; b0 += n_max) {
         const int64_t n = std::min(n_max, B - b0);
@@ -3177,15 +3214,21 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
             A.values = d_val;
         }
         h->stats.h2d_ms += now_ms() - t0;
-        A.beliefs = d_bel;
+        A.beliefs = mx ? nullptr : d_bel.get();
         A.iterations = d_it;
         A.residual = d_res;
         HIP_TRY(h, hipEventRecord(ev0, S));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3((unsigned)P.threads), lds, S, A);
+        if (mx) hipLaunchKernelGGL(max_kernel, dim3((unsigned)n), dim3((unsigned)P.threads), lds, S, MA);
+        else hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3((unsigned)P.threads), lds, S, A);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(ev1, S));
         t0 = now_ms();
-        HIP_TRY(h, hipMemcpyAsync(beliefs + (size_t)b0 * lam, d_bel, (size_t)n * lam * 8, hipMemcpyDeviceToHost, S));
+        if (mx) {
+            HIP_TRY(h, hipMemcpyAsync(mx->codes + (size_t)b0 * nv, d_codes, (size_t)n * nv * 4, hipMemcpyDeviceToHost, S));
+            HIP_TRY(h, hipMemcpyAsync(mx->log_p + b0, d_logp, (size_t)n * 8, hipMemcpyDeviceToHost, S));
+            HIP_TRY(h, hipMemcpyAsync(mx->info ? mx->info + (size_t)b0 * 3 : info_host.data(), d_info, (size_t)n * 12, hipMemcpyDeviceToHost, S));
+        } else
+            HIP_TRY(h, hipMemcpyAsync(beliefs + (size_t)b0 * lam, d_bel, (size_t)n * lam * 8, hipMemcpyDeviceToHost, S));
         HIP_TRY(h, hipMemcpyAsync(iterations + b0, d_it, (size_t)n * 4, hipMemcpyDeviceToHost, S));
         HIP_TRY(h, hipMemcpyAsync(residual + b0, d_res, (size_t)n * 8, hipMemcpyDeviceToHost, S));
         HIP_TRY(h, hipStreamSynchronize(S));
@@ -3194,13 +3237,13 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
         HIP_TRY(h, hipEventElapsedTime(&ms, ev0, ev1));
         double iters = 0;
         for (int64_t r = 0; r < n; ++r) iters += iterations[b0 + r];
-        book_stat(h, kStatBp, 1, ms, P.iter_bytes * iters, (double)n, true, false);
+        book_stat(h, mx ? kStatBpMax : kStatBp, 1, ms, P.iter_bytes * iters, (double)n, true, false);
         h->stats.kernel_ms += ms;
         h->stats.n_launches += 1;
         h->stats.n_workgroups += (double)n;
         h->stats.alg_bytes += P.iter_bytes * iters;
     }
-    if (P.form == BpForm::MsgGlobal) h->stats.arena_bytes = (double)n_max * (double)P.slab_bytes;
+    if (form == BpForm::MsgGlobal) h->stats.arena_bytes = (double)n_max * (double)slab_bytes;
     h->stats.total_ms = now_ms() - t_start;
     return MIBN_OK;
 }
@@ -3214,6 +3257,18 @@ extern "C" int mibn_bp_batch(mibn_t *h, int64_t B, const int64_t *e_off, const i
     if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
     if (int rc = lh.take(B)) return rc;
     return drained_on_error(h, bp_body(h, B, e_off, e_vars, e_codes, max_iterations, tol, damping, beliefs, iterations, residual), drain_main_unchecked);
+}
+
+extern "C" int mibn_bp_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t max_iterations,
+                                 double tol, double damping, int32_t polish_sweeps, int32_t *codes, double *log_p, int32_t *iterations,
+                                 double *residual, int32_t *info) {
+    TakeFindings lh(h);
+    if (!h || B < 0 || (B && (!e_off || !codes || !log_p || !iterations || !residual))) return MIBN_E_ARG;
+    if (int rc = check_state(h, kNeedIdle)) return rc;
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
+    if (int rc = lh.take(B)) return rc;
+    const BpMpeOut mx{polish_sweeps, codes, log_p, info};
+    return drained_on_error(h, bp_body(h, B, e_off, e_vars, e_codes, max_iterations, tol, damping, nullptr, iterations, residual, &mx), drain_main_unchecked);
 }
 
 extern "C" int mibn_sample(mibn_t *h, int64_t n_samples, int32_t n_init, const int32_t *init_vars, const int32_t *init_codes,

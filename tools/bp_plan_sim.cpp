@@ -9,6 +9,8 @@
 //   layout  cells lam_cells                       bp_layout alone
 //   launch  lds_mode chunk budget_bytes           requests of one launch (0: a slab does not fit)
 //   args    max_iterations tol damping            the argument check (tol and damping as strtod reads them: nan, -1, 0x1p-3 ..)
+//   mpe     lds_mode                              mibn_bp_mpe_batch: the colouring (colour of each variable, members per colour as CSR), bp_mpe_layout, the form
+//   mpe_args max_iterations tol damping polish    its argument check
 // output: one line of key=value pairs per command (lists comma separated; edges / vars = the eight words of every record), or
 //   error=<MIBN_* code> msg=<the message, to the end of the line>
 #include <algorithm>
@@ -66,6 +68,25 @@ int main() {
             const int32_t it = (int32_t)geti();
             const double tol = getd(), damping = getd();
             const int rc = bp_check_args(it, tol, damping, err);
+            if (rc) std::printf("error=%d msg=%s\n", rc, err.c_str());
+            else std::printf("ok=1\n");
+        } else if (cmd == "mpe") {
+            const int lds_mode = (int)geti();
+            BpMpePlan M;
+            const int rc = bp_mpe_plan(net, lds_mode, M, err);
+            if (rc) { std::printf("error=%d msg=%s\n", rc, err.c_str()); continue; }
+            const BpMpeLayout<size_t> &L = M.lds;
+            std::printf("form=%s n_colours=%d mu0=%zu mu1=%zu nu=%zu lam=%zu term=%zu part=%zu cur=%zu kept=%zu red=%zu total=%zu slab=%zu threads=%d",
+                        bp_form_name(M.form), M.col.n_colours, L.mu0, L.mu1, L.nu, L.lam, L.term, L.part, L.cur, L.kept, L.red, L.total, M.slab_bytes,
+                        M.bp.threads);
+            put_list("colour", M.col.colour.data(), M.col.colour.size());
+            put_list("col_off", M.col.off.data(), M.col.off.size());
+            put_list("col_members", M.col.members.data(), M.col.members.size());
+            std::printf("\n");
+        } else if (cmd == "mpe_args") {
+            const int32_t it = (int32_t)geti();
+            const double tol = getd(), damping = getd();
+            const int rc = bp_mpe_check_args(it, tol, damping, (int32_t)geti(), err);
             if (rc) std::printf("error=%d msg=%s\n", rc, err.c_str());
             else std::printf("ok=1\n");
         } else if (cmd == "plan" || cmd == "launch") {
