@@ -225,7 +225,7 @@ int mibn_map_batch(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, c
  * CSR layout: request b has the findings l_vars[l_off[b] .. l_off[b + 1]); finding k has the weights values[v_off[k] .. v_off[k + 1]),
  * exactly card(l_vars[k]) of them (v_off has one entry more than l_vars and is indexed like it).
  * The block is copied.  It belongs to the next batch call and is gone when that call returns, whatever it returns:
- *   mibn_query_batch, mibn_query_batch_ex, mibn_mpe_batch, mibn_map_batch, mibn_bp_batch and mibn_bp_mpe_batch consume it; their B must be the block's (MIBN_E_ARG);
+ *   mibn_query_batch, mibn_query_batch_ex, mibn_mpe_batch, mibn_map_batch, mibn_bp_batch, mibn_bp_mpe_batch and mibn_bp_evidence_batch consume it; their B must be the block's (MIBN_E_ARG);
  *   mibn_submit_batch and mibn_expect_batch refuse it with MIBN_E_STATE, mibn_posterior_sample_batch with MIBN_E_ARG.
  * A block without a single finding (B = 0 with a call of no requests, or all rows empty) is legal: the call is bit for bit the call
  * without a block.  A call with findings is planned by the host's workers only - no plan templates, no device planner, no adaptive
@@ -325,6 +325,55 @@ int mibn_bp_mpe_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t 
                       int32_t *codes /* B * n_vars */, double *log_p /* B */,
                       int32_t *iterations /* B */, double *residual /* B */,
                       int32_t *info /* B * 3 or NULL: best_iteration, sweeps run, moves made */);
+
+/*
+ * The Bethe approximation of log P(e) and the belief of every family (a node with its parents) from loopy belief propagation, for B
+ * requests at once, with the family beliefs optionally added into expected-count tables - where mibn_query_batch_ex, its P(e) form
+ * and mibn_expect_batch return MIBN_E_NOMEM or MIBN_E_LIMIT (a 20 x 20 grid).  log_z[b] estimates log of (P(e) times the findings'
+ * weights), as a logarithm: it stays finite where P(e) underflows.  Exact on a polytree once the residual is 0; on a loopy network an
+ * approximation WITHOUT a bound and with either sign of error; on a request that did not converge it is the Bethe value of the
+ * messages of the last step (read `residual`).  Deterministic: no seed, no planner, no per-request program.
+ *   Messages: factor graph, edges, lambda, start, flooding steps 1 to 4, stop rule and zero-mass rule are word for word those of
+ *     mibn_bp_batch.  After the loop has ended at step t:
+ *   Final phase 1: nu* = step 1 applied once more to the final mu (the messages of step t), with its zero rule.  Everything below
+ *     reads the final mu and nu*.
+ *   Factor f = f_v: for every cell c in ascending C-order, t_c = f[c] times nu*_(f,j)(c_j) for ascending j, over ALL positions;
+ *     Z_f = the sum of t_c over ascending c; the family belief is b_f(c) = t_c / Z_f.
+ *   Variable v: Z_v = the sum over ascending x of lambda_v(x) * prod over e in N(v), ascending, of mu_e(x) - the normaliser of the
+ *     belief; the beliefs are exactly those of mibn_bp_batch.
+ *   Edge e: Z_e = the sum over ascending x of mu_e(x) * nu*_e(x).
+ *   Terms: term_v = log Z_(f_v) + log Z_v - log Z_(f_v,0) - log Z_(f_v,1) - .., evaluated left to right over the edges of factor v
+ *     in ascending position (natural logarithm).
+ *   log_z = the sum of the terms by the score rule of mibn_bp_mpe_batch: partial_l = the sum of term_v over v = l, l + 64, ..
+ *     ascending; log_z = the sum of partial_l for l = 0 .. 63 ascending.  The order does not depend on the workgroup size.
+ *   Zero mass - any of these normalisers is 0, or a normaliser of the final phase 1 is 0, or the loop saw one: log_z = -inf, every
+ *     belief and family belief 0.0, residual 0, iterations[b] the step in which it was seen (the last step for the final phase).
+ *   beliefs (may be NULL), iterations, residual: as mibn_bp_batch, byte for byte.
+ *   fbeliefs (may be NULL): fbeliefs[b * fcells + foff[v] + c] = b_(f_v)(c), where foff[v] = the sum of the table cells of the factors
+ *     below v and fcells their total, c the C-order index in the scope (parents.., v) - the tables back to back, not the pool's layout.
+ *   acc (may be NULL; n_acc must be fcells): expected counts, in the layout of a family-belief row.  The call ADDS to what it is given,
+ *     as mibn_expect_batch does: for every cell c, acc[c] = acc[c] + weight[b] * b_f(c) for b ascending over the whole call, one
+ *     addition after the other (no floating-point atomics).  weight NULL: 1.0 each.  A zero-mass request adds weight * 0.0.
+ * The result - acc included - is a function of (network, the requests in their order, max_iterations, tol, damping, weight) alone: bit
+ * for bit the same under any chunking (options "chunk", "arena_gb") and in either memory form; a request's log_z, beliefs and family
+ * beliefs are the same alone or in any batch, at any position.  A request's messages, Z_f, terms and partials live in the LDS of its
+ * workgroup when together they fit in 160 KiB and option "bp_lds" is not 0, else in a slab of the arena.  With fbeliefs or acc the
+ * launch's family beliefs are kept in the arena too, one row per request behind the slabs; a launch holds as many requests as "chunk" allows and as
+ * have a slab (second form) plus such a row in the "arena_gb" budget; MIBN_E_NOMEM only if one request does not fit.
+ * Blocking; plans on the calling thread; changes no option and nothing a later call reads; books nothing into the totals.
+ * mibn_last_stats / mibn_last_kernel_stats describe it in the row "bp_evidence_kernel": launches, HIP-event time, items = requests,
+ * and alg_bytes by bp_kernel's rule plus one more pass over the CPT cells, 8 * fcells, per request; with acc a second row,
+ * "bp_accumulate_kernel", one launch after each of the first (alg_bytes = 8 * fcells * (requests of the launch + 2)).
+ * Consumes a pending mibn_set_likelihoods block (its B must be this call's).
+ * Errors, all before anything is enqueued: those of mibn_bp_batch, and MIBN_E_ARG for n_acc != fcells when acc is given and for a
+ * negative, NaN or infinite weight.
+ */
+int mibn_bp_evidence_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                           int32_t max_iterations, double tol, double damping,
+                           const double *weight /* B or NULL */, double *log_z /* B */,
+                           double *beliefs /* B * sum(card) or NULL */, double *fbeliefs /* B * fcells or NULL */,
+                           int64_t n_acc, double *acc /* fcells, in/out, or NULL */,
+                           int32_t *iterations /* B */, double *residual /* B */);
 
 /* Statistics of the last mibn_query_batch call (for the roofline report). */
 typedef struct mibn_stats {

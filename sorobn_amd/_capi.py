@@ -23,7 +23,7 @@ SYMBOLS = [
     "mibn_comm_reduce_i64", "mibn_comm_allreduce_max_f64", "mibn_comm_barrier", "mibn_gibbs_conditional", "mibn_sample_probe",
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
     "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch", "mibn_map_batch",
-    "mibn_ci_tests", "mibn_set_likelihoods", "mibn_bp_batch", "mibn_bp_mpe_batch",
+    "mibn_ci_tests", "mibn_set_likelihoods", "mibn_bp_batch", "mibn_bp_mpe_batch", "mibn_bp_evidence_batch",
 ]
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
@@ -87,6 +87,8 @@ def lib():
         L.mibn_set_likelihoods.argtypes = [vp, C.c_int64, i64p, i32p, i64p, f64p]
         L.mibn_bp_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, C.c_int32, C.c_double, C.c_double, f64p, i32p, f64p]
         L.mibn_bp_mpe_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, C.c_int32, C.c_double, C.c_double, C.c_int32, i32p, f64p, i32p, f64p, i32p]
+        L.mibn_bp_evidence_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, C.c_int32, C.c_double, C.c_double, f64p, f64p, f64p, f64p, C.c_int64, f64p,
+                                             i32p, f64p]
         L.mibn_posterior_sample_batch.argtypes = [vp, C.c_int64, i64p, i32p, i32p, i64p, C.c_uint64, C.c_uint32, i32p, f64p]
         L.mibn_expect_batch.argtypes = [vp, C.c_uint32, C.c_int64, i64p, i32p, i64p, i32p, i32p, i64p, i64p, f64p, C.c_int64, f64p, f64p]
         L.mibn_plan_order.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, i32p, i32p]
@@ -253,6 +255,7 @@ class Engine:
             self._h, len(card), _p(card, C.c_int32), _p(scope_off, C.c_int64),
             _p(scope_vars, C.c_int32), _p(value_off, C.c_int64), _p(values, C.c_double)))
         self.card = card
+        self.family_off = np.concatenate([[0], np.cumsum(np.diff(value_off))]).astype(np.int64)  # factor v's cells in a family-belief row
         self._card_list = card.tolist()
         self._one = {}
 
@@ -431,6 +434,50 @@ class Engine:
         ecodes = _i32(ecodes).reshape(B, -1)
         e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
         return self.bp_mpe_batch(e_off, evars.reshape(-1), ecodes.reshape(-1), max_iterations, tol, damping, polish_sweeps, likelihoods=likelihoods)
+
+    def bp_evidence_batch(self, e_off, e_vars, e_codes, max_iterations=100, tol=1e-9, damping=0.0, likelihoods=None, weight=None, acc=None,
+                          beliefs=False, fbeliefs=False):
+        """CSR evidence -> (log_z[B] float64, beliefs[B, sum(card)] or None, fbeliefs[B, fcells] or None, iterations[B] int32,
+        residual[B] float64): the Bethe approximation of log P(e) and the belief of every family from loopy belief propagation
+        (mibn_bp_evidence_batch).  Family v's cells are at columns family_off[v] .. family_off[v + 1], in the C-order of (parents.., v).
+        acc: a contiguous float64 array of fcells expected counts, updated IN PLACE - every request's family beliefs are added, times
+        weight[b] (None: 1.0), in request order.  beliefs / fbeliefs: whether to return them.  likelihoods: as in query_batch."""
+        e_off = _i64(e_off)
+        B = len(e_off) - 1
+        e_vars, e_codes = _i32(e_vars), _i32(e_codes)
+        fcells = int(self.family_off[-1])
+        if acc is not None and not (isinstance(acc, np.ndarray) and acc.dtype == np.float64 and acc.flags.c_contiguous and acc.flags.writeable):
+            raise ValueError("acc must be a writeable C-contiguous float64 array (it is updated in place)")
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.float64)
+            if len(w) != B:
+                raise ValueError("weight needs one entry per request")
+        log_z = np.zeros(B, np.float64)
+        bel = np.zeros((B, int(np.sum(self.card, dtype=np.int64))), np.float64) if beliefs else None
+        fbel = np.zeros((B, fcells), np.float64) if fbeliefs else None
+        iterations = np.zeros(B, np.int32)
+        residual = np.zeros(B, np.float64)
+        if likelihoods is not None:
+            self.set_likelihoods(likelihoods)
+        pad, padf = np.zeros(1, np.int32), np.zeros(1, np.float64)
+
+        def opt(a):
+            return None if a is None else _p(a.reshape(-1) if a.size else padf, C.c_double)
+        self._check(self._L.mibn_bp_evidence_batch(
+            self._h, B, _p(e_off, C.c_int64), _p(e_vars if len(e_vars) else pad, C.c_int32), _p(e_codes if len(e_codes) else pad, C.c_int32),
+            int(max_iterations), float(tol), float(damping), opt(w), _p(log_z if B else padf, C.c_double), opt(bel), opt(fbel),
+            int(acc.size) if acc is not None else 0, opt(acc), _p(iterations if B else pad, C.c_int32), _p(residual if B else padf, C.c_double)))
+        return log_z, bel, fbel, iterations, residual
+
+    def bp_evidence(self, evars, ecodes, max_iterations=100, tol=1e-9, damping=0.0, **more):
+        """Fixed-shape batch: evars[B, ne], ecodes[B, ne] -> what bp_evidence_batch returns, like bp."""
+        evars = _i32(evars)
+        B = len(evars)
+        evars = evars.reshape(B, -1)
+        ecodes = _i32(ecodes).reshape(B, -1)
+        e_off = np.arange(B + 1, dtype=np.int64) * evars.shape[1]
+        return self.bp_evidence_batch(e_off, evars.reshape(-1), ecodes.reshape(-1), max_iterations, tol, damping, **more)
 
     def posterior_sample_batch(self, e_off, e_vars, e_codes, s_off, seed=0, flags=0):
         """CSR evidence + sample offsets s_off[B + 1] -> (codes[s_off[B] - s_off[0], n_vars] int32, p_e[B] float64): exact samples of

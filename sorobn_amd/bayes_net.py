@@ -37,7 +37,7 @@ import numpy as np
 import pandas as pd
 
 from . import _capi
-from .events import decode_labels, encode_frame, iter_parts, label_table, part_args, pattern_groups
+from .events import csr_rows, decode_labels, encode_frame, iter_parts, label_table, part_args, pattern_groups
 from .flatten import flatten
 
 __all__ = ["BayesNet", "accelerate", "Backend"]
@@ -1341,7 +1341,23 @@ class BayesNet:
             out = out / z if z > 0 else np.zeros(n, np.float64)
         return out
 
-    def evidence_proba(self, X, log=False, sub_batch=32768):
+    def _bethe_rows(self, be, ev_ids, codes, observed, sub_batch, n_iterations, tol, damping):
+        """(log_z, iterations, residual) of every row of `codes`: the Bethe approximation of log P(row) from loopy belief propagation,
+        one request per row in row order, in engine calls of `sub_batch` rows.  Every CPT takes part; with CPTs that are not all
+        distributions the log_z of the empty event is subtracted: one more request, as `_evidence_rows` does with Z."""
+        n = len(codes)
+        log_z, its, res = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        step = max(1, int(sub_batch))
+        for s in range(0, n, step):
+            rows = slice(s, s + step)
+            log_z[rows], _, _, its[rows], res[rows] = be.engine.bp_evidence_batch(*csr_rows(ev_ids, codes[rows], observed[rows]),
+                                                                                  int(n_iterations), tol, damping)
+        if n and not self._cpts_are_distributions(be):
+            z = float(be.engine.bp_evidence_batch(np.zeros(2, np.int64), [], [], int(n_iterations), tol, damping)[0][0])
+            log_z = log_z - z if np.isfinite(z) else np.full(n, -np.inf)
+        return log_z, its, res
+
+    def evidence_proba(self, X, log=False, sub_batch=32768, algorithm="exact", n_iterations=100, tol=1e-9, damping=0.0, return_info=False):
         """Probability of an observed event, P(e) = the normalised joint summed over every unobserved variable: the reference's
         `predict_proba` "also for a partial event" (bayes_net.py:934-962), without its dense table of the observed columns.
 
@@ -1349,34 +1365,103 @@ class BayesNet:
         in that row (the convention of `query_frame` and `mpe_frame`).  Rows are grouped by their pattern of observed columns, one
         engine call per group (in sub-batches of `sub_batch` rows).  A label outside its domain, or an event of probability zero,
         gives 0 (log: -inf).  Unknown column names raise KeyError before any engine work.  With `log`, natural logarithms; a
-        P(e) below the smallest double reads as 0 and its log as -inf."""
+        P(e) below the smallest double reads as 0 and its log as -inf.
+
+        `algorithm="lbp"`: an APPROXIMATION for networks on which the exact call raises (a 20 x 20 grid) - the Bethe approximation
+        of log P(e) from at most `n_iterations` flooding sweeps of loopy belief propagation (`tol`, `damping` as in `marginals`), one
+        request per row, every CPT taking part.  Exact on polytrees; on a network with loops it has NO error bound, and its error has
+        either sign: it is not a lower bound of log P(e).  With `log` it returns the logarithm itself, never the logarithm of an
+        underflowed number: a fully observed row of a 1 000-variable chain has a finite log.  Without `log`, its exponential.
+        `return_info=True`: (result, info) - for a dict {"iterations", "residual", "converged"}, for a DataFrame a frame of these
+        three columns with X's index (exact: zeros, converged)."""
+        self._mpe_arguments(algorithm, n_iterations, tol, damping, 0)
+        lbp = algorithm == "lbp"
         if isinstance(X, dict):
             cols = list(X)
-            be = self._event_backend(cols)
+            be = self._event_backend(cols, every_cpt=lbp)
             f = be.flat
             ev_ids = np.array([f.id[c] for c in cols], np.int32)
             observed = np.array([X[c] is not None for c in cols], bool).reshape(1, len(cols))
             codes = np.array([f.code_of(int(v), X[c]) if X[c] is not None else -1 for c, v in zip(cols, ev_ids)],
                              np.int32).reshape(1, len(cols))
-            p = float(self._evidence_rows(be, ev_ids, codes, observed, sub_batch)[0])
-            if log:
-                return float(np.log(p)) if p > 0 else -np.inf
-            return p
+            info = {"iterations": 0, "residual": 0.0, "converged": True}
+            if lbp:
+                log_z, its, res = self._bethe_rows(be, ev_ids, codes, observed, sub_batch, n_iterations, tol, damping)
+                info = {"iterations": int(its[0]), "residual": float(res[0]), "converged": bool(res[0] <= tol)}
+                p = float(log_z[0]) if log else float(np.exp(log_z[0]))
+            else:
+                p = float(self._evidence_rows(be, ev_ids, codes, observed, sub_batch)[0])
+                if log:
+                    p = float(np.log(p)) if p > 0 else -np.inf
+            return (p, info) if return_info else p
         cols = list(X.columns)
-        be = self._event_backend(cols)
+        be = self._event_backend(cols, every_cpt=lbp)
         ev_ids, codes, observed = encode_frame(be, cols, X)
-        p = self._evidence_rows(be, ev_ids, codes, observed, sub_batch)
-        if log:
-            with np.errstate(divide="ignore"):
-                p = np.log(p)
-        return pd.Series(p, index=X.index, dtype=np.float64)
+        its, res = np.zeros(len(X), np.int32), np.zeros(len(X), np.float64)
+        if lbp:
+            p, its, res = self._bethe_rows(be, ev_ids, codes, observed, sub_batch, n_iterations, tol, damping)
+            if not log:
+                p = np.exp(p)
+        else:
+            p = self._evidence_rows(be, ev_ids, codes, observed, sub_batch)
+            if log:
+                with np.errstate(divide="ignore"):
+                    p = np.log(p)
+        out = pd.Series(p, index=X.index, dtype=np.float64)
+        if return_info:
+            return out, pd.DataFrame({"iterations": its, "residual": res, "converged": res <= tol}, index=X.index)
+        return out
 
-    def log_likelihood(self, X, sub_batch=32768) -> float:
+    def log_likelihood(self, X, sub_batch=32768, algorithm="exact", n_iterations=100, tol=1e-9, damping=0.0) -> float:
         """Log-likelihood of a data set: the sum over its rows of log P(row) (`evidence_proba`; NaN / None = not observed in
-        that row).  A row of probability zero makes it -inf."""
+        that row).  A row of probability zero makes it -inf.  `algorithm="lbp"`: the sum of the rows' Bethe approximations, as in
+        `evidence_proba` - finite where the rows' probabilities underflow, without an error bound on a network with loops."""
+        more = dict(algorithm=algorithm, n_iterations=n_iterations, tol=tol, damping=damping)
         if isinstance(X, dict):
-            return self.evidence_proba(X, log=True, sub_batch=sub_batch)
-        return float(self.evidence_proba(X, log=True, sub_batch=sub_batch).sum())
+            return self.evidence_proba(X, log=True, sub_batch=sub_batch, **more)
+        return float(self.evidence_proba(X, log=True, sub_batch=sub_batch, **more).sum())
+
+    # ---- the joint of every family (an extension: the factor beliefs of loopy belief propagation, mibn_bp_evidence_batch) ----
+    def family_marginals(self, event: dict = None, likelihood: dict = None, algorithm="lbp", n_iterations=100, tol=1e-9, damping=0.0,
+                         return_info=False):
+        """The posterior joint of every family - a node with its parents - given `event`: {node: Series over [*parents, node]} in
+        the index layout of `bn.P[node]` (every cell present, zeros included; a member the event observes holds its one-hot).
+
+        `algorithm="lbp"` (default): the factor beliefs of loopy belief propagation, one device call for all families - exact on
+        polytrees, on a network with loops an approximation WITHOUT an error bound (`n_iterations`, `tol`, `damping`,
+        `return_info` as in `marginals`).  It answers where `query(*family)` raises (a 20 x 20 grid).
+        `algorithm="exact"`: one `query(*family)` per node, for comparison; it raises what `query` raises where that is refused -
+        a family member in the event among them.  `likelihood`: likelihood findings as in `query`."""
+        self._marginals_algorithm(algorithm)
+        if algorithm == "lbp":
+            self._mpe_arguments(algorithm, n_iterations, tol, damping, 0)
+        event = dict(event or {})
+        be = self._event_backend(list(event) + list(likelihood or {}), every_cpt=True)
+        f = be.flat
+        info = {"iterations": 0, "residual": 0.0, "converged": True}
+        if algorithm == "lbp":
+            findings = be.encode_likelihood(likelihood, event)
+            _, ev, codes = be.encode((), event, findings)
+            more = {"likelihoods": be.likelihood_block([findings])} if findings else {}
+            _, _, fbel, it, res = be.engine.bp_evidence(np.array(ev, np.int32).reshape(1, len(ev)), np.array(codes, np.int32).reshape(1, len(ev)),
+                                                        int(n_iterations), tol, damping, fbeliefs=True, **more)
+            info = {"iterations": int(it[0]), "residual": float(res[0]), "converged": bool(res[0] <= tol)}
+        out = {}
+        off = be.engine.family_off
+        for v, node in enumerate(f.names):
+            members = [f.names[u] for u in f.scope[v]]
+            if len(members) > 1:
+                index = pd.MultiIndex.from_product([f.domains[u] for u in f.scope[v]], names=members)
+            else:
+                index = pd.Index(f.domains[v], name=node)
+            if algorithm == "lbp":
+                values = fbel[0, off[v]:off[v + 1]].copy()
+            else:
+                ans = self.query(*members, event=event, **({"likelihood": likelihood} if likelihood else {}))
+                ans = ans.reorder_levels(members) if len(members) > 1 else ans
+                values = ans.reindex(index, fill_value=0.0).to_numpy()
+            out[node] = pd.Series(values, index=index, name=self.P[node].name if node in self.P else None)
+        return (out, info) if return_info else out
 
     # ---- SURVEY.md section 8f rank 1: the joint and likelihoods (bayes_net.py:398-465, 934-973) -----------------
     # cells of the observed columns' dense table from which predict_proba answers row by row through P(e): the planner builds no
@@ -1477,11 +1562,14 @@ class BayesNet:
         from . import learning
         return learning.fit(self, X)
 
-    def fit_em(self, X: pd.DataFrame, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=32768):
+    def fit_em(self, X: pd.DataFrame, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=32768, algorithm="exact",
+               bp_iterations=100, bp_tol=1e-9, damping=0.0):
         """CPTs from rows with missing values by expectation-maximisation, expected counts on the device (an extension:
-        the reference's `fit` drops incomplete rows) - see `learning.fit_em`."""
+        the reference's `fit` drops incomplete rows) - see `learning.fit_em`.  `algorithm="lbp"`: the E-step from the family
+        beliefs of loopy belief propagation, for networks beyond the reach of the exact one."""
         from . import learning
-        return learning.fit_em(self, X, n_iter=n_iter, tol=tol, prior_count=prior_count, init=init, sub_batch=sub_batch)
+        return learning.fit_em(self, X, n_iter=n_iter, tol=tol, prior_count=prior_count, init=init, sub_batch=sub_batch, algorithm=algorithm,
+                               bp_iterations=bp_iterations, bp_tol=bp_tol, damping=damping)
 
     def score(self, X: pd.DataFrame, score="bic", ess=1.0) -> float:
         """The structure's score on the complete rows of X: the sum of its families' "loglik", "bic", "aic", "bdeu" or "k2"

@@ -16,6 +16,7 @@
 // bp_start, bp_phase1 and bp_phase2 are the ONE copy of the start and of the two message phases; both kernels are made of them.
 // bp_max_kernel adds, after the reduce of every step, the decoder of include/mibn.h - max-marginals, decode, score in the pinned order,
 // keep the best candidate - and after the loop the polish (iterated conditional modes, colour by colour) and the final score.
+// bp_evidence_kernel adds, after bp_kernel's loop, the final phase of mibn_bp_evidence_batch: the Bethe log Z and the family beliefs.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -405,7 +406,149 @@ __global__ __launch_bounds__(64 * kBpMaxWaves) void bp_max_kernel(const BpMaxArg
     }
 }
 
+// ------------------------------------------------------------------------------------------- Bethe log Z and family beliefs
+// bp_evidence_kernel: bp_kernel's loop, then the final phase include/mibn.h pins for mibn_bp_evidence_batch - nu* from the final mu,
+// then a lane per variable v for Z_(f_v) (every cell of the factor, ascending), Z_v with v's belief, the Z_e of factor v's edges and
+// term_v; the 64 partials and their sum as in bp_score; and the family-belief cells, a wave per factor and a lane per cell, each
+// recomputing its t_c in the pinned order and dividing by the published Z_f.
+struct BpEvArgs {
+    BpArgs bp;                 // beliefs may be null
+    const int32_t *foff;       // [n_vars + 1]: factor v's cells in a family-belief row
+    int32_t fcells;
+    double *log_z;             // [n]
+    double *fbeliefs;          // [n][fcells] or null
+};
+
+// t_c of factor F: f[c] times nu_(f,j)(c_j) for ascending j
+__device__ __forceinline__ double bp_family_cell(const BpArgs &A, const BpVar &F, const double *nu, int c) {
+#pragma clang fp contract(off)
+    double t = A.pool[F.table_off + c];
+    for (int j = 0; j < F.scope_len; ++j) {
+        const BpEdge J = A.edges[F.edge_begin + j];
+        t *= nu[J.moff + (c / J.stride) % J.card];
+    }
+    return t;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(64 * kBpMaxWaves) void bp_evidence_kernel(const BpEvArgs M) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const BpArgs &A = M.bp;
+    const BpEvLayout<size_t> L = bp_ev_layout<size_t>((size_t)A.cells, (size_t)A.lam_cells, (size_t)A.n_vars);
+    const size_t req = blockIdx.x;
+    unsigned char *base = LDS ? smem : A.slabs + req * A.slab_bytes;
+    double *mu_prev = reinterpret_cast<double *>(base + L.mu0);
+    double *mu_next = reinterpret_cast<double *>(base + L.mu1);
+    double *nu = reinterpret_cast<double *>(base + L.nu);
+    double *lam = reinterpret_cast<double *>(base + L.lam);
+    double *zf = reinterpret_cast<double *>(base + L.zf);
+    double *term = reinterpret_cast<double *>(base + L.term);
+    double *part = reinterpret_cast<double *>(base + L.part);
+    double *red = reinterpret_cast<double *>(smem + (LDS ? L.red : 0));
+    int *zred = reinterpret_cast<int *>(red + kBpMaxWaves);
+    double *fred = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(red) + kBpRedBytes);  // the final phase's own slots
+    int *fzred = reinterpret_cast<int *>(fred + kBpMaxWaves);
+    const int tid = threadIdx.x, nt = blockDim.x;
+    double *out = A.beliefs ? A.beliefs + req * (size_t)A.lam_cells : nullptr;
+    double *fout = M.fbeliefs ? M.fbeliefs + req * (size_t)M.fcells : nullptr;
+
+    double r = 0.0;
+    bool z = false;
+    bp_start(A, req, mu_prev, lam, red, zred, z);
+    int it = 0;
+    if (!z) {
+        for (it = 1;; ++it) {
+            bp_phase1(A, lam, mu_prev, nu, z);
+            __syncthreads();
+            bp_phase2<false>(A, mu_prev, mu_next, nu, r, z);
+            bp_reduce(r, z, red, zred);
+            double *t = mu_prev; mu_prev = mu_next; mu_next = t;
+            if (z || r <= A.tol || it == A.max_iterations) break;  // the same in every lane
+        }
+    }
+    if (!z) {
+        // ---- final phase 1: nu* from the final mu
+        bp_phase1(A, lam, mu_prev, nu, z);
+        __syncthreads();
+        for (int v = tid; v < A.n_vars; v += nt) {
+            const BpVar V = A.vars[v];
+            double s = 0.0;  // Z_f of factor v
+            for (int c = 0; c < V.table_cells; ++c) s += bp_family_cell(A, V, nu, c);
+            zf[v] = s;
+            z = z || s == 0.0;
+            double tv = log(s);
+            s = 0.0;  // Z_v, and v's belief as bp_kernel forms it
+            for (int x = 0; x < V.card; ++x) {
+                double p = lam[V.loff + x];
+                for (int i = 0; i < V.nb_len; ++i) p *= mu_prev[A.nbr_moff[V.nb_begin + i] + x];
+                if (out) out[V.loff + x] = p;
+                s += p;
+            }
+            z = z || s == 0.0;
+            if (out && s != 0.0)
+                for (int x = 0; x < V.card; ++x) out[V.loff + x] = out[V.loff + x] / s;
+            tv += log(s);
+            for (int j = 0; j < V.scope_len; ++j) {  // Z_e of the edges of factor v
+                const BpEdge J = A.edges[V.edge_begin + j];
+                s = 0.0;
+                for (int x = 0; x < J.card; ++x) s += mu_prev[J.moff + x] * nu[J.moff + x];
+                z = z || s == 0.0;
+                tv -= log(s);
+            }
+            term[v] = tv;
+        }
+        double unused = 0.0;
+        bp_reduce(unused, z, fred, fzred);  // (its barrier publishes zf and term)
+    }
+    double log_z = -INFINITY;
+    if (!z) {
+        if (tid < kBpScoreLanes) {
+            double s = 0.0;
+            for (int v = tid; v < A.n_vars; v += kBpScoreLanes) s += term[v];
+            part[tid] = s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            log_z = part[0];
+            for (int l = 1; l < kBpScoreLanes; ++l) log_z += part[l];
+        }
+        if (fout) {
+            const int lane = tid & 63, wave = tid >> 6, n_waves = (nt + 63) >> 6;
+            for (int v = wave; v < A.n_vars; v += n_waves) {
+                const BpVar V = A.vars[v];
+                const double s = zf[v];
+                for (int c = lane; c < V.table_cells; c += 64) fout[M.foff[v] + c] = bp_family_cell(A, V, nu, c) / s;
+            }
+        }
+    } else {
+        if (out)
+            for (int i = tid; i < A.lam_cells; i += nt) out[i] = 0.0;
+        if (fout)
+            for (int i = tid; i < M.fcells; i += nt) fout[i] = 0.0;
+        r = 0.0;
+    }
+    if (tid == 0) {
+        A.iterations[req] = it;
+        A.residual[req] = r;
+        M.log_z[req] = log_z;
+    }
+}
+
+// acc[c] = acc[c] + weight[b] * b_f(c) for the launch's requests b ascending, one addition after the other: a lane per cell
+__global__ __launch_bounds__(256) void bp_accumulate_kernel(double *acc, const double *fbeliefs, const double *weight, int64_t n, int32_t fcells) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= fcells) return;
+    double a = acc[c];
+    for (int64_t b = 0; b < n; ++b) a = a + (weight ? weight[b] : 1.0) * fbeliefs[b * fcells + c];
+    acc[c] = a;
+}
+
 typedef void (*BpKernel)(const BpArgs);
+typedef void (*BpEvKernel)(const BpEvArgs);
+inline BpEvKernel bp_evidence_kernel_of(BpForm form) { return form == BpForm::MsgLds ? bp_evidence_kernel<true> : bp_evidence_kernel<false>; }
+inline size_t bp_lds_bytes(const BpEvPlan &E) { return E.form == BpForm::MsgLds ? E.lds.total : kBpEvRedBytes; }
 inline BpKernel bp_kernel_of(BpForm form) { return form == BpForm::MsgLds ? bp_kernel<true> : bp_kernel<false>; }
 typedef void (*BpMaxKernel)(const BpMaxArgs);
 inline BpMaxKernel bp_max_kernel_of(BpForm form) { return form == BpForm::MsgLds ? bp_max_kernel<true> : bp_max_kernel<false>; }

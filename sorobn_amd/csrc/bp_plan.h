@@ -1,4 +1,4 @@
-// Host side of loopy belief propagation (mibn_bp_batch, mibn_bp_mpe_batch): everything the call decides before its first HIP call, in plain C++17 - no
+// Host side of loopy belief propagation (mibn_bp_batch, mibn_bp_mpe_batch, mibn_bp_evidence_batch): everything the call decides before its first HIP call, in plain C++17 - no
 // HIP header, so that tools/bp_plan_sim.cpp runs it on a CPU (tests/test_bp_host.py) the way sampler_plan_sim runs sampler_plan.h.
 // bp_layout is the ONE description of a request's message state: bp_kernel takes its pointers from it - into dynamic LDS or into the
 // request's slab of the arena -, the plan takes the launch's LDS size and the slab size from it.
@@ -239,6 +239,79 @@ inline int bp_mpe_plan(const Network &net, int lds_mode, BpMpePlan &M, std::stri
     M.slab_bytes = lds_align16(M.lds.total);
     M.form = lds_mode != 0 && M.lds.total <= kSamplerLdsLimit ? BpForm::MsgLds : BpForm::MsgGlobal;
     return MIBN_OK;
+}
+
+// ------------------------------------------------------------------ Bethe log Z and family beliefs (mibn_bp_evidence_batch)
+// The state of a request: the message arrays and lambda exactly as above, then what the final phase keeps -
+//     zf[n_vars] f64 | term[n_vars] f64 | part[64] f64 | red
+// zf: the normaliser of every factor's belief, which the family-belief cells divide by; term: the Bethe term of every variable; part:
+// the 64 partial sums of the pinned order (the score rule's).  red: the reduction slots of bp_kernel, then as many again for the
+// final phase's own reduction - always in LDS.
+constexpr size_t kBpEvRedBytes = 2 * kBpRedBytes;
+template <typename I>
+struct BpEvLayout {
+    I mu0, mu1, nu, lam, zf, term, part, red, total;
+};
+template <typename I>
+MIBN_HD inline BpEvLayout<I> bp_ev_layout(I cells, I lam_cells, I n_vars) {
+    const BpLayout<I> S = bp_layout<I>(cells, lam_cells);
+    BpEvLayout<I> L;
+    L.mu0 = S.mu0;
+    L.mu1 = S.mu1;
+    L.nu = S.nu;
+    L.lam = S.lam;
+    L.zf = S.red;
+    L.term = L.zf + n_vars * 8;
+    L.part = L.term + n_vars * 8;
+    L.red = L.part + (I)kBpScoreLanes * 8;
+    L.total = L.red + (I)kBpEvRedBytes;
+    return L;
+}
+
+struct BpEvPlan {
+    BpPlan bp;  // the records, threads and iter_bytes; its lds / slab_bytes / form are mibn_bp_batch's and unused here
+    BpEvLayout<size_t> lds{};
+    size_t slab_bytes = 0;
+    BpForm form = BpForm::MsgLds;
+    std::vector<int32_t> foff;  // [n_vars + 1]: factor v's cells in a family-belief row - the tables back to back, not the pool's layout
+    int32_t fcells = 0;         // cells of a family-belief row
+};
+
+// The same rule as bp_plan's on the larger state: in LDS when bp_lds != 0 and the whole of it fits 160 KiB.
+inline int bp_ev_plan(const Network &net, int lds_mode, BpEvPlan &E, std::string &err) {
+    if (int rc = bp_plan(net, lds_mode, E.bp, err)) return rc;
+    E.lds = bp_ev_layout<size_t>((size_t)E.bp.cells, (size_t)E.bp.lam_cells, (size_t)net.n_vars);
+    E.slab_bytes = lds_align16(E.lds.total);
+    E.form = lds_mode != 0 && E.lds.total <= kSamplerLdsLimit ? BpForm::MsgLds : BpForm::MsgGlobal;
+    E.foff.assign(E.bp.vars.size() + 1, 0);
+    int64_t at = 0;  // (at most the pool: below 2^31)
+    for (size_t v = 0; v < E.bp.vars.size(); ++v) {
+        E.foff[v] = (int32_t)at;
+        at += E.bp.vars[v].table_cells;
+    }
+    E.foff.back() = E.fcells = (int32_t)at;
+    return MIBN_OK;
+}
+
+// n_acc must be the family-belief row's length; every weight a finite number >= 0.  `weight` may be null (all ones).
+inline int bp_ev_check_acc(const BpEvPlan &E, bool has_acc, int64_t n_acc, const double *weight, int64_t B, std::string &err) {
+    if (has_acc && n_acc != (int64_t)E.fcells) {
+        err = "bp: n_acc is " + std::to_string(n_acc) + ", the family tables have " + std::to_string(E.fcells) + " cells";
+        return MIBN_E_ARG;
+    }
+    for (int64_t b = 0; weight && b < B; ++b)
+        if (!(weight[b] >= 0.0) || std::isinf(weight[b])) { err = "request " + std::to_string(b) + ": weight must be a finite number >= 0"; return MIBN_E_ARG; }
+    return MIBN_OK;
+}
+
+// Requests of one launch: at most `chunk`, and as many as have, in the budget, a slab (MsgGlobal) plus a family-belief row
+// (`rows`: the call returns family beliefs or accumulates them).  0: one request does not fit.
+inline int64_t bp_ev_launch_requests(const BpEvPlan &E, bool rows, int64_t chunk, double budget_bytes) {
+    chunk = std::max<int64_t>(1, chunk);
+    const double per = (E.form == BpForm::MsgGlobal ? (double)E.slab_bytes : 0.0) + (rows ? 8.0 * (double)E.fcells : 0.0);
+    if (per == 0.0) return chunk;
+    const double fit = std::floor(budget_bytes / per);
+    return fit < 1.0 ? 0 : (int64_t)std::min((double)chunk, fit);
 }
 
 }  // namespace mibn

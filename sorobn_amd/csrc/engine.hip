@@ -190,16 +190,16 @@ constexpr int kLevelStreams = 4;
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
 // steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together), and the two kernels of a call with likelihood
-// findings: the seeds of a planned wave, the tiny kernel's twin, the one kernel of mibn_bp_batch and the one of mibn_bp_mpe_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// findings: the seeds of a planned wave, the tiny kernel's twin, the one kernel of mibn_bp_batch, the one of mibn_bp_mpe_batch and the two of mibn_bp_evidence_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatBpEvidence, kStatBpAccumulate, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel", "bp_evidence_kernel", "bp_accumulate_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -2807,7 +2807,7 @@ int run_map_body(mibn_t *h, uint32_t flags, int64_t B, const int64_t *m_off, con
 
 // ---------------------------------------------------------------------------------------------- likelihood findings
 // mibn_set_likelihoods stages a block for the NEXT batch call.  The calls that consume it (mibn_query_batch, mibn_query_batch_ex,
-// mibn_mpe_batch, mibn_map_batch, mibn_bp_batch, mibn_bp_mpe_batch) take it for their duration - h->lh, null for a block without a single finding: such a call is the call
+// mibn_mpe_batch, mibn_map_batch, mibn_bp_batch, mibn_bp_mpe_batch, mibn_bp_evidence_batch) take it for their duration - h->lh, null for a block without a single finding: such a call is the call
 // without a block, bit for bit -; the others refuse it.  Either way it is gone when the call returns, whatever the call returns.
 namespace {
 void drop_findings(mibn_ctx *h) {
@@ -3069,8 +3069,18 @@ extern "C" int mibn_gibbs_conditional(mibn_t *h, int32_t n_e, const int32_t *e_v
 // mibn_bp_batch: plan (bp_plan.h), upload the records once, then launch by launch - at most `chunk` requests, in the global form as
 // many as have slabs in the arena of lane 0 - upload the evidence, run bp_kernel, download.  Blocking, on the main stream, buffers of
 // its own; last-call statistics only, nothing a later call reads.  mibn_bp_mpe_batch (`mx`) is the same call around bp_max_kernel:
-// the larger state, the colouring next to the records, codes / log_p / info in place of the beliefs.
+// the larger state, the colouring next to the records, codes / log_p / info in place of the beliefs.  mibn_bp_evidence_batch (`evd`)
+// is the same call around bp_evidence_kernel: its own state, log_z beside the beliefs, and - where the caller wants family beliefs
+// or expected counts - one family-belief row per request of the launch, in the arena behind the slabs, which bp_accumulate_kernel adds into
+// `acc` after every launch; `acc` stays on the device between the launches.
 namespace {
+struct BpEvOut {
+    const double *weight;  // or null
+    double *log_z;
+    double *fbeliefs;      // or null
+    int64_t n_acc;
+    double *acc;           // or null
+};
 struct BpMpeOut {
     int32_t polish_sweeps;
     int32_t *codes;
@@ -3078,7 +3088,7 @@ struct BpMpeOut {
     int32_t *info;  // or null
 };
 int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t max_iterations, double tol,
-            double damping, double *beliefs, int32_t *iterations, double *residual, const BpMpeOut *mx = nullptr) {
+            double damping, double *beliefs, int32_t *iterations, double *residual, const BpMpeOut *mx = nullptr, const BpEvOut *evd = nullptr) {
     const double t_start = now_ms();
     reset_last_stats(h);
     const Network &net = h->net;
@@ -3096,10 +3106,14 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
         if (!e.empty()) { h->err = "request " + std::to_string(b) + ": " + e; return MIBN_E_ARG; }
     }
     BpMpePlan M;
-    BpPlan &P = M.bp;
-    if ((rc = mx ? bp_mpe_plan(net, h->bp_lds, M, h->err) : bp_plan(net, h->bp_lds, P, h->err))) return rc;
-    const BpForm form = mx ? M.form : P.form;
-    const size_t slab_bytes = mx ? M.slab_bytes : P.slab_bytes;
+    BpEvPlan E;
+    BpPlan &P = evd ? E.bp : M.bp;
+    if ((rc = mx ? bp_mpe_plan(net, h->bp_lds, M, h->err) : evd ? bp_ev_plan(net, h->bp_lds, E, h->err) : bp_plan(net, h->bp_lds, P, h->err))) return rc;
+    if (evd && (rc = bp_ev_check_acc(E, evd->acc != nullptr, evd->n_acc, evd->weight, B, h->err))) return rc;
+    const BpForm form = mx ? M.form : evd ? E.form : P.form;
+    const size_t slab_bytes = mx ? M.slab_bytes : evd ? E.slab_bytes : P.slab_bytes;
+    const bool rows = evd && (evd->fbeliefs || evd->acc);  // family-belief rows on the device
+    const size_t fc = evd ? (size_t)E.fcells : 0;
     if (B == 0) return MIBN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = drain_streams(h))) return rc;  // (the arena of lane 0 is the query calls' too)
@@ -3107,22 +3121,29 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
     size_t free_b = 0, total_b = 0;
     HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
     const double budget = std::min(h->arena_gb * 1e9, 0.8 * (double)(free_b + h->d_arena[0].cap()));
-    const int64_t per_launch = bp_launch_requests(form, slab_bytes, h->chunk, budget);
-    if (per_launch < 1) { h->err = "bp: one request's messages need " + std::to_string((double)slab_bytes / 1e9) + " GB, above the arena budget"; return MIBN_E_NOMEM; }
+    const int64_t per_launch = evd ? bp_ev_launch_requests(E, rows, h->chunk, budget) : bp_launch_requests(form, slab_bytes, h->chunk, budget);
+    if (per_launch < 1) { h->err = "bp: one request's messages need " + std::to_string((double)(slab_bytes + (rows ? 8 * fc : 0)) / 1e9) + " GB, above the arena budget"; return MIBN_E_NOMEM; }
     const int64_t n_max = std::min(B, per_launch);
     const size_t lam = (size_t)P.lam_cells, nv = (size_t)net.n_vars;
     DevBuf<BpEdge> d_edges;
     DevBuf<BpVar> d_vars;
     DevBuf<int32_t> d_nbr, d_ev, d_ec, d_lv, d_it, d_nbre, d_coff, d_cmem, d_codes, d_info;
     DevBuf<int64_t> d_eoff, d_loff, d_voff;
-    DevBuf<double> d_val, d_bel, d_res, d_logp;
+    DevBuf<double> d_val, d_bel, d_res, d_logp, d_acc, d_w;
+    DevBuf<int32_t> d_foff;
     std::vector<int32_t> info_host;  // (a caller without `info`)
-    Event ev0, ev1;
+    Event ev0, ev1, ev2;
     HIP_TRY(h, d_edges.reset(P.edges.size()));
     HIP_TRY(h, d_vars.reset(P.vars.size()));
     HIP_TRY(h, d_nbr.reset(P.nbr_moff.size()));
     HIP_TRY(h, d_eoff.reset((size_t)n_max + 1));
-    if (!mx) HIP_TRY(h, d_bel.reset((size_t)n_max * lam));
+    if (!mx && beliefs) HIP_TRY(h, d_bel.reset((size_t)n_max * lam));
+    if (evd) {
+        HIP_TRY(h, d_foff.reset(E.foff.size()));
+        HIP_TRY(h, d_logp.reset((size_t)n_max));
+        if (evd->acc) HIP_TRY(h, d_acc.reset(std::max<size_t>(1, fc)));
+        if (evd->acc && evd->weight) HIP_TRY(h, d_w.reset((size_t)n_max));
+    }
     if (mx) {
         HIP_TRY(h, d_nbre.reset(P.nbr.size()));
         HIP_TRY(h, d_coff.reset(M.col.off.size()));
@@ -3136,6 +3157,7 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
     HIP_TRY(h, d_res.reset((size_t)n_max));
     HIP_TRY(h, ev0.ensure());
     HIP_TRY(h, ev1.ensure());
+    HIP_TRY(h, ev2.ensure());
     HIP_TRY(h, hipMemcpyAsync(d_edges, P.edges.data(), P.edges.size() * sizeof(BpEdge), hipMemcpyHostToDevice, S));
     HIP_TRY(h, hipMemcpyAsync(d_vars, P.vars.data(), P.vars.size() * sizeof(BpVar), hipMemcpyHostToDevice, S));
     HIP_TRY(h, hipMemcpyAsync(d_nbr, P.nbr_moff.data(), P.nbr_moff.size() * 4, hipMemcpyHostToDevice, S));
@@ -3144,18 +3166,29 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
         HIP_TRY(h, hipMemcpyAsync(d_coff, M.col.off.data(), M.col.off.size() * 4, hipMemcpyHostToDevice, S));
         HIP_TRY(h, hipMemcpyAsync(d_cmem, M.col.members.data(), M.col.members.size() * 4, hipMemcpyHostToDevice, S));
     }
+    if (evd) {
+        HIP_TRY(h, hipMemcpyAsync(d_foff, E.foff.data(), E.foff.size() * 4, hipMemcpyHostToDevice, S));
+        if (evd->acc && fc) HIP_TRY(h, hipMemcpyAsync(d_acc, evd->acc, fc * 8, hipMemcpyHostToDevice, S));
+    }
     const BpKernel kernel = bp_kernel_of(form);
     const BpMaxKernel max_kernel = bp_max_kernel_of(form);
-    const size_t lds = mx ? bp_lds_bytes(M) : bp_lds_bytes(P);
-    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute(mx ? (const void *)max_kernel : (const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (form == BpForm::MsgGlobal && (rc = grow_arena(h, 0, (size_t)n_max * slab_bytes, (int64_t)(budget / 8.0), S))) return rc;
+    const BpEvKernel ev_kernel = bp_evidence_kernel_of(form);
+    const size_t lds = mx ? bp_lds_bytes(M) : evd ? bp_lds_bytes(E) : bp_lds_bytes(P);
+    if (lds > 64 * 1024)
+        HIP_TRY(h, hipFuncSetAttribute(mx ? (const void *)max_kernel : evd ? (const void *)ev_kernel : (const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // the arena of lane 0: the slabs of the launch's requests (MsgGlobal), then their family-belief rows - both inside the budget the
+    // launch size was cut to, and kept from call to call
+    const size_t slabs_total = form == BpForm::MsgGlobal ? (size_t)n_max * slab_bytes : 0, rows_total = rows ? (size_t)n_max * fc * 8 : 0;
+    if (slabs_total + rows_total != 0 && (rc =grow_arena(h, 0, slabs_total + rows_total, (int64_t)(budget / 8.0), S))) return rc;
     BpMaxArgs MA{};
-    BpArgs &A = MA.bp;
+    BpEvArgs EA{};
+    BpArgs &A = evd ? EA.bp : MA.bp;
     A.pool = h->d_pool;
     A.edges = d_edges;
     A.vars = d_vars;
     A.nbr_moff = d_nbr;
     A.slabs = reinterpret_cast<unsigned char *>(h->d_arena[0].get());
+    double *const d_fb = rows_total ? reinterpret_cast<double *>(A.slabs + slabs_total) : nullptr;
     A.slab_bytes = slab_bytes;
     A.n_vars = net.n_vars;
     A.n_edges = (int32_t)P.edges.size();
@@ -3174,6 +3207,13 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
         MA.log_p = d_logp;
         MA.info = d_info;
     }
+    if (evd) {
+        EA.foff = d_foff;
+        EA.fcells = E.fcells;
+        EA.log_z = d_logp;
+        EA.fbeliefs = d_fb;
+    }
+    const double req_bytes = evd ? 8.0 * (double)fc : 0.0;  // (the final phase: one more pass over the CPT cells)
     std::vector<int64_t> off;
     for (int64_t b0 = 0; b0 < B; b0 += n_max) {
         const int64_t n = std::min(n_max, B - b0);
@@ -3214,21 +3254,33 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
             A.values = d_val;
         }
         h->stats.h2d_ms += now_ms() - t0;
-        A.beliefs = mx ? nullptr : d_bel.get();
+        if (evd && evd->acc && evd->weight) HIP_TRY(h, hipMemcpyAsync(d_w, evd->weight + b0, (size_t)n * 8, hipMemcpyHostToDevice, S));
+        A.beliefs = mx || !beliefs ? nullptr : d_bel.get();
         A.iterations = d_it;
         A.residual = d_res;
         HIP_TRY(h, hipEventRecord(ev0, S));
         if (mx) hipLaunchKernelGGL(max_kernel, dim3((unsigned)n), dim3((unsigned)P.threads), lds, S, MA);
+        else if (evd) hipLaunchKernelGGL(ev_kernel, dim3((unsigned)n), dim3((unsigned)P.threads), lds, S, EA);
         else hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3((unsigned)P.threads), lds, S, A);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(ev1, S));
+        if (evd && evd->acc && fc) {
+            hipLaunchKernelGGL(bp_accumulate_kernel, dim3((unsigned)((fc + 255) / 256)), dim3(256), 0, S, d_acc.get(), (const double *)d_fb,
+                               evd->weight ? (const double *)d_w.get() : nullptr, n, E.fcells);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipEventRecord(ev2, S));
+        }
         t0 = now_ms();
         if (mx) {
             HIP_TRY(h, hipMemcpyAsync(mx->codes + (size_t)b0 * nv, d_codes, (size_t)n * nv * 4, hipMemcpyDeviceToHost, S));
             HIP_TRY(h, hipMemcpyAsync(mx->log_p + b0, d_logp, (size_t)n * 8, hipMemcpyDeviceToHost, S));
             HIP_TRY(h, hipMemcpyAsync(mx->info ? mx->info + (size_t)b0 * 3 : info_host.data(), d_info, (size_t)n * 12, hipMemcpyDeviceToHost, S));
-        } else
+        } else if (beliefs)
             HIP_TRY(h, hipMemcpyAsync(beliefs + (size_t)b0 * lam, d_bel, (size_t)n * lam * 8, hipMemcpyDeviceToHost, S));
+        if (evd) {
+            HIP_TRY(h, hipMemcpyAsync(evd->log_z + b0, d_logp, (size_t)n * 8, hipMemcpyDeviceToHost, S));
+            if (evd->fbeliefs && fc) HIP_TRY(h, hipMemcpyAsync(evd->fbeliefs + (size_t)b0 * fc, d_fb, (size_t)n * fc * 8, hipMemcpyDeviceToHost, S));
+        }
         HIP_TRY(h, hipMemcpyAsync(iterations + b0, d_it, (size_t)n * 4, hipMemcpyDeviceToHost, S));
         HIP_TRY(h, hipMemcpyAsync(residual + b0, d_res, (size_t)n * 8, hipMemcpyDeviceToHost, S));
         HIP_TRY(h, hipStreamSynchronize(S));
@@ -3237,17 +3289,40 @@ int bp_body(mibn_ctx *h, int64_t B, const int64_t *e_off, const int32_t *e_vars,
         HIP_TRY(h, hipEventElapsedTime(&ms, ev0, ev1));
         double iters = 0;
         for (int64_t r = 0; r < n; ++r) iters += iterations[b0 + r];
-        book_stat(h, mx ? kStatBpMax : kStatBp, 1, ms, P.iter_bytes * iters, (double)n, true, false);
+        const double bytes = P.iter_bytes * iters + req_bytes * (double)n;
+        book_stat(h, mx ? kStatBpMax : evd ? kStatBpEvidence : kStatBp, 1, ms, bytes, (double)n, true, false);
         h->stats.kernel_ms += ms;
         h->stats.n_launches += 1;
         h->stats.n_workgroups += (double)n;
-        h->stats.alg_bytes += P.iter_bytes * iters;
+        h->stats.alg_bytes += bytes;
+        if (evd && evd->acc && fc) {  // reads the launch's rows, reads and writes acc
+            HIP_TRY(h, hipEventElapsedTime(&ms, ev1, ev2));
+            book_stat(h, kStatBpAccumulate, 1, ms, 8.0 * (double)fc * (double)(n + 2), (double)n, true, false);
+            h->stats.kernel_ms += ms;
+            h->stats.n_launches += 1;
+        }
+    }
+    if (evd && evd->acc && fc) {
+        HIP_TRY(h, hipMemcpyAsync(evd->acc, d_acc, fc * 8, hipMemcpyDeviceToHost, S));
+        HIP_TRY(h, hipStreamSynchronize(S));
     }
     if (form == BpForm::MsgGlobal) h->stats.arena_bytes = (double)n_max * (double)slab_bytes;
     h->stats.total_ms = now_ms() - t_start;
     return MIBN_OK;
 }
 }  // namespace
+
+extern "C" int mibn_bp_evidence_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes,
+                                      int32_t max_iterations, double tol, double damping, const double *weight, double *log_z, double *beliefs,
+                                      double *fbeliefs, int64_t n_acc, double *acc, int32_t *iterations, double *residual) {
+    TakeFindings lh(h);
+    if (!h || B < 0 || (B && (!e_off || !log_z || !iterations || !residual))) return MIBN_E_ARG;
+    if (int rc = check_state(h, kNeedIdle)) return rc;
+    if (int rc = check_state(h, kNeedDevice | kNeedNet)) return rc;
+    if (int rc = lh.take(B)) return rc;
+    const BpEvOut evd{weight, log_z, fbeliefs, n_acc, acc};
+    return drained_on_error(h, bp_body(h, B, e_off, e_vars, e_codes, max_iterations, tol, damping, beliefs, iterations, residual, nullptr, &evd), drain_main_unchecked);
+}
 
 extern "C" int mibn_bp_batch(mibn_t *h, int64_t B, const int64_t *e_off, const int32_t *e_vars, const int32_t *e_codes, int32_t max_iterations,
                              double tol, double damping, double *beliefs, int32_t *iterations, double *residual) {

@@ -58,6 +58,14 @@ def part_args(ev_ids, codes, part, on):
     return np.broadcast_to(ev_ids[on], (len(part), len(on))), codes[np.ix_(part, on)]
 
 
+def csr_rows(ev_ids, codes, observed):
+    """One request per row, in row order, as CSR evidence: (e_off int64 [n + 1], e_vars, e_codes) - the observed columns of every
+    row, in column order.  For the calls whose requests need not share a shape (belief propagation)."""
+    e_off = np.zeros(len(codes) + 1, np.int64)
+    np.cumsum(observed.sum(axis=1), out=e_off[1:])
+    return e_off, np.broadcast_to(ev_ids, observed.shape)[observed].astype(np.int32), codes[observed].astype(np.int32)
+
+
 def label_table(f, v):
     """Labels of variable v by code, with None at index -1 (code -1 = no answer)."""
     dom = np.empty(int(f.card[v]) + 1, dtype=object)

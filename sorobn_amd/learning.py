@@ -13,6 +13,7 @@ import numpy as np
 import pandas as pd
 
 from . import _capi
+from .events import csr_rows
 
 _engines = {}
 
@@ -368,7 +369,11 @@ def _em_current(bn, nodes, observed_domains):
     return domains, thetas
 
 
-def fit_em(bn, X, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=32768):
+EM_ALGORITHMS = ("exact", "lbp")
+
+
+def fit_em(bn, X, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=32768, algorithm="exact", bp_iterations=100, bp_tol=1e-9,
+           damping=0.0):
     """CPTs from rows with missing values (NaN / None = not observed in that row) by expectation-maximisation.
 
     The structure is the net's.  A column's labels are the sorted labels observed in it (with `init="current"`: the
@@ -383,9 +388,26 @@ def fit_em(bn, X, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=3
     "auto" ("current" where it applies, else "counts").  Stops after n_iter iterations or when the log-likelihood gains
     less than tol * |ll|.  Leaves bn.em_log_likelihood_ (the observed-data log-likelihood of the parameters each E-step
     STARTED from), bn.em_iterations_ and bn._counts (the last expected counts).  A row of probability zero under the
-    current parameters contributes no counts and makes that iteration's entry -inf."""
+    current parameters contributes no counts and makes that iteration's entry -inf.
+
+    algorithm="lbp": an APPROXIMATE E-step for networks on which the exact one is refused (a 20 x 20 grid) - one request of loopy
+    belief propagation per row (`Engine.bp_evidence_batch`: at most `bp_iterations` flooding sweeps, `bp_tol`, `damping`), rows in
+    X's order in engine calls of `sub_batch`; every family of every row receives its belief, so there is no count-kernel pass and
+    no limit on the missing members of a family, and bn.em_log_likelihood_ holds the sums of the rows' Bethe log_z.  Exact on
+    polytrees.  On a network with loops the E-step has no error bound, and the recorded log-likelihood NEED NOT BE MONOTONE: the
+    stopping rule is the same, so it may stop at a decrease."""
     if int(n_iter) < 1:
         raise ValueError("n_iter must be at least 1")
+    if algorithm not in EM_ALGORITHMS:
+        raise ValueError(f"algorithm must be one of {EM_ALGORITHMS}, not {algorithm!r}")
+    lbp = algorithm == "lbp"
+    if lbp:
+        if int(bp_iterations) != bp_iterations or bp_iterations < 1:
+            raise ValueError("bp_iterations must be an integer >= 1")
+        if not bp_tol >= 0:
+            raise ValueError("bp_tol must be a number >= 0")
+        if not 0 <= damping < 1:
+            raise ValueError("damping must be in [0, 1)")
     if not float(prior_count) >= 0:
         raise ValueError("prior_count must not be negative")
     if init not in EM_INITS:
@@ -422,13 +444,13 @@ def fit_em(bn, X, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=3
         codes[:, vid[node]] = lut[raw[:, j]]
     seen = codes >= 0
     for v, sc in enumerate(scopes):
-        if n and int((~seen[:, sc]).sum(axis=1).max()) > EM_MAX_MISSING:
+        if not lbp and n and int((~seen[:, sc]).sum(axis=1).max()) > EM_MAX_MISSING:
             raise ValueError(f"a row misses more than {EM_MAX_MISSING} members of the family of {nodes[v]!r} "
                              f"(the engine takes at most {EM_MAX_MISSING} query variables per expect request)")
     # families complete in a row: counted once (they do not change between iterations)
     full = [v for v in range(V) if all(nodes[u] not in latent for u in scopes[v])]
     hard = np.zeros(int(fam_off[-1]), np.float64)
-    if n and full:
+    if n and full and (not lbp or (thetas is None and init != "uniform")):  # (lbp: only the start of init="counts" reads them)
         na = np.where(seen, codes, card[None, :]).astype(np.uint8)
         cards_na = card + (~seen).any(axis=0)
         if int(cards_na.max()) > 256:
@@ -443,29 +465,38 @@ def fit_em(bn, X, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=3
         else:
             thetas = [em_mstep(hard[fam_off[v]:fam_off[v + 1]] + 1.0, np.zeros(int(fam_off[v + 1] - fam_off[v])), card[v])
                       for v in range(V)]
-    batches = em_sub_batches(codes, scopes, sub_batch)
+    batches = [] if lbp else em_sub_batches(codes, scopes, sub_batch)
     requests = None if len(batches) > 8 else [em_requests(codes, rows, scopes, strides, fam_off) for rows in batches]
     lls, counts = [], hard
+    ids, step = np.arange(V, dtype=np.int32), max(1, int(sub_batch))
     for it in range(int(n_iter)):
         bn.P = {node: _em_series(node, bn.parents.get(node, []), domains, thetas[v]) for v, node in enumerate(nodes)}
         bn.prepare()
         eng = bn.backend.engine
         acc = np.zeros(int(fam_off[-1]), np.float64)
-        p_row = np.zeros(n, np.float64)
-        for k, rows in enumerate(batches):
-            rq = requests[k] if requests is not None else em_requests(codes, rows, scopes, strides, fam_off)
-            p = eng.expect_batch(rq["q_off"], rq["q_vars"], rq["e_off"], rq["e_vars"], rq["e_codes"], rq["acc_base"],
-                                 rq["acc_stride"], acc)
-            p_row[rq["row"][::-1]] = p[::-1]  # (any of a row's requests carries its P(e): the first one stays)
-        counts = acc + hard
-        dead = np.flatnonzero(~(p_row > 0))
-        if len(dead):  # rows of probability zero contribute nothing: their complete families come off again
-            for v in full:
-                sc = np.asarray(scopes[v], np.int64)
-                ok = dead[seen[dead][:, sc].all(axis=1)]
-                np.subtract.at(counts, fam_off[v] + (codes[ok][:, sc] * strides[v]).sum(axis=1), 1.0)
-        with np.errstate(divide="ignore"):
-            lls.append(float(np.log(p_row).sum()) if n else 0.0)
+        if lbp:  # one request per row, in X's order: its family beliefs are the expected counts of EVERY family of the row
+            log_z = np.zeros(n, np.float64)
+            for s in range(0, n, step):
+                rows = slice(s, s + step)
+                log_z[rows] = eng.bp_evidence_batch(*csr_rows(ids, codes[rows], seen[rows]), int(bp_iterations), bp_tol, damping, acc=acc)[0]
+            counts = acc
+            lls.append(float(log_z.sum()) if n else 0.0)
+        else:
+            p_row = np.zeros(n, np.float64)
+            for k, rows in enumerate(batches):
+                rq = requests[k] if requests is not None else em_requests(codes, rows, scopes, strides, fam_off)
+                p = eng.expect_batch(rq["q_off"], rq["q_vars"], rq["e_off"], rq["e_vars"], rq["e_codes"], rq["acc_base"],
+                                     rq["acc_stride"], acc)
+                p_row[rq["row"][::-1]] = p[::-1]  # (any of a row's requests carries its P(e): the first one stays)
+            counts = acc + hard
+            dead = np.flatnonzero(~(p_row > 0))
+            if len(dead):  # rows of probability zero contribute nothing: their complete families come off again
+                for v in full:
+                    sc = np.asarray(scopes[v], np.int64)
+                    ok = dead[seen[dead][:, sc].all(axis=1)]
+                    np.subtract.at(counts, fam_off[v] + (codes[ok][:, sc] * strides[v]).sum(axis=1), 1.0)
+            with np.errstate(divide="ignore"):
+                lls.append(float(np.log(p_row).sum()) if n else 0.0)
         thetas = [em_mstep(counts[fam_off[v]:fam_off[v + 1]], thetas[v], card[v], prior_count) for v in range(V)]
         if it and np.isfinite(lls[-1]) and np.isfinite(lls[-2]) and lls[-1] - lls[-2] < float(tol) * abs(lls[-1]):
             break

@@ -11,6 +11,9 @@
 //   args    max_iterations tol damping            the argument check (tol and damping as strtod reads them: nan, -1, 0x1p-3 ..)
 //   mpe     lds_mode                              mibn_bp_mpe_batch: the colouring (colour of each variable, members per colour as CSR), bp_mpe_layout, the form
 //   mpe_args max_iterations tol damping polish    its argument check
+//   ev      lds_mode                              mibn_bp_evidence_batch: bp_ev_layout, the form, the family-belief row (fcells, foff)
+//   ev_launch lds_mode rows chunk budget_bytes    its requests of one launch (rows != 0: with the family-belief buffer; 0: one does not fit)
+//   ev_acc  lds_mode n_acc B w_0 .. w_(B-1)       its check of n_acc (negative: no acc) and of the weights (B = 0: weight NULL)
 // output: one line of key=value pairs per command (lists comma separated; edges / vars = the eight words of every record), or
 //   error=<MIBN_* code> msg=<the message, to the end of the line>
 #include <algorithm>
@@ -89,6 +92,35 @@ int main() {
             const int rc = bp_mpe_check_args(it, tol, damping, (int32_t)geti(), err);
             if (rc) std::printf("error=%d msg=%s\n", rc, err.c_str());
             else std::printf("ok=1\n");
+        } else if (cmd == "ev" || cmd == "ev_launch" || cmd == "ev_acc") {
+            const int lds_mode = (int)geti();
+            BpEvPlan E;
+            const int rc = bp_ev_plan(net, lds_mode, E, err);
+            if (cmd == "ev_launch") {
+                const bool rows = geti() != 0;
+                const int64_t chunk = geti();
+                const double budget = getd();
+                if (rc) { std::printf("error=%d msg=%s\n", rc, err.c_str()); continue; }
+                std::printf("requests=%lld\n", (long long)bp_ev_launch_requests(E, rows, chunk, budget));
+                continue;
+            }
+            if (cmd == "ev_acc") {
+                const int64_t n_acc = geti(), B = geti();  // n_acc < 0: no acc; then B weights (B = 0: weight NULL)
+                std::vector<double> w((size_t)std::max<int64_t>(0, B));
+                for (auto &x : w) x = getd();
+                if (rc) { std::printf("error=%d msg=%s\n", rc, err.c_str()); continue; }
+                const int rc2 = bp_ev_check_acc(E, n_acc >= 0, n_acc, B ? w.data() : nullptr, B, err);
+                if (rc2) std::printf("error=%d msg=%s\n", rc2, err.c_str());
+                else std::printf("ok=1\n");
+                continue;
+            }
+            if (rc) { std::printf("error=%d msg=%s\n", rc, err.c_str()); continue; }
+            const BpEvLayout<size_t> &L = E.lds;
+            std::printf("form=%s fcells=%d mu0=%zu mu1=%zu nu=%zu lam=%zu zf=%zu term=%zu part=%zu red=%zu total=%zu slab=%zu threads=%d iter_bytes=%.0f",
+                        bp_form_name(E.form), E.fcells, L.mu0, L.mu1, L.nu, L.lam, L.zf, L.term, L.part, L.red, L.total, E.slab_bytes, E.bp.threads,
+                        E.bp.iter_bytes);
+            put_list("foff", E.foff.data(), E.foff.size());
+            std::printf("\n");
         } else if (cmd == "plan" || cmd == "launch") {
             const int lds_mode = (int)geti();
             BpPlan P;
