@@ -598,6 +598,43 @@ int mibn_ci_tests(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const in
                   double *stat, int64_t *adj_dof);
 
 /*
+ * Integer row weights on the counting path: aggregated data (one row per pattern plus a frequency) and bootstrap resamples (a
+ * resample of N rows IS a vector of N multiplicities summing to N) without expanding the rows.  A weight set is uint32[n_rows]; a
+ * table counted under set s is the contingency table with row i counted w_s[i] times, an exact integer whatever the launch
+ * geometry.  Every call below gives, bit for bit, what its unweighted twin gives on the rows written out w_s[i] times each.
+ *
+ * mibn_dataset_set_weights replaces the weight sets of a resident data set by weights[n_sets * n_rows], set-major (set s is
+ * weights[s * n_rows .. (s + 1) * n_rows)); n_sets = 0 drops them (weights may then be NULL).  W_s, the sum of set s, must be at
+ * most 2^32 - 1, else MIBN_E_LIMIT (checked on the host; no partial sum of a workgroup's 32-bit histogram can then overflow).  On
+ * any error the data set keeps the sets it had.
+ *
+ * mibn_dataset_bootstrap replaces the weight sets by n_sets multinomial resamples drawn on the device.  The rule: for set s and
+ * draw j = 0 .. n_rows - 1, u = the Philox4x32-10 uniform of mibn_sample's convention with counter (j_lo, j_hi, s, 0) and key
+ * ((uint32) seed, (uint32)(seed >> 32) ^ 0x85EBCA6B) - 53 bits of the first two output words, a double in [0, 1) -; the drawn row
+ * is min(floor(u * n_rows), n_rows - 1), the product formed in fp64; its weight goes up by one.  Set s is a function of
+ * (seed, s, n_rows) alone, not of n_sets, and every W_s = n_rows.  weights_out (n_sets * n_rows, or NULL) receives the sets.  A data
+ * set of more than 2^32 - 1 rows is MIBN_E_LIMIT.
+ *
+ * mibn_score_families_w / mibn_ci_tests_w: mibn_score_families / mibn_ci_tests with one weight-set index per table, wset[t] in
+ * [-1, n_sets) (else MIBN_E_ARG); -1 = every row once.  N of the BIC penalty and of the zero-row rules is W_s (n_rows for -1);
+ * mibn_ci_tests_w refuses a table whose N is 2^31 or more (MIBN_E_LIMIT).  The reduction is that of the unweighted calls on the
+ * counted tables (the families of a sub-batch are reduced N by N: one launch set per distinct N, one for a bootstrap); sub-batches
+ * (option score_cells), blocking, validation before any launch and statistics are theirs too, the counting booked under
+ * count_weighted_kernel (alg_bytes = codes read + 4 * n_rows per table + the tables) instead of count_kernel.
+ *
+ * mibn_count_tables_w: mibn_count_tables with one weight vector weights[n_rows] (sum at most 2^32 - 1, else MIBN_E_LIMIT).
+ */
+int mibn_dataset_set_weights(mibn_t *h, int32_t id, int32_t n_sets, const uint32_t *weights /* n_sets x n_rows, set-major */);
+int mibn_dataset_bootstrap(mibn_t *h, int32_t id, int32_t n_sets, uint64_t seed, uint32_t *weights_out /* n_sets x n_rows or NULL */);
+int mibn_score_families_w(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off,
+                          const int32_t *scope_cols, const int32_t *wset /* n_fam */, double *scores);
+int mibn_ci_tests_w(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const int64_t *scope_off, const int32_t *scope_cols,
+                    const int32_t *wset /* n_tests */, double *stat, int64_t *adj_dof);
+int mibn_count_tables_w(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t *codes, int32_t row_major, const int32_t *card,
+                        int32_t n_tables, const int64_t *scope_off, const int32_t *scope_cols, const int64_t *counts_off,
+                        const uint32_t *weights /* n_rows */, int64_t *counts);
+
+/*
  * Multi-GPU: one process per GPU, requests / chains sharded with no data-path collective; the
  * only communication is the final gather of the posteriors (exact path) or the sum of the histograms (Gibbs).  These
  * entry points sit directly on RCCL (librccl.so is dlopen'ed by mibn_comm_init - a single-GPU process never loads it) and

@@ -24,7 +24,9 @@ SYMBOLS = [
     "mibn_comm_probe", "mibn_device_info", "mibn_comm_count", "mibn_mpe_batch", "mibn_expect_batch",
     "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch", "mibn_map_batch",
     "mibn_ci_tests", "mibn_set_likelihoods", "mibn_bp_batch", "mibn_bp_mpe_batch", "mibn_bp_evidence_batch",
+    "mibn_dataset_set_weights", "mibn_dataset_bootstrap", "mibn_score_families_w", "mibn_ci_tests_w", "mibn_count_tables_w",
 ]
+MAX_WEIGHT_SUM = 2 ** 32 - 1  # W_s of a weight set (include/mibn.h)
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 Q_NOPRUNE = 1
@@ -120,6 +122,12 @@ def lib():
         L.mibn_dataset_destroy.argtypes = [vp, C.c_int32]
         L.mibn_score_families.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, i64p, i32p, f64p]
         L.mibn_ci_tests.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f64p, i64p]
+        u32p = C.POINTER(C.c_uint32)
+        L.mibn_dataset_set_weights.argtypes = [vp, C.c_int32, C.c_int32, u32p]
+        L.mibn_dataset_bootstrap.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64, u32p]
+        L.mibn_score_families_w.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, i64p, i32p, i32p, f64p]
+        L.mibn_ci_tests_w.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, i32p, f64p, i64p]
+        L.mibn_count_tables_w.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, i32p, C.c_int32, i64p, i32p, i64p, u32p, i64p]
         L.mibn_last_stats.argtypes = [vp, C.POINTER(Stats)]
         L.mibn_last_kernel_stats.argtypes = [vp, C.c_int32, C.POINTER(KernelStat), C.POINTER(C.c_int32)]
         L.mibn_plan_stats.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, C.POINTER(Stats)]
@@ -157,11 +165,33 @@ class Dataset:
         self.id = ds_id
         self.n_rows = n_rows
         self.card = card
+        self.n_sets = 0
 
-    def score_families(self, families, kind="bic", ess=1.0):
+    def set_weights(self, w):
+        """w: non-negative integers [n_sets, n_rows] (or one set [n_rows]), every set summing to at most 2^32 - 1 -> the weight
+        sets of the data set (mibn_dataset_set_weights); None or zero sets drops them."""
+        w = np.zeros((0, self.n_rows), np.uint32) if w is None else np.ascontiguousarray(np.atleast_2d(np.asarray(w)), dtype=np.uint32)
+        if w.ndim != 2 or w.shape[1] != self.n_rows:
+            raise ValueError("weights must be [n_sets, n_rows]")
+        eng = self.engine
+        eng._check(eng._L.mibn_dataset_set_weights(eng._h, self.id, len(w), _p(w if w.size else np.zeros(1, np.uint32), C.c_uint32)))
+        self.n_sets = len(w)
+
+    def bootstrap(self, n_sets, seed=0, return_weights=False):
+        """Replaces the weight sets by `n_sets` multinomial resamples drawn on the device (mibn_dataset_bootstrap: set s is a function of
+        (seed, s, n_rows) alone); with return_weights -> uint32 [n_sets, n_rows]."""
+        w = np.zeros((int(n_sets), self.n_rows), np.uint32) if return_weights else None
+        eng = self.engine
+        eng._check(eng._L.mibn_dataset_bootstrap(eng._h, self.id, int(n_sets), int(seed) & (2 ** 64 - 1),
+                                                 _p(w, C.c_uint32) if w is not None and w.size else None))
+        self.n_sets = int(n_sets)
+        return w
+
+    def score_families(self, families, kind="bic", ess=1.0, wset=None):
         """families: sequences of column indices, parents first, CHILD LAST -> float64 array of their scores (`kind` one of
         SCORE_KINDS, `ess` the equivalent sample size of "bdeu"); one call, whatever the number of families.  After `close()`
-        the library refuses the id (MibnError, E_ARG)."""
+        the library refuses the id (MibnError, E_ARG).  wset: one weight-set index per family (-1 = every row once) ->
+        mibn_score_families_w; None is the unweighted call."""
         if kind not in SCORE_KINDS:
             raise ValueError(f"score must be one of {sorted(SCORE_KINDS)}, not {kind!r}")
         families = [tuple(f) for f in families]
@@ -169,14 +199,23 @@ class Dataset:
         scope_cols = _i32([c for f in families for c in f]) if scope_off[-1] else np.zeros(1, np.int32)
         scores = np.zeros(max(1, len(families)), np.float64)
         eng = self.engine
+        if wset is not None:
+            wset = _i32(wset).reshape(-1)
+            if len(wset) != len(families):
+                raise ValueError("wset needs one entry per family")
+            eng._check(eng._L.mibn_score_families_w(eng._h, self.id, SCORE_KINDS[kind], float(ess), len(families), _p(scope_off, C.c_int64),
+                                                    _p(scope_cols, C.c_int32), _p(wset if len(wset) else np.zeros(1, np.int32), C.c_int32),
+                                                    _p(scores, C.c_double)))
+            return scores[:len(families)]
         eng._check(eng._L.mibn_score_families(eng._h, self.id, SCORE_KINDS[kind], float(ess), len(families), _p(scope_off, C.c_int64),
                                               _p(scope_cols, C.c_int32), _p(scores, C.c_double)))
         return scores[:len(families)]
 
-    def ci_tests(self, tests, kind="g2"):
+    def ci_tests(self, tests, kind="g2", wset=None):
         """tests: sequences of column indices (*Z, x, y), the conditioning columns first -> (stat float64[n], adj_dof int64[n]):
         the G2 or X2 statistic (`kind` one of CI_KINDS) of x and y given Z and the degrees of freedom adjusted for empty rows,
-        columns and strata; one call, whatever the number of tests."""
+        columns and strata; one call, whatever the number of tests.  wset: one weight-set index per test (-1 = every row once) ->
+        mibn_ci_tests_w; None is the unweighted call."""
         if kind not in CI_KINDS:
             raise ValueError(f"test must be one of {sorted(CI_KINDS)}, not {kind!r}")
         tests = [tuple(t) for t in tests]
@@ -185,6 +224,13 @@ class Dataset:
         stat = np.zeros(max(1, len(tests)), np.float64)
         dof = np.zeros(max(1, len(tests)), np.int64)
         eng = self.engine
+        if wset is not None:
+            wset = _i32(wset).reshape(-1)
+            if len(wset) != len(tests):
+                raise ValueError("wset needs one entry per test")
+            eng._check(eng._L.mibn_ci_tests_w(eng._h, self.id, CI_KINDS[kind], len(tests), _p(scope_off, C.c_int64), _p(scope_cols, C.c_int32),
+                                              _p(wset if len(wset) else np.zeros(1, np.int32), C.c_int32), _p(stat, C.c_double), _p(dof, C.c_int64)))
+            return stat[:len(tests)], dof[:len(tests)]
         eng._check(eng._L.mibn_ci_tests(eng._h, self.id, CI_KINDS[kind], len(tests), _p(scope_off, C.c_int64), _p(scope_cols, C.c_int32),
                                         _p(stat, C.c_double), _p(dof, C.c_int64)))
         return stat[:len(tests)], dof[:len(tests)]
@@ -805,9 +851,10 @@ class Engine:
                                                 _p(card if len(card) else np.zeros(1, np.int32), C.c_int32), C.byref(ds_id)))
         return Dataset(self, ds_id.value, n_rows, card)
 
-    def count_tables(self, codes, card, tables):
+    def count_tables(self, codes, card, tables, weights=None):
         """codes: uint8 [n_rows, n_cols] (row- or column-major, sent as it is); tables: list of column-index tuples
-        -> list of dense int64 contingency tables shaped by the cards of their columns."""
+        -> list of dense int64 contingency tables shaped by the cards of their columns.  weights: non-negative integers
+        [n_rows] summing to at most 2^32 - 1, row i counts weights[i] times (mibn_count_tables_w); None: every row once."""
         codes = np.asarray(codes, dtype=np.uint8)
         if codes.ndim != 2:
             raise ValueError("codes must be a [n_rows, n_cols] matrix")
@@ -822,6 +869,15 @@ class Engine:
         counts_off = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
         counts = np.zeros(max(1, int(counts_off[-1])), np.int64)
         sc = scope_cols if len(scope_cols) else np.zeros(1, np.int32)
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.uint32).reshape(-1)
+            if len(w) != n_rows:
+                raise ValueError("weights needs one entry per row")
+            self._check(self._L.mibn_count_tables_w(
+                self._h, n_rows, n_cols, codes.ctypes.data_as(C.POINTER(C.c_uint8)), row_major, _p(card if len(card) else np.zeros(1, np.int32), C.c_int32),
+                len(tables), _p(scope_off, C.c_int64), _p(sc, C.c_int32), _p(counts_off, C.c_int64), _p(w if len(w) else np.zeros(1, np.uint32), C.c_uint32),
+                _p(counts, C.c_int64)))
+            return [counts[a:b].reshape([int(card[c]) for c in t]) for t, a, b in zip(tables, counts_off[:-1], counts_off[1:])]
         self._check(self._L.mibn_count_tables(
             self._h, n_rows, n_cols, codes.ctypes.data_as(C.POINTER(C.c_uint8)), row_major, _p(card if len(card) else np.zeros(1, np.int32), C.c_int32),
             len(tables), _p(scope_off, C.c_int64), _p(sc, C.c_int32), _p(counts_off, C.c_int64), _p(counts, C.c_int64)))

@@ -1554,13 +1554,15 @@ class BayesNet:
         return np.log(self.predict_proba(X))
 
     # ---- parameter learning (bayes_net.py:467-516) ----------------------------------
-    def partial_fit(self, X: pd.DataFrame):
+    def partial_fit(self, X: pd.DataFrame, weights=None):
+        """`weights` (an extension): non-negative integer row multiplicities, or the name of the column of X that holds them -
+        see `learning.row_weights`."""
         from . import learning
-        return learning.partial_fit(self, X)
+        return learning.partial_fit(self, X, weights=weights)
 
-    def fit(self, X: pd.DataFrame):
+    def fit(self, X: pd.DataFrame, weights=None):
         from . import learning
-        return learning.fit(self, X)
+        return learning.fit(self, X, weights=weights)
 
     def fit_em(self, X: pd.DataFrame, n_iter=20, tol=1e-6, prior_count=0.0, init="auto", sub_batch=32768, algorithm="exact",
                bp_iterations=100, bp_tol=1e-9, damping=0.0):
@@ -1571,12 +1573,12 @@ class BayesNet:
         return learning.fit_em(self, X, n_iter=n_iter, tol=tol, prior_count=prior_count, init=init, sub_batch=sub_batch, algorithm=algorithm,
                                bp_iterations=bp_iterations, bp_tol=bp_tol, damping=damping)
 
-    def score(self, X: pd.DataFrame, score="bic", ess=1.0) -> float:
+    def score(self, X: pd.DataFrame, score="bic", ess=1.0, weights=None) -> float:
         """The structure's score on the complete rows of X: the sum of its families' "loglik", "bic", "aic", "bdeu" or "k2"
         scores, counted and reduced on the device (an extension, see `learning.family_scores`).  With "loglik" it is the
-        log-likelihood of X under the CPTs `fit(X)` would learn."""
+        log-likelihood of X under the CPTs `fit(X)` would learn.  `weights`: integer row multiplicities (`learning.row_weights`)."""
         from . import learning
-        return learning.net_score(self, X, score=score, ess=ess)
+        return learning.net_score(self, X, score=score, ess=ess, weights=weights)
 
 
 def accelerate(bn, device=None, backend_factory=None):

@@ -25,6 +25,7 @@
 #include "bp_kernel.hip.h"
 #include "sample_kernel.hip.h"
 #include "count_kernel.hip.h"
+#include "count_weighted_kernel.hip.h"
 #include "score_kernel.hip.h"
 #include "citest_kernel.hip.h"
 #include "planner.h"
@@ -193,13 +194,13 @@ constexpr int kLevelStreams = 4;
 // findings: the seeds of a planned wave, the tiny kernel's twin, the one kernel of mibn_bp_batch, the one of mibn_bp_mpe_batch and the two of mibn_bp_evidence_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatBpEvidence, kStatBpAccumulate, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatBpEvidence, kStatBpAccumulate, kStatCountW, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel", "bp_evidence_kernel", "bp_accumulate_kernel"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel", "bp_evidence_kernel", "bp_accumulate_kernel", "count_weighted_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -419,6 +420,10 @@ struct mibn_ctx {
         int32_t n_cols = 0;
         std::vector<int32_t> card;
         bool live = false;
+        // mibn_dataset_set_weights / mibn_dataset_bootstrap: the weight sets [n_sets][n_rows] and W_s of every set
+        DevBuf<uint32_t> d_weights;
+        int32_t n_sets = 0;
+        std::vector<int64_t> weight_sum;
     };
     std::vector<Dataset> datasets;
     struct Score {
@@ -429,6 +434,7 @@ struct mibn_ctx {
         std::vector<Event> ev;
     } sc;
     int64_t score_cells = kScoreCellBudget;  // option score_cells (test hook: forces sub-batches)
+    int weighted_share = 1;  // option weighted_share: count_weighted_kernel keeps a row's cell index across neighbouring tables of one scope (DESIGN section 24 has both times)
     // options
     double arena_gb = 200.0;  // scratch budget of all lanes together (of the 288 GB)
     int mfma_kernel = 1;            // round 5: the one-table fp64-MFMA pair classes of a level as a launch of ve_mfma_kernel (128 VGPRs, four
@@ -684,6 +690,7 @@ int mibn_set_option(mibn_t *h, const char *name, double value) {
     else if (n == "outer") h->net.outer = value != 0;
     else if (n == "stagger") h->net.stagger = std::max(1, std::min(8, (int)value));  // groups of requests with staggered levels per chunk
     else if (n == "prune") h->net.prune = value != 0;  // 0: multiply every CPT (full_joint_dist / predict_proba semantics)  // OUTER (MFMA) form for products of two big tables  // joint elimination of two variables per pass
+    else if (n == "weighted_share") h->weighted_share = value != 0;
     else if (n == "score_cells") h->score_cells = std::max<int64_t>(1, std::min<int64_t>(int64_t(1) << 28, (int64_t)value));  // test hook: cell budget of a sub-batch of mibn_score_families (2^28: at most 32 768 LDS groups, the grid's y limit is 65 535)
     else if (n == "small_cells") h->net.small_cells = std::max(1, std::min(kMaxT, (int)value));  // test hook: forces FIBER steps on small networks
     else { h->err = "unknown option " + n; return MIBN_E_ARG; }
@@ -3402,6 +3409,17 @@ extern "C" int mibn_count_tables(mibn_t *h, int64_t n_rows, int32_t n_cols, cons
     return count_run(h->stream, n_rows, n_cols, codes, row_major != 0, card, n_tables, scope_off, scope_cols, counts_off, counts, h->err);
 }
 
+extern "C" int mibn_count_tables_w(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t *codes, int32_t row_major, const int32_t *card,
+                                   int32_t n_tables, const int64_t *scope_off, const int32_t *scope_cols, const int64_t *counts_off,
+                                   const uint32_t *weights, int64_t *counts) {
+    if (!h || n_rows < 0 || n_cols < 0 || n_tables < 0 || (n_rows && n_cols && !codes) || !card || !scope_off || !scope_cols ||
+        !counts_off || !counts || (n_rows && !weights) || (row_major != 0 && row_major != 1))
+        return MIBN_E_ARG;
+    if (int rc = check_state(h, kNeedDevice)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return count_run_weighted(h->stream, n_rows, n_cols, codes, row_major != 0, card, n_tables, scope_off, scope_cols, counts_off, weights, counts, h->err);
+}
+
 extern "C" int mibn_dataset_create(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t *codes, int32_t row_major, const int32_t *card, int32_t *id) {
     if (!h || !id || n_rows < 0 || n_cols < 0 || (n_rows && n_cols && !codes) || (n_cols && !card) || (row_major != 0 && row_major != 1)) return MIBN_E_ARG;
     *id = -1;
@@ -3456,7 +3474,57 @@ extern "C" int mibn_dataset_destroy(mibn_t *h, int32_t id) {
     mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, ds.d_codes.release());
+    HIP_TRY(h, ds.d_weights.release());
     ds = mibn_ctx::Dataset{};
+    return MIBN_OK;
+}
+
+static int tables_enter(mibn_ctx *h, int32_t id, const char *what);
+
+static int dataset_of(mibn_ctx *h, int32_t id, const char *what, mibn_ctx::Dataset *&ds) {
+    if (int rc = tables_enter(h, id, what)) return rc;
+    ds = &h->datasets[(size_t)id];
+    return MIBN_OK;
+}
+
+extern "C" int mibn_dataset_set_weights(mibn_t *h, int32_t id, int32_t n_sets, const uint32_t *weights) {
+    if (!h || n_sets < 0) return MIBN_E_ARG;
+    mibn_ctx::Dataset *ds = nullptr;
+    if (int rc = dataset_of(h, id, "weights", ds)) return rc;
+    if (n_sets && ds->n_rows && !weights) { h->err = "weights: no weights given"; return MIBN_E_ARG; }
+    std::vector<int64_t> sums;
+    if (int rc = weight_sums(weights, n_sets, ds->n_rows, sums, h->err)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)n_sets * (size_t)ds->n_rows;
+    DevBuf<uint32_t> fresh;
+    if (n_sets) {
+        HIP_TRY(h, fresh.reset(std::max<size_t>(1, n)));
+        if (n) HIP_TRY(h, hipMemcpyAsync(fresh, weights, 4 * n, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    ds->d_weights = std::move(fresh);
+    ds->n_sets = n_sets;
+    ds->weight_sum = std::move(sums);
+    return MIBN_OK;
+}
+
+extern "C" int mibn_dataset_bootstrap(mibn_t *h, int32_t id, int32_t n_sets, uint64_t seed, uint32_t *weights_out) {
+    if (!h || n_sets < 0) return MIBN_E_ARG;
+    mibn_ctx::Dataset *ds = nullptr;
+    if (int rc = dataset_of(h, id, "bootstrap", ds)) return rc;
+    if (ds->n_rows > 0xffffffffll) { h->err = "bootstrap: the data set has more than 2^32 - 1 rows"; return MIBN_E_LIMIT; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)n_sets * (size_t)ds->n_rows;
+    DevBuf<uint32_t> fresh;
+    if (n_sets) {
+        HIP_TRY(h, fresh.reset(std::max<size_t>(1, n)));
+        HIP_TRY(h, bootstrap_weights_launch(h->stream, fresh, ds->n_rows, n_sets, seed));
+        if (n && weights_out) HIP_TRY(h, hipMemcpyAsync(weights_out, fresh, 4 * n, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    ds->d_weights = std::move(fresh);
+    ds->n_sets = n_sets;
+    ds->weight_sum.assign((size_t)n_sets, ds->n_rows);
     return MIBN_OK;
 }
 
@@ -3467,6 +3535,7 @@ struct TableSub {
     int64_t cells = 0;
     std::vector<int64_t> off;     // first cell of every table in the count buffer (a sub-batch starts at cell 0), then the end
     CountPack pack;
+    CountWeightsPack wpack;       // (weighted calls: where the weight-set arrays lie in pack.i32)
     size_t o_i32 = 0, o_i64 = 0;  // the pack in the metadata buffer
     double count_launches = 0, reduce_launches = 0, reduce_bytes = 0;
 };
@@ -3476,6 +3545,9 @@ struct TableBatch {
     std::vector<TableSub> subs;
     std::vector<char> meta;  // everything the kernels read but the counts: ONE upload per call
     int64_t max_cells = 1;
+    const int32_t *wset = nullptr;  // mibn_score_families_w / mibn_ci_tests_w: the weight set of every table, checked; else NULL
+    // N of table f: W_s of its set, n_rows without one
+    int64_t rows_of(const mibn_ctx::Dataset &ds, int f) const { return wset && wset[f] >= 0 ? ds.weight_sum[(size_t)wset[f]] : ds.n_rows; }
     size_t put(const void *src, size_t bytes) {
         const size_t o = meta.size();
         meta.resize(o + ((bytes + 15) & ~size_t(15)));
@@ -3503,6 +3575,8 @@ static int tables_check(mibn_ctx *h, const mibn_ctx::Dataset &ds, const std::str
         }
         B.cells_of[(size_t)f] = cells;
     }
+    for (int f = 0; B.wset && f < n; ++f)
+        if (B.wset[f] < -1 || B.wset[f] >= ds.n_sets) { h->err = what + " " + std::to_string(f) + ": weight set " + std::to_string(B.wset[f]) + " outside [-1, " + std::to_string(ds.n_sets) + ")"; return MIBN_E_ARG; }
     return MIBN_OK;
 }
 
@@ -3522,6 +3596,7 @@ static int tables_cut(mibn_ctx *h, const mibn_ctx::Dataset &ds, int32_t n, const
         for (int f = S.f0; f < S.f1; ++f) S.off[(size_t)(f - S.f0) + 1] = S.off[(size_t)(f - S.f0)] + B.cells_of[(size_t)f];
         const int rc = count_pack(ds.n_cols, ds.card.data(), S.f1 - S.f0, scope_off + S.f0, scope_cols, S.off.data(), S.pack, h->err);
         if (rc != MIBN_OK) return rc;
+        if (B.wset) count_pack_weights(S.pack, S.f1 - S.f0, scope_off + S.f0, scope_cols, S.off.data(), B.wset + S.f0, h->weighted_share != 0, S.wpack);
         S.o_i64 = B.put(S.pack.i64.data(), S.pack.i64.size() * 8);
         S.o_i32 = B.put(S.pack.i32.data(), S.pack.i32.size() * 4);
         B.max_cells = std::max(B.max_cells, S.cells);
@@ -3554,8 +3629,10 @@ static int tables_count(mibn_ctx *h, const mibn_ctx::Dataset &ds, TableBatch &B,
     TableSub &S = B.subs[s];
     HIP_TRY(h, hipMemsetAsync(X.d_counts, 0, 8 * (size_t)std::max<int64_t>(1, S.cells), h->stream));
     HIP_TRY(h, hipEventRecord(X.ev[3 * s], h->stream));
-    HIP_TRY(h, count_launch(h->stream, ds.d_codes, ds.n_rows, S.pack, reinterpret_cast<const int32_t *>(X.d_meta + S.o_i32),
-                            reinterpret_cast<const int64_t *>(X.d_meta + S.o_i64), X.d_counts));
+    const int32_t *d_i32 = reinterpret_cast<const int32_t *>(X.d_meta + S.o_i32);
+    const int64_t *d_i64 = reinterpret_cast<const int64_t *>(X.d_meta + S.o_i64);
+    if (B.wset) HIP_TRY(h, count_weighted_launch(h->stream, ds.d_codes, ds.n_rows, S.pack, S.wpack, d_i32, d_i64, ds.d_weights, X.d_counts));
+    else HIP_TRY(h, count_launch(h->stream, ds.d_codes, ds.n_rows, S.pack, d_i32, d_i64, X.d_counts));
     S.count_launches = ds.n_rows > 0 ? (S.pack.n_big > 0) + (S.pack.n_small > 0) : 0;
     HIP_TRY(h, hipEventRecord(X.ev[3 * s + 1], h->stream));
     return MIBN_OK;
@@ -3567,10 +3644,11 @@ static int tables_reduced(mibn_ctx *h, size_t s) {
     return MIBN_OK;
 }
 
-// after the stream is synchronised: last-call statistics, the counting under count_kernel and the reduction under `slot`
+// after the stream is synchronised: last-call statistics, the counting under count_kernel (a weighted call: count_weighted_kernel,
+// which also reads 4 bytes of weight per row and table) and the reduction under `slot`
 static int tables_book(mibn_ctx *h, const mibn_ctx::Dataset &ds, const TableBatch &B, const int64_t *scope_off, int slot, double t_start) {
     mibn_ctx::Score &X = h->sc;
-    mibn_kernel_stat &kc = h->kstats[kStatCount], &ks = h->kstats[slot];
+    mibn_kernel_stat &kc = h->kstats[B.wset ? kStatCountW : kStatCount], &ks = h->kstats[slot];
     for (size_t s = 0; s < B.subs.size(); ++s) {
         const TableSub &S = B.subs[s];
         float ms_c = 0, ms_s = 0;
@@ -3580,6 +3658,7 @@ static int tables_book(mibn_ctx *h, const mibn_ctx::Dataset &ds, const TableBatc
         kc.launches += S.count_launches;
         kc.ms += ms_c;
         kc.alg_bytes += (double)ds.n_rows * (double)(scope_off[S.f1] - scope_off[S.f0]) + 8.0 * (double)S.cells;  // codes read per table member + the tables
+        if (B.wset) kc.alg_bytes += 4.0 * (double)ds.n_rows * n;
         kc.items += n;
         ks.launches += S.reduce_launches;
         ks.ms += ms_s;
@@ -3600,9 +3679,10 @@ static int tables_enter(mibn_ctx *h, int32_t id, const char *what) {
     return MIBN_OK;
 }
 
-extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off, const int32_t *scope_cols,
-                                   double *scores) {
-    if (!h || n_fam < 0 || !scope_off || (n_fam && (!scope_cols || !scores))) return MIBN_E_ARG;
+// mibn_score_families (wset = NULL) and mibn_score_families_w: one body.  The kernels take N as one launch argument, so the families of
+// a sub-batch are reduced N by N - one class without weights and in a bootstrap, where every W_s = n_rows.
+static int score_families_run(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off, const int32_t *scope_cols,
+                              const int32_t *wset, double *scores) {
     int rc;
     if ((rc = tables_enter(h, id, "score"))) return rc;
     if (kind < MIBN_SCORE_LOGLIK || kind > MIBN_SCORE_K2) { h->err = "score: unknown kind"; return MIBN_E_ARG; }
@@ -3613,21 +3693,31 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
     if (n_fam == 0) return MIBN_OK;
     // ---- everything is checked and packed on the host before anything is launched
     TableBatch B;
+    B.wset = wset;
     if ((rc = tables_check(h, ds, "score: family", 1, "is empty (the child comes last)", n_fam, scope_off, scope_cols, B))) return rc;
     if ((rc = tables_cut(h, ds, n_fam, scope_off, scope_cols, B))) return rc;
-    struct Sub {
+    struct Class {  // the families of one N
+        int64_t n_rows = 0;
         std::vector<ScoreFam> small, big;
         std::vector<ScoreChunk> chunk;
         std::vector<ScoreBig> big_parts;
-        int32_t n_parts = 0;
         size_t o_small = 0, o_big = 0, o_chunk = 0, o_bp = 0;  // in the metadata buffer
+    };
+    struct Sub {
+        std::vector<Class> classes;  // in the order their N first occurs
+        int32_t n_parts = 0;
     };
     std::vector<Sub> subs(B.subs.size());
     int32_t max_parts = 0;
     for (size_t s = 0; s < subs.size(); ++s) {
         const TableSub &T = B.subs[s];
-        Sub &S = subs[s];
+        Sub &U = subs[s];
         for (int f = T.f0; f < T.f1; ++f) {
+            const int64_t n_rows = B.rows_of(ds, f);
+            size_t c = 0;
+            while (c < U.classes.size() && U.classes[c].n_rows != n_rows) ++c;
+            if (c == U.classes.size()) { U.classes.emplace_back(); U.classes[c].n_rows = n_rows; }
+            Class &S = U.classes[c];
             ScoreFam F;
             F.off = T.off[(size_t)(f - T.f0)];
             F.r = ds.card[(size_t)scope_cols[scope_off[f + 1] - 1]];
@@ -3638,19 +3728,21 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
             } else {
                 const int64_t per = score_chunk_configs(F.r);
                 ScoreBig G;
-                G.part0 = S.n_parts;
+                G.part0 = U.n_parts;
                 G.n_parts = (int32_t)((F.q + per - 1) / per);
-                for (int32_t c = 0; c < G.n_parts; ++c) S.chunk.push_back(ScoreChunk{(int32_t)S.big.size(), S.n_parts + c, (int64_t)c * per});
-                S.n_parts += G.n_parts;
+                for (int32_t i = 0; i < G.n_parts; ++i) S.chunk.push_back(ScoreChunk{(int32_t)S.big.size(), U.n_parts + i, (int64_t)i * per});
+                U.n_parts += G.n_parts;
                 S.big.push_back(F);
                 S.big_parts.push_back(G);
             }
         }
-        max_parts = std::max(max_parts, S.n_parts);
-        S.o_small = B.put(S.small.data(), S.small.size() * sizeof(ScoreFam));
-        S.o_big = B.put(S.big.data(), S.big.size() * sizeof(ScoreFam));
-        S.o_chunk = B.put(S.chunk.data(), S.chunk.size() * sizeof(ScoreChunk));
-        S.o_bp = B.put(S.big_parts.data(), S.big_parts.size() * sizeof(ScoreBig));
+        max_parts = std::max(max_parts, U.n_parts);
+        for (Class &S : U.classes) {
+            S.o_small = B.put(S.small.data(), S.small.size() * sizeof(ScoreFam));
+            S.o_big = B.put(S.big.data(), S.big.size() * sizeof(ScoreFam));
+            S.o_chunk = B.put(S.chunk.data(), S.chunk.size() * sizeof(ScoreChunk));
+            S.o_bp = B.put(S.big_parts.data(), S.big_parts.size() * sizeof(ScoreBig));
+        }
     }
     // ---- device
     if ((rc = tables_begin(h, B))) return rc;
@@ -3659,33 +3751,34 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
     const hipStream_t S0 = h->stream;
     double *d_scores = X.d_f64, *d_parts = X.d_f64 + n_fam;
     for (size_t s = 0; s < subs.size(); ++s) {
-        const Sub &S = subs[s];
         if ((rc = tables_count(h, ds, B, s))) return rc;
-        ScoreArgs A;
-        A.counts = X.d_counts;
-        A.small = reinterpret_cast<const ScoreFam *>(X.d_meta + S.o_small);
-        A.big = reinterpret_cast<const ScoreFam *>(X.d_meta + S.o_big);
-        A.chunk = reinterpret_cast<const ScoreChunk *>(X.d_meta + S.o_chunk);
-        A.big_parts = reinterpret_cast<const ScoreBig *>(X.d_meta + S.o_bp);
-        A.parts = d_parts;
-        A.scores = d_scores;
-        A.ess = ess;
-        A.n_rows = ds.n_rows;
-        A.kind = kind;
-        A.n_small = (int32_t)S.small.size();
-        A.n_big = (int32_t)S.big.size();
-        constexpr int kPerWG = kScoreWG / 64;
         TableSub &T = B.subs[s];
-        if (A.n_small) {
-            hipLaunchKernelGGL(score_kernel, dim3((unsigned)((A.n_small + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
-            T.reduce_launches += 1;
+        for (const Class &S : subs[s].classes) {
+            ScoreArgs A;
+            A.counts = X.d_counts;
+            A.small = reinterpret_cast<const ScoreFam *>(X.d_meta + S.o_small);
+            A.big = reinterpret_cast<const ScoreFam *>(X.d_meta + S.o_big);
+            A.chunk = reinterpret_cast<const ScoreChunk *>(X.d_meta + S.o_chunk);
+            A.big_parts = reinterpret_cast<const ScoreBig *>(X.d_meta + S.o_bp);
+            A.parts = d_parts;
+            A.scores = d_scores;
+            A.ess = ess;
+            A.n_rows = S.n_rows;
+            A.kind = kind;
+            A.n_small = (int32_t)S.small.size();
+            A.n_big = (int32_t)S.big.size();
+            constexpr int kPerWG = kScoreWG / 64;
+            if (A.n_small) {
+                hipLaunchKernelGGL(score_kernel, dim3((unsigned)((A.n_small + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
+                T.reduce_launches += 1;
+            }
+            if (A.n_big) {
+                hipLaunchKernelGGL(score_chunk_kernel, dim3((unsigned)S.chunk.size()), dim3(kScoreWG), 0, S0, A);
+                hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((A.n_big + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
+                T.reduce_launches += 2;
+            }
         }
-        if (A.n_big) {
-            hipLaunchKernelGGL(score_chunk_kernel, dim3((unsigned)S.chunk.size()), dim3(kScoreWG), 0, S0, A);
-            hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((A.n_big + kPerWG - 1) / kPerWG)), dim3(kScoreWG), 0, S0, A);
-            T.reduce_launches += 2;
-        }
-        T.reduce_bytes = 8.0 * ((double)T.cells + (double)(T.f1 - T.f0) + 2.0 * (double)S.n_parts);
+        T.reduce_bytes = 8.0 * ((double)T.cells + (double)(T.f1 - T.f0) + 2.0 * (double)subs[s].n_parts);
         if ((rc = tables_reduced(h, s))) return rc;
     }
     const double t0 = now_ms();
@@ -3695,19 +3788,35 @@ extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double e
     return tables_book(h, ds, B, scope_off, kStatScore, t_start);
 }
 
-extern "C" int mibn_ci_tests(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const int64_t *scope_off, const int32_t *scope_cols, double *stat,
-                             int64_t *adj_dof) {
-    if (!h || n_tests < 0 || !scope_off || (n_tests && (!scope_cols || !stat || !adj_dof))) return MIBN_E_ARG;
+extern "C" int mibn_score_families(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off, const int32_t *scope_cols,
+                                   double *scores) {
+    if (!h || n_fam < 0 || !scope_off || (n_fam && (!scope_cols || !scores))) return MIBN_E_ARG;
+    return score_families_run(h, id, kind, ess, n_fam, scope_off, scope_cols, nullptr, scores);
+}
+
+extern "C" int mibn_score_families_w(mibn_t *h, int32_t id, int32_t kind, double ess, int32_t n_fam, const int64_t *scope_off, const int32_t *scope_cols,
+                                     const int32_t *wset, double *scores) {
+    if (!h || n_fam < 0 || !scope_off || (n_fam && (!scope_cols || !scores || !wset))) return MIBN_E_ARG;
+    static const int32_t none = -1;  // (n_fam = 0: still the weighted path)
+    return score_families_run(h, id, kind, ess, n_fam, scope_off, scope_cols, wset ? wset : &none, scores);
+}
+
+// mibn_ci_tests (wset = NULL) and mibn_ci_tests_w: one body (the kernels read no N)
+static int ci_tests_run(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const int64_t *scope_off, const int32_t *scope_cols, const int32_t *wset,
+                        double *stat, int64_t *adj_dof) {
     int rc;
     if ((rc = tables_enter(h, id, "ci"))) return rc;
     if (kind != MIBN_CI_G2 && kind != MIBN_CI_X2) { h->err = "ci: unknown kind"; return MIBN_E_ARG; }
     const mibn_ctx::Dataset &ds = h->datasets[(size_t)id];
     if (ds.n_rows >= (int64_t(1) << 31)) { h->err = "ci: the data set has 2^31 rows or more (the statistics' products are 64-bit integers)"; return MIBN_E_LIMIT; }
+    for (int f = 0; wset && f < n_tests; ++f)
+        if (wset[f] >= 0 && wset[f] < ds.n_sets && ds.weight_sum[(size_t)wset[f]] >= (int64_t(1) << 31)) { h->err = "ci: test " + std::to_string(f) + ": its weight set sums to 2^31 or more (the statistics' products are 64-bit integers)"; return MIBN_E_LIMIT; }
     const double t_start = now_ms();
     reset_last_stats(h);
     if (n_tests == 0) return MIBN_OK;
     // ---- everything is checked and packed on the host before anything is launched
     TableBatch B;
+    B.wset = wset;
     if ((rc = tables_check(h, ds, "ci: test", 2, "names fewer than two columns (conditioning columns, then X, then Y)", n_tests, scope_off, scope_cols, B))) return rc;
     if ((rc = tables_cut(h, ds, n_tests, scope_off, scope_cols, B))) return rc;
     struct Sub {
@@ -3815,6 +3924,19 @@ extern "C" int mibn_ci_tests(mibn_t *h, int32_t id, int32_t kind, int32_t n_test
     HIP_TRY(h, hipStreamSynchronize(S0));
     h->stats.d2h_ms += now_ms() - t0;
     return tables_book(h, ds, B, scope_off, kStatCiTest, t_start);
+}
+
+extern "C" int mibn_ci_tests(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const int64_t *scope_off, const int32_t *scope_cols, double *stat,
+                             int64_t *adj_dof) {
+    if (!h || n_tests < 0 || !scope_off || (n_tests && (!scope_cols || !stat || !adj_dof))) return MIBN_E_ARG;
+    return ci_tests_run(h, id, kind, n_tests, scope_off, scope_cols, nullptr, stat, adj_dof);
+}
+
+extern "C" int mibn_ci_tests_w(mibn_t *h, int32_t id, int32_t kind, int32_t n_tests, const int64_t *scope_off, const int32_t *scope_cols,
+                               const int32_t *wset, double *stat, int64_t *adj_dof) {
+    if (!h || n_tests < 0 || !scope_off || (n_tests && (!scope_cols || !stat || !adj_dof || !wset))) return MIBN_E_ARG;
+    static const int32_t none = -1;
+    return ci_tests_run(h, id, kind, n_tests, scope_off, scope_cols, wset ? wset : &none, stat, adj_dof);
 }
 
 extern "C" int mibn_plan_order(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,

@@ -61,10 +61,10 @@ def encode_columns(X, columns):
     return codes.T, domains, cards
 
 
-def count_tables_dropna(engine, codes, domains, cards, tables):
+def count_tables_dropna(engine, codes, domains, cards, tables, **more):
     """Dense contingency tables over the *labels*: rows with a missing value in any of a table's columns are dropped
     (the NA slice, where a column has one, is cut off) - pandas' dropna=True."""
-    dense = engine.count_tables(codes, cards, tables)
+    dense = engine.count_tables(codes, cards, tables, **more)
     out = []
     for d, t in zip(dense, tables):
         cut = tuple(slice(0, len(domains[c])) for c in t)
@@ -84,23 +84,55 @@ def count_series(counts, domains, names):
     return pd.Series(flat[keep], index=idx)
 
 
-def grouped_counts(X, tables, device=None):
-    """`tables`: list of column-name tuples -> list of `X.groupby(list(t)).size()`-like Series, one GPU launch."""
+def row_weights(X, weights):
+    """The `weights` argument of the learning calls -> (X without the weight column, uint32 weights or None).  A weight vector
+    is 1-D, of length len(X), and holds non-negative integers (floats only when integral) whose sum is at most 2^32 - 1: row
+    i counts weights[i] times, exactly as if it were written out that often - except that the label domains (and with them
+    the cardinalities in BIC / AIC / BDeu) are those of ALL rows of X, weight 0 included.  Alternatively the NAME of a column
+    of X: that column is the weight and not a variable (aggregated data: one row per pattern plus a frequency).  Anything
+    else is a ValueError.  None -> (X, None): the unweighted path."""
+    if weights is None:
+        return X, None
+    if isinstance(weights, (str, bytes)) or np.isscalar(weights):
+        if weights not in X.columns:
+            raise ValueError(f"weights: X has no column {weights!r}")
+        w, X = X[weights].to_numpy(), X.drop(columns=[weights])
+    else:
+        w = weights.to_numpy() if hasattr(weights, "to_numpy") else np.asarray(weights)
+    if w.ndim != 1 or len(w) != len(X):
+        raise ValueError(f"weights must be one-dimensional with one entry per row of X ({len(X)})")
+    if w.dtype.kind == "b" or w.dtype.kind not in "iuf":
+        raise ValueError("weights must be non-negative integers")
+    if w.dtype.kind == "f" and not (np.isfinite(w).all() and (w == np.floor(w)).all()):
+        raise ValueError("weights must be integral (real-valued weights are not supported)")
+    if len(w) and w.min() < 0:
+        raise ValueError("weights must not be negative")
+    if math.fsum(w.tolist()) > _capi.MAX_WEIGHT_SUM:
+        raise ValueError("weights sum to more than 2^32 - 1")
+    return X, w.astype(np.uint32)
+
+
+def grouped_counts(X, tables, device=None, weights=None):
+    """`tables`: list of column-name tuples -> list of `X.groupby(list(t)).size()`-like Series, one GPU launch.  `weights`
+    (uint32 per row, from `row_weights`): row i counts weights[i] times."""
     columns = sorted({c for t in tables for c in t}, key=list(X.columns).index)
     codes, domains, cards = encode_columns(X, columns)
     pos = {c: j for j, c in enumerate(columns)}
-    dense = count_tables_dropna(counting_engine(device), codes, domains, cards, [tuple(pos[c] for c in t) for t in tables])
+    more = {} if weights is None else {"weights": weights}
+    dense = count_tables_dropna(counting_engine(device), codes, domains, cards, [tuple(pos[c] for c in t) for t in tables], **more)
     return [count_series(d, [domains[pos[c]] for c in t], list(t)) for d, t in zip(dense, tables)]
 
 
 # ------------------------------------------------------------------------------------------------ rank 3: fit
-def partial_fit(bn, X):
+def partial_fit(bn, X, weights=None):
     """BayesNet.partial_fit (bayes_net.py:467-510): update every CPT with the rows of X.  Exact integer counts are
-    kept per node (`bn._counts`), so fitting in chunks gives bit-identical CPTs to fitting at once."""
+    kept per node (`bn._counts`), so fitting in chunks gives bit-identical CPTs to fitting at once.  `weights`: see
+    `row_weights` - the counts are those of the rows written out weights[i] times."""
+    X, weights = row_weights(X, weights)
     if not hasattr(bn, "_counts") or bn._counts is None:
         bn._counts = {}
     tables = [tuple([*bn.parents[c], c]) for c in bn.parents] + [(r,) for r in bn.roots]
-    fresh = grouped_counts(X, tables, device=getattr(bn, "_device", None))
+    fresh = grouped_counts(X, tables, device=getattr(bn, "_device", None), weights=weights)
     for names, new in zip(tables, fresh):
         node = names[-1]
         new = new.astype(np.float64)
@@ -126,11 +158,12 @@ def partial_fit(bn, X):
     return bn
 
 
-def fit(bn, X):
+def fit(bn, X, weights=None):
     """BayesNet.fit (bayes_net.py:512-516)."""
+    X, weights = row_weights(X, weights)
     bn.P = {}
     bn._counts = {}
-    return partial_fit(bn, X)
+    return partial_fit(bn, X, weights=weights)
 
 
 # ------------------------------------------------------------------------------------------- rank 4: Chow-Liu
@@ -535,11 +568,21 @@ def encode_complete(X, columns):
     return codes, domains, cards
 
 
-def family_scores(X, families, score="bic", ess=1.0, device=None):
+def _weighted(ds, weights):
+    """The keyword of `Dataset.score_families` / `ci_tests` for n tables of a call under `weights` - which become set 0 of
+    the data set; none without weights: the unweighted calls, exactly as before."""
+    if weights is None:
+        return lambda n: {}
+    ds.set_weights(weights)
+    return lambda n: {"wset": np.zeros(n, np.int32)}
+
+
+def family_scores(X, families, score="bic", ess=1.0, device=None, weights=None):
     """Decomposable scores of families on the rows of X: `families` is a list of (child, parents) name pairs -> float64
     array, one launch pair for all of them.  score: "loglik", "bic", "aic", "bdeu" (equivalent sample size `ess`) or
-    "k2", in natural logs (include/mibn.h gives the formulas)."""
+    "k2", in natural logs (include/mibn.h gives the formulas).  `weights`: see `row_weights`; N is then their sum."""
     _check_score(score, ess)
+    X, weights = row_weights(X, weights)
     fams = []
     for child, parents in families:
         parents = [parents] if isinstance(parents, str) or not hasattr(parents, "__iter__") else list(parents)
@@ -556,7 +599,8 @@ def family_scores(X, families, score="bic", ess=1.0, device=None):
         return np.zeros(0, np.float64)
     pos = {c: j for j, c in enumerate(used)}
     with counting_engine(device).dataset(codes, cards) as ds:
-        return ds.score_families([tuple(sorted(pos[p] for p in parents)) + (pos[child],) for child, parents in fams], score, ess)
+        return ds.score_families([tuple(sorted(pos[p] for p in parents)) + (pos[child],) for child, parents in fams], score, ess,
+                                 **_weighted(ds, weights)(len(fams)))
 
 
 def _edge_list(edges, columns, what):
@@ -623,25 +667,108 @@ class _Graph:
         return any(self.anc[p, u] for p in self.pa[v] if p != u)
 
 
-def hill_climb(X, score="bic", ess=1.0, max_parents=3, start=None, required=(), forbidden=(), max_iter=None, epsilon=1e-4,
-               device=None, return_trace=False):
-    """Greedy hill climbing over DAGs with a decomposable score: from `start` (an edge list, e.g. `chow_liu(X)`; default the
-    empty graph) apply the legal move - add u -> v, delete u -> v, reverse u -> v - with the largest gain in score while
-    that gain exceeds `epsilon`.  Legal: the graph stays acyclic, no node gets more than `max_parents` parents, a `required`
-    edge is never removed or reversed (required edges are part of the start graph), a `forbidden` one never created.  Equal
-    gains: add before delete before reverse, then by the position of the edge's child, then of its parent, in X.columns -
-    the result is a function of the scores alone.
+class _Climb:
+    """One greedy search as a step-wise object, so that `hill_climb` and the lockstep `bootstrap` drive the same code:
+    `needs()` lists the (child, parent set) keys the next step reads and the cache lacks, `feed` stores their scores,
+    `advance()` refreshes the gains of the children whose parents changed, then makes the best legal move (or finishes)."""
 
-    Returns what `BayesNet(*result)` accepts: (parent, child) tuples plus the bare names of isolated columns.  With
-    `return_trace`: (result, [(op, u, v, gain), ...] - the edge u -> v as it was before the move, for "add" the new edge -
-    and the total score of the result).
+    def __init__(self, columns, begin, req, forb, max_parents, max_iter, epsilon):
+        self.columns, self.n = columns, len(columns)
+        n = self.n
+        self.g = _Graph(n, begin)
+        for v in range(n):
+            if len(self.g.pa[v]) > max_parents:
+                raise ValueError(f"start gives {columns[v]!r} {len(self.g.pa[v])} parents (max_parents = {max_parents})")
+        self.max_parents, self.max_iter, self.epsilon = max_parents, max_iter, float(epsilon)
+        self.R = np.zeros((n, n), bool)  # [child, parent]
+        self.F = np.zeros((n, n), bool)
+        for u, v in req:
+            self.R[v, u] = True
+        for u, v in forb:
+            self.F[v, u] = True
+        self.not_self = ~np.eye(n, dtype=bool)
+        self.cache, self.trace = {}, []
+        # delta[v, u]: what toggling the edge u -> v adds to the score of v's family (NaN: not a candidate)
+        self.delta = np.full((n, n), np.nan)
+        self.pending = list(range(n))  # children whose row of delta is stale
+        self.it, self.done = 0, False
 
-    The search runs on the host; the rows are uploaded once and every iteration sends the device one batch of the families it
-    has not scored yet (scores are cached by (child, parent set): after the first sweep of n + n (n - 1) families only the one
-    or two children whose parents changed need new ones).  Complete data only.
+    def candidates(self, v):
+        """The families a move into / out of child v needs."""
+        pa = frozenset(self.g.pa[v])
+        keys = [(v, pa)] + [(v, pa - {p}) for p in sorted(pa)]
+        if len(pa) < self.max_parents:
+            keys += [(v, pa | {u}) for u in range(self.n) if u != v and u not in pa]
+        return keys
 
-    epsilon: a design choice, not a measured quantity - far above the rounding noise of a score (~1e-9 at a million rows), far
-    below any gain that matters (one BIC parameter costs 0.5 ln N >= 0.35)."""
+    def needs(self):
+        return [k for k in dict.fromkeys(k for v in self.pending for k in self.candidates(v)) if k not in self.cache]
+
+    def feed(self, keys, scores):
+        for k, s in zip(keys, scores):
+            self.cache[k] = float(s)
+
+    def advance(self):
+        g, n, delta, cache, max_parents = self.g, self.n, self.delta, self.cache, self.max_parents
+        for v in self.pending:
+            pa = frozenset(g.pa[v])
+            base = cache[(v, pa)]
+            delta[v, :] = np.nan
+            for p in pa:
+                delta[v, p] = cache[(v, pa - {p})] - base
+            if len(pa) < max_parents:
+                for u in range(n):
+                    if u != v and u not in pa:
+                        delta[v, u] = cache[(v, pa | {u})] - base
+        self.pending = []
+        if self.max_iter is not None and self.it >= int(self.max_iter):
+            self.done = True
+            return
+        R, F = self.R, self.F
+        npar = np.array([len(p) for p in g.pa])
+        room = (npar < max_parents)[:, None]
+        E = g.edge
+        gains = []
+        add_ok = ~E & self.not_self & room & ~F & ~g.anc.T  # (anc.T[v, u]: v is an ancestor of u)
+        gains.append(np.where(add_ok, delta, -np.inf))
+        gains.append(np.where(E & ~R, delta, -np.inf))
+        rev = np.full((n, n), -np.inf)
+        for v, u in zip(*np.nonzero(E & ~R & ~F.T & room.T)):  # (room.T[v, u]: u can take another parent)
+            if not g.reverse_makes_cycle(u, v):
+                rev[v, u] = delta[v, u] + delta[u, v]
+        gains.append(rev)
+        best = max(float(m.max()) if m.size else -np.inf for m in gains)
+        if not best > self.epsilon:
+            self.done = True
+            return
+        op = next(k for k, m in enumerate(gains) if m.size and float(m.max()) == best)
+        v, u = np.unravel_index(int(np.argmax(gains[op])), (n, n))  # first maximum in [child, parent] order
+        v, u = int(v), int(u)
+        if op == 0:
+            g.add(u, v)
+            changed = [v]
+        elif op == 1:
+            g.delete(u, v)
+            changed = [v]
+        else:
+            g.delete(u, v)
+            g.add(v, u)
+            changed = [v, u]
+        self.trace.append((MOVES[op], self.columns[u], self.columns[v], best))
+        self.pending = changed
+        self.it += 1
+
+    def result(self, return_trace):
+        g, n, columns = self.g, self.n, self.columns
+        total = math.fsum(self.cache[(v, frozenset(g.pa[v]))] for v in range(n))
+        result = [(columns[u], columns[v]) for v in range(n) for u in sorted(g.pa[v])]
+        linked = {c for e in result for c in e}
+        result += [c for c in columns if c not in linked]
+        return (result, self.trace, total) if return_trace else result
+
+
+def _climb_plan(X, score, ess, max_parents, start, required, forbidden, max_iter, epsilon):
+    """The argument checks of `hill_climb` -> (columns, a factory of fresh `_Climb` objects); no engine is touched."""
     _check_score(score, ess)
     columns = list(X.columns)
     n = len(columns)
@@ -665,98 +792,57 @@ def hill_climb(X, score="bic", ess=1.0, max_parents=3, start=None, required=(), 
     for e in begin:
         if e in forb:
             raise ValueError(f"start contains the forbidden edge {columns[e[0]]!r} -> {columns[e[1]]!r}")
-    g = _Graph(n, begin)
-    for v in range(n):
-        if len(g.pa[v]) > max_parents:
-            raise ValueError(f"start gives {columns[v]!r} {len(g.pa[v])} parents (max_parents = {max_parents})")
+
+    def fresh():
+        return _Climb(columns, begin, req, forb, max_parents, max_iter, epsilon)
+
+    fresh()  # (the checks of the start graph)
+    return columns, fresh
+
+
+def _family_scope(key):
+    child, parents = key
+    return tuple(sorted(parents)) + (child,)
+
+
+def hill_climb(X, score="bic", ess=1.0, max_parents=3, start=None, required=(), forbidden=(), max_iter=None, epsilon=1e-4,
+               device=None, return_trace=False, weights=None):
+    """Greedy hill climbing over DAGs with a decomposable score: from `start` (an edge list, e.g. `chow_liu(X)`; default the
+    empty graph) apply the legal move - add u -> v, delete u -> v, reverse u -> v - with the largest gain in score while
+    that gain exceeds `epsilon`.  Legal: the graph stays acyclic, no node gets more than `max_parents` parents, a `required`
+    edge is never removed or reversed (required edges are part of the start graph), a `forbidden` one never created.  Equal
+    gains: add before delete before reverse, then by the position of the edge's child, then of its parent, in X.columns -
+    the result is a function of the scores alone.
+
+    Returns what `BayesNet(*result)` accepts: (parent, child) tuples plus the bare names of isolated columns.  With
+    `return_trace`: (result, [(op, u, v, gain), ...] - the edge u -> v as it was before the move, for "add" the new edge -
+    and the total score of the result).
+
+    The search runs on the host; the rows are uploaded once and every iteration sends the device one batch of the families it
+    has not scored yet (scores are cached by (child, parent set): after the first sweep of n + n (n - 1) families only the one
+    or two children whose parents changed need new ones).  Complete data only.  `weights`: see `row_weights` - the search on
+    the rows written out weights[i] times, bit for bit, without writing them out.
+
+    epsilon: a design choice, not a measured quantity - far above the rounding noise of a score (~1e-9 at a million rows), far
+    below any gain that matters (one BIC parameter costs 0.5 ln N >= 0.35)."""
+    X, weights = row_weights(X, weights)
+    columns, fresh = _climb_plan(X, score, ess, max_parents, start, required, forbidden, max_iter, epsilon)
     codes, _, cards = encode_complete(X, columns)
-    R = np.zeros((n, n), bool)  # [child, parent]
-    F = np.zeros((n, n), bool)
-    for u, v in req:
-        R[v, u] = True
-    for u, v in forb:
-        F[v, u] = True
-    not_self = ~np.eye(n, dtype=bool)
-    cache = {}
-    trace = []
+    climb = fresh()
     with counting_engine(device).dataset(codes, cards) as ds:
-
-        def ensure(keys):
-            new = [k for k in dict.fromkeys(keys) if k not in cache]
+        under = _weighted(ds, weights)
+        while not climb.done:
+            new = climb.needs()
             if new:
-                got = ds.score_families([tuple(sorted(ps)) + (c,) for c, ps in new], score, ess)
-                for k, s in zip(new, got):
-                    cache[k] = float(s)
-
-        def candidates(v):
-            """The families a move into / out of child v needs."""
-            pa = frozenset(g.pa[v])
-            keys = [(v, pa)] + [(v, pa - {p}) for p in sorted(pa)]
-            if len(pa) < max_parents:
-                keys += [(v, pa | {u}) for u in range(n) if u != v and u not in pa]
-            return keys
-
-        # delta[v, u]: what toggling the edge u -> v adds to the score of v's family (NaN: not a candidate)
-        delta = np.full((n, n), np.nan)
-
-        def refresh(children):
-            ensure([k for v in children for k in candidates(v)])
-            for v in children:
-                pa = frozenset(g.pa[v])
-                base = cache[(v, pa)]
-                delta[v, :] = np.nan
-                for p in pa:
-                    delta[v, p] = cache[(v, pa - {p})] - base
-                if len(pa) < max_parents:
-                    for u in range(n):
-                        if u != v and u not in pa:
-                            delta[v, u] = cache[(v, pa | {u})] - base
-
-        refresh(range(n))
-        it = 0
-        while max_iter is None or it < int(max_iter):
-            npar = np.array([len(p) for p in g.pa])
-            room = (npar < max_parents)[:, None]
-            E = g.edge
-            gains = []
-            add_ok = ~E & not_self & room & ~F & ~g.anc.T  # (anc.T[v, u]: v is an ancestor of u)
-            gains.append(np.where(add_ok, delta, -np.inf))
-            gains.append(np.where(E & ~R, delta, -np.inf))
-            rev = np.full((n, n), -np.inf)
-            for v, u in zip(*np.nonzero(E & ~R & ~F.T & room.T)):  # (room.T[v, u]: u can take another parent)
-                if not g.reverse_makes_cycle(u, v):
-                    rev[v, u] = delta[v, u] + delta[u, v]
-            gains.append(rev)
-            best = max(float(m.max()) if m.size else -np.inf for m in gains)
-            if not best > float(epsilon):
-                break
-            op = next(k for k, m in enumerate(gains) if m.size and float(m.max()) == best)
-            v, u = np.unravel_index(int(np.argmax(gains[op])), (n, n))  # first maximum in [child, parent] order
-            v, u = int(v), int(u)
-            if op == 0:
-                g.add(u, v)
-                changed = [v]
-            elif op == 1:
-                g.delete(u, v)
-                changed = [v]
-            else:
-                g.delete(u, v)
-                g.add(v, u)
-                changed = [v, u]
-            trace.append((MOVES[op], columns[u], columns[v], best))
-            refresh(changed)
-            it += 1
-        total = math.fsum(cache[(v, frozenset(g.pa[v]))] for v in range(n))
-    result = [(columns[u], columns[v]) for v in range(n) for u in sorted(g.pa[v])]
-    linked = {c for e in result for c in e}
-    result += [c for c in columns if c not in linked]
-    return (result, trace, total) if return_trace else result
+                climb.feed(new, ds.score_families([_family_scope(k) for k in new], score, ess, **under(len(new))))
+            climb.advance()
+    return climb.result(return_trace)
 
 
-def net_score(bn, X, score="bic", ess=1.0):
+def net_score(bn, X, score="bic", ess=1.0, weights=None):
     """The sum of the family scores of the net's own structure on the rows of X (`BayesNet.score`)."""
     fams = [(node, list(bn.parents.get(node, []))) for node in bn.nodes]
-    return math.fsum(family_scores(X, fams, score=score, ess=ess, device=getattr(bn, "_device", None)).tolist())
+    return math.fsum(family_scores(X, fams, score=score, ess=ess, device=getattr(bn, "_device", None), weights=weights).tolist())
 
 
 # ------------------------------------------------------ constraint-based structure learning: CI tests and PC-stable
@@ -817,9 +903,10 @@ def _check_ci(test, dof):
         raise ValueError(f"dof must be one of {CI_DOFS}, not {dof!r}")
 
 
-def _ci_batch(ds, cards, n_rows, batch, test, dof):
-    """batch: (x, y, Z) column positions -> (stat, dof, p_value) arrays through ONE `Dataset.ci_tests` call."""
-    stat, adj = ds.ci_tests([(*Z, x, y) for x, y, Z in batch], "g2" if test == "mi" else test)
+def _ci_batch(ds, cards, n_rows, batch, test, dof, **under):
+    """batch: (x, y, Z) column positions -> (stat, dof, p_value) arrays through ONE `Dataset.ci_tests` call (`under`: its
+    weight-set keyword, if any; n_rows is then the sets' N)."""
+    stat, adj = ds.ci_tests([(*Z, x, y) for x, y, Z in batch], "g2" if test == "mi" else test, **under)
     if dof == "classic":
         d = np.array([math.prod(int(cards[z]) for z in Z) * (int(cards[x]) - 1) * (int(cards[y]) - 1) for x, y, Z in batch], np.int64)
     else:
@@ -830,13 +917,15 @@ def _ci_batch(ds, cards, n_rows, batch, test, dof):
     return np.asarray(stat, np.float64), d.reshape(-1), p
 
 
-def ci_tests(X, tests, test="g2", dof="classic", device=None):
+def ci_tests(X, tests, test="g2", dof="classic", device=None, weights=None):
     """Conditional-independence tests on the rows of X: `tests` is a list of (x, y, given) names (`given` a name or a
     sequence of names, possibly empty) -> DataFrame with one row per test: `stat`, `dof`, `p_value`.  test: "g2" (the
     likelihood-ratio statistic), "x2" (Pearson's) or "mi" (G2 / (2 N) as `stat`, the p-value of G2).  dof: "classic" =
     q (rx - 1)(ry - 1) over the cardinalities of the encoded columns, "adjusted" = summed over the strata that occur, from
-    the rows and columns that occur in each.  dof == 0 gives p_value 1.  One launch pair for all tests; complete data only."""
+    the rows and columns that occur in each.  dof == 0 gives p_value 1.  One launch pair for all tests; complete data only.
+    `weights`: see `row_weights`; N is then their sum."""
     _check_ci(test, dof)
+    X, weights = row_weights(X, weights)
     asked = []
     for t in tests:
         if not (isinstance(t, (tuple, list)) and len(t) == 3):
@@ -858,7 +947,8 @@ def ci_tests(X, tests, test="g2", dof="classic", device=None):
     pos = {c: j for j, c in enumerate(used)}
     with counting_engine(device).dataset(codes, cards) as ds:
         batch = [(pos[x], pos[y], tuple(sorted(pos[z] for z in given))) for x, y, given in asked]
-        out["stat"], out["dof"], out["p_value"] = _ci_batch(ds, cards, len(X), batch, test, dof)
+        n_rows = len(X) if weights is None else int(weights.sum(dtype=np.int64))
+        out["stat"], out["dof"], out["p_value"] = _ci_batch(ds, cards, n_rows, batch, test, dof, **_weighted(ds, weights)(len(batch)))
     return out
 
 
@@ -885,25 +975,33 @@ def _meek(n, adj, arrow):
                     changed = True
 
 
-def _pc_search(n, tester, alpha, max_cond=3, required=(), forbidden=()):
-    """PC-stable over the columns 0 .. n - 1.  tester: a list of (x, y, S) with x < y and S an ascending tuple -> their
-    p-values; it is called ONCE per level.  required / forbidden: (u, v) position pairs for u -> v.  A pair forbidden in both
-    directions is never adjacent; a required edge is never tested and starts directed; an edge forbidden one way is directed
-    the other way if it survives.  -> dict(adj, arrow, sepsets, levels, trace)."""
-    required, forbidden = list(required), set(forbidden)
-    adj = [{v for v in range(n) if v != u and not ((u, v) in forbidden and (v, u) in forbidden)} for u in range(n)]
-    fixed = {frozenset(e) for e in required}
-    for u, v in required:
-        adj[u].add(v)
-        adj[v].add(u)
-    sepsets, levels, trace = {}, [], []
-    level = 0
-    while level <= max_cond:
+class _Skeleton:
+    """The skeleton phase of PC-stable as a step-wise object (`_pc_search` and the lockstep `bootstrap` drive the same code):
+    `next_batch()` gives the tests of the next level - None when the search is over -, `feed` takes their p-values,
+    `finish()` orients what is left."""
+
+    def __init__(self, n, alpha, max_cond=3, required=(), forbidden=()):
+        self.n, self.alpha, self.max_cond = n, alpha, max_cond
+        self.required, self.forbidden = list(required), set(forbidden)
+        forbidden = self.forbidden
+        self.adj = [{v for v in range(n) if v != u and not ((u, v) in forbidden and (v, u) in forbidden)} for u in range(n)]
+        self.fixed = {frozenset(e) for e in self.required}
+        for u, v in self.required:
+            self.adj[u].add(v)
+            self.adj[v].add(u)
+        self.sepsets, self.levels, self.trace = {}, [], []
+        self.level = 0
+        self.batch = self.per_pair = None
+
+    def next_batch(self):
+        if self.level > self.max_cond:
+            return None
+        n, adj, level = self.n, self.adj, self.level
         frozen = [sorted(a) for a in adj]  # the adjacency of the whole level
         batch, index, per_pair = [], {}, {}
         for x in range(n):
             for y in frozen[x]:
-                if frozenset((x, y)) in fixed:
+                if frozenset((x, y)) in self.fixed:
                     continue
                 others = [z for z in frozen[x] if z != y]
                 pair = (min(x, y), max(x, y))
@@ -914,38 +1012,60 @@ def _pc_search(n, tester, alpha, max_cond=3, required=(), forbidden=()):
                         batch.append(key)
                         per_pair.setdefault(pair, []).append(index[key])
         if not batch:
-            break
-        p = [float(v) for v in tester(batch)]
-        levels.append(len(batch))
-        trace += [(level, x, y, S, pv) for (x, y, S), pv in zip(batch, p)]
-        for (x, y), asked in per_pair.items():
-            hit = next((i for i in asked if p[i] > alpha), None)
+            return None
+        self.batch, self.per_pair = batch, per_pair
+        return batch
+
+    def feed(self, p_values):
+        adj, batch, level = self.adj, self.batch, self.level
+        p = [float(v) for v in p_values]
+        self.levels.append(len(batch))
+        self.trace += [(level, x, y, S, pv) for (x, y, S), pv in zip(batch, p)]
+        for (x, y), asked in self.per_pair.items():
+            hit = next((i for i in asked if p[i] > self.alpha), None)
             if hit is not None:  # the first separating set in enumeration order
                 adj[x].discard(y)
                 adj[y].discard(x)
-                sepsets[(x, y)] = batch[hit][2]
-        level += 1
-    # ---- orientation: background knowledge, v-structures in column order (the first orientation of an edge stays), Meek
-    arrow = set()
+                self.sepsets[(x, y)] = batch[hit][2]
+        self.level += 1
 
-    def orient(u, v):
-        if v in adj[u] and (v, u) not in arrow and (u, v) not in forbidden:
-            arrow.add((u, v))
+    def finish(self):
+        """Orientation: background knowledge, v-structures in column order (the first orientation of an edge stays), Meek."""
+        n, adj, sepsets, forbidden = self.n, self.adj, self.sepsets, self.forbidden
+        arrow = set()
 
-    for u, v in required:
-        orient(u, v)
-    for u, v in sorted(forbidden):
-        orient(v, u)
-    for x in range(n):
-        for y in range(x + 1, n):
-            if y in adj[x] or (x, y) not in sepsets:
-                continue
-            for z in sorted(adj[x] & adj[y]):
-                if z not in sepsets[(x, y)]:
-                    orient(x, z)
-                    orient(y, z)
-    _meek(n, adj, arrow)
-    return {"adj": adj, "arrow": arrow, "sepsets": sepsets, "levels": levels, "trace": trace}
+        def orient(u, v):
+            if v in adj[u] and (v, u) not in arrow and (u, v) not in forbidden:
+                arrow.add((u, v))
+
+        for u, v in self.required:
+            orient(u, v)
+        for u, v in sorted(forbidden):
+            orient(v, u)
+        for x in range(n):
+            for y in range(x + 1, n):
+                if y in adj[x] or (x, y) not in sepsets:
+                    continue
+                for z in sorted(adj[x] & adj[y]):
+                    if z not in sepsets[(x, y)]:
+                        orient(x, z)
+                        orient(y, z)
+        _meek(n, adj, arrow)
+        return {"adj": adj, "arrow": arrow, "sepsets": sepsets, "levels": self.levels, "trace": self.trace}
+
+
+def _pc_search(n, tester, alpha, max_cond=3, required=(), forbidden=()):
+    """PC-stable over the columns 0 .. n - 1.  tester: a list of (x, y, S) with x < y and S an ascending tuple -> their
+    p-values; it is called ONCE per level.  required / forbidden: (u, v) position pairs for u -> v.  A pair forbidden in both
+    directions is never adjacent; a required edge is never tested and starts directed; an edge forbidden one way is directed
+    the other way if it survives.  -> dict(adj, arrow, sepsets, levels, trace)."""
+    search = _Skeleton(n, alpha, max_cond, required, forbidden)
+    while True:
+        batch = search.next_batch()
+        if batch is None:
+            break
+        search.feed(tester(batch))
+    return search.finish()
 
 
 class PCResult:
@@ -993,17 +1113,8 @@ class PCResult:
         return result + [c for c in self.columns if c not in linked]
 
 
-def pc(X, alpha=0.01, test="g2", dof="classic", max_cond=3, required=(), forbidden=(), device=None, return_trace=False):
-    """The PC algorithm in its order-independent ("stable") form.  Skeleton: from the complete graph, level l = 0, 1, ...,
-    max_cond tests every pair still adjacent given every l-subset of either end's other neighbours - the adjacency frozen at
-    the start of the level, so ALL tests of a level go to the device as one batch - and drops an edge as soon as one of its
-    tests has p > alpha; the separating set is the first such subset (pairs in column order, subsets lexicographic).
-    Orientation: v-structures from the separating sets in column order (the first orientation of an edge stays, no
-    bidirected edges), then Meek's rules 1 to 3 to closure.  `required` / `forbidden` are (parent, child) pairs: a required
-    edge is kept and directed, a forbidden one never directed that way (forbidden both ways: never adjacent).
-
-    test, dof: see `ci_tests`.  Returns a `PCResult`; `PCResult.dag()` gives `BayesNet(*edges).fit(X)` a member of the class.
-    Complete data only; the rows are uploaded once."""
+def _pc_plan(X, alpha, test, dof, max_cond, required, forbidden):
+    """The argument checks of `pc` -> (columns, required, forbidden as position pairs); no engine is touched."""
     _check_ci(test, dof)
     if not 0.0 < float(alpha) < 1.0:
         raise ValueError("alpha must lie strictly between 0 and 1")
@@ -1019,7 +1130,165 @@ def pc(X, alpha=0.01, test="g2", dof="classic", max_cond=3, required=(), forbidd
             raise ValueError(f"the edge {columns[u]!r} -> {columns[v]!r} is both required and forbidden")
         if (v, u) in req:
             raise ValueError(f"{columns[u]!r} and {columns[v]!r} are required in both directions")
+    return columns, req, forb
+
+
+def pc(X, alpha=0.01, test="g2", dof="classic", max_cond=3, required=(), forbidden=(), device=None, return_trace=False, weights=None):
+    """The PC algorithm in its order-independent ("stable") form.  Skeleton: from the complete graph, level l = 0, 1, ...,
+    max_cond tests every pair still adjacent given every l-subset of either end's other neighbours - the adjacency frozen at
+    the start of the level, so ALL tests of a level go to the device as one batch - and drops an edge as soon as one of its
+    tests has p > alpha; the separating set is the first such subset (pairs in column order, subsets lexicographic).
+    Orientation: v-structures from the separating sets in column order (the first orientation of an edge stays, no
+    bidirected edges), then Meek's rules 1 to 3 to closure.  `required` / `forbidden` are (parent, child) pairs: a required
+    edge is kept and directed, a forbidden one never directed that way (forbidden both ways: never adjacent).
+
+    test, dof: see `ci_tests`.  Returns a `PCResult`; `PCResult.dag()` gives `BayesNet(*edges).fit(X)` a member of the class.
+    Complete data only; the rows are uploaded once.  `weights`: see `row_weights`."""
+    X, weights = row_weights(X, weights)
+    columns, req, forb = _pc_plan(X, alpha, test, dof, max_cond, required, forbidden)
     codes, _, cards = encode_complete(X, columns)
     with counting_engine(device).dataset(codes, cards) as ds:
-        found = _pc_search(len(columns), lambda batch: _ci_batch(ds, cards, len(X), batch, test, dof)[2], float(alpha), int(max_cond), req, forb)
+        under = _weighted(ds, weights)
+        found = _pc_search(len(columns), lambda batch: _ci_batch(ds, cards, len(X), batch, test, dof, **under(len(batch)))[2], float(alpha),
+                           int(max_cond), req, forb)
     return PCResult(columns, found, return_trace)
+
+
+# ------------------------------------------------------ bootstrap arc strengths (Friedman, Goldszmidt and Wyner 1999)
+# One search says nothing about which of its arcs to believe; the standard answer is to repeat it on bootstrap resamples and count
+# the arcs.  A resample of N rows is a vector of N multiplicities: the rows stay resident once, the device draws the weight sets
+# (`Dataset.bootstrap`), and all replicates advance in LOCKSTEP - one `score_families` / `ci_tests` call per search iteration / level
+# carries every (table, set) pair any replicate still lacks (csrc/count_weighted_kernel.hip.h).
+BOOTSTRAP_LEARNERS = ("hill_climb", "pc")
+
+
+def _replicate_arcs(rep, pos):
+    """A replicate's result - what `hill_climb` returns (with or without its trace) or a `PCResult` - -> (directed position pairs,
+    undirected ones)."""
+    if hasattr(rep, "directed"):
+        return [(pos[u], pos[v]) for u, v in rep.directed], [(pos[u], pos[v]) for u, v in rep.undirected]
+    if isinstance(rep, tuple):
+        rep = rep[0]
+    return [(pos[e[0]], pos[e[1]]) for e in rep if isinstance(e, tuple)], []
+
+
+class ArcStrength:
+    """Arc strengths over the replicates of `bootstrap`.  `frame`: one row per unordered pair of columns adjacent in at least one
+    replicate, `from` before `to` in X.columns order (rows in that order too): `strength` = the fraction of replicates holding
+    the arc in either direction, `direction` = the share of those with from -> to (an undirected `pc` edge counts half each
+    way).  `n_boot`, `columns`."""
+
+    def __init__(self, columns, replicates):
+        self.columns = list(columns)
+        self.n_boot = len(replicates)
+        pos = {c: j for j, c in enumerate(self.columns)}
+        seen = {}  # (i, j), i < j -> [i -> j, j -> i, undirected]
+        for rep in replicates:
+            directed, undirected = _replicate_arcs(rep, pos)
+            for kind, arcs in ((None, directed), (2, undirected)):
+                for u, v in arcs:
+                    seen.setdefault((min(u, v), max(u, v)), [0, 0, 0])[(0 if u < v else 1) if kind is None else 2] += 1
+        pairs = sorted(seen)
+        total = [sum(seen[p]) for p in pairs]
+        self.frame = pd.DataFrame({
+            "from": [self.columns[i] for i, _ in pairs], "to": [self.columns[j] for _, j in pairs],
+            "strength": np.array([t / self.n_boot for t in total], np.float64),
+            "direction": np.array([(seen[p][0] + 0.5 * seen[p][2]) / t for p, t in zip(pairs, total)], np.float64)})
+
+    def edges(self, threshold=0.5):
+        """The averaged DAG as `BayesNet(*edges)` takes it: the pairs with strength >= threshold in descending strength (ties by the
+        columns' positions), each oriented by the majority (a tie goes to from -> to) and skipped where it would close a cycle;
+        then the bare names of the isolated columns."""
+        pos = {c: j for j, c in enumerate(self.columns)}
+        rows = [(-float(s), pos[u], pos[v], float(d)) for u, v, s, d in self.frame.itertuples(index=False) if s >= threshold]
+        g = _Graph(len(self.columns), [])
+        out = []
+        for _, i, j, d in sorted(rows):
+            u, v = (i, j) if d >= 0.5 else (j, i)
+            if g.anc[u, v]:  # v is an ancestor of u
+                continue
+            g.add(u, v)
+            out.append((self.columns[u], self.columns[v]))
+        linked = {c for e in out for c in e}
+        return out + [c for c in self.columns if c not in linked]
+
+
+def _lockstep(ds, searches, wanted, scope_of, ask):
+    """One round of every unfinished replicate: `wanted(search)` -> the keys it lacks; ONE device call - `ask(scopes, sets)` ->
+    one value per pair - carries them all, pairs of one scope next to each other (the count kernel then computes a row's cell
+    once per scope); -> {replicate: (keys, values)}."""
+    keys = {r: wanted(s) for r, s in enumerate(searches)}
+    pairs = sorted((scope_of(k), r, i) for r, ks in keys.items() for i, k in enumerate(ks or ()))
+    if not pairs:
+        return {}
+    values = ask([p[0] for p in pairs], np.array([p[1] for p in pairs], np.int32))
+    got = {r: [None] * len(ks) for r, ks in keys.items() if ks}
+    for (_, r, i), v in zip(pairs, values):
+        got[r][i] = v
+    return {r: (keys[r], vs) for r, vs in got.items()}
+
+
+def bootstrap(X, n_boot=100, learner="hill_climb", seed=0, return_replicates=False, device=None, **learner_args):
+    """Bootstrap arc strengths: `learner` ("hill_climb" or "pc", with `learner_args`) on `n_boot` multinomial resamples of the rows
+    of X -> an `ArcStrength`; with `return_replicates`: (ArcStrength, [the learner's result per replicate]).
+
+    Replicate r is `learner(X, weights=w_r, **learner_args)`, exactly, where w_r is set r of `Dataset.bootstrap(n_boot, seed)`
+    (a function of (seed, r, len(X)) alone: the same seed gives the same strengths, and more replicates extend the list).  The rows
+    are encoded and uploaded once and never expanded; the replicates advance in lockstep.  Complete data only."""
+    if learner not in BOOTSTRAP_LEARNERS:
+        raise ValueError(f"learner must be one of {BOOTSTRAP_LEARNERS}, not {learner!r}")
+    if int(n_boot) != n_boot or n_boot < 1:
+        raise ValueError("n_boot must be an integer >= 1")
+    if int(seed) != seed:
+        raise ValueError("seed must be an integer")
+    for k in ("weights", "device"):
+        if k in learner_args:
+            raise ValueError(f"bootstrap: {k!r} is not a learner argument (a weighted frame is not resampled)")
+    n_boot = int(n_boot)
+    if learner == "hill_climb":
+        names = ("score", "ess", "max_parents", "start", "required", "forbidden", "max_iter", "epsilon")
+        defaults = ("bic", 1.0, 3, None, (), (), None, 1e-4)
+    else:
+        names = ("alpha", "test", "dof", "max_cond", "required", "forbidden")
+        defaults = (0.01, "g2", "classic", 3, (), ())
+    keep_trace = bool(learner_args.pop("return_trace", False))
+    for k in learner_args:
+        if k not in names:
+            raise ValueError(f"bootstrap: {learner} has no argument {k!r}")
+    a = {k: learner_args.get(k, d) for k, d in zip(names, defaults)}
+    if learner == "hill_climb":
+        columns, fresh = _climb_plan(X, *[a[k] for k in names])
+    else:
+        columns, req, forb = _pc_plan(X, a["alpha"], a["test"], a["dof"], a["max_cond"], a["required"], a["forbidden"])
+    codes, _, cards = encode_complete(X, columns)
+    with counting_engine(device).dataset(codes, cards) as ds:
+        ds.bootstrap(n_boot, seed)
+        if learner == "hill_climb":
+            searches = [fresh() for _ in range(n_boot)]
+            while not all(s.done for s in searches):
+                got = _lockstep(ds, searches, lambda s: None if s.done else s.needs(), _family_scope,
+                                lambda scopes, sets: ds.score_families(scopes, a["score"], a["ess"], wset=sets))
+                for r, s in enumerate(searches):
+                    if not s.done:
+                        if r in got:
+                            s.feed(*got[r])
+                        s.advance()
+            replicates = [s.result(keep_trace) for s in searches]
+        else:
+            searches = [_Skeleton(len(columns), float(a["alpha"]), int(a["max_cond"]), req, forb) for _ in range(n_boot)]
+            live = list(searches)
+
+            def wanted(s):
+                if s in live and s.next_batch() is None:
+                    live.remove(s)
+                return s.batch if s in live else None
+
+            while live:
+                got = _lockstep(ds, searches, wanted, lambda k: k,
+                                lambda tests, sets: _ci_batch(ds, cards, len(X), tests, a["test"], a["dof"], wset=sets)[2])
+                for r, s in enumerate(searches):
+                    if r in got:
+                        s.feed(got[r][1])
+            replicates = [PCResult(columns, s.finish(), keep_trace) for s in searches]
+    strength = ArcStrength(columns, replicates)
+    return (strength, replicates) if return_replicates else strength
