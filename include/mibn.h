@@ -635,6 +635,42 @@ int mibn_count_tables_w(mibn_t *h, int64_t n_rows, int32_t n_cols, const uint8_t
                         const uint32_t *weights /* n_rows */, int64_t *counts);
 
 /*
+ * Exact structure learning: the best-scoring DAG under a decomposable score, by dynamic programming over variable subsets
+ * (Silander and Myllymaki 2006; Koivisto and Sood 2004).  The call takes no network and no data set - its input is a list of local
+ * scores, e.g. those of mibn_score_families or mibn_score_families_w, unchanged.
+ *
+ * Candidates.  Candidate f says: child fam_child[f] may take exactly the parent set fam_parents[f] (bit u = column u is a parent)
+ * at score fam_score[f].  A child's parent set is always one of its candidates; a set that is not listed is not allowed - limits on
+ * the number of parents, required and forbidden edges are expressed by what is listed.
+ *
+ * Validation, on the host before any launch.  MIBN_E_ARG: n_vars < 1, a child outside [0, n_vars), a parent bit at or above n_vars
+ * or the child's own bit, a non-finite score (NaN, +-inf), the same (child, parent set) listed twice.  MIBN_E_LIMIT: n_vars above
+ * MIBN_BEST_DAG_MAX_VARS (the tables take 12 n 2^(n-1) + 9 2^n bytes: 2.6 GB at 24).  MIBN_E_HIP if their allocation fails.
+ *
+ * Phase A, best parent sets.  For child v and every C inside V \ {v}: bps[v][C] = the best candidate (score, parent mask) of v with
+ * parents inside C, "best" being the maximum of one TOTAL order: the higher score first; at equal score (==) the smaller mask as an
+ * unsigned integer.  The winner's pair is kept whole, score bits and mask together; without such a candidate the entry is
+ * (-inf, 0xFFFFFFFF).  The order being total, the table is a function of the candidate list alone, whatever schedule computed it.
+ *
+ * Phase B, sinks.  best[{}] = 0; best[S] = max over v in S of (best[S \ {v}] + bps[v][S \ {v}].score) - one fp64 addition per
+ * term, the terms compared in ascending v with a strict > starting from -inf, so that ties go to the smallest v.  sink[S] is that v,
+ * or 255 if every term is -inf.
+ *
+ * Traceback.  From S = V: v = sink[S], parents_out[v] = bps[v][S \ {v}].mask, S = S \ {v}, n_vars times.  order_out is a
+ * topological order, roots first: the reverse of the sinks peeled.  total_out = best[V], that nested sum - equal to the sum of the
+ * chosen candidates' scores only up to rounding.  No DAG possible from the candidates (best[V] = -inf): MIBN_OK with total_out =
+ * -inf, every parents_out[v] = 0xFFFFFFFF and every order_out[v] = -1.
+ *
+ * Blocking.  Writes no option or policy state; bit-for-bit repeatable in any call and through any handle (the options
+ * dag_tile_bits / dag_group_bits - test hooks that shape phase A's passes - change no bit).  Last-call statistics only: the row
+ * dag_subset_kernel is the fill, the scatter of the candidates and the passes of phase A (alg_bytes: entries read and written),
+ * dag_sink_kernel the n_vars + 1 levels of phase B and the traceback.
+ */
+#define MIBN_BEST_DAG_MAX_VARS 24
+int mibn_best_dag(mibn_t *h, int32_t n_vars, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents /* bit u = column u is a parent */,
+                  const double *fam_score, uint32_t *parents_out /* n_vars */, int32_t *order_out /* n_vars */, double *total_out);
+
+/*
  * Multi-GPU: one process per GPU, requests / chains sharded with no data-path collective; the
  * only communication is the final gather of the posteriors (exact path) or the sum of the histograms (Gibbs).  These
  * entry points sit directly on RCCL (librccl.so is dlopen'ed by mibn_comm_init - a single-GPU process never loads it) and

@@ -28,6 +28,7 @@
 #include "count_weighted_kernel.hip.h"
 #include "score_kernel.hip.h"
 #include "citest_kernel.hip.h"
+#include "dag_kernel.hip.h"
 #include "planner.h"
 #include "plan_policy.h"
 #include "tiny_kernel.hip.h"
@@ -191,16 +192,17 @@ constexpr int kLevelStreams = 4;
 // launched, the two of mibn_mpe_batch, the one of mibn_expect_batch, the two phases of mibn_score_families and the two of
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
 // steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together), and the two kernels of a call with likelihood
-// findings: the seeds of a planned wave, the tiny kernel's twin, the one kernel of mibn_bp_batch, the one of mibn_bp_mpe_batch and the two of mibn_bp_evidence_batch.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// findings: the seeds of a planned wave, the tiny kernel's twin, the one kernel of mibn_bp_batch, the one of mibn_bp_mpe_batch and the two of mibn_bp_evidence_batch,
+// the weighted counting, and the two phases of mibn_best_dag.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatBpEvidence, kStatBpAccumulate, kStatCountW, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatBpEvidence, kStatBpAccumulate, kStatCountW, kStatDagSubset, kStatDagSink, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel", "bp_evidence_kernel", "bp_accumulate_kernel", "count_weighted_kernel"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel", "bp_evidence_kernel", "bp_accumulate_kernel", "count_weighted_kernel", "dag_subset_kernel", "dag_sink_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -434,6 +436,16 @@ struct mibn_ctx {
         std::vector<Event> ev;
     } sc;
     int64_t score_cells = kScoreCellBudget;  // option score_cells (test hook: forces sub-batches)
+    // mibn_best_dag: the tables of a call (kept between calls up to kDagKeepBytes) and its candidate / result block
+    struct Dag {
+        DevBuf<double> d_score, d_best;
+        DevBuf<uint32_t> d_mask;
+        DevBuf<uint8_t> d_sink;
+        DevBuf<char> d_io;  // [fam_score | fam_child | fam_parents] then [total | parents_out | order_out]
+        Event ev[3];
+    } dag;
+    int dag_tile_bits = kDagTileBits;    // options dag_tile_bits / dag_group_bits (test hooks: force multi-pass schedules at small n;
+    int dag_group_bits = kDagGroupBits;  // no bit of any result depends on them, dag_plan.h says why)
     int weighted_share = 1;  // option weighted_share: count_weighted_kernel keeps a row's cell index across neighbouring tables of one scope (DESIGN section 24 has both times)
     // options
     double arena_gb = 200.0;  // scratch budget of all lanes together (of the 288 GB)
@@ -691,6 +703,8 @@ int mibn_set_option(mibn_t *h, const char *name, double value) {
     else if (n == "stagger") h->net.stagger = std::max(1, std::min(8, (int)value));  // groups of requests with staggered levels per chunk
     else if (n == "prune") h->net.prune = value != 0;  // 0: multiply every CPT (full_joint_dist / predict_proba semantics)  // OUTER (MFMA) form for products of two big tables  // joint elimination of two variables per pass
     else if (n == "weighted_share") h->weighted_share = value != 0;
+    else if (n == "dag_tile_bits") h->dag_tile_bits = dag_clamp_bits((int64_t)value);
+    else if (n == "dag_group_bits") h->dag_group_bits = dag_clamp_bits((int64_t)value);
     else if (n == "score_cells") h->score_cells = std::max<int64_t>(1, std::min<int64_t>(int64_t(1) << 28, (int64_t)value));  // test hook: cell budget of a sub-batch of mibn_score_families (2^28: at most 32 768 LDS groups, the grid's y limit is 65 535)
     else if (n == "small_cells") h->net.small_cells = std::max(1, std::min(kMaxT, (int)value));  // test hook: forces FIBER steps on small networks
     else { h->err = "unknown option " + n; return MIBN_E_ARG; }
@@ -3937,6 +3951,108 @@ extern "C" int mibn_ci_tests_w(mibn_t *h, int32_t id, int32_t kind, int32_t n_te
     if (!h || n_tests < 0 || !scope_off || (n_tests && (!scope_cols || !stat || !adj_dof || !wset))) return MIBN_E_ARG;
     static const int32_t none = -1;
     return ci_tests_run(h, id, kind, n_tests, scope_off, scope_cols, wset ? wset : &none, stat, adj_dof);
+}
+
+// ---- mibn_best_dag: check (dag_plan.h), tables, fill + scatter + the passes of phase A, the n + 1 levels of phase B, the traceback.
+// Everything on the main stream, one synchronisation; three events give the two statistics rows.  Tables above kDagKeepBytes are
+// freed when the call returns (2.6 GB at n = 24 would otherwise stay with a context that may never ask again).
+constexpr size_t kDagKeepBytes = size_t(1) << 28;
+
+template <class T>
+static hipError_t dag_room(DevBuf<T> &buf, size_t need) {  // exactly `need`: no headroom on gigabytes
+    if (need <= buf.cap()) return hipSuccess;
+    const hipError_t e = buf.reset(need);
+    if (e != hipSuccess) (void)hipGetLastError();  // (a refused allocation must not be what a later call's launch check finds)
+    return e;
+}
+
+static int best_dag_run(mibn_t *h, int32_t n, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score,
+                        uint32_t *parents_out, int32_t *order_out, double *total_out) {
+    int rc;
+    if ((rc = check_state(h, kNeedDevice))) return rc;
+    if ((rc = check_state(h, kNeedIdle))) return rc;
+    const double t_start = now_ms();
+    reset_last_stats(h);
+    if ((rc = dag_check(n, n_fam, fam_child, fam_parents, fam_score, h->err))) return rc;
+    const DagPlan D = dag_plan(n, h->dag_tile_bits, h->dag_group_bits);
+    mibn_ctx::Dag &X = h->dag;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t bps = (size_t)n * (size_t)D.entries, subsets = size_t(1) << n, fam = (size_t)std::max<int64_t>(1, n_fam);
+    struct Release {  // on every exit, after the stream is drained (hipFree waits for the device)
+        mibn_ctx::Dag &X;
+        bool on;
+        ~Release() {
+            if (!on) return;
+            (void)X.d_score.release();
+            (void)X.d_mask.release();
+            (void)X.d_best.release();
+            (void)X.d_sink.release();
+        }
+    } release{X, 12 * bps + 9 * subsets > kDagKeepBytes};
+    HIP_TRY(h, dag_room(X.d_score, bps));
+    HIP_TRY(h, dag_room(X.d_mask, bps));
+    HIP_TRY(h, dag_room(X.d_best, subsets));
+    HIP_TRY(h, dag_room(X.d_sink, subsets));
+    const size_t o_child = 8 * fam, o_par = o_child + 4 * fam, o_total = (o_par + 4 * fam + 15) & ~size_t(15), o_pout = o_total + 8, o_order = o_pout + 4 * (size_t)n;
+    HIP_TRY(h, X.d_io.ensure(o_order + 4 * (size_t)n));
+    for (Event &e : X.ev) HIP_TRY(h, e.ensure());
+    const hipStream_t S0 = h->stream;
+    const double t0 = now_ms();
+    if (n_fam) {
+        HIP_TRY(h, hipMemcpyAsync(X.d_io, fam_score, 8 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+        HIP_TRY(h, hipMemcpyAsync(X.d_io + o_child, fam_child, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+        HIP_TRY(h, hipMemcpyAsync(X.d_io + o_par, fam_parents, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+    }
+    h->stats.h2d_ms += now_ms() - t0;
+    double *d_total = reinterpret_cast<double *>(X.d_io + o_total);
+    uint32_t *d_pout = reinterpret_cast<uint32_t *>(X.d_io + o_pout);
+    int32_t *d_order = reinterpret_cast<int32_t *>(X.d_io + o_order);
+    // phase A
+    HIP_TRY(h, hipEventRecord(X.ev[0], S0));
+    double launches_a = 1, bytes_a = 12.0 * (double)bps;
+    hipLaunchKernelGGL(dag_fill_kernel, dim3((unsigned)std::min<size_t>((bps + kDagWG - 1) / kDagWG, 65536)), dim3(kDagWG), 0, S0, X.d_score.get(), X.d_mask.get(), (int64_t)bps);
+    if (n_fam) {
+        hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)((n_fam + kDagWG - 1) / kDagWG)), dim3(kDagWG), 0, S0, reinterpret_cast<const int32_t *>(X.d_io + o_child),
+                           reinterpret_cast<const uint32_t *>(X.d_io + o_par), reinterpret_cast<const double *>(X.d_io.get()), n_fam, n, X.d_score.get(), X.d_mask.get());
+        launches_a += 1;
+        bytes_a += 28.0 * (double)n_fam;
+    }
+    for (const DagPass &P : D.passes) {
+        hipLaunchKernelGGL(dag_subset_kernel, dim3((unsigned)D.grid(P)), dim3(kDagWG), 0, S0, X.d_score.get(), X.d_mask.get(), P, n, D.tiles_per_child(P));
+        launches_a += 1;
+        bytes_a += 24.0 * (double)bps;
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(X.ev[1], S0));
+    // phase B and the traceback
+    for (int32_t level = 0; level <= n; ++level)
+        hipLaunchKernelGGL(dag_sink_kernel, dim3((unsigned)((subsets + kDagWG - 1) / kDagWG)), dim3(kDagWG), 0, S0, X.d_score.get(), X.d_best.get(), X.d_sink.get(), n, level);
+    hipLaunchKernelGGL(dag_traceback_kernel, dim3(1), dim3(64), 0, S0, X.d_mask.get(), X.d_best.get(), X.d_sink.get(), n, d_pout, d_order, d_total);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(X.ev[2], S0));
+    const double t1 = now_ms();
+    HIP_TRY(h, hipMemcpyAsync(total_out, d_total, 8, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipMemcpyAsync(parents_out, d_pout, 4 * (size_t)n, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipMemcpyAsync(order_out, d_order, 4 * (size_t)n, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipStreamSynchronize(S0));
+    h->stats.d2h_ms += now_ms() - t1;
+    float ms_a = 0, ms_b = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms_a, X.ev[0], X.ev[1]));
+    HIP_TRY(h, hipEventElapsedTime(&ms_b, X.ev[1], X.ev[2]));
+    book_stat(h, kStatDagSubset, launches_a, ms_a, bytes_a, (double)n_fam, true, false);
+    // every bps score and every best entry read once per member, best and sink written once per subset; the traceback's 2 n reads
+    book_stat(h, kStatDagSink, (double)n + 2.0, ms_b, 16.0 * (double)bps + 9.0 * (double)subsets, (double)subsets, true, false);
+    h->stats.kernel_ms = ms_a + ms_b;
+    h->stats.n_launches = launches_a + (double)n + 2.0;
+    h->stats.alg_bytes = bytes_a + 16.0 * (double)bps + 9.0 * (double)subsets;
+    h->stats.total_ms = now_ms() - t_start;
+    return MIBN_OK;
+}
+
+extern "C" int mibn_best_dag(mibn_t *h, int32_t n_vars, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score,
+                             uint32_t *parents_out, int32_t *order_out, double *total_out) {
+    if (!h || n_fam < 0 || (n_fam && (!fam_child || !fam_parents || !fam_score)) || !parents_out || !order_out || !total_out) return MIBN_E_ARG;
+    return drained_on_error(h, best_dag_run(h, n_vars, n_fam, fam_child, fam_parents, fam_score, parents_out, order_out, total_out), drain_main_unchecked);
 }
 
 extern "C" int mibn_plan_order(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,

@@ -839,6 +839,154 @@ def hill_climb(X, score="bic", ess=1.0, max_parents=3, start=None, required=(), 
     return climb.result(return_trace)
 
 
+# ------------------------------------------------------ exact structure learning: the best-scoring DAG by subset DP
+# An extension, like hill climbing above - and its yardstick: every score here is decomposable, so the globally best DAG
+# follows from local scores alone by dynamic programming over variable subsets (csrc/dag_kernel.hip.h, `mibn_best_dag`).
+EXACT_MAX_COLUMNS = _capi.BEST_DAG_MAX_VARS
+_MAX_TABLE_CELLS = 1 << 28  # of one family's contingency table (mibn_score_families)
+
+
+def _dag_result(columns, parents):
+    """Parent masks -> the result form of `hill_climb`: edges, children in column order and parents ascending, then isolated names."""
+    n = len(columns)
+    result = [(columns[u], columns[v]) for v in range(n) for u in range(n) if (int(parents[v]) >> u) & 1]
+    linked = {c for e in result for c in e}
+    return result + [c for c in columns if c not in linked]
+
+
+def _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards):
+    """The argument checks of `exact_search` -> (columns, candidates [(child, parent mask)]); no engine is touched.  `cards`
+    is a callable (evaluated after the cheaper checks) giving the cardinalities."""
+    _check_score(score, ess)
+    columns = list(X.columns)
+    n = len(columns)
+    if len(set(columns)) != n:
+        raise ValueError("X has duplicate column names")
+    if n < 1:
+        raise ValueError("X has no columns")
+    if n > EXACT_MAX_COLUMNS:
+        raise ValueError(f"exact_search handles at most {EXACT_MAX_COLUMNS} columns, X has {n} (the tables double with every column): "
+                         f"use hill_climb or pc")
+    max_parents = int(max_parents)
+    if max_parents < 0:
+        raise ValueError("max_parents must not be negative")
+    req = _edge_list(required, columns, "required")
+    forb = _edge_list(forbidden, columns, "forbidden")
+    for e in req:
+        if e in forb:
+            raise ValueError(f"the edge {columns[e[0]]!r} -> {columns[e[1]]!r} is both required and forbidden")
+    try:
+        _Graph(n, req)
+    except ValueError:
+        raise ValueError("the required edges form a cycle") from None
+    need = [sum(1 << u for u, c in req if c == v) for v in range(n)]
+    ban = [sum(1 << u for u, c in forb if c == v) for v in range(n)]
+    free = []  # the columns a child may or may not take
+    for v in range(n):
+        k = bin(need[v]).count("1")
+        if k > max_parents:
+            raise ValueError(f"{columns[v]!r} has {k} required parents (max_parents = {max_parents})")
+        free.append([u for u in range(n) if u != v and not ((need[v] | ban[v]) >> u) & 1])
+    count = sum(math.comb(len(free[v]), j) for v in range(n) for j in range(max_parents - bin(need[v]).count("1") + 1))
+    if count > int(max_families):
+        raise ValueError(f"{count} candidate families (max_families = {int(max_families)}): lower max_parents or raise max_families")
+    card = cards()
+    cand = []
+    for v in range(n):
+        k0 = bin(need[v]).count("1")
+        sets = [(k0 + j, need[v] | sum(1 << u for u in extra)) for j in range(max_parents - k0 + 1) for extra in itertools.combinations(free[v], j)]
+        for _, pm in sorted(sets):
+            cells = card[v]
+            for u in range(n):
+                if (pm >> u) & 1:
+                    cells *= card[u]
+            if cells > _MAX_TABLE_CELLS:
+                raise ValueError(f"the family of {columns[v]!r} with parents {[columns[u] for u in range(n) if (pm >> u) & 1]} has a table of "
+                                 f"{cells} cells (at most 2^28): lower max_parents")
+            cand.append((v, pm))
+    return columns, cand
+
+
+def _mask_scope(child, pm):
+    return tuple(u for u in range(pm.bit_length()) if (pm >> u) & 1) + (child,)
+
+
+def exact_search(X, score="bic", ess=1.0, max_parents=3, required=(), forbidden=(), max_families=2_000_000, device=None, return_info=False,
+                 weights=None):
+    """The globally best DAG under a decomposable score, by dynamic programming over column subsets (Silander and Myllymaki 2006)
+    on the device - for up to 24 columns; beyond that `hill_climb` and `pc` remain.  The candidates of child v are every parent
+    set P with |P| <= max_parents that holds the `required` parents of v and none of its `forbidden` ones (enumerated per child
+    in ascending (|P|, mask) order, children in column order); all of them are scored by ONE `score_families` call, and the scores
+    go to `mibn_best_dag` (include/mibn.h pins the tie rules: the result is a function of the scores alone).  More than
+    `max_families` candidates is an error that names the count.
+
+    Returns what `hill_climb` returns: (parent, child) tuples, children in column order and parents ascending, then the bare
+    names of isolated columns.  With `return_info`: (result, info) - info["total"] the `math.fsum` of the chosen families'
+    scores in column order (comparable bit for bit with `hill_climb`'s total of the same graph), info["dp_total"] the call's
+    own nested sum, info["order"] a topological order of the column names (roots first), info["n_families"].
+
+    Complete data only.  `weights`: see `row_weights` - the search on the rows written out weights[i] times, bit for bit."""
+    X, weights = row_weights(X, weights)
+    encoded = []
+
+    def cards():
+        encoded.append(encode_complete(X, list(X.columns)))
+        return encoded[0][2]
+
+    columns, cand = _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards)
+    codes, _, card = encoded[0]
+    n = len(columns)
+    engine = counting_engine(device)
+    with engine.dataset(codes, card) as ds:
+        scores = ds.score_families([_mask_scope(v, pm) for v, pm in cand], score, ess, **_weighted(ds, weights)(len(cand)))
+    parents, order, dp_total = engine.best_dag(n, [v for v, _ in cand], [pm for _, pm in cand], scores)
+    if not dp_total > -math.inf:
+        raise RuntimeError("best_dag found no DAG although every child has its required parents as a candidate")
+    at = {k: i for i, k in enumerate(cand)}
+    result = _dag_result(columns, parents)
+    if not return_info:
+        return result
+    info = {"total": math.fsum(float(scores[at[(v, int(parents[v]))]]) for v in range(n)), "dp_total": dp_total,
+            "order": [columns[int(v)] for v in order], "n_families": len(cand)}
+    return result, info
+
+
+def best_dag(columns, candidates, scores, device=None):
+    """The best DAG from local scores of the caller's own: `candidates` is a list of (child, parents) name pairs - child may take
+    exactly that parent set -, `scores` one number per candidate (higher is better; a child's parent set is always one of its
+    candidates).  Returns the result form of `exact_search`.  ValueError when no DAG can be formed from the candidates."""
+    columns = list(columns)
+    n = len(columns)
+    if len(set(columns)) != n:
+        raise ValueError("duplicate column names")
+    if not 1 <= n <= EXACT_MAX_COLUMNS:
+        raise ValueError(f"best_dag handles 1 to {EXACT_MAX_COLUMNS} columns, not {n}")
+    pos = {c: j for j, c in enumerate(columns)}
+    scores = np.asarray(scores, np.float64).reshape(-1)
+    if len(scores) != len(candidates):
+        raise ValueError("scores needs one entry per candidate")
+    if not np.isfinite(scores).all():
+        raise ValueError("scores must be finite")
+    children, masks, seen = [], [], set()
+    for child, parents in candidates:
+        parents = [parents] if isinstance(parents, str) or not hasattr(parents, "__iter__") else list(parents)
+        for c in [child, *parents]:
+            if c not in pos:
+                raise ValueError(f"unknown column {c!r}")
+        if child in parents or len(set(parents)) != len(parents):
+            raise ValueError(f"the family of {child!r} names a column twice")
+        key = (pos[child], sum(1 << pos[p] for p in parents))
+        if key in seen:
+            raise ValueError(f"the family of {child!r} with parents {parents} is listed twice")
+        seen.add(key)
+        children.append(key[0])
+        masks.append(key[1])
+    parents, _, total = counting_engine(device).best_dag(n, children, masks, scores)
+    if not total > -math.inf:
+        raise ValueError("no DAG can be formed from these candidates")
+    return _dag_result(columns, parents)
+
+
 def net_score(bn, X, score="bic", ess=1.0, weights=None):
     """The sum of the family scores of the net's own structure on the rows of X (`BayesNet.score`)."""
     fams = [(node, list(bn.parents.get(node, []))) for node in bn.nodes]
