@@ -671,6 +671,60 @@ int mibn_best_dag(mibn_t *h, int32_t n_vars, int64_t n_fam, const int32_t *fam_c
                   const double *fam_score, uint32_t *parents_out /* n_vars */, int32_t *order_out /* n_vars */, double *total_out);
 
 /*
+ * Exact Bayesian arc posteriors: the posterior probability of every candidate parent set and of every arc, averaged over ALL
+ * DAGs, by the sum-product form of the same subset DP (Koivisto and Sood 2004; Koivisto 2006).  Input and validation are
+ * mibn_best_dag's - the same candidates, the same rules and error codes; MIBN_E_LIMIT above MIBN_ARC_POSTERIOR_MAX_VARS (the
+ * tables take 8 n 2^(n-1) + 16 2^n bytes: 1.9 GB at 24).  The scores are log weights: with log marginal likelihoods (bdeu, k2)
+ * the results are Bayesian posteriors.
+ *
+ * The prior.  The results are posteriors under an ORDER-MODULAR prior: the sum runs over pairs (linear order, parent sets
+ * consistent with it), so a DAG weighs its number of linear extensions times prod exp(score) - NOT uniform over DAGs.  At
+ * n_vars = 2 with every candidate listed the empty graph counts twice, each one-arc graph once.
+ *
+ * Arithmetic.  Everything is a natural logarithm in fp64.  a (+) b = m + log1p(exp(-|a - b|)) with m = max(a, b), and m itself
+ * when m = -inf or the other operand is -inf: a single term passes through bit for bit, no NaN can form.
+ *
+ * Centring.  c_v = the maximum score among child v's candidates, 0 if it has none; the DP runs on s' = s - c_v (one fp64
+ * subtraction).  The posteriors do not depend on c_v; the rounding errors scale with the magnitudes that are left.
+ *
+ * Subset sums.  For child v and every C inside V \ {v}: alpha_v(C) = (+) over the candidates P of v inside C of s'_v(P), -inf
+ * without one - one step per index bit b of the child's table, entry[i | 1 << b] = entry[i | 1 << b] (+) entry[i], the bits in
+ * the order of the pass schedule (mibn_best_dag's; the options dag_tile_bits / dag_group_bits shape it).
+ *
+ * Forward and backward.  L({}) = R({}) = 0; L(S) = (+) over v in S of (L(S \ v) + alpha_v(S \ v)); R(T) = (+) over v in T of
+ * (alpha_v(V \ T) + R(T \ v)) - the terms folded in ascending v from -inf.  L(V) = R(V) up to rounding; L(V) is the one used.
+ * log_evidence_out = L(V) + c_0 + c_1 + .., the c_v added one by one in ascending v.
+ *
+ * Gaps.  For S inside V \ {v}: g_v(S) = L(S) + R(V \ S \ {v}); Gamma_v(P) = (+) over S with P inside S inside V \ {v} of g_v(S) -
+ * one step per index bit, entry[i] = entry[i] (+) entry[i | 1 << b], in the order of the same schedule.
+ *
+ * Outputs.  log_post_out[f] = (s'_f + Gamma_v(P_f)) - L(V): the log posterior that child v has exactly the parent set P_f; over
+ * one child's candidates the exp of these sums to 1.  arc_out[u * n_vars + v] = sum over the candidates f of child v with u in P_f
+ * of exp(log_post_out[f]) - a linear sum in ONE order, a function of the candidate list alone (no floating-point atomics): the
+ * list is cut into segments of 65 536 consecutive candidates; within a segment lane t of 256 adds its candidates first + t,
+ * first + t + 256, .. in ascending f starting from 0.0; the 256 lanes are folded in a tree, lane[t] += lane[t + h] for h = 128,
+ * 64, .., 1; the segments' results are added in ascending order starting from 0.0.
+ *
+ * No candidate structure (L(V) = -inf): MIBN_OK with log_evidence_out = -inf, every log_post_out = -inf and every arc 0.
+ *
+ * Accuracy.  A sum has no total order behind it: unlike mibn_best_dag's, these results are NOT schedule-independent in their
+ * last bits - the order in which the index bits are taken is part of the value.  Under fixed options a call is bit-for-bit
+ * repeatable, in any call and through any handle; across schedules (the options dag_tile_bits / dag_group_bits) - and against a
+ * twin that uses another exp / log1p - the results agree within 8 D 2^-53 (1 + M), D = n^2 + 2 n + ceil(log2(n_fam + 1)) the
+ * depth of roundings and M the largest finite magnitude among L, R and the centred scores: absolute on log_post and
+ * log_evidence, and on the arcs as probabilities.  (The schedules of today all take the bits in ascending order, whatever the
+ * tiling, which gives every entry the same chain of operations; that is a property of this planner, not of the contract.)
+ *
+ * Blocking.  Writes no option or policy state.  Last-call statistics only: dag_post_subset_kernel is the fill, the scatter and
+ * the passes of the subset sum, dag_post_level_kernel the n_vars + 1 levels of L and R, dag_post_superset_kernel the passes of
+ * the superset sum, dag_post_arc_kernel the candidate kernel and the two kernels of the arc sums.
+ */
+#define MIBN_ARC_POSTERIOR_MAX_VARS 24
+int mibn_arc_posteriors(mibn_t *h, int32_t n_vars, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents /* bit u = column u is a parent */,
+                        const double *fam_score, double *log_post_out /* n_fam */, double *arc_out /* n_vars x n_vars, row = from */,
+                        double *log_evidence_out);
+
+/*
  * Multi-GPU: one process per GPU, requests / chains sharded with no data-path collective; the
  * only communication is the final gather of the posteriors (exact path) or the sum of the histograms (Gibbs).  These
  * entry points sit directly on RCCL (librccl.so is dlopen'ed by mibn_comm_init - a single-GPU process never loads it) and

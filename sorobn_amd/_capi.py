@@ -25,10 +25,11 @@ SYMBOLS = [
     "mibn_dataset_create", "mibn_dataset_destroy", "mibn_score_families", "mibn_posterior_sample_batch", "mibn_map_batch",
     "mibn_ci_tests", "mibn_set_likelihoods", "mibn_bp_batch", "mibn_bp_mpe_batch", "mibn_bp_evidence_batch",
     "mibn_dataset_set_weights", "mibn_dataset_bootstrap", "mibn_score_families_w", "mibn_ci_tests_w", "mibn_count_tables_w",
-    "mibn_best_dag",
+    "mibn_best_dag", "mibn_arc_posteriors",
 ]
 MAX_WEIGHT_SUM = 2 ** 32 - 1  # W_s of a weight set (include/mibn.h)
 BEST_DAG_MAX_VARS = 24  # MIBN_BEST_DAG_MAX_VARS
+ARC_POSTERIOR_MAX_VARS = 24  # MIBN_ARC_POSTERIOR_MAX_VARS
 NO_PARENTS = 0xFFFFFFFF  # parents_out of mibn_best_dag where no DAG exists
 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
@@ -132,6 +133,7 @@ def lib():
         L.mibn_ci_tests_w.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, i32p, f64p, i64p]
         L.mibn_count_tables_w.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, i32p, C.c_int32, i64p, i32p, i64p, u32p, i64p]
         L.mibn_best_dag.argtypes = [vp, C.c_int32, C.c_int64, i32p, u32p, f64p, u32p, i32p, f64p]
+        L.mibn_arc_posteriors.argtypes = [vp, C.c_int32, C.c_int64, i32p, u32p, f64p, f64p, f64p, f64p]
         L.mibn_last_stats.argtypes = [vp, C.POINTER(Stats)]
         L.mibn_last_kernel_stats.argtypes = [vp, C.c_int32, C.POINTER(KernelStat), C.POINTER(C.c_int32)]
         L.mibn_plan_stats.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p, C.POINTER(Stats)]
@@ -871,6 +873,24 @@ class Engine:
                                           _p(np.zeros(1, np.uint32) if pad else masks, C.c_uint32), _p(np.zeros(1, np.float64) if pad else sc, C.c_double),
                                           _p(parents, C.c_uint32), _p(order, C.c_int32), C.byref(total)))
         return parents[:n], order[:n], float(total.value)
+
+    def arc_posteriors(self, n_vars, children, parent_masks, scores):
+        """Exact posteriors over all DAGs from a list of local log scores (mibn_arc_posteriors; the candidates as in `best_dag`) ->
+        (log_post float64[n_fam]: the log posterior that a candidate's child has exactly its parent set, arc float64[n_vars,
+        n_vars]: arc[u, v] = P(u -> v), log_evidence).  Under an order-modular prior, not a uniform one (include/mibn.h).  No DAG
+        from these candidates: log_evidence -inf, every log_post -inf, every arc 0."""
+        child = _i32(children).reshape(-1)
+        masks = np.ascontiguousarray(parent_masks, dtype=np.uint32).reshape(-1)
+        sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+        if not len(child) == len(masks) == len(sc):
+            raise ValueError("children, parent_masks and scores need one entry per candidate")
+        n = max(0, int(n_vars))
+        log_post, arc, evidence = np.zeros(max(1, len(child)), np.float64), np.zeros(max(1, n * n), np.float64), C.c_double(0.0)
+        pad = len(child) == 0
+        self._check(self._L.mibn_arc_posteriors(self._h, int(n_vars), len(child), _p(np.zeros(1, np.int32) if pad else child, C.c_int32),
+                                                _p(np.zeros(1, np.uint32) if pad else masks, C.c_uint32), _p(np.zeros(1, np.float64) if pad else sc, C.c_double),
+                                                _p(log_post, C.c_double), _p(arc, C.c_double), C.byref(evidence)))
+        return log_post[:len(child)], arc[:n * n].reshape(n, n), float(evidence.value)
 
     def count_tables(self, codes, card, tables, weights=None):
         """codes: uint8 [n_rows, n_cols] (row- or column-major, sent as it is); tables: list of column-index tuples

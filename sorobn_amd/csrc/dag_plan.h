@@ -17,6 +17,9 @@
 // The defaults T = 12, G = 6 give 4 096-entry tiles (48 KiB of LDS: three workgroups per CU) and runs of 2^6 entries - 512 bytes of
 // scores, 256 of masks - in the later passes; n = 20 is three passes (12 + 6 + 1 bits), n = 24 three (12 + 6 + 5).
 #pragma once
+#include <math.h>
+
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -106,6 +109,95 @@ inline int dag_check(int32_t n_vars, int64_t n_fam, const int32_t *child, const 
         seen[(size_t)(at >> 6)] |= uint64_t(1) << (at & 63);
     }
     return MIBN_OK;
+}
+
+// ---- mibn_arc_posteriors (dag_post_kernel.hip.h): the same tables and the same pass schedule with the maximum replaced by a sum
+// in log space.  A sum of doubles has no total order behind it: its last bits DO depend on the order the index bits are taken in,
+// so - unlike mibn_best_dag - the options dag_tile_bits / dag_group_bits are allowed to move the last bits of its results (within
+// the bound of include/mibn.h); under fixed options a call is bit-for-bit repeatable.  (dag_plan takes the bits in ascending order
+// under every tiling, so every entry goes through the same chain of operations and today's schedules agree bit for bit; a planner
+// that reorders bits would not, and nothing may rely on it.)  What device, tools/dag_post_sim.cpp and the tests share:
+
+// log(exp(a) + exp(b)), pinned: m + log1p(exp(-|a - b|)) with m = max(a, b); m itself when the other operand is -inf (or both
+// are): a single term passes through bit for bit and no NaN can form.  Never called with +inf or NaN.
+MIBN_HD inline double dag_logaddexp(double a, double b) {
+    const double m = a > b ? a : b, o = a > b ? b : a;
+    if (o == -HUGE_VAL) return m;
+    return m + ::log1p(::exp(-::fabs(a - b)));
+}
+
+// index in child v's table -> the subset: bit v put back as 0 (the inverse of dag_squeeze)
+MIBN_HD inline uint32_t dag_unsqueeze(uint32_t i, int v) { return (i & ((1u << v) - 1u)) | ((i >> v) << (v + 1)); }
+
+// The level kernel gives lane k of level l the k-th subset of l members in colexicographic order - the combinatorial number
+// system: S = {c_l > .. > c_1}, k = C(c_l, l) + .. + C(c_1, 1) - so that every lane of a wave has a subset of the level (of 64
+// consecutive masks at most 20 share a popcount).  binom[c * kDagBinomStride + i] = C(c, i) for c, i in [0, 24]; at most
+// C(24, 12) = 2 704 156.
+constexpr int kDagBinomStride = 25;
+inline void dag_binomials(uint32_t *binom /* kDagBinomStride x kDagBinomStride */) {
+    for (int c = 0; c < kDagBinomStride; ++c)
+        for (int i = 0; i < kDagBinomStride; ++i)
+            binom[c * kDagBinomStride + i] = i == 0 ? 1u : c == 0 ? 0u : binom[(c - 1) * kDagBinomStride + i - 1] + binom[(c - 1) * kDagBinomStride + i];
+}
+// k in [0, C(n, level)) -> the subset; n <= 24
+MIBN_HD inline uint32_t dag_unrank(uint32_t k, int level, int n, const uint32_t *binom) {
+    uint32_t S = 0;
+    int c = n - 1;
+    for (int i = level; i >= 1; --i) {
+        while (binom[c * kDagBinomStride + i] > k) --c;  // (ends at c = i - 1 at the latest: C(i - 1, i) = 0)
+        S |= 1u << c;
+        k -= binom[c * kDagBinomStride + i];
+        --c;
+    }
+    return S;
+}
+
+// Centring.  c_v = the maximum score among child v's candidates, 0 without one; the tables hold s' = s - c_v (one subtraction, the
+// same wherever it is made).  log_evidence = L(V) + c_0 + c_1 + .. added one by one in ascending v.
+inline void dag_centres(int32_t n, int64_t n_fam, const int32_t *child, const double *score, double *c) {
+    std::vector<char> any((size_t)n, 0);
+    for (int v = 0; v < n; ++v) c[v] = 0.0;
+    for (int64_t f = 0; f < n_fam; ++f) {
+        const int v = child[f];
+        if (!any[(size_t)v] || score[f] > c[v]) c[v] = score[f];
+        any[(size_t)v] = 1;
+    }
+}
+MIBN_HD inline double dag_centred(double s, double c) { return s - c; }
+inline double dag_log_evidence(double l_full, int32_t n, const double *c) {
+    double e = l_full;
+    for (int v = 0; v < n; ++v) e += c[v];
+    return e;
+}
+
+// The order of the arc sums, a function of the candidate list alone.  The list is cut into segments of kDagArcSegment consecutive
+// candidates.  For the arc u -> v and segment j, lane t of kDagArcLanes adds exp(log_post[f]) over the segment's candidates
+// f = first + t, first + t + kDagArcLanes, .. in ascending f, starting from 0.0 - a candidate of another child, or without u
+// among its parents, adds +0.0, which changes no bit of a non-negative sum; the lanes' sums are folded in a tree, lane[t] +=
+// lane[t + h] for h = kDagArcLanes / 2, .., 1; arc[u * n + v] = the segments' results added in ascending j, starting from 0.0.
+constexpr int kDagArcLanes = 256;
+constexpr int64_t kDagArcSegment = int64_t(1) << 16;
+MIBN_HD inline int64_t dag_arc_segments(int64_t n_fam) { return n_fam > 0 ? (n_fam + kDagArcSegment - 1) / kDagArcSegment : 1; }
+
+// the same order on a CPU (tools/dag_post_sim.cpp); arc: n * n, row = from
+inline void dag_arc_reduce(int32_t n, int64_t n_fam, const int32_t *child, const uint32_t *parents, const double *log_post, double *arc) {
+    std::vector<double> lane((size_t)n * (size_t)n * kDagArcLanes);
+    for (int k = 0; k < n * n; ++k) arc[k] = 0.0;
+    for (int64_t j = 0; j < dag_arc_segments(n_fam); ++j) {
+        std::fill(lane.begin(), lane.end(), 0.0);
+        const int64_t first = j * kDagArcSegment, last = first + kDagArcSegment < n_fam ? first + kDagArcSegment : n_fam;
+        for (int64_t f = first; f < last; ++f) {
+            const double p = ::exp(log_post[f]);
+            for (int u = 0; u < n; ++u)
+                if ((parents[f] >> u) & 1u) lane[((size_t)u * (size_t)n + (size_t)child[f]) * kDagArcLanes + (size_t)((f - first) % kDagArcLanes)] += p;
+        }
+        for (int k = 0; k < n * n; ++k) {
+            double *s = &lane[(size_t)k * kDagArcLanes];
+            for (int h = kDagArcLanes / 2; h >= 1; h /= 2)
+                for (int t = 0; t < h; ++t) s[t] += s[t + h];
+            arc[k] += s[0];
+        }
+    }
 }
 
 }  // namespace mibn

@@ -29,6 +29,7 @@
 #include "score_kernel.hip.h"
 #include "citest_kernel.hip.h"
 #include "dag_kernel.hip.h"
+#include "dag_post_kernel.hip.h"
 #include "planner.h"
 #include "plan_policy.h"
 #include "tiny_kernel.hip.h"
@@ -193,16 +194,18 @@ constexpr int kLevelStreams = 4;
 // mibn_posterior_sample_batch, the two of mibn_map_batch and - no kernels: what ve_map_kernel's launches held - its tiled sum and max
 // steps, and the reduction of mibn_ci_tests (ci_lane_kernel, ci_wave_kernel and ci_finish_kernel together), and the two kernels of a call with likelihood
 // findings: the seeds of a planned wave, the tiny kernel's twin, the one kernel of mibn_bp_batch, the one of mibn_bp_mpe_batch and the two of mibn_bp_evidence_batch,
-// the weighted counting, and the two phases of mibn_best_dag.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
+// the weighted counting, the two phases of mibn_best_dag and the four of mibn_arc_posteriors.  Order and names are what mibn_last_kernel_stats reports: a new slot goes to the end of both lists.
 enum StatSlot : int {
     kStatLevel = kNumKernels, kStatTiny, kStatSweepDma, kStatPlanner, kStatLevelGroup, kStatSegment, kStatMfma, kStatMax, kStatTraceback,
-    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatBpEvidence, kStatBpAccumulate, kStatCountW, kStatDagSubset, kStatDagSink, kStatSlots
+    kStatExpect, kStatCount, kStatScore, kStatSum, kStatDraw, kStatMap, kStatMapTraceback, kStatMapSumTiles, kStatMapMaxTiles, kStatCiTest, kStatSeed, kStatTinyLh, kStatBp, kStatBpMax, kStatBpEvidence, kStatBpAccumulate, kStatCountW, kStatDagSubset, kStatDagSink,
+    kStatDagPostSubset, kStatDagPostLevel, kStatDagPostSuperset, kStatDagPostArc, kStatSlots
 };
 constexpr const char *kStatSlotNames[kStatSlots - kNumKernels] = {
     "ve_level_kernel", "tiny_kernel", "ve_sweep_dma_kernel", "order_kernel+emit_kernel",
     "level:ve_level_kernel||ve_mfma_kernel||ve_sweep_dma_kernel||ve_segment_kernel", "ve_segment_kernel", "ve_mfma_kernel", "ve_max_kernel",
     "mpe_traceback_kernel", "expect_kernel", "count_kernel", "score_kernel", "ve_sum_kernel", "posterior_draw_kernel",
-    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel", "bp_evidence_kernel", "bp_accumulate_kernel", "count_weighted_kernel", "dag_subset_kernel", "dag_sink_kernel"};
+    "ve_map_kernel", "map_traceback_kernel", "ve_map_kernel:sum tiles", "ve_map_kernel:max tiles", "citest_kernel", "likelihood_seed_kernel", "tiny_lh_kernel", "bp_kernel", "bp_max_kernel", "bp_evidence_kernel", "bp_accumulate_kernel", "count_weighted_kernel", "dag_subset_kernel", "dag_sink_kernel",
+    "dag_post_subset_kernel", "dag_post_level_kernel", "dag_post_superset_kernel", "dag_post_arc_kernel"};
 // mibn_score_families: cells of the device buffer its count tables are written to (8 bytes each, 32 MiB).  A sweep of hill climbing over
 // 100 four-state columns with up to three parents - 10 000 families of at most 256 cells, 2.6 M cells at worst - fits one sub-batch, so
 // the usual call is one counting and one scoring launch; zeroing the buffer takes microseconds at HBM rate, and it stays negligible
@@ -443,9 +446,13 @@ struct mibn_ctx {
         DevBuf<uint8_t> d_sink;
         DevBuf<char> d_io;  // [fam_score | fam_child | fam_parents] then [total | parents_out | order_out]
         Event ev[3];
+        // mibn_arc_posteriors: alpha / Gamma in d_score, L in d_best, R here; its own candidate / result block
+        DevBuf<double> d_right;
+        DevBuf<char> d_post_io;  // [fam_score | fam_child | fam_parents | centres] then [log_post | arc | segment sums]
+        Event post_ev[5];
     } dag;
     int dag_tile_bits = kDagTileBits;    // options dag_tile_bits / dag_group_bits (test hooks: force multi-pass schedules at small n;
-    int dag_group_bits = kDagGroupBits;  // no bit of any result depends on them, dag_plan.h says why)
+    int dag_group_bits = kDagGroupBits;  // no bit of mibn_best_dag depends on them, the last bits of mibn_arc_posteriors do: dag_plan.h says why)
     int weighted_share = 1;  // option weighted_share: count_weighted_kernel keeps a row's cell index across neighbouring tables of one scope (DESIGN section 24 has both times)
     // options
     double arena_gb = 200.0;  // scratch budget of all lanes together (of the 288 GB)
@@ -4053,6 +4060,144 @@ extern "C" int mibn_best_dag(mibn_t *h, int32_t n_vars, int64_t n_fam, const int
                              uint32_t *parents_out, int32_t *order_out, double *total_out) {
     if (!h || n_fam < 0 || (n_fam && (!fam_child || !fam_parents || !fam_score)) || !parents_out || !order_out || !total_out) return MIBN_E_ARG;
     return drained_on_error(h, best_dag_run(h, n_vars, n_fam, fam_child, fam_parents, fam_score, parents_out, order_out, total_out), drain_main_unchecked);
+}
+
+// ---- mibn_arc_posteriors: mibn_best_dag's check and schedule; fill + scatter + the passes of the subset sum, the n + 1 levels of
+// L and R, the passes of the superset sum (the first forms g from L and R), the candidate kernel and the arc sums.  Everything on
+// the main stream, one synchronisation; five events give the four statistics rows.  The tables are mibn_best_dag's buffers (alpha
+// in d_score, L in d_best) and d_right, freed on return by the same rule.
+static int arc_posteriors_run(mibn_t *h, int32_t n, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score,
+                              double *log_post_out, double *arc_out, double *log_evidence_out) {
+    int rc;
+    if ((rc = check_state(h, kNeedDevice))) return rc;
+    if ((rc = check_state(h, kNeedIdle))) return rc;
+    const double t_start = now_ms();
+    reset_last_stats(h);
+    static_assert(MIBN_ARC_POSTERIOR_MAX_VARS == MIBN_BEST_DAG_MAX_VARS, "dag_check's limit is the one of both calls");
+    if ((rc = dag_check(n, n_fam, fam_child, fam_parents, fam_score, h->err))) {
+        if (h->err.rfind("best_dag", 0) == 0) h->err.replace(0, 8, "arc_posteriors");
+        return rc;
+    }
+    const DagPlan D = dag_plan(n, h->dag_tile_bits, h->dag_group_bits);
+    std::vector<DagPass> down = D.passes;  // the superset sum: the same passes; n = 1 has none, and g is formed by a pass without bits
+    if (down.empty()) down.push_back(DagPass{0, 0, 0});
+    std::vector<double> centre((size_t)n);
+    dag_centres(n, n_fam, fam_child, fam_score, centre.data());
+    mibn_ctx::Dag &X = h->dag;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t bps = (size_t)n * (size_t)D.entries, subsets = size_t(1) << n, fam = (size_t)std::max<int64_t>(1, n_fam), nn = (size_t)n * (size_t)n;
+    const int64_t segments = dag_arc_segments(n_fam);
+    struct Release {  // on every exit, after the stream is drained (hipFree waits for the device)
+        mibn_ctx::Dag &X;
+        bool on;
+        ~Release() {
+            if (!on) return;
+            (void)X.d_score.release();
+            (void)X.d_best.release();
+            (void)X.d_right.release();
+        }
+    } release{X, 8 * bps + 16 * subsets > kDagKeepBytes};
+    HIP_TRY(h, dag_room(X.d_score, bps));
+    HIP_TRY(h, dag_room(X.d_best, subsets));
+    HIP_TRY(h, dag_room(X.d_right, subsets));
+    const size_t o_child = 8 * fam, o_par = o_child + 4 * fam, o_centre = (o_par + 4 * fam + 15) & ~size_t(15), o_post = o_centre + 8 * (size_t)n,
+                 o_arc = o_post + 8 * fam, o_part = o_arc + 8 * nn, o_binom = o_part + 8 * nn * (size_t)segments;
+    static const std::vector<uint32_t> binom = [] {
+        std::vector<uint32_t> b((size_t)kDagBinomStride * kDagBinomStride);
+        dag_binomials(b.data());
+        return b;
+    }();
+    HIP_TRY(h, X.d_post_io.ensure(o_binom + 4 * binom.size()));
+    for (Event &e : X.post_ev) HIP_TRY(h, e.ensure());
+    const hipStream_t S0 = h->stream;
+    const double t0 = now_ms();
+    if (n_fam) {
+        HIP_TRY(h, hipMemcpyAsync(X.d_post_io, fam_score, 8 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+        HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_child, fam_child, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+        HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_par, fam_parents, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+    }
+    HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_centre, centre.data(), 8 * (size_t)n, hipMemcpyHostToDevice, S0));  // (pageable: staged before the call returns)
+    HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_binom, binom.data(), 4 * binom.size(), hipMemcpyHostToDevice, S0));
+    h->stats.h2d_ms += now_ms() - t0;
+    const double *d_fam = reinterpret_cast<const double *>(X.d_post_io.get());
+    const int32_t *d_child = reinterpret_cast<const int32_t *>(X.d_post_io + o_child);
+    const uint32_t *d_par = reinterpret_cast<const uint32_t *>(X.d_post_io + o_par);
+    const double *d_centre = reinterpret_cast<const double *>(X.d_post_io + o_centre);
+    double *d_post = reinterpret_cast<double *>(X.d_post_io + o_post), *d_arc = reinterpret_cast<double *>(X.d_post_io + o_arc),
+           *d_part = reinterpret_cast<double *>(X.d_post_io + o_part);
+    const uint32_t *d_binom = reinterpret_cast<const uint32_t *>(X.d_post_io + o_binom);
+    double *alpha = X.d_score.get(), *L = X.d_best.get(), *R = X.d_right.get();
+    const dim3 wg(kDagWG), per_fam((unsigned)((fam + kDagWG - 1) / kDagWG));
+    // the subset sum
+    HIP_TRY(h, hipEventRecord(X.post_ev[0], S0));
+    double launches_a = 1, bytes_a = 8.0 * (double)bps;
+    hipLaunchKernelGGL(dag_post_fill_kernel, dim3((unsigned)std::min<size_t>((bps + kDagWG - 1) / kDagWG, 65536)), wg, 0, S0, alpha, (int64_t)bps);
+    if (n_fam) {
+        hipLaunchKernelGGL(dag_post_scatter_kernel, per_fam, wg, 0, S0, d_child, d_par, d_fam, d_centre, n_fam, n, alpha);
+        launches_a += 1;
+        bytes_a += 32.0 * (double)n_fam;
+    }
+    for (const DagPass &P : D.passes) {
+        hipLaunchKernelGGL(dag_post_subset_kernel, dim3((unsigned)D.grid(P)), wg, 0, S0, alpha, P, n, D.tiles_per_child(P));
+        launches_a += 1;
+        bytes_a += 16.0 * (double)bps;
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(X.post_ev[1], S0));
+    // L and R
+    for (int32_t level = 0; level <= n; ++level)
+        hipLaunchKernelGGL(dag_post_level_kernel, dim3((binom[(size_t)n * kDagBinomStride + (size_t)level] + kDagWG - 1) / kDagWG), wg, 0, S0, alpha, L, R, d_binom,
+                           n, level);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(X.post_ev[2], S0));
+    // the superset sum of g into alpha's storage
+    double bytes_c = 0;
+    for (size_t k = 0; k < down.size(); ++k) {
+        hipLaunchKernelGGL(dag_post_superset_kernel, dim3((unsigned)D.grid(down[k])), wg, 0, S0, alpha, L, R, down[k], n, D.tiles_per_child(down[k]), (int32_t)(k == 0));
+        bytes_c += (k == 0 ? 24.0 : 16.0) * (double)bps;  // the first pass reads L and R per entry and writes the entry
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(X.post_ev[3], S0));
+    // the candidates' posteriors and the arc sums
+    double launches_d = 2;
+    if (n_fam) {
+        hipLaunchKernelGGL(dag_post_candidate_kernel, per_fam, wg, 0, S0, d_child, d_par, d_fam, d_centre, alpha, L, n_fam, n, d_post);
+        launches_d += 1;
+    }
+    hipLaunchKernelGGL(dag_post_arc_kernel, dim3((unsigned)segments, (unsigned)n), wg, 0, S0, d_child, d_par, d_post, n_fam, n, d_part);
+    hipLaunchKernelGGL(dag_post_arc_sum_kernel, dim3((unsigned)((nn + kDagWG - 1) / kDagWG)), wg, 0, S0, d_part, segments, n, d_arc);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(X.post_ev[4], S0));
+    const double t1 = now_ms();
+    double l_full = 0;
+    HIP_TRY(h, hipMemcpyAsync(&l_full, L + (subsets - 1), 8, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipMemcpyAsync(arc_out, d_arc, 8 * nn, hipMemcpyDeviceToHost, S0));
+    if (n_fam) HIP_TRY(h, hipMemcpyAsync(log_post_out, d_post, 8 * (size_t)n_fam, hipMemcpyDeviceToHost, S0));
+    HIP_TRY(h, hipStreamSynchronize(S0));
+    h->stats.d2h_ms += now_ms() - t1;
+    *log_evidence_out = dag_log_evidence(l_full, n, centre.data());
+    float ms[4] = {};
+    for (int k = 0; k < 4; ++k) HIP_TRY(h, hipEventElapsedTime(&ms[k], X.post_ev[k], X.post_ev[k + 1]));
+    // L and R: every alpha entry read twice and every L / R entry once per member, both written once per subset
+    const double bytes_b = 32.0 * (double)bps + 16.0 * (double)subsets;
+    // a candidate's 24 bytes, its Gamma and its log_post; the arc kernel reads child per (candidate, child), masks and log_post once
+    const double bytes_d = 40.0 * (double)n_fam + (4.0 * (double)n + 12.0) * (double)n_fam + 8.0 * (double)nn * ((double)segments + 1.0);
+    book_stat(h, kStatDagPostSubset, launches_a, ms[0], bytes_a, (double)n_fam, true, false);
+    book_stat(h, kStatDagPostLevel, (double)n + 1.0, ms[1], bytes_b, (double)subsets, true, false);
+    book_stat(h, kStatDagPostSuperset, (double)down.size(), ms[2], bytes_c, (double)bps, true, false);
+    book_stat(h, kStatDagPostArc, launches_d, ms[3], bytes_d, (double)n_fam, true, false);
+    h->stats.kernel_ms = ms[0] + ms[1] + ms[2] + ms[3];
+    h->stats.n_launches = launches_a + (double)n + 1.0 + (double)down.size() + launches_d;
+    h->stats.alg_bytes = bytes_a + bytes_b + bytes_c + bytes_d;
+    h->stats.total_ms = now_ms() - t_start;
+    return MIBN_OK;
+}
+
+extern "C" int mibn_arc_posteriors(mibn_t *h, int32_t n_vars, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score,
+                                   double *log_post_out, double *arc_out, double *log_evidence_out) {
+    if (!h || n_fam < 0 || (n_fam && (!fam_child || !fam_parents || !fam_score || !log_post_out)) || !arc_out || !log_evidence_out) return MIBN_E_ARG;
+    return drained_on_error(h, arc_posteriors_run(h, n_vars, n_fam, fam_child, fam_parents, fam_score, log_post_out, arc_out, log_evidence_out),
+                            drain_main_unchecked);
 }
 
 extern "C" int mibn_plan_order(mibn_t *h, int32_t n_q, const int32_t *q_vars, int32_t n_e, const int32_t *e_vars,

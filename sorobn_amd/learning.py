@@ -854,9 +854,10 @@ def _dag_result(columns, parents):
     return result + [c for c in columns if c not in linked]
 
 
-def _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards):
-    """The argument checks of `exact_search` -> (columns, candidates [(child, parent mask)]); no engine is touched.  `cards`
-    is a callable (evaluated after the cheaper checks) giving the cardinalities."""
+def _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards, who="exact_search", instead="hill_climb or pc"):
+    """The argument checks of `exact_search` (and of `arc_posteriors`: `who`, and what it points to beyond 24 columns) ->
+    (columns, candidates [(child, parent mask)]); no engine is touched.  `cards` is a callable (evaluated after the cheaper
+    checks) giving the cardinalities."""
     _check_score(score, ess)
     columns = list(X.columns)
     n = len(columns)
@@ -865,8 +866,8 @@ def _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, c
     if n < 1:
         raise ValueError("X has no columns")
     if n > EXACT_MAX_COLUMNS:
-        raise ValueError(f"exact_search handles at most {EXACT_MAX_COLUMNS} columns, X has {n} (the tables double with every column): "
-                         f"use hill_climb or pc")
+        raise ValueError(f"{who} handles at most {EXACT_MAX_COLUMNS} columns, X has {n} (the tables double with every column): "
+                         f"use {instead}")
     max_parents = int(max_parents)
     if max_parents < 0:
         raise ValueError("max_parents must not be negative")
@@ -955,12 +956,125 @@ def best_dag(columns, candidates, scores, device=None):
     """The best DAG from local scores of the caller's own: `candidates` is a list of (child, parents) name pairs - child may take
     exactly that parent set -, `scores` one number per candidate (higher is better; a child's parent set is always one of its
     candidates).  Returns the result form of `exact_search`.  ValueError when no DAG can be formed from the candidates."""
+    columns, children, masks, scores = _named_candidates(columns, candidates, scores, "best_dag")
+    n = len(columns)
+    parents, _, total = counting_engine(device).best_dag(n, children, masks, scores)
+    if not total > -math.inf:
+        raise ValueError("no DAG can be formed from these candidates")
+    return _dag_result(columns, parents)
+
+
+# ------------------------------------------------------ exact Bayesian arc posteriors: the sum-product form of the same DP
+# `exact_search` returns one graph; with a few thousand rows many DAGs lie within a few units of log score of it.  The same
+# subset DP with the maximum replaced by a sum (csrc/dag_post_kernel.hip.h, `mibn_arc_posteriors`; Koivisto and Sood 2004) gives
+# the posterior probability of every arc, averaged over ALL DAGs - at about the cost of one `exact_search`.
+PARENT_PRIORS = ("uniform", "size")
+
+
+def _averaged_edges(columns, frame, threshold):
+    """The body of `ArcStrength.edges` / `ArcPosterior.edges`: the pairs of `frame` (from, to, strength, direction) with strength
+    >= threshold in descending strength (ties by the columns' positions), each oriented by the majority (a tie goes to from ->
+    to) and skipped where it would close a cycle; then the bare names of the isolated columns."""
+    pos = {c: j for j, c in enumerate(columns)}
+    rows = [(-float(s), pos[u], pos[v], float(d)) for u, v, s, d in frame.itertuples(index=False) if s >= threshold]
+    g = _Graph(len(columns), [])
+    out = []
+    for _, i, j, d in sorted(rows):
+        u, v = (i, j) if d >= 0.5 else (j, i)
+        if g.anc[u, v]:  # v is an ancestor of u
+            continue
+        g.add(u, v)
+        out.append((columns[u], columns[v]))
+    linked = {c for e in out for c in e}
+    return out + [c for c in columns if c not in linked]
+
+
+class ArcPosterior:
+    """Exact posteriors over all DAGs (`arc_posteriors`), under an ORDER-MODULAR prior: a DAG weighs its number of linear
+    extensions times the product of its families' weights - not uniform over DAGs (at two columns the empty graph counts twice).
+
+    `matrix`: DataFrame, row = from, column = to, P(from -> to | data).  `frame`: `ArcStrength.frame`'s four columns - one row
+    per unordered pair with `strength` = P(u -> v) + P(v -> u) > 0, `from` before `to` in column order (rows in that order
+    too), `direction` = P(from -> to) / strength.  `log_evidence`: the log of the sum over every (order, DAG) pair of the product
+    of the weights.  `columns`, `n_families`."""
+
+    def __init__(self, columns, candidates, log_post, arc, log_evidence):
+        self.columns = list(columns)
+        self.n_families = len(candidates)
+        self.log_evidence = float(log_evidence)
+        self._candidates = [(int(v), int(pm)) for v, pm in candidates]
+        self._log_post = np.asarray(log_post, np.float64).reshape(-1)
+        n = len(self.columns)
+        arc = np.asarray(arc, np.float64).reshape(n, n)
+        self.matrix = pd.DataFrame(arc, index=self.columns, columns=self.columns)
+        pairs = [(i, j) for i in range(n) for j in range(i + 1, n) if arc[i, j] + arc[j, i] > 0.0]
+        strength = np.array([arc[i, j] + arc[j, i] for i, j in pairs], np.float64)
+        self.frame = pd.DataFrame({
+            "from": [self.columns[i] for i, _ in pairs], "to": [self.columns[j] for _, j in pairs], "strength": strength,
+            "direction": np.array([arc[i, j] for i, j in pairs], np.float64) / strength if pairs else strength})
+
+    def edges(self, threshold=0.5):
+        """The averaged DAG as `BayesNet(*edges)` takes it, by `ArcStrength.edges`'s rule: the pairs with strength >= threshold in
+        descending strength, each oriented by the majority and skipped where it would close a cycle; then the isolated columns."""
+        return _averaged_edges(self.columns, self.frame, threshold)
+
+    def parent_sets(self, child):
+        """The posterior of every candidate parent set of `child`: a Series indexed by tuples of parent names (in column
+        order), descending (ties in candidate order); it sums to 1."""
+        if child not in self.columns:
+            raise ValueError(f"unknown column {child!r}")
+        v = self.columns.index(child)
+        own = [f for f, (c, _) in enumerate(self._candidates) if c == v]
+        own.sort(key=lambda f: (-self._log_post[f], f))
+        index = [tuple(self.columns[u] for u in range(len(self.columns)) if (self._candidates[f][1] >> u) & 1) for f in own]
+        out = pd.Series(np.exp(self._log_post[own]), index=pd.Index(index, tupleize_cols=False), name=child, dtype=np.float64)
+        return out
+
+
+def arc_posteriors(X, score="bdeu", ess=1.0, max_parents=3, required=(), forbidden=(), parent_prior="uniform", max_families=2_000_000, device=None,
+                   weights=None):
+    """The exact posterior probability of every arc given the rows of X, averaged over every DAG whose families are among the
+    candidates, for up to 24 columns (Koivisto and Sood 2004) -> an `ArcPosterior`.  Beyond 24 columns `bootstrap` remains.
+
+    The candidates are `exact_search`'s - every parent set P of child v with |P| <= max_parents that holds the `required` parents
+    of v and none of its `forbidden` ones, in the same order -, scored by ONE `score_families` call; the scores go to
+    `mibn_arc_posteriors` as log weights.  With `bdeu` or `k2` (log marginal likelihoods) the result is a Bayesian posterior;
+    with `bic` or `aic` an approximation of one.  `parent_prior`: "uniform" leaves the scores as they are; "size" adds
+    -log C(n - 1, |P|) to each (Koivisto's choice: every parent-set size equally likely a priori).
+
+    The prior over structures is ORDER-MODULAR, not uniform over DAGs: a DAG counts once per linear order it is consistent with
+    (see `ArcPosterior`).  Complete data only.  `weights`: see `row_weights`."""
+    if parent_prior not in PARENT_PRIORS:
+        raise ValueError(f"parent_prior must be one of {PARENT_PRIORS}, not {parent_prior!r}")
+    X, weights = row_weights(X, weights)
+    encoded = []
+
+    def cards():
+        encoded.append(encode_complete(X, list(X.columns)))
+        return encoded[0][2]
+
+    columns, cand = _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards, who="arc_posteriors", instead="bootstrap")
+    codes, _, card = encoded[0]
+    n = len(columns)
+    engine = counting_engine(device)
+    with engine.dataset(codes, card) as ds:
+        scores = np.asarray(ds.score_families([_mask_scope(v, pm) for v, pm in cand], score, ess, **_weighted(ds, weights)(len(cand))), np.float64)
+    if parent_prior == "size":
+        scores = scores - np.array([math.log(math.comb(n - 1, bin(pm).count("1"))) for _, pm in cand], np.float64)
+    log_post, arc, log_evidence = engine.arc_posteriors(n, [v for v, _ in cand], [pm for _, pm in cand], scores)
+    if not log_evidence > -math.inf:
+        raise RuntimeError("arc_posteriors found no DAG although every child has its required parents as a candidate")
+    return ArcPosterior(columns, cand, log_post, arc, log_evidence)
+
+
+def _named_candidates(columns, candidates, scores, who):
+    """The checks `best_dag` and `arc_posteriors_from_scores` share -> (columns, children, masks, scores)."""
     columns = list(columns)
     n = len(columns)
     if len(set(columns)) != n:
         raise ValueError("duplicate column names")
     if not 1 <= n <= EXACT_MAX_COLUMNS:
-        raise ValueError(f"best_dag handles 1 to {EXACT_MAX_COLUMNS} columns, not {n}")
+        raise ValueError(f"{who} handles 1 to {EXACT_MAX_COLUMNS} columns, not {n}")
     pos = {c: j for j, c in enumerate(columns)}
     scores = np.asarray(scores, np.float64).reshape(-1)
     if len(scores) != len(candidates):
@@ -981,10 +1095,17 @@ def best_dag(columns, candidates, scores, device=None):
         seen.add(key)
         children.append(key[0])
         masks.append(key[1])
-    parents, _, total = counting_engine(device).best_dag(n, children, masks, scores)
-    if not total > -math.inf:
+    return columns, children, masks, scores
+
+
+def arc_posteriors_from_scores(columns, candidates, scores, device=None):
+    """`arc_posteriors` from local log scores of the caller's own - the mirror of `best_dag`: `candidates` is a list of (child,
+    parents) name pairs, `scores` one log weight per candidate -> an `ArcPosterior`.  ValueError when no DAG can be formed."""
+    columns, children, masks, scores = _named_candidates(columns, candidates, scores, "arc_posteriors_from_scores")
+    log_post, arc, log_evidence = counting_engine(device).arc_posteriors(len(columns), children, masks, scores)
+    if not log_evidence > -math.inf:
         raise ValueError("no DAG can be formed from these candidates")
-    return _dag_result(columns, parents)
+    return ArcPosterior(columns, list(zip(children, masks)), log_post, arc, log_evidence)
 
 
 def net_score(bn, X, score="bic", ess=1.0, weights=None):
@@ -1347,18 +1468,7 @@ class ArcStrength:
         """The averaged DAG as `BayesNet(*edges)` takes it: the pairs with strength >= threshold in descending strength (ties by the
         columns' positions), each oriented by the majority (a tie goes to from -> to) and skipped where it would close a cycle;
         then the bare names of the isolated columns."""
-        pos = {c: j for j, c in enumerate(self.columns)}
-        rows = [(-float(s), pos[u], pos[v], float(d)) for u, v, s, d in self.frame.itertuples(index=False) if s >= threshold]
-        g = _Graph(len(self.columns), [])
-        out = []
-        for _, i, j, d in sorted(rows):
-            u, v = (i, j) if d >= 0.5 else (j, i)
-            if g.anc[u, v]:  # v is an ancestor of u
-                continue
-            g.add(u, v)
-            out.append((self.columns[u], self.columns[v]))
-        linked = {c for e in out for c in e}
-        return out + [c for c in self.columns if c not in linked]
+        return _averaged_edges(self.columns, self.frame, threshold)
 
 
 def _lockstep(ds, searches, wanted, scope_of, ask):
