@@ -162,6 +162,20 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _candidate_args(children, parent_masks, scores):
+    """The candidate list of mibn_best_dag / mibn_arc_posteriors -> (n_fam, (fam_child, fam_parents, fam_score) as pointers); an
+    empty list is padded to one entry, so that no pointer is null."""
+    child = _i32(children).reshape(-1)
+    masks = np.ascontiguousarray(parent_masks, dtype=np.uint32).reshape(-1)
+    sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+    if not len(child) == len(masks) == len(sc):
+        raise ValueError("children, parent_masks and scores need one entry per candidate")
+    n_fam = len(child)
+    if n_fam == 0:
+        child, masks, sc = np.zeros(1, np.int32), np.zeros(1, np.uint32), np.zeros(1, np.float64)
+    return n_fam, (_p(child, C.c_int32), _p(masks, C.c_uint32), _p(sc, C.c_double))  # (a pointer keeps its array alive)
+
+
 class Dataset:
     """A code matrix resident on the device (mibn_dataset_create), made by `Engine.dataset`.  Closed by `close()`, by leaving its
     `with` block, or when it is garbage collected; it keeps its engine alive until then."""
@@ -861,17 +875,10 @@ class Engine:
         """The best-scoring DAG from a list of local scores (mibn_best_dag): candidate f lets child children[f] take exactly the parent
         set parent_masks[f] (bit u = column u) at scores[f] -> (parents uint32[n_vars], order int32[n_vars] roots first, total).  No
         DAG from these candidates: total -inf, every parents entry NO_PARENTS."""
-        child = _i32(children).reshape(-1)
-        masks = np.ascontiguousarray(parent_masks, dtype=np.uint32).reshape(-1)
-        sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
-        if not len(child) == len(masks) == len(sc):
-            raise ValueError("children, parent_masks and scores need one entry per candidate")
+        n_fam, fam = _candidate_args(children, parent_masks, scores)
         n = max(0, int(n_vars))
         parents, order, total = np.zeros(max(1, n), np.uint32), np.zeros(max(1, n), np.int32), C.c_double(0.0)
-        pad = len(child) == 0
-        self._check(self._L.mibn_best_dag(self._h, int(n_vars), len(child), _p(np.zeros(1, np.int32) if pad else child, C.c_int32),
-                                          _p(np.zeros(1, np.uint32) if pad else masks, C.c_uint32), _p(np.zeros(1, np.float64) if pad else sc, C.c_double),
-                                          _p(parents, C.c_uint32), _p(order, C.c_int32), C.byref(total)))
+        self._check(self._L.mibn_best_dag(self._h, int(n_vars), n_fam, *fam, _p(parents, C.c_uint32), _p(order, C.c_int32), C.byref(total)))
         return parents[:n], order[:n], float(total.value)
 
     def arc_posteriors(self, n_vars, children, parent_masks, scores):
@@ -879,18 +886,11 @@ class Engine:
         (log_post float64[n_fam]: the log posterior that a candidate's child has exactly its parent set, arc float64[n_vars,
         n_vars]: arc[u, v] = P(u -> v), log_evidence).  Under an order-modular prior, not a uniform one (include/mibn.h).  No DAG
         from these candidates: log_evidence -inf, every log_post -inf, every arc 0."""
-        child = _i32(children).reshape(-1)
-        masks = np.ascontiguousarray(parent_masks, dtype=np.uint32).reshape(-1)
-        sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
-        if not len(child) == len(masks) == len(sc):
-            raise ValueError("children, parent_masks and scores need one entry per candidate")
+        n_fam, fam = _candidate_args(children, parent_masks, scores)
         n = max(0, int(n_vars))
-        log_post, arc, evidence = np.zeros(max(1, len(child)), np.float64), np.zeros(max(1, n * n), np.float64), C.c_double(0.0)
-        pad = len(child) == 0
-        self._check(self._L.mibn_arc_posteriors(self._h, int(n_vars), len(child), _p(np.zeros(1, np.int32) if pad else child, C.c_int32),
-                                                _p(np.zeros(1, np.uint32) if pad else masks, C.c_uint32), _p(np.zeros(1, np.float64) if pad else sc, C.c_double),
-                                                _p(log_post, C.c_double), _p(arc, C.c_double), C.byref(evidence)))
-        return log_post[:len(child)], arc[:n * n].reshape(n, n), float(evidence.value)
+        log_post, arc, evidence = np.zeros(max(1, n_fam), np.float64), np.zeros(max(1, n * n), np.float64), C.c_double(0.0)
+        self._check(self._L.mibn_arc_posteriors(self._h, int(n_vars), n_fam, *fam, _p(log_post, C.c_double), _p(arc, C.c_double), C.byref(evidence)))
+        return log_post[:n_fam], arc[:n * n].reshape(n, n), float(evidence.value)
 
     def count_tables(self, codes, card, tables, weights=None):
         """codes: uint8 [n_rows, n_cols] (row- or column-major, sent as it is); tables: list of column-index tuples

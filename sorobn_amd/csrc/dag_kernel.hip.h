@@ -1,6 +1,8 @@
 // Kernels of mibn_best_dag: the best-scoring DAG by dynamic programming over variable subsets (Silander and Myllymaki 2006).
-// include/mibn.h pins what is computed; dag_plan.h has the pass schedule of phase A, why it cannot change a bit, and the index
-// functions used here.  Plain HIP for gfx950, wave64: no inline assembly, no atomics, no scratch.
+// include/mibn.h pins what is computed; dag_plan.h has the pass schedule of phase A, why it cannot change a bit, the index
+// functions and the bodies of the tile pass, a level's subset and the traceback - shared with tools/dag_plan_sim.cpp; a kernel
+// here is its lane-to-work mapping, its LDS arrays and its stores.  Plain HIP for gfx950, wave64: no inline assembly, no atomics,
+// no scratch.
 //
 // Tables (every offset in 64 bits: 2.0e8 entries and 1.6e9 bytes at n = 24):
 //   score[v * 2^(n-1) + i] fp64, mask[..] uint32    bps of child v, i = the subset with bit v squeezed out (dag_squeeze)
@@ -9,7 +11,7 @@
 //   dag_fill_kernel       every bps entry <- (-inf, none)
 //   dag_scatter_kernel    one lane per candidate writes its entry (duplicates were refused on the host: no two lanes share one)
 //   dag_subset_kernel     one pass of phase A: a workgroup loads a tile (dag_gather) into LDS - scores and masks as two arrays -,
-//                         runs the pass's bits over it with a barrier between bits, and writes it back
+//                         runs the pass's bits over it with a barrier between bits, and writes it back (dag_tile_pass, DagMaxTile)
 //   dag_sink_kernel       one level of phase B: the lanes run over all subsets, those of `level` members take part
 //   dag_traceback_kernel  one lane peels the sinks from V and writes parents, order and total
 #pragma once
@@ -36,12 +38,16 @@ __global__ __launch_bounds__(kDagWG) void dag_scatter_kernel(const int32_t *__re
                                                              double *__restrict__ score, uint32_t *__restrict__ mask) {
     const int64_t f = (int64_t)blockIdx.x * kDagWG + threadIdx.x;
     if (f >= n_fam) return;
-    const int v = child[f];
     const uint32_t pm = parents[f];
-    const int64_t at = ((int64_t)v << (n - 1)) + dag_squeeze(pm, v);
+    const int64_t at = dag_entry(child[f], pm, n);
     score[at] = fam_score[f];
     mask[at] = pm;
 }
+
+// a workgroup's barrier as dag_tile_pass's sync
+struct DagBarrier {
+    __device__ void operator()() const { __syncthreads(); }
+};
 
 // grid: n * tiles_per_child workgroups, child-major
 __global__ __launch_bounds__(kDagWG) void dag_subset_kernel(double *__restrict__ score, uint32_t *__restrict__ mask, DagPass P, int32_t n,
@@ -51,31 +57,7 @@ __global__ __launch_bounds__(kDagWG) void dag_subset_kernel(double *__restrict__
     const int64_t wg = blockIdx.x;
     const int64_t v = wg / tiles_per_child, t = wg - v * tiles_per_child;
     const int64_t base = v << (n - 1);
-    const int size = 1 << (P.g + P.c);
-    for (int e = threadIdx.x; e < size; e += kDagWG) {
-        const int64_t at = base + dag_gather(P, t, e);
-        s_score[e] = score[at];
-        s_mask[e] = mask[at];
-    }
-    __syncthreads();
-    for (int b = P.c; b < P.c + P.g; ++b) {
-        const int low = (1 << b) - 1;
-        for (int p = threadIdx.x; p < size / 2; p += kDagWG) {
-            const int e0 = (p & low) | ((p & ~low) << 1), e1 = e0 | (1 << b);  // (a pair is touched by one thread only)
-            const double s0 = s_score[e0];
-            const uint32_t m0 = s_mask[e0];
-            if (dag_better(s0, m0, s_score[e1], s_mask[e1])) {
-                s_score[e1] = s0;
-                s_mask[e1] = m0;
-            }
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < size; e += kDagWG) {
-        const int64_t at = base + dag_gather(P, t, e);
-        score[at] = s_score[e];
-        mask[at] = s_mask[e];
-    }
+    dag_tile_pass<true>(DagMaxTile{score, mask, base, s_score, s_mask}, P, t, threadIdx.x, kDagWG, DagBarrier{});
 }
 
 // level = popcount of the subsets that take part; level 0 writes best[0] = 0
@@ -83,42 +65,17 @@ __global__ __launch_bounds__(kDagWG) void dag_sink_kernel(const double *__restri
                                                           int32_t n, int32_t level) {
     const int64_t S64 = (int64_t)blockIdx.x * kDagWG + threadIdx.x;
     if (S64 >= (int64_t(1) << n)) return;
-    const uint32_t S = (uint32_t)S64;
-    if (__popc(S) != level) return;
-    double top = S ? -__builtin_huge_val() : 0.0;
-    int who = kDagNoSink;
-    for (uint32_t rest = S; rest; rest &= rest - 1) {
-        const int v = __ffs(rest) - 1;
-        const uint32_t C = S ^ (1u << v);
-        const double term = best[C] + score[((int64_t)v << (n - 1)) + dag_squeeze(C, v)];
-        if (term > top) {
-            top = term;
-            who = v;
-        }
-    }
-    best[S64] = top;
-    sink[S64] = (uint8_t)who;
+    if (__builtin_popcount((uint32_t)S64) != level) return;
+    const DagSink r = dag_sink((uint32_t)S64, n, score, best);
+    best[S64] = r.top;
+    sink[S64] = (uint8_t)r.who;
 }
 
 // out: parents uint32[n] | order int32[n] (as words), total in `total_out`
 __global__ void dag_traceback_kernel(const uint32_t *__restrict__ mask, const double *__restrict__ best, const uint8_t *__restrict__ sink, int32_t n,
                                      uint32_t *__restrict__ parents_out, int32_t *__restrict__ order_out, double *__restrict__ total_out) {
     if (blockIdx.x || threadIdx.x) return;
-    uint32_t S = n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u;
-    *total_out = best[S];
-    if (sink[S] == kDagNoSink) {  // no DAG from these candidates
-        for (int v = 0; v < n; ++v) {
-            parents_out[v] = kDagNoMask;
-            order_out[v] = -1;
-        }
-        return;
-    }
-    for (int k = n - 1; k >= 0; --k) {
-        const int v = sink[S];
-        S ^= 1u << v;
-        parents_out[v] = mask[((int64_t)v << (n - 1)) + dag_squeeze(S, v)];
-        order_out[k] = v;
-    }
+    dag_traceback(mask, best, sink, n, parents_out, order_out, total_out);
 }
 
 }  // namespace mibn

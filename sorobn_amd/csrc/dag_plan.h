@@ -1,6 +1,9 @@
-// Host side of mibn_best_dag (exact structure learning by dynamic programming over variable subsets): the argument check, the
-// pass schedule of phase A and the index functions the kernels of dag_kernel.hip.h share with it, in plain C++17 - no HIP header,
-// so that tools/dag_plan_sim.cpp executes the same schedule, tile by tile, on a CPU (tests/test_exact_host.py).
+// Host side of mibn_best_dag (exact structure learning by dynamic programming over variable subsets) and of mibn_arc_posteriors
+// (the same DP with the maximum replaced by a sum): the argument check, the pass schedule, the index functions and - as MIBN_HD
+// inlines - the BODIES of the passes and levels.  The kernels of dag_kernel.hip.h / dag_post_kernel.hip.h and the CPU programs
+// tools/dag_plan_sim.cpp / tools/dag_post_sim.cpp (tests/test_exact_host.py, tests/test_arc_posterior_host.py) call the same
+// bodies: a kernel adds its lane-to-work mapping, its LDS arrays and its barrier, a CPU program runs them with one lane.  Plain
+// C++17 - no HIP header.
 //
 // Phase A turns the table of child v - 2^(n-1) entries (score, parent mask), entry i = the candidate whose parent set, with bit v
 // squeezed out, is exactly i - into its superset maximum: entry i = the best candidate with parents inside i.  That is one step
@@ -32,6 +35,13 @@
 #else
 #define MIBN_HD
 #endif
+// First statement of a body whose sums must round where they are written: no contraction into FMAs.  (g++ has no such pragma:
+// tools/dag_post_sim.cpp is built with -ffp-contract=off.)
+#if defined(__clang__)
+#define MIBN_FP_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define MIBN_FP_NO_CONTRACT
+#endif
 
 namespace mibn {
 
@@ -43,13 +53,15 @@ constexpr int kDagNoSink = 255;
 
 // C (a subset of the columns without v) -> the index of child v's table: bit v squeezed out
 MIBN_HD inline uint32_t dag_squeeze(uint32_t C, int v) { return (C & ((1u << v) - 1u)) | ((C >> (v + 1)) << v); }
+// the entry of child v for the subset `mask` (without v) in a child-major table of n children (64 bits: 2.0e8 entries at n = 24)
+MIBN_HD inline int64_t dag_entry(int v, uint32_t mask, int32_t n) { return ((int64_t)v << (n - 1)) + dag_squeeze(mask, v); }
 
 // the total order of phase A: is (sa, ma) better than (sb, mb)?  Higher score first; at equal score the smaller mask.
 MIBN_HD inline bool dag_better(double sa, uint32_t ma, double sb, uint32_t mb) { return sa > sb || (sa == sb && ma < mb); }
 
 struct DagPass {
     int32_t b0, g, c;
-    MIBN_HD int64_t tile_entries() const { return int64_t(1) << (g + c); }
+    MIBN_HD int tile_size() const { return 1 << (g + c); }  // entries of a tile
 };
 
 // local entry e of tile t -> index in the child's table
@@ -58,6 +70,109 @@ MIBN_HD inline int64_t dag_gather(const DagPass &P, int64_t t, int64_t e) {
     const int mid_bits = P.b0 - P.c;
     const int64_t mid = t & ((int64_t(1) << mid_bits) - 1), hi = t >> mid_bits;
     return r | (mid << P.c) | (j << P.b0) | (hi << (P.b0 + P.g));
+}
+
+// One tile of one pass, by `lanes` lanes of which the caller is `lane`: load the tile (dag_tile_load), then (dag_tile_run) run
+// the pass's bits over it (size = P.tile_size(), taken once by whoever calls the two halves apart) - for each bit the entry pairs (e0, e1 = e0 | bit), a pair by one lane, a sync() before the first
+// bit and after every bit - and store it.  kUp: combine into e1 (subset sums and maxima); else into e0 (superset sums).  A
+// workgroup passes (threadIdx.x, its size, a barrier), a CPU (0, 1, DagNoSync).  Tile is a policy over the tile's storage and the
+// tables behind it (DagMaxTile below; DagSumTile and the load-only DagGapTile further down):
+//     load(e, i) / store(e, i)    local entry e <- / -> entry i of the child's table
+//     combine(dst, src)           local entry dst <- dst (+) src
+struct DagNoSync {
+    MIBN_HD void operator()() const {}
+};
+template <class Tile>
+MIBN_HD inline void dag_tile_load(const Tile &T, const DagPass &P, int size, int64_t t, int lane, int lanes) {
+    for (int e = lane; e < size; e += lanes) T.load(e, dag_gather(P, t, e));
+}
+template <bool kUp, class Tile, class Sync>
+MIBN_HD inline void dag_tile_run(const Tile &T, const DagPass &P, int size, int64_t t, int lane, int lanes, Sync sync) {
+    sync();
+    for (int b = P.c; b < P.c + P.g; ++b) {
+        const int low = (1 << b) - 1;
+        for (int p = lane; p < size / 2; p += lanes) {
+            const int e0 = (p & low) | ((p & ~low) << 1), e1 = e0 | (1 << b);
+            if constexpr (kUp) T.combine(e1, e0);
+            else T.combine(e0, e1);
+        }
+        sync();
+    }
+    for (int e = lane; e < size; e += lanes) T.store(e, dag_gather(P, t, e));
+}
+template <bool kUp, class Tile, class Sync>
+MIBN_HD inline void dag_tile_pass(const Tile &T, const DagPass &P, int64_t t, int lane, int lanes, Sync sync) {
+    const int size = P.tile_size();
+    dag_tile_load(T, P, size, t, lane, lanes);
+    dag_tile_run<kUp>(T, P, size, t, lane, lanes, sync);
+}
+
+// mibn_best_dag's tile: (score, mask) entries as two arrays of 2^kDagMaxTileBits; combine = the better of the two (dag_better)
+struct DagMaxTile {
+    double *score;  // the tables; the child's entries from `base`
+    uint32_t *mask;
+    int64_t base;
+    double *s_score;  // the tile
+    uint32_t *s_mask;
+    MIBN_HD void load(int e, int64_t i) const {
+        const int64_t at = base + i;  // (one sum for both arrays: written apart, the base is folded into both pointers per workgroup)
+        s_score[e] = score[at];
+        s_mask[e] = mask[at];
+    }
+    MIBN_HD void store(int e, int64_t i) const {
+        const int64_t at = base + i;
+        score[at] = s_score[e];
+        mask[at] = s_mask[e];
+    }
+    MIBN_HD void combine(int dst, int src) const {
+        const double s = s_score[src];
+        const uint32_t m = s_mask[src];
+        if (dag_better(s, m, s_score[dst], s_mask[dst])) {
+            s_score[dst] = s;
+            s_mask[dst] = m;
+        }
+    }
+};
+
+// Phase B, one subset S: best[S] = max over the members v of S of best[S \ v] + bps_v(S \ v), the first v in ascending order at
+// a tie; the empty set has 0 and no sink.  `score`: the table phase A left.
+struct DagSink {
+    double top;
+    int who;
+};
+MIBN_HD inline DagSink dag_sink(uint32_t S, int32_t n, const double *score, const double *best) {
+    DagSink r{S ? -HUGE_VAL : 0.0, kDagNoSink};
+    for (uint32_t rest = S; rest; rest &= rest - 1) {
+        const int v = __builtin_ctz(rest);
+        const uint32_t C = S ^ (1u << v);
+        const double term = best[C] + score[dag_entry(v, C, n)];
+        if (term > r.top) {
+            r.top = term;
+            r.who = v;
+        }
+    }
+    return r;
+}
+
+// The traceback: peel the sinks from V; parents_out[n], order_out[n] (roots first), *total_out = best[V].  No DAG from the
+// candidates: every parents entry kDagNoMask, every order entry -1.
+MIBN_HD inline void dag_traceback(const uint32_t *mask, const double *best, const uint8_t *sink, int32_t n, uint32_t *parents_out, int32_t *order_out,
+                                  double *total_out) {
+    uint32_t S = n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u;
+    *total_out = best[S];
+    if (sink[S] == kDagNoSink) {
+        for (int v = 0; v < n; ++v) {
+            parents_out[v] = kDagNoMask;
+            order_out[v] = -1;
+        }
+        return;
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        const int v = sink[S];
+        S ^= 1u << v;
+        parents_out[v] = mask[dag_entry(v, S, n)];
+        order_out[k] = v;
+    }
 }
 
 struct DagPlan {
@@ -88,24 +203,25 @@ inline DagPlan dag_plan(int32_t n, int tile_bits, int group_bits) {
     return D;
 }
 
-// what mibn_best_dag refuses before anything is launched (include/mibn.h has the contract)
-inline int dag_check(int32_t n_vars, int64_t n_fam, const int32_t *child, const uint32_t *parents, const double *score, std::string &err) {
-    if (n_vars < 1) { err = "best_dag: n_vars must be at least 1"; return MIBN_E_ARG; }
+// what mibn_best_dag and mibn_arc_posteriors refuse before anything is launched (include/mibn.h has the contract); `who`: the
+// call's name in the message ("best_dag", "arc_posteriors")
+inline int dag_check(const std::string &who, int32_t n_vars, int64_t n_fam, const int32_t *child, const uint32_t *parents, const double *score, std::string &err) {
+    if (n_vars < 1) { err = who + ": n_vars must be at least 1"; return MIBN_E_ARG; }
     if (n_vars > MIBN_BEST_DAG_MAX_VARS) {
-        err = "best_dag: " + std::to_string(n_vars) + " variables (at most " + std::to_string(MIBN_BEST_DAG_MAX_VARS) + ": the tables double with every variable)";
+        err = who + ": " + std::to_string(n_vars) + " variables (at most " + std::to_string(MIBN_BEST_DAG_MAX_VARS) + ": the tables double with every variable)";
         return MIBN_E_LIMIT;
     }
     const int64_t entries = int64_t(1) << (n_vars - 1);
     std::vector<uint64_t> seen((size_t)((n_vars * entries + 63) / 64), 0);
     for (int64_t f = 0; f < n_fam; ++f) {
-        const std::string who = "best_dag: candidate " + std::to_string(f);
+        const std::string cand = who + ": candidate " + std::to_string(f);
         const int32_t v = child[f];
-        if (v < 0 || v >= n_vars) { err = who + ": child outside [0, n_vars)"; return MIBN_E_ARG; }
-        if (n_vars < 32 && (parents[f] >> n_vars)) { err = who + ": a parent bit at or above n_vars"; return MIBN_E_ARG; }
-        if ((parents[f] >> v) & 1u) { err = who + ": the child is its own parent"; return MIBN_E_ARG; }
-        if (!std::isfinite(score[f])) { err = who + ": its score is not finite"; return MIBN_E_ARG; }
-        const int64_t at = (int64_t)v * entries + dag_squeeze(parents[f], v);
-        if ((seen[(size_t)(at >> 6)] >> (at & 63)) & 1u) { err = who + ": the same (child, parent set) is listed twice"; return MIBN_E_ARG; }
+        if (v < 0 || v >= n_vars) { err = cand + ": child outside [0, n_vars)"; return MIBN_E_ARG; }
+        if (n_vars < 32 && (parents[f] >> n_vars)) { err = cand + ": a parent bit at or above n_vars"; return MIBN_E_ARG; }
+        if ((parents[f] >> v) & 1u) { err = cand + ": the child is its own parent"; return MIBN_E_ARG; }
+        if (!std::isfinite(score[f])) { err = cand + ": its score is not finite"; return MIBN_E_ARG; }
+        const int64_t at = dag_entry(v, parents[f], n_vars);
+        if ((seen[(size_t)(at >> 6)] >> (at & 63)) & 1u) { err = cand + ": the same (child, parent set) is listed twice"; return MIBN_E_ARG; }
         seen[(size_t)(at >> 6)] |= uint64_t(1) << (at & 63);
     }
     return MIBN_OK;
@@ -134,10 +250,12 @@ MIBN_HD inline uint32_t dag_unsqueeze(uint32_t i, int v) { return (i & ((1u << v
 // consecutive masks at most 20 share a popcount).  binom[c * kDagBinomStride + i] = C(c, i) for c, i in [0, 24]; at most
 // C(24, 12) = 2 704 156.
 constexpr int kDagBinomStride = 25;
-inline void dag_binomials(uint32_t *binom /* kDagBinomStride x kDagBinomStride */) {
+inline std::vector<uint32_t> dag_binomials() {
+    std::vector<uint32_t> binom((size_t)kDagBinomStride * kDagBinomStride);
     for (int c = 0; c < kDagBinomStride; ++c)
         for (int i = 0; i < kDagBinomStride; ++i)
             binom[c * kDagBinomStride + i] = i == 0 ? 1u : c == 0 ? 0u : binom[(c - 1) * kDagBinomStride + i - 1] + binom[(c - 1) * kDagBinomStride + i];
+    return binom;
 }
 // k in [0, C(n, level)) -> the subset; n <= 24
 MIBN_HD inline uint32_t dag_unrank(uint32_t k, int level, int n, const uint32_t *binom) {
@@ -168,6 +286,60 @@ inline double dag_log_evidence(double l_full, int32_t n, const double *c) {
     double e = l_full;
     for (int v = 0; v < n; ++v) e += c[v];
     return e;
+}
+
+// mibn_arc_posteriors' tile (dag_tile_pass): one array of 2^kDagMaxTileBits doubles over one child's table; combine = dag_logaddexp.
+// The subset sum turns s' into alpha_v (kUp), the superset sum g_v into Gamma_v (not kUp).
+struct DagSumTile {
+    double *table;  // the child's entries from `base`
+    int64_t base;
+    double *s_val;  // the tile
+    MIBN_HD void load(int e, int64_t i) const { s_val[e] = table[base + i]; }
+    MIBN_HD void store(int e, int64_t i) const { table[base + i] = s_val[e]; }
+    MIBN_HD void combine(int dst, int src) const {
+        MIBN_FP_NO_CONTRACT
+        s_val[dst] = dag_logaddexp(s_val[dst], s_val[src]);
+    }
+};
+// What the FIRST pass of the superset sum loads its tile with (dag_tile_load; the pass goes on over a DagSumTile): nothing is read
+// from the table, entry S of child v is formed as g_v(S) = L(S) + R(V \ S \ {v}) - g never exists in memory.
+struct DagGapTile {
+    double *s_val;  // the tile
+    const double *L, *R;
+    int v;
+    uint32_t others;  // V \ {v}
+    MIBN_HD DagGapTile(double *tile, const double *L_, const double *R_, int v_, int32_t n)
+        : s_val(tile), L(L_), R(R_), v(v_), others(((1u << n) - 1u) ^ (1u << v_)) {}
+    MIBN_HD void load(int e, int64_t i) const {
+        MIBN_FP_NO_CONTRACT
+        const uint32_t S = dag_unsqueeze((uint32_t)i, v);
+        s_val[e] = L[S] + R[others ^ S];
+    }
+};
+
+// L and R of one subset S, the terms of either sum in ascending v; the empty set has 0:
+//     L(S) = (+) over v in S of L(S \ v) + alpha_v(S \ v)           R(S) = (+) over v in S of alpha_v(V \ S) + R(S \ v)
+struct DagLR {
+    double l, r;
+};
+MIBN_HD inline DagLR dag_level(uint32_t S, int32_t n, const double *alpha, const double *L, const double *R) {
+    MIBN_FP_NO_CONTRACT
+    const uint32_t outside = ((1u << n) - 1u) ^ S;  // (n <= 24)
+    DagLR x{S ? -HUGE_VAL : 0.0, S ? -HUGE_VAL : 0.0};
+    for (uint32_t rest = S; rest; rest &= rest - 1) {
+        const int v = __builtin_ctz(rest);
+        const uint32_t C = S ^ (1u << v);
+        x.l = dag_logaddexp(x.l, L[C] + alpha[dag_entry(v, C, n)]);
+        x.r = dag_logaddexp(x.r, alpha[dag_entry(v, outside, n)] + R[C]);
+    }
+    return x;
+}
+
+// log posterior of the candidate (v, pm) with score s: (s' + Gamma_v(pm)) - L(V); -inf when no structure exists (never -inf - -inf)
+MIBN_HD inline double dag_log_post(int v, uint32_t pm, double s, double centre_v, const double *gamma, double whole, int32_t n) {
+    MIBN_FP_NO_CONTRACT
+    const double g = gamma[dag_entry(v, pm, n)];
+    return whole == -HUGE_VAL ? whole : (dag_centred(s, centre_v) + g) - whole;
 }
 
 // The order of the arc sums, a function of the candidate list alone.  The list is cut into segments of kDagArcSegment consecutive

@@ -1,8 +1,10 @@
 // Kernels of mibn_arc_posteriors: the posterior probability of every candidate parent set and of every arc, averaged over all
 // DAGs under an order-modular prior, by the sum-product form of the subset DP (Koivisto and Sood 2004, Koivisto 2006).
-// include/mibn.h pins what is computed; dag_plan.h has the pass schedule - mibn_best_dag's, unchanged -, dag_logaddexp, the centring
-// and the order of the arc sums.  Plain HIP for gfx950, wave64, fp64: no inline assembly, no atomics, no scratch; contraction
-// into FMAs is off in this file's arithmetic, so that device, tools/dag_post_sim.cpp and the numpy twin round at the same places.
+// include/mibn.h pins what is computed; dag_plan.h has the pass schedule - mibn_best_dag's, unchanged -, dag_logaddexp, the centring,
+// the order of the arc sums and the bodies of the tile pass, a level's subset and a candidate's posterior - shared with
+// tools/dag_post_sim.cpp; a kernel here is its lane-to-work mapping, its LDS array and its stores.  Plain HIP for gfx950, wave64,
+// fp64: no inline assembly, no atomics, no scratch; contraction into FMAs is off in this arithmetic (MIBN_FP_NO_CONTRACT), so that
+// device, tools/dag_post_sim.cpp and the numpy twin round at the same places.
 //
 // Tables (every offset in 64 bits: 2.0e8 entries of alpha at n = 24; 8 n 2^(n-1) + 16 2^n bytes in all, 1.9 GB there):
 //   alpha[v * 2^(n-1) + i] fp64     i = the subset with bit v squeezed out (dag_squeeze) - dag_kernel's score layout, no mask array;
@@ -11,7 +13,7 @@
 //
 //   dag_post_fill_kernel       every alpha entry <- -inf
 //   dag_post_scatter_kernel    one lane per candidate writes s' = s - c_v (duplicates were refused on the host)
-//   dag_post_subset_kernel     one pass of the subset sum: dag_subset_kernel's tile loop, entry[e | bit] = entry[e | bit] (+) entry[e]
+//   dag_post_subset_kernel     one pass of the subset sum: dag_subset_kernel's tile pass over a DagSumTile, entry[e | bit] = entry[e | bit] (+) entry[e]
 //   dag_post_level_kernel      L and R of one popcount level, both in one launch (they do not depend on each other)
 //                              - a lane per subset OF THE LEVEL, found from its rank (dag_unrank), not a lane per mask
 //   dag_post_superset_kernel   one pass of the superset sum, entry[e] = entry[e] (+) entry[e | bit]; the FIRST pass reads no table
@@ -43,105 +45,61 @@ __global__ __launch_bounds__(kDagWG) void dag_post_fill_kernel(double *__restric
 __global__ __launch_bounds__(kDagWG) void dag_post_scatter_kernel(const int32_t *__restrict__ child, const uint32_t *__restrict__ parents,
                                                                   const double *__restrict__ fam_score, const double *__restrict__ centre,
                                                                   int64_t n_fam, int32_t n, double *__restrict__ alpha) {
-#pragma clang fp contract(off)
+    MIBN_FP_NO_CONTRACT
     const int64_t f = (int64_t)blockIdx.x * kDagWG + threadIdx.x;
     if (f >= n_fam) return;
     const int v = child[f];
-    alpha[((int64_t)v << (n - 1)) + dag_squeeze(parents[f], v)] = dag_centred(fam_score[f], centre[v]);
+    alpha[dag_entry(v, parents[f], n)] = dag_centred(fam_score[f], centre[v]);
 }
 
 // grid: n * tiles_per_child workgroups, child-major
 __global__ __launch_bounds__(kDagWG) void dag_post_subset_kernel(double *__restrict__ alpha, DagPass P, int32_t n, int64_t tiles_per_child) {
-#pragma clang fp contract(off)
     __shared__ double s_val[1 << kDagMaxTileBits];
     const int64_t wg = blockIdx.x;
     const int64_t v = wg / tiles_per_child, t = wg - v * tiles_per_child;
-    const int64_t base = v << (n - 1);
-    const int size = 1 << (P.g + P.c);
-    for (int e = threadIdx.x; e < size; e += kDagWG) s_val[e] = alpha[base + dag_gather(P, t, e)];
-    __syncthreads();
-    for (int b = P.c; b < P.c + P.g; ++b) {
-        const int low = (1 << b) - 1;
-        for (int p = threadIdx.x; p < size / 2; p += kDagWG) {
-            const int e0 = (p & low) | ((p & ~low) << 1), e1 = e0 | (1 << b);  // (a pair is touched by one thread only)
-            s_val[e1] = dag_logaddexp(s_val[e1], s_val[e0]);
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < size; e += kDagWG) alpha[base + dag_gather(P, t, e)] = s_val[e];
+    dag_tile_pass<true>(DagSumTile{alpha, v << (n - 1), s_val}, P, t, threadIdx.x, kDagWG, DagBarrier{});
 }
 
-// level = popcount of the subsets that take part; level 0 writes L[0] = R[0] = 0.  The terms of either sum in ascending v.
+// level = popcount of the subsets that take part; level 0 writes L[0] = R[0] = 0.
 // grid: C(n, level) lanes - lane k takes the k-th subset of the level (dag_unrank), so no lane of a wave idles while others work.
 __global__ __launch_bounds__(kDagWG) void dag_post_level_kernel(const double *__restrict__ alpha, double *__restrict__ L, double *__restrict__ R,
                                                                 const uint32_t *__restrict__ binom, int32_t n, int32_t level) {
-#pragma clang fp contract(off)
     const uint32_t k = blockIdx.x * kDagWG + threadIdx.x;
     if (k >= binom[n * kDagBinomStride + level]) return;
     const uint32_t S = dag_unrank(k, level, n, binom);
-    const int64_t S64 = S;
-    const uint32_t outside = ((1u << n) - 1u) ^ S;  // (n <= 24)
-    double l = S ? -__builtin_huge_val() : 0.0, r = l;
-    for (uint32_t rest = S; rest; rest &= rest - 1) {
-        const int v = __ffs(rest) - 1;
-        const uint32_t C = S ^ (1u << v);
-        const int64_t base = (int64_t)v << (n - 1);
-        l = dag_logaddexp(l, L[C] + alpha[base + dag_squeeze(C, v)]);
-        r = dag_logaddexp(r, alpha[base + dag_squeeze(outside, v)] + R[C]);
-    }
-    L[S64] = l;
-    R[S64] = r;
+    const DagLR x = dag_level(S, n, alpha, L, R);
+    L[(int64_t)S] = x.l;
+    R[(int64_t)S] = x.r;
 }
 
 // grid: n * tiles_per_child workgroups, child-major.  first != 0: the tile is formed from L and R, nothing is read from gamma.
 __global__ __launch_bounds__(kDagWG) void dag_post_superset_kernel(double *__restrict__ gamma, const double *__restrict__ L, const double *__restrict__ R,
                                                                    DagPass P, int32_t n, int64_t tiles_per_child, int32_t first) {
-#pragma clang fp contract(off)
     __shared__ double s_val[1 << kDagMaxTileBits];
     const int64_t wg = blockIdx.x;
     const int64_t v = wg / tiles_per_child, t = wg - v * tiles_per_child;
-    const int64_t base = v << (n - 1);
-    const int size = 1 << (P.g + P.c);
-    if (first) {
-        const uint32_t others = ((1u << n) - 1u) ^ (1u << (int)v);
-        for (int e = threadIdx.x; e < size; e += kDagWG) {
-            const uint32_t S = dag_unsqueeze((uint32_t)dag_gather(P, t, e), (int)v);
-            s_val[e] = L[S] + R[others ^ S];
-        }
-    } else {
-        for (int e = threadIdx.x; e < size; e += kDagWG) s_val[e] = gamma[base + dag_gather(P, t, e)];
-    }
-    __syncthreads();
-    for (int b = P.c; b < P.c + P.g; ++b) {
-        const int low = (1 << b) - 1;
-        for (int p = threadIdx.x; p < size / 2; p += kDagWG) {
-            const int e0 = (p & low) | ((p & ~low) << 1), e1 = e0 | (1 << b);
-            s_val[e0] = dag_logaddexp(s_val[e0], s_val[e1]);
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < size; e += kDagWG) gamma[base + dag_gather(P, t, e)] = s_val[e];
+    const DagSumTile T{gamma, v << (n - 1), s_val};
+    const int size = P.tile_size();
+    if (first) dag_tile_load(DagGapTile(s_val, L, R, (int)v, n), P, size, t, threadIdx.x, kDagWG);
+    else dag_tile_load(T, P, size, t, threadIdx.x, kDagWG);
+    dag_tile_run<false>(T, P, size, t, threadIdx.x, kDagWG, DagBarrier{});
 }
 
 __global__ __launch_bounds__(kDagWG) void dag_post_candidate_kernel(const int32_t *__restrict__ child, const uint32_t *__restrict__ parents,
                                                                     const double *__restrict__ fam_score, const double *__restrict__ centre,
                                                                     const double *__restrict__ gamma, const double *__restrict__ L, int64_t n_fam,
                                                                     int32_t n, double *__restrict__ log_post) {
-#pragma clang fp contract(off)
     const int64_t f = (int64_t)blockIdx.x * kDagWG + threadIdx.x;
     if (f >= n_fam) return;
     const int v = child[f];
-    const double whole = L[(int64_t(1) << n) - 1];
-    const double s = dag_centred(fam_score[f], centre[v]);
-    const double g = gamma[((int64_t)v << (n - 1)) + dag_squeeze(parents[f], v)];
-    log_post[f] = whole == -__builtin_huge_val() ? whole : (s + g) - whole;  // (no candidate structure: -inf, never -inf - -inf)
+    log_post[f] = dag_log_post(v, parents[f], fam_score[f], centre[v], gamma, L[(int64_t(1) << n) - 1], n);
 }
 
 // grid (segments, n): workgroup (j, v) writes part[(j * n + u) * n + v] for every u.  A lane keeps one sum per u in registers (the
 // loops over u have a compile-time bound: no array is indexed by a run-time value).
 __global__ __launch_bounds__(kDagWG) void dag_post_arc_kernel(const int32_t *__restrict__ child, const uint32_t *__restrict__ parents,
                                                               const double *__restrict__ log_post, int64_t n_fam, int32_t n, double *__restrict__ part) {
-#pragma clang fp contract(off)
+    MIBN_FP_NO_CONTRACT
     __shared__ double s_lane[kDagWG];
     const int64_t j = blockIdx.x;
     const int v = blockIdx.y;
@@ -172,7 +130,7 @@ __global__ __launch_bounds__(kDagWG) void dag_post_arc_kernel(const int32_t *__r
 }
 
 __global__ __launch_bounds__(kDagWG) void dag_post_arc_sum_kernel(const double *__restrict__ part, int64_t segments, int32_t n, double *__restrict__ arc) {
-#pragma clang fp contract(off)
+    MIBN_FP_NO_CONTRACT
     const int k = blockIdx.x * kDagWG + threadIdx.x;
     if (k >= n * n) return;
     double sum = 0.0;

@@ -17,6 +17,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/mibn.h"
@@ -439,17 +440,15 @@ struct mibn_ctx {
         std::vector<Event> ev;
     } sc;
     int64_t score_cells = kScoreCellBudget;  // option score_cells (test hook: forces sub-batches)
-    // mibn_best_dag: the tables of a call (kept between calls up to kDagKeepBytes) and its candidate / result block
+    // mibn_best_dag and mibn_arc_posteriors (both blocking, on an idle context): the tables of a call (kept between calls up to
+    // kDagKeepBytes), its candidate / result block and the events between its phases
     struct Dag {
-        DevBuf<double> d_score, d_best;
+        DevBuf<double> d_score, d_best;  // mibn_arc_posteriors: alpha / Gamma in d_score, L in d_best, R in d_right
         DevBuf<uint32_t> d_mask;
         DevBuf<uint8_t> d_sink;
-        DevBuf<char> d_io;  // [fam_score | fam_child | fam_parents] then [total | parents_out | order_out]
-        Event ev[3];
-        // mibn_arc_posteriors: alpha / Gamma in d_score, L in d_best, R here; its own candidate / result block
         DevBuf<double> d_right;
-        DevBuf<char> d_post_io;  // [fam_score | fam_child | fam_parents | centres] then [log_post | arc | segment sums]
-        Event post_ev[5];
+        DevBuf<char> d_io;  // [fam_score | fam_child | fam_parents] then what the call carves behind them (DagFrame::carve)
+        Event ev[5];
     } dag;
     int dag_tile_bits = kDagTileBits;    // options dag_tile_bits / dag_group_bits (test hooks: force multi-pass schedules at small n;
     int dag_group_bits = kDagGroupBits;  // no bit of mibn_best_dag depends on them, the last bits of mibn_arc_posteriors do: dag_plan.h says why)
@@ -3960,9 +3959,11 @@ extern "C" int mibn_ci_tests_w(mibn_t *h, int32_t id, int32_t kind, int32_t n_te
     return ci_tests_run(h, id, kind, n_tests, scope_off, scope_cols, wset ? wset : &none, stat, adj_dof);
 }
 
-// ---- mibn_best_dag: check (dag_plan.h), tables, fill + scatter + the passes of phase A, the n + 1 levels of phase B, the traceback.
-// Everything on the main stream, one synchronisation; three events give the two statistics rows.  Tables above kDagKeepBytes are
-// freed when the call returns (2.6 GB at n = 24 would otherwise stay with a context that may never ask again).
+// ---- mibn_best_dag and mibn_arc_posteriors: one driver frame.  Both check and plan (dag_plan.h), make room for their tables,
+// upload the candidates, run fill + scatter + the passes and then their levels on the main stream with an event between phases,
+// download, synchronise once and turn the events into statistics rows.  DagFrame holds what the calls share, the
+// two *_run functions what differs.  Tables above kDagKeepBytes are freed when the call returns (2.6 GB at n = 24 would otherwise
+// stay with a context that may never ask again).
 constexpr size_t kDagKeepBytes = size_t(1) << 28;
 
 template <class T>
@@ -3973,87 +3974,140 @@ static hipError_t dag_room(DevBuf<T> &buf, size_t need) {  // exactly `need`: no
     return e;
 }
 
+struct DagRow {  // a statistics row: its slot, launches, algorithmic bytes and items; row k runs between the events k and k + 1
+    int slot;
+    double launches, bytes, items;
+    void add(double b) { launches += 1; bytes += b; }
+};
+
+struct DagFrame {
+    mibn_t *h;
+    mibn_ctx::Dag &X;
+    int32_t n = 0;
+    int64_t n_fam = 0;
+    DagPlan D;
+    size_t bps = 0, subsets = 0, fam = 0;  // entries of all children's tables, subsets, max(1, n_fam)
+    hipStream_t S0 = nullptr;
+    dim3 wg{kDagWG}, per_fam;
+    double t_start = 0, t_mark = 0;
+    int marks = 0;  // events recorded
+    // the block d_io, carved in descending alignment: the candidates, then what the call asks for
+    double *d_fam = nullptr;
+    int32_t *d_child = nullptr;
+    uint32_t *d_par = nullptr;
+    char *d_free = nullptr;
+    template <class T>
+    T *carve(size_t count) { return reinterpret_cast<T *>(std::exchange(d_free, d_free + sizeof(T) * count)); }
+
+    // the entry checks and the plan
+    int enter(const char *who, int32_t n_vars, int64_t n_fam_, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score) {
+        if (int rc = check_state(h, kNeedDevice)) return rc;
+        if (int rc = check_state(h, kNeedIdle)) return rc;
+        t_start = now_ms();
+        reset_last_stats(h);
+        static_assert(MIBN_ARC_POSTERIOR_MAX_VARS == MIBN_BEST_DAG_MAX_VARS, "dag_check's limit is the one of both calls");
+        if (int rc = dag_check(who, n_vars, n_fam_, fam_child, fam_parents, fam_score, h->err)) return rc;
+        n = n_vars, n_fam = n_fam_, S0 = h->stream;
+        D = dag_plan(n, h->dag_tile_bits, h->dag_group_bits);
+        HIP_TRY(h, hipSetDevice(h->device));
+        bps = (size_t)n * (size_t)D.entries, subsets = size_t(1) << n, fam = (size_t)std::max<int64_t>(1, n_fam);
+        per_fam = dim3((unsigned)((fam + kDagWG - 1) / kDagWG));
+        return MIBN_OK;
+    }
+    // d_io <- [fam_score | fam_child | fam_parents] (16 fam bytes: what follows stays 16-aligned), then `rest` bytes for the call
+    // to carve; the events
+    int upload(const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score, size_t rest) {
+        HIP_TRY(h, X.d_io.ensure(16 * fam + rest));
+        for (Event &e : X.ev) HIP_TRY(h, e.ensure());
+        d_free = X.d_io;
+        d_fam = carve<double>(fam), d_child = carve<int32_t>(fam), d_par = carve<uint32_t>(fam);
+        const double t0 = now_ms();
+        if (n_fam) {
+            HIP_TRY(h, hipMemcpyAsync(d_fam, fam_score, 8 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+            HIP_TRY(h, hipMemcpyAsync(d_child, fam_child, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+            HIP_TRY(h, hipMemcpyAsync(d_par, fam_parents, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
+        }
+        h->stats.h2d_ms += now_ms() - t0;
+        return MIBN_OK;
+    }
+    // the end of a phase: its launches are checked and the next event is recorded
+    int mark() {
+        if (marks) HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(X.ev[marks++], S0));
+        t_mark = now_ms();
+        return MIBN_OK;
+    }
+    // the first phase of both calls, launches and bytes counted: fill(grid), scatter() if there are candidates, pass(grid, P) for
+    // each pass of the plan.  A table entry has `entry_bytes` (written by fill, read and written by a pass), a candidate moves `fam_bytes`.
+    template <class Fill, class Scatter, class Pass>
+    DagRow fill_scatter_passes(int slot, double entry_bytes, double fam_bytes, Fill &&fill, Scatter &&scatter, Pass &&pass) const {
+        DagRow row{slot, 0, 0, (double)n_fam};
+        fill(dim3((unsigned)std::min<size_t>((bps + kDagWG - 1) / kDagWG, 65536)));
+        row.add(entry_bytes * (double)bps);
+        if (n_fam) {
+            scatter();
+            row.add(fam_bytes * (double)n_fam);
+        }
+        for (const DagPass &P : D.passes) {
+            pass(dim3((unsigned)D.grid(P)), P);
+            row.add(2.0 * entry_bytes * (double)bps);
+        }
+        return row;
+    }
+    // after the downloads were queued: the one synchronisation, then the events as statistics rows
+    int finish(std::initializer_list<DagRow> rows) {
+        HIP_TRY(h, hipStreamSynchronize(S0));
+        h->stats.d2h_ms += now_ms() - t_mark;
+        for (size_t k = 0; k < rows.size(); ++k) {
+            const DagRow &r = rows.begin()[k];
+            float ms = 0;
+            HIP_TRY(h, hipEventElapsedTime(&ms, X.ev[k], X.ev[k + 1]));
+            book_stat(h, r.slot, r.launches, ms, r.bytes, r.items, true, false);
+            h->stats.kernel_ms += ms, h->stats.n_launches += r.launches, h->stats.alg_bytes += r.bytes;
+        }
+        h->stats.total_ms = now_ms() - t_start;
+        return MIBN_OK;
+    }
+};
+
+// mibn_best_dag: fill + scatter + the passes of phase A | the n + 1 levels of phase B and the traceback: two statistics rows
 static int best_dag_run(mibn_t *h, int32_t n, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score,
                         uint32_t *parents_out, int32_t *order_out, double *total_out) {
-    int rc;
-    if ((rc = check_state(h, kNeedDevice))) return rc;
-    if ((rc = check_state(h, kNeedIdle))) return rc;
-    const double t_start = now_ms();
-    reset_last_stats(h);
-    if ((rc = dag_check(n, n_fam, fam_child, fam_parents, fam_score, h->err))) return rc;
-    const DagPlan D = dag_plan(n, h->dag_tile_bits, h->dag_group_bits);
-    mibn_ctx::Dag &X = h->dag;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t bps = (size_t)n * (size_t)D.entries, subsets = size_t(1) << n, fam = (size_t)std::max<int64_t>(1, n_fam);
-    struct Release {  // on every exit, after the stream is drained (hipFree waits for the device)
+    DagFrame F{h, h->dag};
+    if (int rc = F.enter("best_dag", n, n_fam, fam_child, fam_parents, fam_score)) return rc;
+    mibn_ctx::Dag &X = F.X;
+    const size_t bps = F.bps, subsets = F.subsets;
+    struct Release {  // the call's tables, on every exit (hipFree waits for the device)
         mibn_ctx::Dag &X;
         bool on;
-        ~Release() {
-            if (!on) return;
-            (void)X.d_score.release();
-            (void)X.d_mask.release();
-            (void)X.d_best.release();
-            (void)X.d_sink.release();
-        }
+        ~Release() { if (on) (void)X.d_score.release(), (void)X.d_mask.release(), (void)X.d_best.release(), (void)X.d_sink.release(); }
     } release{X, 12 * bps + 9 * subsets > kDagKeepBytes};
     HIP_TRY(h, dag_room(X.d_score, bps));
     HIP_TRY(h, dag_room(X.d_mask, bps));
     HIP_TRY(h, dag_room(X.d_best, subsets));
     HIP_TRY(h, dag_room(X.d_sink, subsets));
-    const size_t o_child = 8 * fam, o_par = o_child + 4 * fam, o_total = (o_par + 4 * fam + 15) & ~size_t(15), o_pout = o_total + 8, o_order = o_pout + 4 * (size_t)n;
-    HIP_TRY(h, X.d_io.ensure(o_order + 4 * (size_t)n));
-    for (Event &e : X.ev) HIP_TRY(h, e.ensure());
-    const hipStream_t S0 = h->stream;
-    const double t0 = now_ms();
-    if (n_fam) {
-        HIP_TRY(h, hipMemcpyAsync(X.d_io, fam_score, 8 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
-        HIP_TRY(h, hipMemcpyAsync(X.d_io + o_child, fam_child, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
-        HIP_TRY(h, hipMemcpyAsync(X.d_io + o_par, fam_parents, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
-    }
-    h->stats.h2d_ms += now_ms() - t0;
-    double *d_total = reinterpret_cast<double *>(X.d_io + o_total);
-    uint32_t *d_pout = reinterpret_cast<uint32_t *>(X.d_io + o_pout);
-    int32_t *d_order = reinterpret_cast<int32_t *>(X.d_io + o_order);
+    if (int rc = F.upload(fam_child, fam_parents, fam_score, 8 + 8 * (size_t)n)) return rc;
+    double *d_total = F.carve<double>(1);
+    uint32_t *d_pout = F.carve<uint32_t>((size_t)n);
+    int32_t *d_order = F.carve<int32_t>((size_t)n);
+    const hipStream_t S0 = F.S0;
     // phase A
-    HIP_TRY(h, hipEventRecord(X.ev[0], S0));
-    double launches_a = 1, bytes_a = 12.0 * (double)bps;
-    hipLaunchKernelGGL(dag_fill_kernel, dim3((unsigned)std::min<size_t>((bps + kDagWG - 1) / kDagWG, 65536)), dim3(kDagWG), 0, S0, X.d_score.get(), X.d_mask.get(), (int64_t)bps);
-    if (n_fam) {
-        hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)((n_fam + kDagWG - 1) / kDagWG)), dim3(kDagWG), 0, S0, reinterpret_cast<const int32_t *>(X.d_io + o_child),
-                           reinterpret_cast<const uint32_t *>(X.d_io + o_par), reinterpret_cast<const double *>(X.d_io.get()), n_fam, n, X.d_score.get(), X.d_mask.get());
-        launches_a += 1;
-        bytes_a += 28.0 * (double)n_fam;
-    }
-    for (const DagPass &P : D.passes) {
-        hipLaunchKernelGGL(dag_subset_kernel, dim3((unsigned)D.grid(P)), dim3(kDagWG), 0, S0, X.d_score.get(), X.d_mask.get(), P, n, D.tiles_per_child(P));
-        launches_a += 1;
-        bytes_a += 24.0 * (double)bps;
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipEventRecord(X.ev[1], S0));
+    if (int rc = F.mark()) return rc;
+    const DagRow a = F.fill_scatter_passes(
+        kStatDagSubset, 12.0, 28.0, [&](dim3 grid) { hipLaunchKernelGGL(dag_fill_kernel, grid, F.wg, 0, S0, X.d_score.get(), X.d_mask.get(), (int64_t)bps); },
+        [&] { hipLaunchKernelGGL(dag_scatter_kernel, F.per_fam, F.wg, 0, S0, F.d_child, F.d_par, F.d_fam, n_fam, n, X.d_score.get(), X.d_mask.get()); },
+        [&](dim3 grid, const DagPass &P) { hipLaunchKernelGGL(dag_subset_kernel, grid, F.wg, 0, S0, X.d_score.get(), X.d_mask.get(), P, n, F.D.tiles_per_child(P)); });
+    if (int rc = F.mark()) return rc;
     // phase B and the traceback
     for (int32_t level = 0; level <= n; ++level)
-        hipLaunchKernelGGL(dag_sink_kernel, dim3((unsigned)((subsets + kDagWG - 1) / kDagWG)), dim3(kDagWG), 0, S0, X.d_score.get(), X.d_best.get(), X.d_sink.get(), n, level);
+        hipLaunchKernelGGL(dag_sink_kernel, dim3((unsigned)((subsets + kDagWG - 1) / kDagWG)), F.wg, 0, S0, X.d_score.get(), X.d_best.get(), X.d_sink.get(), n, level);
     hipLaunchKernelGGL(dag_traceback_kernel, dim3(1), dim3(64), 0, S0, X.d_mask.get(), X.d_best.get(), X.d_sink.get(), n, d_pout, d_order, d_total);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipEventRecord(X.ev[2], S0));
-    const double t1 = now_ms();
+    if (int rc = F.mark()) return rc;
     HIP_TRY(h, hipMemcpyAsync(total_out, d_total, 8, hipMemcpyDeviceToHost, S0));
     HIP_TRY(h, hipMemcpyAsync(parents_out, d_pout, 4 * (size_t)n, hipMemcpyDeviceToHost, S0));
     HIP_TRY(h, hipMemcpyAsync(order_out, d_order, 4 * (size_t)n, hipMemcpyDeviceToHost, S0));
-    HIP_TRY(h, hipStreamSynchronize(S0));
-    h->stats.d2h_ms += now_ms() - t1;
-    float ms_a = 0, ms_b = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms_a, X.ev[0], X.ev[1]));
-    HIP_TRY(h, hipEventElapsedTime(&ms_b, X.ev[1], X.ev[2]));
-    book_stat(h, kStatDagSubset, launches_a, ms_a, bytes_a, (double)n_fam, true, false);
-    // every bps score and every best entry read once per member, best and sink written once per subset; the traceback's 2 n reads
-    book_stat(h, kStatDagSink, (double)n + 2.0, ms_b, 16.0 * (double)bps + 9.0 * (double)subsets, (double)subsets, true, false);
-    h->stats.kernel_ms = ms_a + ms_b;
-    h->stats.n_launches = launches_a + (double)n + 2.0;
-    h->stats.alg_bytes = bytes_a + 16.0 * (double)bps + 9.0 * (double)subsets;
-    h->stats.total_ms = now_ms() - t_start;
-    return MIBN_OK;
+    // phase B: every bps score and every best entry read once per member, best and sink written once per subset; the traceback's 2 n reads
+    return F.finish({a, {kStatDagSink, (double)n + 2.0, 16.0 * (double)bps + 9.0 * (double)subsets, (double)subsets}});
 }
 
 extern "C" int mibn_best_dag(mibn_t *h, int32_t n_vars, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score,
@@ -4062,134 +4116,75 @@ extern "C" int mibn_best_dag(mibn_t *h, int32_t n_vars, int64_t n_fam, const int
     return drained_on_error(h, best_dag_run(h, n_vars, n_fam, fam_child, fam_parents, fam_score, parents_out, order_out, total_out), drain_main_unchecked);
 }
 
-// ---- mibn_arc_posteriors: mibn_best_dag's check and schedule; fill + scatter + the passes of the subset sum, the n + 1 levels of
-// L and R, the passes of the superset sum (the first forms g from L and R), the candidate kernel and the arc sums.  Everything on
-// the main stream, one synchronisation; five events give the four statistics rows.  The tables are mibn_best_dag's buffers (alpha
-// in d_score, L in d_best) and d_right, freed on return by the same rule.
+// mibn_arc_posteriors: fill + scatter + the passes of the subset sum | the n + 1 levels of L and R | the passes of the superset sum
+// (the first forms g from L and R) | the candidate kernel and the arc sums: four statistics rows
 static int arc_posteriors_run(mibn_t *h, int32_t n, int64_t n_fam, const int32_t *fam_child, const uint32_t *fam_parents, const double *fam_score,
                               double *log_post_out, double *arc_out, double *log_evidence_out) {
-    int rc;
-    if ((rc = check_state(h, kNeedDevice))) return rc;
-    if ((rc = check_state(h, kNeedIdle))) return rc;
-    const double t_start = now_ms();
-    reset_last_stats(h);
-    static_assert(MIBN_ARC_POSTERIOR_MAX_VARS == MIBN_BEST_DAG_MAX_VARS, "dag_check's limit is the one of both calls");
-    if ((rc = dag_check(n, n_fam, fam_child, fam_parents, fam_score, h->err))) {
-        if (h->err.rfind("best_dag", 0) == 0) h->err.replace(0, 8, "arc_posteriors");
-        return rc;
-    }
-    const DagPlan D = dag_plan(n, h->dag_tile_bits, h->dag_group_bits);
-    std::vector<DagPass> down = D.passes;  // the superset sum: the same passes; n = 1 has none, and g is formed by a pass without bits
+    DagFrame F{h, h->dag};
+    if (int rc = F.enter("arc_posteriors", n, n_fam, fam_child, fam_parents, fam_score)) return rc;
+    std::vector<DagPass> down = F.D.passes;  // the superset sum: the same passes; n = 1 has none, and g is formed by a pass without bits
     if (down.empty()) down.push_back(DagPass{0, 0, 0});
     std::vector<double> centre((size_t)n);
     dag_centres(n, n_fam, fam_child, fam_score, centre.data());
-    mibn_ctx::Dag &X = h->dag;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t bps = (size_t)n * (size_t)D.entries, subsets = size_t(1) << n, fam = (size_t)std::max<int64_t>(1, n_fam), nn = (size_t)n * (size_t)n;
+    mibn_ctx::Dag &X = F.X;
+    const size_t bps = F.bps, subsets = F.subsets, nn = (size_t)n * (size_t)n;
     const int64_t segments = dag_arc_segments(n_fam);
-    struct Release {  // on every exit, after the stream is drained (hipFree waits for the device)
+    struct Release {  // the call's tables, on every exit (hipFree waits for the device)
         mibn_ctx::Dag &X;
         bool on;
-        ~Release() {
-            if (!on) return;
-            (void)X.d_score.release();
-            (void)X.d_best.release();
-            (void)X.d_right.release();
-        }
+        ~Release() { if (on) (void)X.d_score.release(), (void)X.d_best.release(), (void)X.d_right.release(); }
     } release{X, 8 * bps + 16 * subsets > kDagKeepBytes};
     HIP_TRY(h, dag_room(X.d_score, bps));
     HIP_TRY(h, dag_room(X.d_best, subsets));
     HIP_TRY(h, dag_room(X.d_right, subsets));
-    const size_t o_child = 8 * fam, o_par = o_child + 4 * fam, o_centre = (o_par + 4 * fam + 15) & ~size_t(15), o_post = o_centre + 8 * (size_t)n,
-                 o_arc = o_post + 8 * fam, o_part = o_arc + 8 * nn, o_binom = o_part + 8 * nn * (size_t)segments;
-    static const std::vector<uint32_t> binom = [] {
-        std::vector<uint32_t> b((size_t)kDagBinomStride * kDagBinomStride);
-        dag_binomials(b.data());
-        return b;
-    }();
-    HIP_TRY(h, X.d_post_io.ensure(o_binom + 4 * binom.size()));
-    for (Event &e : X.post_ev) HIP_TRY(h, e.ensure());
-    const hipStream_t S0 = h->stream;
+    static const std::vector<uint32_t> binom = dag_binomials();
+    if (int rc = F.upload(fam_child, fam_parents, fam_score, 8 * ((size_t)n + F.fam + nn + nn * (size_t)segments) + 4 * binom.size())) return rc;
+    double *d_centre = F.carve<double>((size_t)n), *d_post = F.carve<double>(F.fam), *d_arc = F.carve<double>(nn), *d_part = F.carve<double>(nn * (size_t)segments);
+    uint32_t *d_binom = F.carve<uint32_t>(binom.size());
+    const hipStream_t S0 = F.S0;
     const double t0 = now_ms();
-    if (n_fam) {
-        HIP_TRY(h, hipMemcpyAsync(X.d_post_io, fam_score, 8 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
-        HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_child, fam_child, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
-        HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_par, fam_parents, 4 * (size_t)n_fam, hipMemcpyHostToDevice, S0));
-    }
-    HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_centre, centre.data(), 8 * (size_t)n, hipMemcpyHostToDevice, S0));  // (pageable: staged before the call returns)
-    HIP_TRY(h, hipMemcpyAsync(X.d_post_io + o_binom, binom.data(), 4 * binom.size(), hipMemcpyHostToDevice, S0));
+    HIP_TRY(h, hipMemcpyAsync(d_centre, centre.data(), 8 * (size_t)n, hipMemcpyHostToDevice, S0));  // (pageable: staged before the call returns)
+    HIP_TRY(h, hipMemcpyAsync(d_binom, binom.data(), 4 * binom.size(), hipMemcpyHostToDevice, S0));
     h->stats.h2d_ms += now_ms() - t0;
-    const double *d_fam = reinterpret_cast<const double *>(X.d_post_io.get());
-    const int32_t *d_child = reinterpret_cast<const int32_t *>(X.d_post_io + o_child);
-    const uint32_t *d_par = reinterpret_cast<const uint32_t *>(X.d_post_io + o_par);
-    const double *d_centre = reinterpret_cast<const double *>(X.d_post_io + o_centre);
-    double *d_post = reinterpret_cast<double *>(X.d_post_io + o_post), *d_arc = reinterpret_cast<double *>(X.d_post_io + o_arc),
-           *d_part = reinterpret_cast<double *>(X.d_post_io + o_part);
-    const uint32_t *d_binom = reinterpret_cast<const uint32_t *>(X.d_post_io + o_binom);
     double *alpha = X.d_score.get(), *L = X.d_best.get(), *R = X.d_right.get();
-    const dim3 wg(kDagWG), per_fam((unsigned)((fam + kDagWG - 1) / kDagWG));
     // the subset sum
-    HIP_TRY(h, hipEventRecord(X.post_ev[0], S0));
-    double launches_a = 1, bytes_a = 8.0 * (double)bps;
-    hipLaunchKernelGGL(dag_post_fill_kernel, dim3((unsigned)std::min<size_t>((bps + kDagWG - 1) / kDagWG, 65536)), wg, 0, S0, alpha, (int64_t)bps);
-    if (n_fam) {
-        hipLaunchKernelGGL(dag_post_scatter_kernel, per_fam, wg, 0, S0, d_child, d_par, d_fam, d_centre, n_fam, n, alpha);
-        launches_a += 1;
-        bytes_a += 32.0 * (double)n_fam;
-    }
-    for (const DagPass &P : D.passes) {
-        hipLaunchKernelGGL(dag_post_subset_kernel, dim3((unsigned)D.grid(P)), wg, 0, S0, alpha, P, n, D.tiles_per_child(P));
-        launches_a += 1;
-        bytes_a += 16.0 * (double)bps;
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipEventRecord(X.post_ev[1], S0));
+    if (int rc = F.mark()) return rc;
+    const DagRow a = F.fill_scatter_passes(
+        kStatDagPostSubset, 8.0, 32.0, [&](dim3 grid) { hipLaunchKernelGGL(dag_post_fill_kernel, grid, F.wg, 0, S0, alpha, (int64_t)bps); },
+        [&] { hipLaunchKernelGGL(dag_post_scatter_kernel, F.per_fam, F.wg, 0, S0, F.d_child, F.d_par, F.d_fam, d_centre, n_fam, n, alpha); },
+        [&](dim3 grid, const DagPass &P) { hipLaunchKernelGGL(dag_post_subset_kernel, grid, F.wg, 0, S0, alpha, P, n, F.D.tiles_per_child(P)); });
+    if (int rc = F.mark()) return rc;
     // L and R
     for (int32_t level = 0; level <= n; ++level)
-        hipLaunchKernelGGL(dag_post_level_kernel, dim3((binom[(size_t)n * kDagBinomStride + (size_t)level] + kDagWG - 1) / kDagWG), wg, 0, S0, alpha, L, R, d_binom,
+        hipLaunchKernelGGL(dag_post_level_kernel, dim3((binom[(size_t)n * kDagBinomStride + (size_t)level] + kDagWG - 1) / kDagWG), F.wg, 0, S0, alpha, L, R, d_binom,
                            n, level);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipEventRecord(X.post_ev[2], S0));
+    if (int rc = F.mark()) return rc;
     // the superset sum of g into alpha's storage
-    double bytes_c = 0;
+    DagRow c{kStatDagPostSuperset, 0, 0, (double)bps};
     for (size_t k = 0; k < down.size(); ++k) {
-        hipLaunchKernelGGL(dag_post_superset_kernel, dim3((unsigned)D.grid(down[k])), wg, 0, S0, alpha, L, R, down[k], n, D.tiles_per_child(down[k]), (int32_t)(k == 0));
-        bytes_c += (k == 0 ? 24.0 : 16.0) * (double)bps;  // the first pass reads L and R per entry and writes the entry
+        hipLaunchKernelGGL(dag_post_superset_kernel, dim3((unsigned)F.D.grid(down[k])), F.wg, 0, S0, alpha, L, R, down[k], n, F.D.tiles_per_child(down[k]), (int32_t)(k == 0));
+        c.add((k == 0 ? 24.0 : 16.0) * (double)bps);  // the first pass reads L and R per entry and writes the entry
     }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipEventRecord(X.post_ev[3], S0));
+    if (int rc = F.mark()) return rc;
     // the candidates' posteriors and the arc sums
     double launches_d = 2;
     if (n_fam) {
-        hipLaunchKernelGGL(dag_post_candidate_kernel, per_fam, wg, 0, S0, d_child, d_par, d_fam, d_centre, alpha, L, n_fam, n, d_post);
+        hipLaunchKernelGGL(dag_post_candidate_kernel, F.per_fam, F.wg, 0, S0, F.d_child, F.d_par, F.d_fam, d_centre, alpha, L, n_fam, n, d_post);
         launches_d += 1;
     }
-    hipLaunchKernelGGL(dag_post_arc_kernel, dim3((unsigned)segments, (unsigned)n), wg, 0, S0, d_child, d_par, d_post, n_fam, n, d_part);
-    hipLaunchKernelGGL(dag_post_arc_sum_kernel, dim3((unsigned)((nn + kDagWG - 1) / kDagWG)), wg, 0, S0, d_part, segments, n, d_arc);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipEventRecord(X.post_ev[4], S0));
-    const double t1 = now_ms();
+    hipLaunchKernelGGL(dag_post_arc_kernel, dim3((unsigned)segments, (unsigned)n), F.wg, 0, S0, F.d_child, F.d_par, d_post, n_fam, n, d_part);
+    hipLaunchKernelGGL(dag_post_arc_sum_kernel, dim3((unsigned)((nn + kDagWG - 1) / kDagWG)), F.wg, 0, S0, d_part, segments, n, d_arc);
+    if (int rc = F.mark()) return rc;
     double l_full = 0;
     HIP_TRY(h, hipMemcpyAsync(&l_full, L + (subsets - 1), 8, hipMemcpyDeviceToHost, S0));
     HIP_TRY(h, hipMemcpyAsync(arc_out, d_arc, 8 * nn, hipMemcpyDeviceToHost, S0));
     if (n_fam) HIP_TRY(h, hipMemcpyAsync(log_post_out, d_post, 8 * (size_t)n_fam, hipMemcpyDeviceToHost, S0));
-    HIP_TRY(h, hipStreamSynchronize(S0));
-    h->stats.d2h_ms += now_ms() - t1;
-    *log_evidence_out = dag_log_evidence(l_full, n, centre.data());
-    float ms[4] = {};
-    for (int k = 0; k < 4; ++k) HIP_TRY(h, hipEventElapsedTime(&ms[k], X.post_ev[k], X.post_ev[k + 1]));
     // L and R: every alpha entry read twice and every L / R entry once per member, both written once per subset
     const double bytes_b = 32.0 * (double)bps + 16.0 * (double)subsets;
     // a candidate's 24 bytes, its Gamma and its log_post; the arc kernel reads child per (candidate, child), masks and log_post once
     const double bytes_d = 40.0 * (double)n_fam + (4.0 * (double)n + 12.0) * (double)n_fam + 8.0 * (double)nn * ((double)segments + 1.0);
-    book_stat(h, kStatDagPostSubset, launches_a, ms[0], bytes_a, (double)n_fam, true, false);
-    book_stat(h, kStatDagPostLevel, (double)n + 1.0, ms[1], bytes_b, (double)subsets, true, false);
-    book_stat(h, kStatDagPostSuperset, (double)down.size(), ms[2], bytes_c, (double)bps, true, false);
-    book_stat(h, kStatDagPostArc, launches_d, ms[3], bytes_d, (double)n_fam, true, false);
-    h->stats.kernel_ms = ms[0] + ms[1] + ms[2] + ms[3];
-    h->stats.n_launches = launches_a + (double)n + 1.0 + (double)down.size() + launches_d;
-    h->stats.alg_bytes = bytes_a + bytes_b + bytes_c + bytes_d;
-    h->stats.total_ms = now_ms() - t_start;
+    if (int rc = F.finish({a, {kStatDagPostLevel, (double)n + 1.0, bytes_b, (double)subsets}, c, {kStatDagPostArc, launches_d, bytes_d, (double)n_fam}})) return rc;
+    *log_evidence_out = dag_log_evidence(l_full, n, centre.data());
     return MIBN_OK;
 }
 

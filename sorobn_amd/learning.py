@@ -912,6 +912,24 @@ def _mask_scope(child, pm):
     return tuple(u for u in range(pm.bit_length()) if (pm >> u) & 1) + (child,)
 
 
+def _exact_scores(X, weights, score, ess, max_parents, required, forbidden, max_families, device, **who):
+    """The opening `exact_search` and `arc_posteriors` share: the row weights, `_exact_plan` (`who`: its naming arguments), the
+    data set and the ONE `score_families` call -> (engine, columns, candidates, scores)."""
+    X, weights = row_weights(X, weights)
+    encoded = []
+
+    def cards():
+        encoded.append(encode_complete(X, list(X.columns)))
+        return encoded[0][2]
+
+    columns, cand = _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards, **who)
+    codes, _, card = encoded[0]
+    engine = counting_engine(device)
+    with engine.dataset(codes, card) as ds:
+        scores = ds.score_families([_mask_scope(v, pm) for v, pm in cand], score, ess, **_weighted(ds, weights)(len(cand)))
+    return engine, columns, cand, scores
+
+
 def exact_search(X, score="bic", ess=1.0, max_parents=3, required=(), forbidden=(), max_families=2_000_000, device=None, return_info=False,
                  weights=None):
     """The globally best DAG under a decomposable score, by dynamic programming over column subsets (Silander and Myllymaki 2006)
@@ -927,19 +945,8 @@ def exact_search(X, score="bic", ess=1.0, max_parents=3, required=(), forbidden=
     own nested sum, info["order"] a topological order of the column names (roots first), info["n_families"].
 
     Complete data only.  `weights`: see `row_weights` - the search on the rows written out weights[i] times, bit for bit."""
-    X, weights = row_weights(X, weights)
-    encoded = []
-
-    def cards():
-        encoded.append(encode_complete(X, list(X.columns)))
-        return encoded[0][2]
-
-    columns, cand = _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards)
-    codes, _, card = encoded[0]
+    engine, columns, cand, scores = _exact_scores(X, weights, score, ess, max_parents, required, forbidden, max_families, device)
     n = len(columns)
-    engine = counting_engine(device)
-    with engine.dataset(codes, card) as ds:
-        scores = ds.score_families([_mask_scope(v, pm) for v, pm in cand], score, ess, **_weighted(ds, weights)(len(cand)))
     parents, order, dp_total = engine.best_dag(n, [v for v, _ in cand], [pm for _, pm in cand], scores)
     if not dp_total > -math.inf:
         raise RuntimeError("best_dag found no DAG although every child has its required parents as a candidate")
@@ -1046,19 +1053,10 @@ def arc_posteriors(X, score="bdeu", ess=1.0, max_parents=3, required=(), forbidd
     (see `ArcPosterior`).  Complete data only.  `weights`: see `row_weights`."""
     if parent_prior not in PARENT_PRIORS:
         raise ValueError(f"parent_prior must be one of {PARENT_PRIORS}, not {parent_prior!r}")
-    X, weights = row_weights(X, weights)
-    encoded = []
-
-    def cards():
-        encoded.append(encode_complete(X, list(X.columns)))
-        return encoded[0][2]
-
-    columns, cand = _exact_plan(X, score, ess, max_parents, required, forbidden, max_families, cards, who="arc_posteriors", instead="bootstrap")
-    codes, _, card = encoded[0]
+    engine, columns, cand, scores = _exact_scores(X, weights, score, ess, max_parents, required, forbidden, max_families, device,
+                                                  who="arc_posteriors", instead="bootstrap")
     n = len(columns)
-    engine = counting_engine(device)
-    with engine.dataset(codes, card) as ds:
-        scores = np.asarray(ds.score_families([_mask_scope(v, pm) for v, pm in cand], score, ess, **_weighted(ds, weights)(len(cand))), np.float64)
+    scores = np.asarray(scores, np.float64)
     if parent_prior == "size":
         scores = scores - np.array([math.log(math.comb(n - 1, bin(pm).count("1"))) for _, pm in cand], np.float64)
     log_post, arc, log_evidence = engine.arc_posteriors(n, [v for v, _ in cand], [pm for _, pm in cand], scores)

@@ -142,7 +142,7 @@ def test_logaddexp_as_pinned():
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("dagpost") / "dag_post_sim")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tools", "dag_post_sim.cpp"), "-o", exe],
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tools", "dag_post_sim.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
 
